@@ -15,7 +15,11 @@ forward -> NxN distance matrix -> mine-and-select -> hinge -> backward -> (RCCL 
 (siamese: two branch forwards -> pair distance -> contrastive loss -> backward -> optimizer).  fp32 throughout.
 Rank 0 prints ONE JSON line; details go to stderr.
 
-roofline: every kernel launch of libembnet_hip.so is timed with HIP events on the launch stream (embnet_trace_*), on
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own or slows the timed
+steps: the per-kernel trace and roofline below, the sustained leg, the secondary batch-hard timing and the CPU baseline.
+--dump-outputs DIR writes what the last timed step handed its caller to DIR/<name>.npy (see dump_outputs).
+
+roofline (--full): every kernel launch of libembnet_hip.so is timed with HIP events on the launch stream (embnet_trace_*), on
 one to three of the timed steps (by the length of the timed region); the kernel with the largest total time is reported against the roofline that bounds it — for the
 convolution kernels the 16-bit MFMA peak (16 x 157.3 TFLOP/s) with the 16-bit FLOP they execute (each fp32 product = 3 fp16
 MFMA terms of a two-piece split in the kernels that read pre-split planes or know their operands' ranges (conv_*_h_kernel), 6 bf16
@@ -242,6 +246,37 @@ def roofline_from_trace(records, traced_steps, ms_per_step, workload, conv_terms
     return roof, by
 
 
+DUMP_BUDGET = 48 << 20      # bytes of model state written by --dump-outputs (the rest of the 64 MB holds the small arrays)
+
+
+def dump_outputs(path, loss, trainer, model):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float32 / float64:
+      loss         [1] the step's return value (triplet / contrastive loss)
+      total_loss   [1] that loss plus the kernel regularisers (what Keras reports as `loss`)
+      triplets     [T, 3] the mined (anchor, positive, negative) rows of the batch, sorted (triplet mode; float64, exact)
+      state        [S] every floating-point tensor of model.state_dict() after the step's update, flattened in state_dict
+                   order — weights and BatchNorm statistics; above DUMP_BUDGET the positions
+                   torch.randperm(S_full, generator=torch.Generator().manual_seed(0))[:DUMP_BUDGET // 4], sorted"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": loss.detach().float().reshape(1)}
+    if getattr(trainer, "last_total", None) is not None:
+        out["total_loss"] = trainer.last_total.detach().float().reshape(1)
+    if getattr(trainer, "last_triplets", None) is not None:
+        trip, count = trainer.last_triplets
+        rows = trip[: int(count[0].item())].cpu().numpy().astype(np.float64)
+        out["triplets"] = torch.from_numpy(rows[np.lexsort(rows.T[::-1])])     # the kernels append rows in no fixed order
+    flat = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+    n_keep = DUMP_BUDGET // 4
+    if flat.numel() > n_keep:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n_keep].sort().values
+        flat = flat[idx.to(flat.device)]
+    out["state"] = flat
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    log(f"  outputs of the last timed step -> {path}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in out.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -259,6 +294,11 @@ def main():
     ap.add_argument("--mining", default=None, choices=["hardest", "semihard", "random_hard", "batch_hard"])
     ap.add_argument("--optimizer", default="radam", choices=["radam", "adam", "rms_prop", "sgd"])
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: kernel trace + roofline, sustained leg, batch-hard timing, "
+                         "CPU baseline (each can still be switched off by its --no-* / --sustain-seconds option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-batch-hard", action="store_true", help="skip the secondary batch-hard timing behind a 'hardest' run")
@@ -275,6 +315,9 @@ def main():
     ap.add_argument("--sustain-seconds", type=float, default=3.0,
                     help="after the timed region: keep stepping this long (untimed for `value`) and report the steady-state ms/step")
     args = ap.parse_args()
+    if not args.full:               # a plain run: the timed steps and the line, nothing measured beside them
+        args.no_cpu_baseline = args.no_kernel_timer = args.no_batch_hard = True
+        args.sustain_seconds = 0.0
     for key, val in {**dict(k_classes=32, k_samples=4, pairs=256, mining="hardest"), **CONFIGS[args.config]}.items():
         if getattr(args, key, None) is None:
             setattr(args, key, val)
@@ -403,6 +446,8 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = n_local * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:         # before the --full legs step the model any further
+        dump_outputs(args.dump_outputs, loss, trainer, model)
     # sustained leg (not part of `value`): the chip lowers its clock under sustained matrix load, so a 0.2-0.6 s timed
     # region is a short-burst number; keep stepping and report what the step time settles at
     sustained, sus_traced = None, set()

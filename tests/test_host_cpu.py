@@ -577,6 +577,7 @@ def test_bench_gpus_n_spawns_its_own_ranks_and_relays_the_worst_exit_code():
     WORLD_SIZE / MASTER_* set) before touching any GPU and returns the worst child exit code.  Without a GPU every rank joins the
     gloo world and then stops with the product's 'needs an MI355X' message: a non-zero exit, no JSON line, both ranks heard."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"          # no GPU for the ranks, also where the test runs on a machine that has one
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode != 0

@@ -99,6 +99,40 @@ def test_bench_reports_a_live_problem_and_refuses_a_dead_one():
     assert out.returncode == 0 and d["config"]["loss_min_timed"] == 0.0 and d["config"]["active_triplets_min"] == 1
 
 
+def test_bench_plain_run_dumps_the_last_step(dev, tmp_path):
+    """A plain run (none of the switches that turn the secondary legs off) measures nothing beside its timed steps: kernel
+    trace, sustained leg, batch-hard timing and CPU baseline are --full's.  --dump-outputs writes what the last timed step
+    returned and left in the model (float32 / float64 within 64 MB): the state is the trained model, not the initial one,
+    and two runs with the same arguments write the same arrays."""
+    from embeddingnet_amd import backbones as B
+    runs = []
+    for i in range(2):
+        path = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--config", "c1",
+                              "--mining", "hardest", "--pool", "8", "--dump-outputs", str(path)],
+                             capture_output=True, text=True, timeout=900)
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert out.returncode == 0 and lines, out.stderr[-3000:]
+        d = json.loads(lines[-1])
+        assert d["steps"] == 6 and d["ms_per_step"] > 0 and d["roofline"] is None and "cpu_baseline" not in d
+        assert d["config"]["sustained"] is None and d["config"]["batch_hard"] is None
+        got = {p.stem: np.load(p) for p in path.glob("*.npy")}
+        assert set(got) == {"loss", "total_loss", "triplets", "state"}, sorted(got)
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert got["loss"][0] == np.float32(d["config"]["final_loss"]) and got["loss"][0] > 0
+        assert got["triplets"].shape[1] == 3 and got["triplets"].shape[0] >= d["config"]["active_triplets_min"] > 1
+        runs.append(got)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+    # the model bench.py starts from (same constructor, same seed): the dumped state has its layout and has moved away from it
+    model, _ = B.get_backbone((64, 64, 3), encodings_len=256, backbone_name="simple2", backbone_weights=None, seed=0, device=dev)
+    init = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()]).cpu().numpy()
+    state = runs[0]["state"]
+    assert state.shape == init.shape
+    assert np.count_nonzero(state != init) > 0.25 * state.size, "the dump holds the model before the timed steps"
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` (no launcher on the command line, the form of the driver's N = 1 command): the parent
     spawns one child per rank BEFORE touching the GPU and relays rank 0's JSON line.  Two ranks share this box's one GPU

@@ -122,11 +122,11 @@ print("reducer ok", res[0][0])
 
 
 def test_bench_under_torchrun_single_rank():
-    """bench.py through the driver's launch line (torch.distributed.run, 1 rank) prints one JSON line."""
+    """bench.py through the driver's launch line (torch.distributed.run, 1 rank) prints one JSON line (--full: with its roofline)."""
     import json
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29544", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--backbone", "simple2",
+                          "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--backbone", "simple2",
                           "--image", "64", "--k-classes", "8"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

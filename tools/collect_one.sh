@@ -14,5 +14,5 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/pmc_write
 python3 tools/pmc_traffic.py "$out/pmc_fetch" "$out/pmc_write" "$out/pmc_traffic.json" $c "$PCMD --config $c" > "$out/pmc_traffic_$c.txt"
 rm -rf "$out/pmc_fetch" "$out/pmc_write"
 cp "$out/pmc_traffic.json" "$root/profiles/${tag}_pmc_traffic.json"
-python3 bench.py --config $c --steps 20 --warmup 5 --cpu-seconds 8 > "$out/bench_$c.json" 2> "$out/bench_$c.err"
+python3 bench.py --full --config $c --steps 20 --warmup 5 --cpu-seconds 8 > "$out/bench_$c.json" 2> "$out/bench_$c.err"
 head -c 600 "$out/bench_$c.json"; echo; tail -24 "$out/bench_$c.err"

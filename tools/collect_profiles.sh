@@ -17,13 +17,13 @@ for c in c2 c1 c1s c3 c5; do
   rm -rf "$out/pmc_fetch" "$out/pmc_write"
 done
 cp "$out/pmc_traffic.json" "$root/profiles/${tag}_pmc_traffic.json"
-python3 bench.py > "$out/bench_c2.json" 2> "$out/bench_c2.err"
-python3 bench.py --mining batch_hard --steps 30 --no-cpu-baseline > "$out/bench_c2_batch_hard.json" 2> "$out/bench_c2_batch_hard.err"
+python3 bench.py --full > "$out/bench_c2.json" 2> "$out/bench_c2.err"
+python3 bench.py --full --mining batch_hard --steps 30 --no-cpu-baseline > "$out/bench_c2_batch_hard.json" 2> "$out/bench_c2_batch_hard.err"
 for c in c1 c1s c3 c5; do
-  python3 bench.py --config $c --steps 20 --warmup 5 --cpu-seconds 8 > "$out/bench_$c.json" 2> "$out/bench_$c.err"
+  python3 bench.py --full --config $c --steps 20 --warmup 5 --cpu-seconds 8 > "$out/bench_$c.json" 2> "$out/bench_$c.err"
 done
-EMBNET_CONV_PATCH=0 python3 bench.py --no-cpu-baseline > "$out/bench_c2_gather_convs.json" 2> "$out/bench_c2_gather_convs.err"
-CMD="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-graph --no-batch-hard --sustain-seconds 0"
+EMBNET_CONV_PATCH=0 python3 bench.py --full --no-cpu-baseline > "$out/bench_c2_gather_convs.json" 2> "$out/bench_c2_gather_convs.err"
+CMD="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-graph --no-batch-hard --sustain-seconds 0"
 rocprofv3 --kernel-trace --output-format csv -d "$out/trace" -- $CMD > "$out/trace_bench.json" 2> "$out/trace.err"
 python3 tools/kernel_stats.py "$out"/trace/*/*_kernel_trace.csv 13 "$out/kernel_stats" \
     "rocprofv3 --kernel-trace of \`$CMD\` (13 steps in the trace)" > /dev/null

@@ -16,5 +16,5 @@ for t in 0 1; do
   BCFG=c3 EMBNET_PATCH_BN_SUMS=$t timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --sustain-seconds 0 --no-kernel-timer 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'])" >> $O
 done
 echo "== c2 kernel table (flag on)" >> $O
-BCFG=c2 timeout 300 python bench.py --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "x +[0-9]+/step|traced kernels" | head -14 >> $O
+BCFG=c2 timeout 300 python bench.py --full --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "x +[0-9]+/step|traced kernels" | head -14 >> $O
 cat $O

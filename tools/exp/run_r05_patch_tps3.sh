@@ -5,4 +5,4 @@ for i in 1 2 3; do
   one BCFG=c2 EMBNET_PATCH_TPS3=0
   one BCFG=c2 EMBNET_PATCH_TPS3=1
 done
-EMBNET_PATCH_TPS3=1 EMBNET_BENCH_ROWS=6 timeout 300 python bench.py --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep "conv_patch"
+EMBNET_PATCH_TPS3=1 EMBNET_BENCH_ROWS=6 timeout 300 python bench.py --full --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep "conv_patch"

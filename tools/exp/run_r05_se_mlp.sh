@@ -12,6 +12,6 @@ for r in 1 2 3; do
 done
 for t in 0 1; do
   echo "== c5 kernel trace EMBNET_SE_MLP=$t (se / dense / act / colsum rows)" >> $O
-  BCFG=c5 EMBNET_SE_MLP=$t EMBNET_BENCH_ROWS=60 timeout 300 python bench.py --steps 10 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "semlp|dense_|act_fwd|act_bwd|colsum|step mode|enqueue loop|traced kernels" >> $O
+  BCFG=c5 EMBNET_SE_MLP=$t EMBNET_BENCH_ROWS=60 timeout 300 python bench.py --full --steps 10 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "semlp|dense_|act_fwd|act_bwd|colsum|step mode|enqueue loop|traced kernels" >> $O
 done
 cat $O

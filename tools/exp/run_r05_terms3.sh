@@ -18,14 +18,14 @@ V=$(pwd)/tools/exp/_variants/terms3.so
 line() { tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], 'loss', d['config'].get('loss_last_timed'), r['kernel'][:60], r['avg_us'])"; }
 for r in 1 2 3; do
   echo "== c2 six terms (product) round=$r" >> $O
-  BCFG=c2 timeout 300 python bench.py --steps 40 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
+  BCFG=c2 timeout 300 python bench.py --full --steps 40 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
   echo "== c2 three terms (variant) round=$r" >> $O
-  BCFG=c2 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --steps 40 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
+  BCFG=c2 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --full --steps 40 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
 done
 echo "== c3 six terms" >> $O
-BCFG=c3 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
+BCFG=c3 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
 echo "== c3 three terms" >> $O
-BCFG=c3 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
+BCFG=c3 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --sustain-seconds 0 2>/dev/null | line >> $O
 echo "== c2 three terms: kernel table" >> $O
-BCFG=c2 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "x +[0-9]+/step|traced kernels" | head -8 >> $O
+BCFG=c2 EMBNET_LIB=$V EMBNET_LIB_LAX=1 timeout 300 python bench.py --full --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "x +[0-9]+/step|traced kernels" | head -8 >> $O
 cat $O

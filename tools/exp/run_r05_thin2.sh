@@ -4,4 +4,4 @@ for i in 1 2; do
   one BCFG=c5 EMBNET_CONV_THIN=0
   one BCFG=c5 EMBNET_CONV_THIN=1
 done
-EMBNET_BENCH_ROWS=8 EMBNET_BENCH_DETAIL=thin timeout 300 python bench.py --config c5 --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "thin|traced"
+EMBNET_BENCH_ROWS=8 EMBNET_BENCH_DETAIL=thin timeout 300 python bench.py --full --config c5 --steps 20 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "thin|traced"

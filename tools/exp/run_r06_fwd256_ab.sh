@@ -9,11 +9,11 @@ done
 for rep in 1 2 3; do
   for v in 0 1; do
     echo "== C2 EMBNET_FWD_256=$v rep $rep" >> $out
-    EMBNET_FWD_256=$v python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "conv_fwd_h_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
+    EMBNET_FWD_256=$v python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "conv_fwd_h_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
   done
 done
 for v in 0 1; do
   echo "== C3 EMBNET_FWD_256=$v" >> $out
-  EMBNET_FWD_256=$v python bench.py --config c3 --steps 12 --warmup 4 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "traced kernels|\"metric\"" | cut -c1-230 >> $out
+  EMBNET_FWD_256=$v python bench.py --full --config c3 --steps 12 --warmup 4 --no-cpu-baseline --sustain-seconds 0 2>&1 | grep -E "traced kernels|\"metric\"" | cut -c1-230 >> $out
 done
 python -m pytest tests/test_backbone_gpu.py tests/test_full_size_gpu.py tests/test_conv_ranges_gpu.py -q -x 2>&1 | tail -4 >> $out

@@ -7,7 +7,7 @@ for rep in 1 2; do
   for cfg in c1s c1; do
     for v in 0 1; do
       echo "== $cfg EMBNET_CONV_F16=$v rep $rep" >> $out
-      EMBNET_CONV_F16=$v python bench.py --config $cfg --steps 200 --warmup 30 --no-cpu-baseline --sustain-seconds 0 --force-graph 2>&1 | grep -E "enqueue loop|step mode|traced kernels|\"metric\"" | cut -c1-250 >> $out
+      EMBNET_CONV_F16=$v python bench.py --full --config $cfg --steps 200 --warmup 30 --no-cpu-baseline --sustain-seconds 0 --force-graph 2>&1 | grep -E "enqueue loop|step mode|traced kernels|\"metric\"" | cut -c1-250 >> $out
     done
   done
 done

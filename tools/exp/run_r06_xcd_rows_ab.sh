@@ -6,13 +6,13 @@ out=gpurun_out/r06_exp_xcd_rows.txt
 for rep in 1 2 3; do
   for v in 0 1; do
     echo "== C2 EMBNET_PATCH_XCD_ROWS=$v rep $rep" >> $out
-    EMBNET_PATCH_XCD_ROWS=$v python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "enqueue loop|conv_patch_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
+    EMBNET_PATCH_XCD_ROWS=$v python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "enqueue loop|conv_patch_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
   done
 done
 for rep in 1 2; do
   for v in 1 0; do
     echo "== C2 EMBNET_WGRAD_256=$v rep $rep" >> $out
-    EMBNET_WGRAD_256=$v python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "enqueue loop|conv_wgrad_h_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
+    EMBNET_WGRAD_256=$v python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-batch-hard --sustain-seconds 0 2>&1 | grep -E "enqueue loop|conv_wgrad_h_kernel|traced kernels|\"metric\"" | cut -c1-230 >> $out
   done
 done
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
