@@ -144,13 +144,16 @@ class ENDataGenerator:
 
 
 class TripletsDataGenerator(ENDataGenerator):
+    # build-defined rules that exist only inside the fused step (train_step.TripletTrainer): accepted here so that a config
+    # names them for tools/train.py, refused by the reference-structured mine_batch / __getitem__
+    STEP_ONLY_MODES = ("batch_hard", "batch_all")
 
     def __init__(self, embedding_model, class_files_paths, class_names, n_batches=10, input_shape=None,
                  batch_size=32, augmentations=None, k_classes=5, k_samples=5, margin=0.5,
                  negatives_selection_mode='semihard'):
         super().__init__(class_files_paths=class_files_paths, class_names=class_names, input_shape=input_shape,
                          batch_size=batch_size, n_batches=n_batches, augmentations=augmentations)
-        if negatives_selection_mode not in ops.MINING_MODES:
+        if negatives_selection_mode not in tuple(ops.MINING_MODES) + self.STEP_ONLY_MODES:
             raise KeyError(negatives_selection_mode)
         self.embedding_model = embedding_model
         self.k_classes, self.k_samples, self.margin = k_classes, k_samples, margin
@@ -222,6 +225,9 @@ class TripletsDataGenerator(ENDataGenerator):
         """reference :211-258 on a given class-contiguous batch [P*K,H,W,3] (NumPy or device tensor): predict() ->
         distance matrix -> negative selection -> ([A,P,N], ones[T]).  The mined row indices stay in
         `self.last_triplets` (int64 [T,3], device)."""
+        if self.mode in self.STEP_ONLY_MODES:
+            raise ValueError(f"negatives_selection_mode '{self.mode}' has no reference-structured mining: it runs inside the "
+                             "fused step only (embeddingnet_amd.train_step.TripletTrainer)")
         dev = next(self.embedding_model.parameters()).device
         x = images.to(dev) if torch.is_tensor(images) else torch.from_numpy(np.asarray(images, np.float32)).to(dev)
         was = self.embedding_model.training

@@ -4,6 +4,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   contrastive_loss(y_true, y_pred)          reference :4-11
   triplet_loss(margin)(y_true, y_pred)      reference :14-44  -> per-row [T] (caller means)
   accuracy(y_true, y_pred)                  reference :47-50
+  batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
 from . import ops
@@ -20,6 +21,17 @@ def triplet_loss(margin=0.5):
 
     def loss_function(y_true, y_pred):
         return ops.triplet_hinge(y_pred, margin)
+
+    return loss_function
+
+
+def batch_all_triplet_loss(k_classes, k_samples, margin=0.5):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] embedding
+    block, y_true is ignored (Keras signature).  Batch-all (build-defined, not in the reference): the mean of
+    d(a,p) - d(a,n) + margin over every valid triplet of the block where it is > 0 (d squared L2)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.batch_all_triplet_loss(y_pred, k_classes, k_samples, margin)[0]
 
     return loss_function
 

@@ -185,6 +185,57 @@ def fused_triplet_loss(emb, k_classes, k_samples, margin, mode, seed=0, seed_dev
     return _FusedTripletLoss.apply(emb, int(k_classes), int(k_samples), float(margin), mode, int(seed), seed_dev)
 
 
+_BATCH_ALL_WS = {}
+BATCH_ALL_PATHS = {"auto": 0, "per_class": 1, "distance_matrix": 2}
+
+
+class _BatchAllLoss(torch.autograd.Function):
+    """Batch-all triplet loss (include/embnet.h, embnet_batch_all_loss_fwd/bwd): one forward launch on the per-class path,
+    distance matrix + sweep above it; one backward launch.  The pair weights W stay saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, emb, p, k, margin, path):
+        emb = _prep(emb)
+        n, e = emb.shape
+        if n != p * k:
+            raise _lib.EmbnetError(f"batch_all_triplet_loss: {n} rows != k_classes*k_samples = {p}*{k}")
+        lib = _lib.lib()
+        w = _new((n, n), emb)
+        n_active = _new((1,), emb, torch.int32)
+        frac, mean = _new((), emb), _new((), emb)
+        key = (emb.device.index, stream(), p, k, e)
+        ws = _BATCH_ALL_WS.get(key)
+        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
+            nbytes = lib.embnet_batch_all_workspace_bytes(p, k, e)
+            ws = _BATCH_ALL_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
+        check(lib.embnet_batch_all_loss_fwd(ptr(emb), p, k, e, f32(margin), BATCH_ALL_PATHS[path], ptr(w), ptr(n_active),
+                                            ptr(frac), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
+        ctx.save_for_backward(emb, w, n_active)
+        ctx.mark_non_differentiable(n_active, frac, w)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return mean, n_active, frac, w
+
+    @staticmethod
+    def backward(ctx, dmean, _dn, _dfrac, _dw):
+        if dmean is None:
+            return None, None, None, None, None
+        emb, w, n_active = ctx.saved_tensors
+        n, e = emb.shape
+        demb = torch.empty_like(emb)
+        check(_lib.lib().embnet_batch_all_loss_bwd(ptr(emb), n, e, ptr(w), ptr(n_active), ptr(_prep(dmean)), ptr(demb),
+                                                   stream()))
+        return demb, None, None, None, None
+
+
+def batch_all_triplet_loss(emb, k_classes, k_samples, margin, path="auto", return_weights=False):
+    """Batch-all triplet loss over a class-contiguous [P*K, E] block: the mean of b = d(a,p) - d(a,n) + margin over every
+    valid triplet with b > 0 (d squared L2).  -> (mean [autograd], n_active int32 [1], frac_active []) on the device, no host
+    synchronisation; return_weights adds the pair-weight matrix W [N,N] the backward uses.  path: 'auto', 'per_class' or
+    'distance_matrix' (include/embnet.h)."""
+    out = _BatchAllLoss.apply(emb, int(k_classes), int(k_samples), float(margin), path)
+    return out if return_weights else out[:3]
+
+
 # --------------------------------------------------------------------------- contrastive / accuracy
 class _Contrastive(torch.autograd.Function):
     @staticmethod

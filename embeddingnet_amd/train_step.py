@@ -31,9 +31,12 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path; anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
-    all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly."""
+    all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
+    negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
+    (Hermans: one triplet per anchor) or 'batch_all' (every valid triplet, mean over those with a positive hinge; there are
+    no triplet rows, so last_triplets = (None, n_active)).  Under data parallelism every mode mines and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
 
@@ -48,7 +51,7 @@ class TripletTrainer:
         self.ctx = L.StepContext(f"TripletTrainer@{id(self):x}")       # this trainer's fused hand-overs (layers.StepContext)
         # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
         self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
-        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",):
+        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all"):
             raise KeyError(self.mode)
         from .optimizers import KerasOptimizer
         self._keras_opt = isinstance(optimizer, KerasOptimizer)
@@ -74,7 +77,12 @@ class TripletTrainer:
         if images.shape[0] != self.p * self.k:
             raise ValueError(f"batch of {images.shape[0]} images != k_classes*k_samples = {self.p * self.k}")
         emb = self.model(images)
-        if self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
+        if self.mode == "batch_all":
+            # every valid triplet, mean over the active ones (ops.batch_all_triplet_loss, at every batch size and whatever
+            # EMBNET_FUSED_LOSS says); there are no triplet rows: last_triplets = (None, n_active)
+            mean, count, _ = ops.batch_all_triplet_loss(emb, self.p, self.k, self.margin)
+            self.last_triplets = (None, count)
+        elif self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
             seed_dev = self._state.data_ptr() + 24 if self._graph_state_live() else None     # uint64 behind the 6 floats
             mean, _, trip, count = ops.fused_triplet_loss(emb, self.p, self.k, self.margin, self.mode,
                                                           seed=(self.seed << 20) + self.step_no, seed_dev=seed_dev)
@@ -90,7 +98,7 @@ class TripletTrainer:
         return getattr(self, "_state", None) is not None and torch.cuda.is_current_stream_capturing()
 
     def _graph_supported(self, images):
-        if not self._keras_opt or not self.fused_loss:
+        if not self._keras_opt or not (self.fused_loss or self.mode == "batch_all"):
             return False
         return self.opt.rule != "radam" or self.opt.iterations >= 6      # RAdam switches kernels while it warms up
 

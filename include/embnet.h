@@ -713,6 +713,33 @@ int embnet_fused_triplet_loss_fwd(const float* emb, int p, int k, int e, float m
                                   float* loss, float* active, float* mean_loss, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/* Batch-all triplet loss (Moindrot; Hermans et al. name it beside batch-hard; README.md cites both, the reference has no
+ * code for it): build-defined, selected as TripletTrainer(negatives_selection_mode="batch_all").  Additions only: the ABI
+ * version stays 22, since no existing entry point changed and older callers never see these symbols.
+ *   emb[n,e], n = p*k class-contiguous; d(i,j) = sum_c (x_ic - x_jc)^2; valid triplets (a,p,n): p in a's class, p != a,
+ *   n in another class, T = n (k-1) (n-k).  b = (d(a,p) - d(a,n)) + margin; ACTIVE iff b > 0 (strict; the `active` flags
+ *   of the selection rules above use b >= 0).  A = #active:
+ *     *n_active = A,  *frac_active = A / T,  *mean_loss = sum_active b / max(A, 1)   (0 when A = 0)
+ *     pair_w[n][n]: W[a,p] = #{n : (a,p,n) active}, W[a,n] = -#{p : (a,p,n) active}, 0 elsewhere (integers, exact)
+ *   bwd, A held constant: demb_i = (2 g / max(A,1)) * sum_j (W_ij + W_ji) (x_i - x_j), g = *upstream (NULL = 1); A is read
+ *   from n_active in device memory.
+ * Range: p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096 and T <= 2^31 - 1 (n_active is int32; at n = 4096 that is k <= 128);
+ * anything else is rejected before a launch.  path: 0 = auto (embnet_batch_all_path), EMBNET_BATCH_ALL_PER_CLASS = one launch,
+ * a workgroup per class with the distances in LDS in the difference form (n <= 512, k <= 16, k*(e+n) floats in 64 KiB),
+ * EMBNET_BATCH_ALL_DISTANCE_MATRIX = embnet_pairwise_dist_f32(squared) into the workspace (Gram-form rounding) + a sweep
+ * launch over the anchor rows.  The backward is one launch (f64 matrix instructions: every product of an integer weight and
+ * an fp32 x is exact).  No floating-point atomics: bitwise reproducible; no host synchronisation or allocation.
+ * workspace (embnet_batch_all_workspace_bytes, either path, 16-byte aligned): zero-filled ONCE by the caller; every launch
+ * leaves its arrival counter zeroed. */
+enum { EMBNET_BATCH_ALL_PER_CLASS = 1, EMBNET_BATCH_ALL_DISTANCE_MATRIX = 2 };
+int embnet_batch_all_path(int p, int k, int e);          /* the path `auto` takes; 0 outside the range */
+size_t embnet_batch_all_workspace_bytes(int p, int k, int e);
+int embnet_batch_all_loss_fwd(const float* emb, int p, int k, int e, float margin, int path, float* pair_w,
+                              int32_t* n_active, float* frac_active, float* mean_loss, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int embnet_batch_all_loss_bwd(const float* emb, int n, int e, const float* pair_w, const int32_t* n_active,
+                              const float* upstream, float* demb, void* stream);
+
 /* ------------------------------------------------------------------ optimizer update
  * utils.py:143-153 get_optimizer(name, lr): `Adam(lr)`, `RMSprop(lr)`, `keras_radam.RAdam(lr)`, else `SGD(lr)`
  * with the library defaults — applied by Keras after train.py:160-177's compile/fit.  One launch updates every

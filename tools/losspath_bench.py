@@ -4,7 +4,8 @@
   python tools/losspath_bench.py [--json profiles/r02_losspath.json]          (GPU box)
 
 For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2 batch-hard and C5 (64x4 = 256, E = 512,
-semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings:
+semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
+run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -24,7 +25,9 @@ import torch  # noqa: E402
 from embeddingnet_amd import _lib, ops  # noqa: E402
 
 CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batch_hard", 32, 4, 256, "batch_hard"),
-         ("c5", 64, 4, 512, "semihard")]
+         ("c5", 64, 4, 512, "semihard"),
+         ("c1_batch_all", 8, 4, 256, "batch_all"), ("c2_batch_all", 32, 4, 256, "batch_all"),
+         ("c5_batch_all", 64, 4, 512, "batch_all")]
 
 
 def measure(fn, iters):
@@ -73,6 +76,21 @@ def main():
             x.grad = None
             ops.fused_triplet_loss(x, p, k, 0.5, mode, seed=1)[0].backward()
 
+        def batch_all():
+            x.grad = None
+            ops.batch_all_triplet_loss(x, p, k, 0.5)[0].backward()
+
+        def hardest_fused():
+            x.grad = None
+            ops.fused_triplet_loss(x, p, k, 0.5, "hardest", seed=1)[0].backward()
+
+        if mode == "batch_all":                             # batch-all beside the fused `hardest` path, same shape and process
+            row = dict(config=name, N=n, E=e, mining=mode, batch_all=measure(batch_all, a.iters),
+                       hardest_fused=measure(hardest_fused, a.iters))
+            row["device_ratio_vs_hardest"] = round(row["batch_all"]["device_us"] / row["hardest_fused"]["device_us"], 3)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         row = dict(config=name, N=n, E=e, mining=mode, separate=measure(separate, a.iters))
         if ops.fused_loss_supported(p, k, e):
             row["fused"] = measure(fused, a.iters)
