@@ -150,11 +150,21 @@ class TripletsDataGenerator(ENDataGenerator):
 
     def __init__(self, embedding_model, class_files_paths, class_names, n_batches=10, input_shape=None,
                  batch_size=32, augmentations=None, k_classes=5, k_samples=5, margin=0.5,
-                 negatives_selection_mode='semihard'):
+                 negatives_selection_mode='semihard', device_augmentations=None):
+        """device_augmentations: an augment.DeviceAugment applied on the GPU by the feeder (input_pipeline.Feeder) to every
+        training batch it delivers; exclusive with the host `augmentations` callable, file-backed datasets only."""
         super().__init__(class_files_paths=class_files_paths, class_names=class_names, input_shape=input_shape,
                          batch_size=batch_size, n_batches=n_batches, augmentations=augmentations)
         if negatives_selection_mode not in tuple(ops.MINING_MODES) + self.STEP_ONLY_MODES:
             raise KeyError(negatives_selection_mode)
+        if device_augmentations is not None:
+            if augmentations is not None:
+                raise ValueError("TripletsDataGenerator: set either the host `augmentations` callable or "
+                                 "`device_augmentations`, not both")
+            if any(isinstance(v, np.ndarray) for v in class_files_paths.values()):
+                raise ValueError("device_augmentations augment decoded uint8 image files on the GPU; an in-memory float "
+                                 "dataset (--synthetic) has none: drop GENERATOR.device_augmentations")
+        self.device_augmentations = device_augmentations
         self.embedding_model = embedding_model
         self.k_classes, self.k_samples, self.margin = k_classes, k_samples, margin
         self.mode = negatives_selection_mode

@@ -98,11 +98,14 @@ class DeviceImageStore:
     def bytes_needed(class_files_paths, input_shape):
         return sum(len(v) for v in class_files_paths.values()) * int(input_shape[0]) * int(input_shape[1]) * 3
 
-    def batch(self, plan, pad_to=None):
-        """plan = (classes, idxs) as TripletsDataGenerator.sample_plan() draws it -> float32 [P*K, H, W, 3] on the device."""
+    def batch(self, plan, pad_to=None, augment=None):
+        """plan = (classes, idxs) as TripletsDataGenerator.sample_plan() draws it -> float32 [P*K, H, W, 3] on the device;
+        augment (a DeviceAugment): gathered, augmented and converted by its kernel instead."""
         classes, idxs = plan
         rows = np.concatenate([self.first[cl] + np.asarray(ix, np.int64) for cl, ix in zip(classes, idxs)]).astype(np.int32)
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
+        if augment is not None:
+            return augment.apply(self.data, index, len(rows), pad_to=pad_to)
         return u8_to_f32(self.data, index, len(rows), pad_to=pad_to)
 
 
@@ -172,10 +175,12 @@ class BatchPrefetcher:
     sampling stream stays single-threaded and in order); `load_fn(plan, out_u8)` fills a [B, H, W, 3] uint8 array from worker
     threads."""
 
-    def __init__(self, plan_fn, load_fn, batch_shape, device, depth=10, workers=None, paths_fn=None, input_shape=None, rows_per_task=8):
+    def __init__(self, plan_fn, load_fn, batch_shape, device, depth=10, workers=None, paths_fn=None, input_shape=None, rows_per_task=8,
+                 augment=None):
         """paths_fn(plan) -> the batch's file paths in row order (with input_shape): the decode then runs in worker PROCESSES
-        (DecodeProcesses) that fill the staging buffers directly; without it `load_fn(plan, out)` runs on worker threads."""
-        self.plan_fn, self.load_fn = plan_fn, load_fn
+        (DecodeProcesses) that fill the staging buffers directly; without it `load_fn(plan, out)` runs on worker threads.
+        augment (a DeviceAugment): the staged batch is augmented and converted by its kernel instead of u8_to_f32."""
+        self.plan_fn, self.load_fn, self.augment = plan_fn, load_fn, augment
         self.device = torch.device(device)
         self.depth = max(2, int(depth))
         self.shape = tuple(int(v) for v in batch_shape)                # (B, H, W, 3)
@@ -263,7 +268,10 @@ class BatchPrefetcher:
         k, done = self._ahead if self._ahead is not None else self._issue_copy()
         main = torch.cuda.current_stream(self.device)
         main.wait_event(done)
-        out = u8_to_f32(self.staged[k], None, self.shape[0], pad_to=pad_to)
+        if self.augment is not None:
+            out = self.augment.apply(self.staged[k], None, self.shape[0], pad_to=pad_to)
+        else:
+            out = u8_to_f32(self.staged[k], None, self.shape[0], pad_to=pad_to)
         ev = torch.cuda.Event()
         ev.record(main)
         self.read_done[k] = ev
@@ -290,13 +298,17 @@ class BatchPrefetcher:
 
 class Feeder:
     """What tools/train.py steps on: `.next()` -> the next class-contiguous float32 device batch of a TripletsDataGenerator.
-    In-memory float datasets (synthetic): the generator's own batch, copied; files without augmentations that fit
-    `store_budget` bytes: DeviceImageStore; otherwise: BatchPrefetcher."""
+    In-memory float datasets (synthetic): the generator's own batch, copied; files without host augmentations that fit
+    `store_budget` bytes: DeviceImageStore; otherwise: BatchPrefetcher.  The generator's `device_augmentations` (a DeviceAugment)
+    augment every batch on the GPU, on either file path."""
 
     def __init__(self, gen, device, depth=10, workers=None, store_budget=32 << 30, log=None):
         self.gen, self.device = gen, torch.device(device)
         any_src = next(iter(gen.class_files_paths.values()))
         self.kind, self.store, self.prefetch = "memory", None, None
+        self.augment = getattr(gen, "device_augmentations", None)
+        if self.augment is not None and isinstance(any_src, np.ndarray):
+            raise ValueError("device augmentation needs decoded uint8 image files; in-memory float datasets have none")
         if not isinstance(any_src, np.ndarray):
             need = DeviceImageStore.bytes_needed(gen.class_files_paths, gen.input_shape)
             if gen.augmentations is None and need <= store_budget and os.environ.get("EMBNET_IMAGE_STORE", "1") != "0":
@@ -309,13 +321,13 @@ class Feeder:
                 self.kind = "prefetch (worker processes)" if procs else "prefetch (worker threads)"
                 self.prefetch = BatchPrefetcher(gen.sample_plan, gen.load_plan_u8, (b, gen.input_shape[1], gen.input_shape[0], 3),
                                                 device, depth, workers, paths_fn=gen.plan_paths if procs else None,
-                                                input_shape=gen.input_shape)
+                                                input_shape=gen.input_shape, augment=self.augment)
         if log:
             log(f"input pipeline: {self.kind}")
 
     def next(self):
         if self.store is not None:
-            return self.store.batch(self.gen.sample_plan())
+            return self.store.batch(self.gen.sample_plan(), augment=self.augment)
         if self.prefetch is not None:
             return self.prefetch.next()
         return torch.from_numpy(self.gen.sample_batch()).to(self.device)

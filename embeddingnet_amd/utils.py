@@ -5,7 +5,8 @@ section keys; MODEL.input_shape mirrored into GENERATOR and SOFTMAX_PRETRAINING;
 section replaced by an optimizer object; `augmentations` keys set).  One structural difference: Keras
 optimizers are constructed without parameters, ours need them, so the optimizer object is an
 `OptimizerSpec` whose `.build(parameters)` returns the optimizer (embeddingnet_amd/optimizers.py: the
-Keras update rules and defaults, one HIP launch per step).
+Keras update rules and defaults, one HIP launch per step).  GENERATOR keys pass through as written, among them
+`device_augmentations` / `augment_seed` (tools/train.py: on-device augmentation, embeddingnet_amd/augment.py).
 """
 import yaml
 

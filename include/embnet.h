@@ -424,6 +424,41 @@ int embnet_conv2d_wgrad_planes_f32(const void* x_planes, const void* dy_planes, 
 int embnet_u8_to_f32(const void* src, const int32_t* index, int n, long pixels, int c_in, int c_out, float denom, float* dst,
                      void* stream);
 
+/* Device augmentation (csrc/augment.hip): the augmenting form of embnet_u8_to_f32, seeded and reproducible.  Stands in for the
+ * albumentations pipelines of the reference (embedding_net/augmentations.py), which its configs never build.  Additions only:
+ * the ABI version stays 22.
+ * OPS: a host array of n_ops <= 8 records of 8 floats { opcode, p, a0, a1, a2, a3, 0, 0 }; an op fires with probability p:
+ *   1 random_resized_crop  a0, a1 = scale (lo, hi), a2, a3 = ratio (lo, hi): torchvision's rule, 10 attempts, centre fallback
+ *   2 center_crop          a0 = frac of the current box, resized back to h x w
+ *   3 horizontal_flip      4 vertical_flip      5 random_rotate90 (k uniform in 0..3; square images only)
+ *   6 brightness_contrast  a0 = brightness limit, a1 = contrast limit:  v * (1 + U(+-a1)) + U(+-a0) * 255
+ *   7 gamma                a0, a1 = gamma_limit (lo, hi):  255 (v / 255)^(U(lo, hi) / 100)
+ *   8 hue_saturation_value a0, a1, a2 = hue, sat, val shift limits: OpenCV 8-bit float HSV of the BGR pixel (H wraps at 180)
+ *   9 blur                 a0 = blur_limit (1..7): k x k box, odd k uniform in [3, max(3, limit)], reflect-101 borders
+ *  10 gauss_noise          a0, a1 = var_limit (lo, hi): sigma = sqrt(U(lo, hi)), one normal draw per element
+ * Only 6-8 may repeat.  Application order is fixed: geometry (every crop in list order, each inside the previous box, then
+ * rot90, hflip, vflip composed into one output -> source map, bilinear with half-pixel centres and clamped borders; a map
+ * without a crop is integer and reads one texel), the pixel ops 6-8 in list order, blur, noise, then v / 255.f.  Float32 on
+ * the 0..255 scale, clipped to [0, 255] after every op.  Rejected before a launch: n_ops > 8, an unknown opcode, p outside
+ * [0, 1], a repeated non-pixel op, rot90 with h != w, blur_limit > 7, limits out of order, null pointers.
+ * RNG: u(op i, draw j) = top 24 bits of rng_u32(seed, batch_no * 65536 + row, 32 i + j) / 2^24 (csrc/common.h); draw 0
+ *   decides firing (u < p); noise element e = (y w + x) c_in + ch uses b = 2^32 + 2 (e / 2) and + 1 for a Box-Muller pair
+ *   (cos for even e, sin for odd).  A row's values depend on (seed, batch_no, row) only.
+ * TABLE: float32 [n][embnet_augment_param_floats() = 48], 16-byte aligned:
+ *   0-3 crop box x0, y0, w, h in source pixels ((0, 0, w, h) = no crop); 4 hflip; 5 vflip; 6 rot90 k; 7 blur k (0 = off);
+ *   8 noise sigma; 9 noise fired; 10 number of ops fired; 11-15 zero;
+ *   16 + 4 i .. 19 + 4 i, op i: { opcode if it fired else 0, s0, s1, s2 }: rrc (w, h, attempt 1-10 or 0 = fallback),
+ *   center_crop (w, h), rot90 (k), brightness_contrast (alpha, beta), gamma (gamma), hsv (dh, ds, dv), blur (k),
+ *   gauss_noise (sigma, variance); zeros for ops not fired or beyond n_ops.
+ * APPLY: src uint8 [*, h, w, c_in] (1 <= c_in <= 4), index as embnet_u8_to_f32, dst float32 [n, h, w, c_out] (c_out <= 16,
+ *   zero padding), table from embnet_augment_params for the same (n, h, w).  seed and batch_no key the noise.  An image with
+ *   no op fired is bit for bit what embnet_u8_to_f32(denom = 255) writes.  n <= 65535, 4 <= h, w <= 16384. */
+size_t embnet_augment_param_floats(void);
+int embnet_augment_params(const float* ops, int n_ops, uint64_t seed, uint64_t batch_no, int n, int h, int w, float* table,
+                          void* stream);
+int embnet_augment_apply(const void* src, const int32_t* index, int n, int h, int w, int c_in, int c_out, const float* table,
+                         uint64_t seed, uint64_t batch_no, float* dst, void* stream);
+
 /* Dense (backbones.py:35,72,75,114,116; models.py:44): x[m,in], w[in,out], y[m,out].
  * workspace (optional, may be NULL/0): >= embnet_dense_fwd_workspace_bytes lets a forward with few output tiles and a long
  * reduction (simple2's Flatten -> Dense(512): 12 800 x 512 at batch 32) cut K over workgroups (partial slabs + fixed-order

@@ -8,6 +8,9 @@ the fused triplet step of a bench config (c1: simple2 64x64 8x4; c2: ResNet18 22
   prefetch     input_pipeline.BatchPrefetcher: worker PROCESSES decode `depth` batches ahead into a shared, page-locked uint8
                staging array, side-stream copy (prefetch_threads: the same with a thread pool — GIL-bound)
   store        input_pipeline.DeviceImageStore: dataset decoded once, uint8 resident in HBM, one gather+convert kernel per batch
+  store_augmented (--augment PRESET)  the store with device augmentation (embeddingnet_amd/augment.py): the batch is gathered,
+               augmented and converted by the augment kernels; timed in --rounds alternating rounds with the plain store leg,
+               medians reported (--store-only skips the sequential and prefetch legs)
 Prints one JSON object (images/s each, the host core count, decode rate, store build time)."""
 import argparse
 import json
@@ -44,6 +47,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--workers", type=int, default=0)
+    ap.add_argument("--augment", default=None, help="device augmentation preset of the store_augmented leg (e.g. crop_flip)")
+    ap.add_argument("--rounds", type=int, default=3, help="alternating store / store_augmented rounds (with --augment)")
+    ap.add_argument("--store-only", action="store_true", help="skip the sequential and prefetch legs")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     from embeddingnet_amd import backbones as B
@@ -102,6 +108,36 @@ def main():
         return res_pool[tick[0] % len(res_pool)]
     out["resident_images_per_s"], out["resident_ms_per_step"] = timed(cyc)
     seq_steps = max(6, min(args.steps, int(20 * out["decode_images_per_s_one_thread"] / n)))       # ~20 s of it at most
+    if not args.store_only:
+        prefetch_legs(out, timed, gen, IP, n, shape, dev, args, workers, seq_steps)
+    msgs = []
+    store = IP.DeviceImageStore(dl.train_data, dl.class_names, shape, dev, workers=workers, log=msgs.append)
+    out["store_build_s"], out["store_mib"] = round(store.decode_seconds, 2), round(store.data.numel() / 2 ** 20, 1)
+    if args.augment:
+        from embeddingnet_amd.augment import DeviceAugment
+        aug = DeviceAugment.from_config(args.augment, list(shape), seed=0)
+        plain, augd = [], []
+        for _ in range(args.rounds):
+            plain.append(timed(lambda: store.batch(gen.sample_plan())))
+            augd.append(timed(lambda: store.batch(gen.sample_plan(), augment=aug)))
+        out["augment"], out["rounds"] = args.augment, args.rounds
+        out["store_images_per_s_rounds"] = [r[0] for r in plain]
+        out["store_augmented_images_per_s_rounds"] = [r[0] for r in augd]
+        out["store_images_per_s"], out["store_ms_per_step"] = sorted(plain)[len(plain) // 2]
+        out["store_augmented_images_per_s"], out["store_augmented_ms_per_step"] = sorted(augd)[len(augd) // 2]
+        out["store_augmented_over_store"] = round(out["store_augmented_images_per_s"] / out["store_images_per_s"], 4)
+    else:
+        out["store_images_per_s"], out["store_ms_per_step"] = timed(lambda: store.batch(gen.sample_plan()))
+    for key in ("sequential", "prefetch", "store"):
+        if f"{key}_images_per_s" in out:
+            out[f"{key}_over_resident"] = round(out[f"{key}_images_per_s"] / out["resident_images_per_s"], 3)
+    out["step_mode"] = "hip graph" if getattr(trainer, "_graph", None) is not None else "eager"
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+    print(json.dumps(out))
+
+
+def prefetch_legs(out, timed, gen, IP, n, shape, dev, args, workers, seq_steps):
     out["sequential_images_per_s"], out["sequential_ms_per_step"] = timed(lambda: torch.from_numpy(gen.sample_batch()).to(dev),
                                                                           steps=seq_steps, warm=2)
     pf = IP.BatchPrefetcher(gen.sample_plan, gen.load_plan_u8, (n,) + shape, dev, depth=args.depth, workers=workers)
@@ -112,16 +148,6 @@ def main():
     out["prefetch_staging_pinned"] = bool(getattr(pf, "pinned", False))
     out["prefetch_images_per_s"], out["prefetch_ms_per_step"] = timed(pf.next)
     pf.close()
-    msgs = []
-    store = IP.DeviceImageStore(dl.train_data, dl.class_names, shape, dev, workers=workers, log=msgs.append)
-    out["store_build_s"], out["store_mib"] = round(store.decode_seconds, 2), round(store.data.numel() / 2 ** 20, 1)
-    out["store_images_per_s"], out["store_ms_per_step"] = timed(lambda: store.batch(gen.sample_plan()))
-    for key in ("sequential", "prefetch", "store"):
-        out[f"{key}_over_resident"] = round(out[f"{key}_images_per_s"] / out["resident_images_per_s"], 3)
-    out["step_mode"] = "hip graph" if getattr(trainer, "_graph", None) is not None else "eager"
-    import shutil
-    shutil.rmtree(tmp, ignore_errors=True)
-    print(json.dumps(out))
 
 
 if __name__ == "__main__":

@@ -119,9 +119,27 @@ def apply_gpu_ids(gpu_ids):
         sys.exit(launch.spawn(len(ids), [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
 
 
+def device_augmentations(cfg, synthetic=0, rank=0):
+    """GENERATOR.device_augmentations (a preset name, an op list or 'none'; embeddingnet_amd/augment.py) -> the DeviceAugment
+    of this rank's triplet training batches, or None.  Seeded from GENERATOR.augment_seed (default 0) mixed with the rank, so
+    that data-parallel ranks draw differently.  Validation and encodings are never augmented; the softmax pre-training does
+    not read the key.  Refused (ValueError) with --synthetic (no uint8 images to augment) and in Siamese mode."""
+    from embeddingnet_amd.augment import DeviceAugment, rank_seed
+    value = cfg['generator'].get('device_augmentations')
+    aug = DeviceAugment.from_config(value, cfg['model']['input_shape'],
+                                    rank_seed(cfg['generator'].get('augment_seed', 0), rank))
+    if aug is not None and cfg['model']['mode'] == 'siamese':
+        raise ValueError("GENERATOR.device_augmentations applies to triplet training batches; Siamese mode has none")
+    if aug is not None and synthetic:
+        raise ValueError("GENERATOR.device_augmentations augments decoded image files on the GPU; --synthetic datasets are "
+                         "in-memory float arrays: drop the key or train on files")
+    return aug
+
+
 def main():
     args = parse_args()
     cfg = parse_params(args.config)
+    device_augmentations(cfg, args.synthetic)          # a bad GENERATOR.device_augmentations fails before the GPU is touched
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
     paths = create_save_folders(cfg['general'])
@@ -143,7 +161,7 @@ def main():
     else:
         data_loader = ENDataLoader(**{k: v for k, v in p_loader.items() if k != 'csv_file'})
     monitor = 'val_loss' if data_loader.validate else 'loss'
-    gen_kw = {k: v for k, v in p_gen.items()}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -158,7 +176,8 @@ def main():
         if world > 1:                                 # whole classes per rank, mining stays local
             _, gen_kw['k_classes'] = shard_classes(p_gen['k_classes'], world, rank)
         train_gen = TripletsDataGenerator(embedding_model=model.base_model, class_files_paths=data_loader.train_data,
-                                          class_names=data_loader.class_names, **gen_kw)
+                                          class_names=data_loader.class_names, **gen_kw,
+                                          device_augmentations=device_augmentations(cfg, args.synthetic, rank))
         val_gen = SimpleTripletsDataGenerator(data_loader.val_data, data_loader.class_names,
                                               **gen_kw) if data_loader.validate else None
         trainable = model.base_model
