@@ -20,10 +20,16 @@ Ops (name: parameters, defaults):
     hue_saturation_value  p=0.5, hue_shift_limit=20, sat_shift_limit=30, val_shift_limit=20   (3-channel BGR images)
     blur                  p=0.5, blur_limit=7                         box, odd k in [3, max(3, blur_limit)], blur_limit <= 7
     gauss_noise           p=0.5, var_limit=(10, 50)
-Geometry runs first, then the pixel ops in list order, then blur, then noise (include/embnet.h has the exact rules).
+    clahe                 p=0.5, clip_limit=(1, 4), tile_grid_size=(8, 8)   OpenCV's CLAHE on the gray value or on L* of the BGR
+                                                                            pixel; a scalar clip_limit c is (1, c); grid
+                                                                            (columns, rows), each in 1..16; at most one clahe
+Geometry runs first, then the pixel ops in list order (clahe among them, where it is listed), then blur, then noise
+(include/embnet.h has the exact rules).  CLAHE needs every tile's histogram first, so a pipeline with it runs three kernels
+(parameters, LUTs, apply) instead of two; it keeps out of the 8 op slots, so every other op draws the same with or without it.
 
-Presets mirror the reference's pipelines.  CLAHE (in `default` and `plates2`) is not implemented and is left out of both;
-`plates` is refused: its RandomCrop returns 2/3-size images, which cannot form a batch of input_shape.
+Presets mirror the reference's pipelines.  `default` and `plates2` leave the reference's CLAHE out (runs and tests pin them);
+`default_clahe` and `plates2_clahe` are the reference's full pipelines.  `plates` is refused: its RandomCrop returns 2/3-size
+images, which cannot form a batch of input_shape.
 """
 import numpy as np
 import torch
@@ -32,7 +38,7 @@ from . import _lib
 from ._lib import check, ptr, stream
 
 OPCODES = {"random_resized_crop": 1, "center_crop": 2, "horizontal_flip": 3, "vertical_flip": 4, "random_rotate90": 5,
-           "brightness_contrast": 6, "gamma": 7, "hue_saturation_value": 8, "blur": 9, "gauss_noise": 10}
+           "brightness_contrast": 6, "gamma": 7, "hue_saturation_value": 8, "blur": 9, "gauss_noise": 10, "clahe": 11}
 # op -> (default p, [(parameter, default)]); a tuple-valued parameter fills two record fields
 _PARAMS = {
     "random_resized_crop": (1.0, [("scale", (0.08, 1.0)), ("ratio", (3 / 4, 4 / 3))]),
@@ -45,9 +51,11 @@ _PARAMS = {
     "hue_saturation_value": (0.5, [("hue_shift_limit", 20.0), ("sat_shift_limit", 30.0), ("val_shift_limit", 20.0)]),
     "blur": (0.5, [("blur_limit", 7)]),
     "gauss_noise": (0.5, [("var_limit", (10.0, 50.0))]),
+    "clahe": (0.5, [("clip_limit", (1.0, 4.0)), ("tile_grid_size", (8, 8))]),
 }
 GEOMETRY = ("random_resized_crop", "center_crop", "horizontal_flip", "vertical_flip", "random_rotate90")
 MAX_OPS, RECORD = 8, 8
+MAX_CLAHE_GRID = 16
 
 PRESETS = {
     "deepfake": [("horizontal_flip", {"p": 0.5})],
@@ -71,6 +79,11 @@ PRESETS = {
     "crop_flip": [("random_resized_crop", {"p": 1.0, "scale": (0.16, 1.0), "ratio": (3 / 4, 4 / 3)}),
                   ("horizontal_flip", {"p": 0.5})],
 }
+# the reference's full pipelines: `default` with its CLAHE(p=0.4) after HSV, `plates2` with its CLAHE(clip_limit=(1, 4), p=0.3)
+# first among the pixel ops (after the geometry, which runs first anyway)
+PRESETS["default_clahe"] = PRESETS["default"][:3] + [("clahe", {"p": 0.4, "clip_limit": (1, 4), "tile_grid_size": (8, 8)})] + \
+    PRESETS["default"][3:]
+PRESETS["plates2_clahe"] = [("clahe", {"p": 0.3, "clip_limit": (1, 4), "tile_grid_size": (8, 8)})] + PRESETS["plates2"]
 
 
 def _normalise(ops):
@@ -96,6 +109,25 @@ def _normalise(ops):
     return out
 
 
+def _clip_limit(v):
+    """clahe's clip_limit: a scalar c is (1, c) as in albumentations (sorted), a pair (lo, hi) needs 0 < lo <= hi."""
+    lo, hi = (min(1.0, float(v)), max(1.0, float(v))) if np.isscalar(v) else (float(v[0]), float(v[1]))
+    if not (0 < lo <= hi < float("inf")):
+        raise ValueError(f"device augmentation: clahe clip_limit={v!r} (0 < lo <= hi)")
+    return (lo, hi)
+
+
+def _grid(v):
+    """clahe's tile_grid_size (columns, rows): integers in 1..16."""
+    try:
+        gx, gy = v
+    except (TypeError, ValueError):
+        raise ValueError(f"device augmentation: clahe tile_grid_size={v!r} (a pair (columns, rows))") from None
+    if not all(float(g) == int(g) and 1 <= int(g) <= MAX_CLAHE_GRID for g in (gx, gy)):
+        raise ValueError(f"device augmentation: clahe tile_grid_size={v!r} (integers in 1..{MAX_CLAHE_GRID})")
+    return (int(gx), int(gy))
+
+
 def _record(name, kw):
     rec = [float(OPCODES[name]), float(kw["p"])]
     for key, _ in _PARAMS[name][1]:
@@ -111,20 +143,35 @@ class DeviceAugment:
 
     def __init__(self, ops, seed=0):
         self.ops = _normalise(ops)
-        if len(self.ops) > MAX_OPS:
-            raise ValueError(f"device augmentation: {len(self.ops)} ops (at most {MAX_OPS})")
+        names = [n for n, _ in self.ops]
+        if names.count("clahe") > 1:
+            raise ValueError(f"device augmentation: {names.count('clahe')} clahe ops (at most one)")
+        # CLAHE keeps out of the op slots: its record and position (the number of other ops before it) are kept apart, and
+        # `records` is what the list without it gives
+        self.clahe, self.clahe_pos = None, 0
+        if "clahe" in names:
+            self.clahe_pos = names.index("clahe")
+            kw = self.ops[self.clahe_pos][1]
+            kw["clip_limit"] = _clip_limit(kw["clip_limit"])
+            kw["tile_grid_size"] = _grid(kw["tile_grid_size"])
+            self.clahe = np.float32(_record("clahe", kw))
+        base = [(n, kw) for n, kw in self.ops if n != "clahe"]
+        if len(base) > MAX_OPS:
+            raise ValueError(f"device augmentation: {len(base)} ops (at most {MAX_OPS}, plus one clahe)")
         for name, kw in self.ops:
             if not 0.0 <= kw["p"] <= 1.0:
                 raise ValueError(f"device augmentation: {name} p={kw['p']} outside [0, 1]")
             if name == "blur" and not 1 <= kw["blur_limit"] <= 7:
                 raise ValueError(f"device augmentation: blur_limit={kw['blur_limit']} (1..7; the box filter is at most 7x7)")
-        self.records = np.zeros((max(1, len(self.ops)), RECORD), np.float32)
-        for i, (name, kw) in enumerate(self.ops):
+        self.n_ops = len(base)
+        self.records = np.zeros((max(1, len(base)), RECORD), np.float32)
+        for i, (name, kw) in enumerate(base):
             self.records[i] = _record(name, kw)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.batch_no = 0
         self.hw = None
         self._table = None
+        self._luts = None
 
     @classmethod
     def from_config(cls, value, input_shape, seed=0):
@@ -149,7 +196,19 @@ class DeviceAugment:
             raise ValueError(f"device augmentation: random_rotate90 needs square images (got {h}x{w})")
         if "hue_saturation_value" in names and c != 3:
             raise ValueError(f"device augmentation: hue_saturation_value needs 3-channel BGR images (got {c} channels)")
+        if self.clahe is not None:
+            if c not in (1, 3):
+                raise ValueError(f"device augmentation: clahe needs 1-channel or 3-channel BGR images (got {c} channels)")
+            gx, gy = self.grid
+            if 2 * gx > w or 2 * gy > h:
+                raise ValueError(f"device augmentation: clahe tile_grid_size=({gx}, {gy}) too large for {h}x{w} images "
+                                 f"(2 * columns <= width, 2 * rows <= height)")
         self.hw = (h, w)
+
+    @property
+    def grid(self):
+        """CLAHE's tile grid (columns, rows), or None without clahe."""
+        return None if self.clahe is None else (int(self.clahe[4]), int(self.clahe[5]))
 
     def params(self, n, batch_no, hw=None):
         """The parameter table [n, embnet_augment_param_floats()] of batch `batch_no` on the current device (tests, debugging)."""
@@ -158,9 +217,40 @@ class DeviceAugment:
         if self._table is None or self._table.shape[0] < n or self._table.device != torch.device("cuda", torch.cuda.current_device()):
             self._table = torch.empty((max(n, 128), f), device="cuda", dtype=torch.float32)
         table = self._table[:n]
-        check(_lib.lib().embnet_augment_params(self.records.ctypes.data, len(self.ops), self.seed, int(batch_no), n, h, w,
-                                               ptr(table), stream()))
+        if self.clahe is None:
+            check(_lib.lib().embnet_augment_params(self.records.ctypes.data, self.n_ops, self.seed, int(batch_no), n, h, w,
+                                                   ptr(table), stream()))
+        else:
+            check(_lib.lib().embnet_augment_params_clahe(self.records.ctypes.data, self.n_ops, self.clahe.ctypes.data,
+                                                         self.clahe_pos, self.seed, int(batch_no), n, h, w, ptr(table), stream()))
         return table
+
+    def _lut_buffer(self, n, device):
+        """CLAHE's LUTs uint8 [n, gy, gx, 256]: a buffer kept like the parameter table (reused call after call on the current
+        stream; kernels on one stream run in order, so a call's LUTs are read before the next call writes them)."""
+        gx, gy = self.grid
+        if self._luts is None or self._luts.shape[0] < n or self._luts.device != device:
+            self._luts = torch.empty((max(n, 128), gy, gx, 256), device=device, dtype=torch.uint8)
+        return self._luts[:n]
+
+    def _clahe_luts(self, src_u8, index, n, table):
+        _, h, w, c = src_u8.shape
+        gx, gy = self.grid
+        luts = self._lut_buffer(n, src_u8.device)
+        check(_lib.lib().embnet_augment_clahe_luts(ptr(src_u8), ptr(index), n, h, w, c, gx, gy, ptr(table), ptr(luts), stream()))
+        return luts
+
+    def clahe_luts(self, src_u8, index, n, batch_no):
+        """CLAHE's LUTs uint8 [n, gy, gx, 256] of batch `batch_no` (tests, debugging): zeros for the rows where CLAHE did not
+        fire.  A view of the buffer the next call overwrites."""
+        if self.clahe is None:
+            raise ValueError("device augmentation: clahe_luts() needs a pipeline with clahe")
+        _, h, w, c = src_u8.shape
+        if self.hw != (h, w):
+            self.check_shape(h, w, c)
+        table = self.params(n, batch_no, (h, w))
+        self._lut_buffer(n, src_u8.device).zero_()
+        return self._clahe_luts(src_u8, index, n, table)
 
     def apply(self, src_u8, index, n, batch_no=None, out=None, pad_to=None):
         """float32 [n, H, W, C'] = augment(src_u8[index or :n]) / 255 on the device.  Batch `batch_no`, or the next of this
@@ -175,8 +265,14 @@ class DeviceAugment:
         if out is None:
             out = torch.empty((n, h, w, c_out), device=src_u8.device, dtype=torch.float32)
         table = self.params(n, batch_no, (h, w))
-        check(_lib.lib().embnet_augment_apply(ptr(src_u8), ptr(index), n, h, w, c, c_out, ptr(table), self.seed, int(batch_no),
-                                              ptr(out), stream()))
+        if self.clahe is None:
+            check(_lib.lib().embnet_augment_apply(ptr(src_u8), ptr(index), n, h, w, c, c_out, ptr(table), self.seed,
+                                                  int(batch_no), ptr(out), stream()))
+        else:
+            luts = self._clahe_luts(src_u8, index, n, table)
+            gx, gy = self.grid
+            check(_lib.lib().embnet_augment_apply_clahe(ptr(src_u8), ptr(index), n, h, w, c, c_out, ptr(table), ptr(luts), gx, gy,
+                                                        self.seed, int(batch_no), ptr(out), stream()))
         return out
 
     def __repr__(self):

@@ -11,6 +11,14 @@
 //                          geometry (one output -> source map, bilinear), the per-pixel ops in list order, an optional k x k box
 //                          blur over an LDS tile with its halo, Gaussian noise, then v / 255.f.  Float32 on the 0..255 scale,
 //                          clipped to [0, 255] after every op, no rounding between ops.
+// CLAHE (OpenCV's contrast-limited adaptive histogram equalisation) needs the histogram of every tile of the image as it stands
+// before it, so it adds a kernel and keeps out of the 8 op slots:
+//   augment_params_clahe_kernel  the parameter row above, then the CLAHE draws (RNG op index 8) into fields 10-14
+//   augment_clahe_lut_kernel     one workgroup per (tile, image): recomputes geometry + the pixel ops before CLAHE for the
+//                                tile's pixels, counts their bins in per-wave LDS histograms, and one wave turns the histogram
+//                                into the tile's 256 LUT bytes
+//   augment_apply_kernel<..., CLAHE = true>  (traced as augment_apply_clahe_kernel) the apply kernel with the CLAHE stage
+//                                between the pixel ops before and after it
 // The table layout, the op records and the RNG counters are documented in include/embnet.h ("Device augmentation").
 #include "common.h"
 #include "../../include/embnet.h"
@@ -23,16 +31,18 @@ constexpr int AUG_REC = 8;           // floats per op record: opcode, p, four pa
 constexpr int AUG_TILE = 32;         // output tile edge
 constexpr int AUG_HALO = 3;          // blur k <= 7
 constexpr int AUG_LT = AUG_TILE + 2 * AUG_HALO;   // 38: LDS tile edge with the halo
-constexpr uint64_t AUG_NOISE_B0 = 1ull << 32;     // first RNG counter `b` of the noise draws (parameter draws use b < 256)
+constexpr uint64_t AUG_NOISE_B0 = 1ull << 32;     // first RNG counter `b` of the noise draws (parameter draws use b < 258)
+constexpr int AUG_CLAHE_OP = AUG_MAX_OPS;         // RNG op index of the CLAHE draws (b = 256, 257): no slot uses it
+constexpr int AUG_CLAHE_MAX_GRID = 16;
 
 enum : int {
   AUG_RRC = 1, AUG_CENTER_CROP = 2, AUG_HFLIP = 3, AUG_VFLIP = 4, AUG_ROT90 = 5,
-  AUG_BRIGHTNESS_CONTRAST = 6, AUG_GAMMA = 7, AUG_HSV = 8, AUG_BLUR = 9, AUG_GAUSS_NOISE = 10,
+  AUG_BRIGHTNESS_CONTRAST = 6, AUG_GAMMA = 7, AUG_HSV = 8, AUG_BLUR = 9, AUG_GAUSS_NOISE = 10, AUG_CLAHE = 11,
 };
 // table fields
 enum : int {
   T_X0 = 0, T_Y0 = 1, T_CW = 2, T_CH = 3, T_HFLIP = 4, T_VFLIP = 5, T_ROT = 6, T_BLUR_K = 7, T_NOISE_SIGMA = 8,
-  T_NOISE_ON = 9, T_FIRED = 10, T_SLOTS = 16,
+  T_NOISE_ON = 9, T_FIRED = 10, T_CLAHE_CLIP = 11, T_CLAHE_POS = 12, T_CLAHE_GX = 13, T_CLAHE_GY = 14, T_SLOTS = 16,
 };
 
 struct AugOps {
@@ -139,6 +149,39 @@ __global__ __launch_bounds__(256) void augment_params_kernel(AugOps ops, uint64_
   if (row < n) augment_params_row(ops, seed, batch_no, row, h, w, table);
 }
 
+// The CLAHE record { AUG_CLAHE, p, clip lo, clip hi, gx, gy, 0, 0 } (checked on the host) and pos, the number of other ops
+// listed before it.
+struct AugClahe {
+  float p, lo, hi;
+  int gx, gy, pos;
+};
+
+// CLAHE's draws for a row that augment_params_row has written (host and device).  Fields 10-14 change only when it fires, so a
+// row where it did not is, bit for bit, the row of the list without it.
+__host__ __device__ inline void augment_clahe_row(const AugClahe& c, uint64_t seed, uint64_t batch_no, int row,
+                                                  float* __restrict__ table) {
+#pragma clang fp contract(off)
+  const uint64_t a = batch_no * 65536ull + (uint64_t)row;
+  const uint64_t key = mix64(seed ^ (a * 0xD6E8FEB86659FD93ull));
+  auto draw = [&](int j) { return (uint32_t)(mix64(key + (uint64_t)(32 * AUG_CLAHE_OP + j)) >> 32); };
+  if (!(unit24(draw(0)) < c.p)) return;
+  float* trow = table + (long)row * AUG_F;
+  trow[T_FIRED] += 1.f;
+  trow[T_CLAHE_CLIP] = c.lo + (c.hi - c.lo) * unit24(draw(1));
+  trow[T_CLAHE_POS] = (float)c.pos;
+  trow[T_CLAHE_GX] = (float)c.gx;
+  trow[T_CLAHE_GY] = (float)c.gy;
+}
+
+__global__ __launch_bounds__(256) void augment_params_clahe_kernel(AugOps ops, AugClahe clahe, uint64_t seed, uint64_t batch_no,
+                                                                   int n, int h, int w, float* __restrict__ table) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row < n) {
+    augment_params_row(ops, seed, batch_no, row, h, w, table);
+    augment_clahe_row(clahe, seed, batch_no, row, table);
+  }
+}
+
 __device__ __forceinline__ float clip255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
 
 // OpenCV's float HSV with 8-bit ranges (H in [0, 180), S and V in [0, 255]) on a BGR pixel, shifted, and back
@@ -167,6 +210,92 @@ __device__ __forceinline__ void hsv_shift(float& b, float& g, float& r, float dh
   else if (k == 4) { rr = u; gg = p; bb = val; }
   else { rr = val; gg = p; bb = q; }
   b = clip255(bb); g = clip255(gg); r = clip255(rr);
+}
+
+// OpenCV's float Lab (D65 white Xn = 0.950456, Zn = 1.088754) of a BGR pixel on the 0..255 scale, with the sRGB companding
+// formula: l8 = L* 255 / 100, la = a*, lb = b*.  (OpenCV's float path interpolates the companding from a table; the formula is
+// the definition here.)
+constexpr float LAB_T = 0.008856f, LAB_K = 7.787f, LAB_B = 16.f / 116.f, LAB_KAPPA = 903.3f;
+__device__ __forceinline__ float srgb_to_linear(float c) { return c <= 0.04045f ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f); }
+__device__ __forceinline__ float linear_to_srgb(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.f / 2.4f) - 0.055f; }
+__device__ __forceinline__ float lab_f(float t) { return t > LAB_T ? cbrtf(t) : LAB_K * t + LAB_B; }
+__device__ __forceinline__ float lab_f_inv(float f) { return f <= LAB_K * LAB_T + LAB_B ? (f - LAB_B) / LAB_K : f * f * f; }
+
+__device__ __forceinline__ void bgr_to_lab(const float* v, float& l8, float& la, float& lb) {
+#pragma clang fp contract(off)
+  const float b = srgb_to_linear(v[0] / 255.f), g = srgb_to_linear(v[1] / 255.f), r = srgb_to_linear(v[2] / 255.f);
+  const float x = (float)(0.412453 / 0.950456) * r + (float)(0.357580 / 0.950456) * g + (float)(0.180423 / 0.950456) * b;
+  const float y = 0.212671f * r + 0.715160f * g + 0.072169f * b;
+  const float z = (float)(0.019334 / 1.088754) * r + (float)(0.119193 / 1.088754) * g + (float)(0.950227 / 1.088754) * b;
+  const float fx = lab_f(x), fy = lab_f(y), fz = lab_f(z);
+  l8 = (y > LAB_T ? 116.f * fy - 16.f : LAB_KAPPA * y) * (255.f / 100.f);
+  la = 500.f * (fx - fy);
+  lb = 200.f * (fy - fz);
+}
+
+// ... and back: L* (0..100), a*, b* -> BGR on the 0..255 scale (linear values clipped to [0, 1] before the companding)
+__device__ __forceinline__ void lab_to_bgr(float l, float la, float lb, float* v) {
+#pragma clang fp contract(off)
+  float y, fy;
+  if (l <= LAB_T * LAB_KAPPA) { y = l / LAB_KAPPA; fy = LAB_K * y + LAB_B; }
+  else { fy = (l + 16.f) / 116.f; y = fy * fy * fy; }
+  const float x = lab_f_inv(la / 500.f + fy) * 0.950456f, z = lab_f_inv(fy - lb / 200.f) * 1.088754f;
+  const float r = 3.240479f * x - 1.53715f * y - 0.498535f * z;
+  const float g = -0.969256f * x + 1.875991f * y + 0.041556f * z;
+  const float b = 0.055648f * x - 0.204043f * y + 1.057311f * z;
+  v[0] = clip255(255.f * linear_to_srgb(fminf(fmaxf(b, 0.f), 1.f)));
+  v[1] = clip255(255.f * linear_to_srgb(fminf(fmaxf(g, 0.f), 1.f)));
+  v[2] = clip255(255.f * linear_to_srgb(fminf(fmaxf(r, 0.f), 1.f)));
+}
+
+// The value CLAHE equalises, on the 0..255 scale: the gray value, or L* 255 / 100 of the BGR pixel (la, lb: its a*, b*)
+template <int CI>
+__device__ __forceinline__ float clahe_value(const float* v, float& la, float& lb) {
+  if (CI == 3) {
+    float l8;
+    bgr_to_lab(v, l8, la, lb);
+    return l8;
+  }
+  la = lb = 0.f;
+  return v[0];
+}
+__device__ __forceinline__ int clahe_bin(float l8) { return (int)rintf(fminf(fmaxf(l8, 0.f), 255.f)); }
+
+// OpenCV pads an image whose w % gx or h % gy is non-zero on BOTH axes (bottom / right, reflect-101) by g - size % g pixels, so
+// an axis that divides evenly gains a full g; the tiles are then padded_w / gx x padded_h / gy.
+__host__ __device__ __forceinline__ void clahe_tile(int h, int w, int gx, int gy, int& tw, int& th) {
+  const bool pad = w % gx != 0 || h % gy != 0;
+  tw = (pad ? w + gx - w % gx : w) / gx;
+  th = (pad ? h + gy - h % gy : h) / gy;
+}
+
+// Per-image constants of the CLAHE stage (one image per workgroup)
+struct AugClaheImage {
+  const unsigned char* lut;          // this image's LUTs [gy][gx][256]
+  int on, pos, gx, gy;
+  float inv_tw, inv_th;
+};
+
+// The CLAHE stage on one pixel at output (y, x): OpenCV's bilinear blend of the four nearest tiles' LUTs at the pixel's bin,
+// kept as a float; for BGR put back as L* with the pixel's own a*, b*.
+template <int CI>
+__device__ __forceinline__ void aug_clahe(const AugClaheImage& c, int y, int x, float* v) {
+#pragma clang fp contract(off)
+  float la, lb;
+  const int bin = clahe_bin(clahe_value<CI>(v, la, lb));
+  const float txf = (float)x * c.inv_tw - 0.5f, tyf = (float)y * c.inv_th - 0.5f;
+  int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
+  const float xa = txf - (float)tx1, ya = tyf - (float)ty1;
+  const int tx2 = min(tx1 + 1, c.gx - 1), ty2 = min(ty1 + 1, c.gy - 1);
+  tx1 = min(max(tx1, 0), c.gx - 1);            // (the upper clamp only matters for the unwritten pixels past the image)
+  ty1 = min(max(ty1, 0), c.gy - 1);
+  const unsigned char* l1 = c.lut + ty1 * c.gx * 256 + bin;
+  const unsigned char* l2 = c.lut + ty2 * c.gx * 256 + bin;
+  const float xa1 = 1.f - xa, ya1 = 1.f - ya;
+  const float res = ((float)l1[tx1 * 256] * xa1 + (float)l1[tx2 * 256] * xa) * ya1 +
+                    ((float)l2[tx1 * 256] * xa1 + (float)l2[tx2 * 256] * xa) * ya;
+  if (CI == 3) lab_to_bgr(res * (100.f / 255.f), la, lb, v);
+  else v[0] = res;
 }
 
 // Per-image constants of the apply kernel, read once from the table row (scalar loads: one image per workgroup).
@@ -214,10 +343,11 @@ __device__ __forceinline__ void aug_geometry(const unsigned char* __restrict__ s
   }
 }
 
-// Step 2 on NP pixels: the per-pixel ops of the table's slots in list order (slot opcode 0: did not fire / not a pixel op).
+// Step 2 on NP pixels: the per-pixel ops of the table's slots [i0, i1) in list order (slot opcode 0: did not fire / not a pixel
+// op).  CLAHE splits the slots at its position.
 template <int CI, int NP>
-__device__ __forceinline__ void aug_pixel_ops(const float* __restrict__ tp, float (&v)[NP][CI]) {
-  for (int i = 0; i < AUG_MAX_OPS; ++i) {
+__device__ __forceinline__ void aug_pixel_ops(const float* __restrict__ tp, float (&v)[NP][CI], int i0 = 0, int i1 = AUG_MAX_OPS) {
+  for (int i = i0; i < i1; ++i) {
     const int code = (int)tp[T_SLOTS + 4 * i];
     const float a0 = tp[T_SLOTS + 4 * i + 1], a1 = tp[T_SLOTS + 4 * i + 2], a2 = tp[T_SLOTS + 4 * i + 3];
     if (code == AUG_BRIGHTNESS_CONTRAST) {
@@ -257,12 +387,40 @@ __device__ __forceinline__ void noise_pair(uint64_t key, uint64_t e_even, float&
 
 __device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
+// The per-image constants for the CLAHE LUT kernel: the same loads as augment_apply_kernel's, which keeps its own inline copy so
+// that its instantiations without CLAHE compile to the code they compiled to before CLAHE was added.
+__device__ __forceinline__ AugImage aug_image(const float* __restrict__ tp, int h, int w) {
+  AugImage g;
+  g.x0 = tp[T_X0]; g.y0 = tp[T_Y0]; g.cw = tp[T_CW]; g.ch = tp[T_CH];
+  g.hflip = tp[T_HFLIP] != 0.f; g.vflip = tp[T_VFLIP] != 0.f; g.rot = h == w ? ((int)tp[T_ROT] & 3) : 0;   // (never off the image)
+  g.blur_k = (int)tp[T_BLUR_K]; g.noise_on = tp[T_NOISE_ON] != 0.f; g.sigma = tp[T_NOISE_SIGMA];
+  g.crop = !(g.x0 == 0.f && g.y0 == 0.f && g.cw == (float)w && g.ch == (float)h);
+  return g;
+}
+
+// Step 2 with the CLAHE stage at the pixels' output coordinates (c.on: CLAHE fired for this image)
+template <int CI, int NP>
+__device__ __forceinline__ void aug_pixel_stage(const float* __restrict__ tp, const AugClaheImage& c, const int (&ys)[NP],
+                                                const int (&xs)[NP], float (&v)[NP][CI]) {
+  if (c.on) {
+    aug_pixel_ops<CI, NP>(tp, v, 0, c.pos);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) aug_clahe<CI>(c, ys[p], xs[p], v[p]);
+    aug_pixel_ops<CI, NP>(tp, v, c.pos, AUG_MAX_OPS);
+  } else {
+    aug_pixel_ops<CI, NP>(tp, v);
+  }
+}
+
 // One workgroup of 256 threads per 32 x 32 output tile; thread t owns the 4 pixels (ty + t / 8, tx + 4 (t % 8) + 0..3).
-// VEC: W % 4 == 0 and 16-byte aligned dst: the 4 pixels' CO channels leave as CO float4 stores.
-template <int CI, int CO, bool VEC>
+// VEC: W % 4 == 0 and 16-byte aligned dst: the 4 pixels' CO channels leave as CO float4 stores.  CLAHE: the CLAHE stage is
+// compiled in (embnet_augment_apply_clahe, traced as augment_apply_clahe_kernel); without it luts, gx and gy are unused and the
+// kernel is the one embnet_augment_apply has always launched.
+template <int CI, int CO, bool VEC, bool CLAHE>
 __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char* __restrict__ src, const int* __restrict__ index,
                                                             int h, int w, int c_out_rt, const float* __restrict__ table,
-                                                            uint64_t seed, uint64_t batch_no, float* __restrict__ dst) {
+                                                            uint64_t seed, uint64_t batch_no, float* __restrict__ dst,
+                                                            const unsigned char* __restrict__ luts, int gx, int gy) {
   __shared__ float lds[CI][AUG_LT][AUG_LT + 1];
   const int img = blockIdx.y;
   const int tiles_x = (w + AUG_TILE - 1) / AUG_TILE;
@@ -273,6 +431,18 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char*
   g.hflip = tp[T_HFLIP] != 0.f; g.vflip = tp[T_VFLIP] != 0.f; g.rot = h == w ? ((int)tp[T_ROT] & 3) : 0;   // (never off the image)
   g.blur_k = (int)tp[T_BLUR_K]; g.noise_on = tp[T_NOISE_ON] != 0.f; g.sigma = tp[T_NOISE_SIGMA];
   g.crop = !(g.x0 == 0.f && g.y0 == 0.f && g.cw == (float)w && g.ch == (float)h);
+  AugClaheImage c{};
+  if constexpr (CLAHE) {
+    c.on = tp[T_CLAHE_CLIP] != 0.f;
+    c.pos = min(max((int)tp[T_CLAHE_POS], 0), AUG_MAX_OPS);
+    c.gx = gx;
+    c.gy = gy;
+    int tw, th;
+    clahe_tile(h, w, gx, gy, tw, th);
+    c.inv_tw = 1.f / (float)tw;
+    c.inv_th = 1.f / (float)th;
+    c.lut = luts + (long)img * gy * gx * 256;
+  }
   const unsigned char* s = src + (index ? (long)index[img] : (long)img) * h * w * CI;
   const int c_out = CO > 0 ? CO : c_out_rt;
   float* d = dst + (long)img * h * w * c_out;
@@ -287,7 +457,8 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char*
       float u[1][CI];
       if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
         aug_geometry<CI>(s, g, h, w, yy, xx, u[0]);
-        aug_pixel_ops<CI, 1>(tp, u);
+        if constexpr (CLAHE) aug_pixel_stage<CI, 1>(tp, c, {yy}, {xx}, u);   // (a halo pixel gets CLAHE at its reflected coordinates)
+        else aug_pixel_ops<CI, 1>(tp, u);
       } else {                                   // beyond the reflection (only past a partial tile's far edge): never read
 #pragma unroll
         for (int j = 0; j < CI; ++j) u[0][j] = 0.f;
@@ -322,7 +493,8 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char*
         for (int j = 0; j < CI; ++j) v[p][j] = 0.f;
       }
     }
-    aug_pixel_ops<CI, 4>(tp, v);
+    if constexpr (CLAHE) aug_pixel_stage<CI, 4>(tp, c, {oy, oy, oy, oy}, {ox0, ox0 + 1, ox0 + 2, ox0 + 3}, v);
+    else aug_pixel_ops<CI, 4>(tp, v);
   }
   if (oy >= h) return;
   if (g.noise_on) {
@@ -361,6 +533,69 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char*
       for (int j = CI; j < c_out; ++j) o[j] = 0.f;
     }
   }
+}
+
+// One workgroup of 256 threads (4 waves) per (tile, image): the tile's pixels of the padded image through geometry and the pixel
+// ops before CLAHE (the apply kernel's device code), their bins counted in one LDS histogram per wave (integer adds: the same
+// counts every run; per wave, so a flat tile's pixels do not all queue on one address), then wave 0 sums the four, clips,
+// redistributes, scans and writes the tile's 256 LUT bytes, one 32-bit word per lane.  OpenCV's CLAHE_CalcLut_Body.
+template <int CI>
+__global__ __launch_bounds__(256) void augment_clahe_lut_kernel(const unsigned char* __restrict__ src, const int* __restrict__ index,
+                                                                int h, int w, int gx, int gy, const float* __restrict__ table,
+                                                                unsigned char* __restrict__ luts) {
+  __shared__ int hist[4][256];
+  const int img = blockIdx.y, tx = (int)blockIdx.x % gx, ty = (int)blockIdx.x / gx;
+  const float* tp = table + (long)img * AUG_F;
+  const float clip_f = tp[T_CLAHE_CLIP];
+  if (clip_f == 0.f) return;                         // CLAHE did not fire for this image (uniform over the workgroup)
+  for (int i = threadIdx.x; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0;
+  __syncthreads();
+  const AugImage g = aug_image(tp, h, w);
+  const int pos = min(max((int)tp[T_CLAHE_POS], 0), AUG_MAX_OPS);
+  const unsigned char* s = src + (index ? (long)index[img] : (long)img) * h * w * CI;
+  int tw, th;
+  clahe_tile(h, w, gx, gy, tw, th);
+  int* my = hist[threadIdx.x / 64];
+  for (int q = threadIdx.x; q < tw * th; q += 256) {
+    const int py = ty * th + q / tw, px = tx * tw + q % tw;
+    const int yy = py < h ? py : 2 * h - 2 - py, xx = px < w ? px : 2 * w - 2 - px;     // the reflect-101 pad (< h, w)
+    float u[1][CI], la, lb;
+    aug_geometry<CI>(s, g, h, w, yy, xx, u[0]);
+    aug_pixel_ops<CI, 1>(tp, u, 0, pos);
+    atomicAdd(&my[clahe_bin(clahe_value<CI>(u[0], la, lb))], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, total = tw * th;
+  int hb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) hb[k] = hist[0][4 * lane + k] + hist[1][4 * lane + k] + hist[2][4 * lane + k] + hist[3][4 * lane + k];
+  const int clip = max((int)((double)clip_f * (double)total / 256.0), 1);
+  int excess = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (hb[k] > clip) { excess += hb[k] - clip; hb[k] = clip; }
+  }
+  for (int o = 32; o > 0; o >>= 1) excess += __shfl_xor(excess, o, 64);
+  // excess / 256 to every bin, then one more to bins 0, step, 2 step, ... until the remainder is used up
+  const int batch = excess / 256, resid = excess % 256, step = resid ? max(256 / resid, 1) : 1;
+  int cum[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = 4 * lane + k;
+    cum[k] = (k ? cum[k - 1] : 0) + hb[k] + batch + (resid != 0 && i % step == 0 && i / step < resid ? 1 : 0);
+  }
+  int run = cum[3];                                  // inclusive scan of the lanes' sums
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(run, o, 64);
+    if (lane >= o) run += t;
+  }
+  const int base = run - cum[3];
+  const float scale = 255.f / (float)total;
+  uint32_t word = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) word |= (uint32_t)min(max((int)rintf((float)(base + cum[k]) * scale), 0), 255) << (8 * k);
+  reinterpret_cast<uint32_t*>(luts + (((long)img * gy + ty) * gx + tx) * 256)[lane] = word;
 }
 
 // host-side validation of an op list (before any launch)
@@ -414,6 +649,30 @@ static int check_ops(const float* ops, int n_ops, int h, int w, AugOps& out) {
   return EMBNET_OK;
 }
 
+// host-side validation of a CLAHE grid against the image size (the pad, at most g, stays below the image size)
+static int check_clahe_grid(const char* what, int gx, int gy, int h, int w) {
+  EMBNET_CHECK_ARG(gx >= 1 && gx <= AUG_CLAHE_MAX_GRID && gy >= 1 && gy <= AUG_CLAHE_MAX_GRID,
+                   "%s: clahe tile_grid_size=(%d, %d) (1..%d each)", what, gx, gy, AUG_CLAHE_MAX_GRID);
+  EMBNET_CHECK_ARG(2 * gx <= w && 2 * gy <= h, "%s: clahe tile_grid_size=(%d, %d) too large for %dx%d images (2 gx <= w, 2 gy <= h)",
+                   what, gx, gy, h, w);
+  return EMBNET_OK;
+}
+
+// host-side validation of a CLAHE record and its position in an op list of n_ops other ops (before any launch)
+static int check_clahe(const float* r, int pos, int n_ops, int h, int w, AugClahe& out) {
+  EMBNET_CHECK_ARG(r[0] == (float)AUG_CLAHE, "augment: clahe record: opcode %g (expected %d)", r[0], AUG_CLAHE);
+  EMBNET_CHECK_ARG(r[1] >= 0.f && r[1] <= 1.f, "augment: clahe p=%g outside [0, 1]", r[1]);
+  EMBNET_CHECK_ARG(r[2] > 0.f && r[2] <= r[3] && r[3] <= 3.0e38f, "augment: clahe clip_limit=(%g, %g) (0 < lo <= hi)", r[2], r[3]);
+  EMBNET_CHECK_ARG(r[4] >= 1.f && r[4] <= (float)AUG_CLAHE_MAX_GRID && r[4] == (float)(int)r[4] && r[5] >= 1.f &&
+                   r[5] <= (float)AUG_CLAHE_MAX_GRID && r[5] == (float)(int)r[5],
+                   "augment: clahe tile_grid_size=(%g, %g) (integers in 1..%d)", r[4], r[5], AUG_CLAHE_MAX_GRID);
+  const int rc = check_clahe_grid("augment", (int)r[4], (int)r[5], h, w);
+  if (rc != EMBNET_OK) return rc;
+  EMBNET_CHECK_ARG(pos >= 0 && pos <= n_ops, "augment: clahe pos=%d outside [0, n_ops=%d]", pos, n_ops);
+  out = AugClahe{r[1], r[2], r[3], (int)r[4], (int)r[5], pos};
+  return EMBNET_OK;
+}
+
 }  // namespace embnet
 
 using namespace embnet;
@@ -435,6 +694,50 @@ extern "C" int embnet_augment_params(const float* ops, int n_ops, uint64_t seed,
   return check_launch("augment_params");
 }
 
+extern "C" int embnet_augment_params_clahe(const float* ops, int n_ops, const float* clahe_rec, int clahe_pos, uint64_t seed,
+                                           uint64_t batch_no, int n, int h, int w, float* table, void* stream) {
+  if (!clahe_rec) return embnet_augment_params(ops, n_ops, seed, batch_no, n, h, w, table, stream);
+  EMBNET_CHECK_ARG(table, "augment_params_clahe: null pointer (table)");
+  EMBNET_CHECK_ARG(n > 0 && n <= 65535 && h >= 4 && w >= 4 && h <= 16384 && w <= 16384,
+                   "augment_params_clahe: n=%d h=%d w=%d (1 <= n <= 65535, 4 <= h, w <= 16384)", n, h, w);
+  EMBNET_CHECK_ARG(((uintptr_t)table & 15) == 0, "augment_params_clahe: table not 16-byte aligned");
+  AugOps rec;
+  int rc = check_ops(ops, n_ops, h, w, rec);
+  if (rc != EMBNET_OK) return rc;
+  AugClahe clahe;
+  rc = check_clahe(clahe_rec, clahe_pos, n_ops, h, w, clahe);
+  if (rc != EMBNET_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  EMBNET_TRACE("embnet::augment_params_clahe_kernel", TRACE_BYTES, (double)n * AUG_F * 4.0, st);
+  augment_params_clahe_kernel<<<cdiv(n, 256), 256, 0, st>>>(rec, clahe, seed, batch_no, n, h, w, table);
+  return check_launch("augment_params_clahe");
+}
+
+extern "C" size_t embnet_augment_clahe_lut_bytes(int n, int gx, int gy) {
+  return n > 0 && gx > 0 && gy > 0 ? (size_t)n * (size_t)gy * (size_t)gx * 256u : 0;
+}
+
+extern "C" int embnet_augment_clahe_luts(const void* src, const int32_t* index, int n, int h, int w, int c_in, int gx, int gy,
+                                         const float* table, void* luts, void* stream) {
+  EMBNET_CHECK_ARG(src && table && luts, "augment_clahe_luts: null pointer");
+  EMBNET_CHECK_ARG(n > 0 && n <= 65535 && h >= 4 && w >= 4 && h <= 16384 && w <= 16384,
+                   "augment_clahe_luts: n=%d h=%d w=%d (1 <= n <= 65535, 4 <= h, w <= 16384)", n, h, w);
+  EMBNET_CHECK_ARG(c_in == 1 || c_in == 3, "augment_clahe_luts: c_in=%d (clahe takes 1-channel or 3-channel BGR images)", c_in);
+  const int rc = check_clahe_grid("augment_clahe_luts", gx, gy, h, w);
+  if (rc != EMBNET_OK) return rc;
+  EMBNET_CHECK_ARG(((uintptr_t)luts & 3) == 0, "augment_clahe_luts: luts not 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  int tw, th;
+  clahe_tile(h, w, gx, gy, tw, th);
+  EMBNET_TRACE("embnet::augment_clahe_lut_kernel", TRACE_BYTES, (double)n * ((double)gx * tw * gy * th * c_in + gx * gy * 256.0), st);
+  const dim3 grid((unsigned)(gx * gy), (unsigned)n);
+  const unsigned char* s = (const unsigned char*)src;
+  unsigned char* l = (unsigned char*)luts;
+  if (c_in == 3) augment_clahe_lut_kernel<3><<<grid, 256, 0, st>>>(s, index, h, w, gx, gy, table, l);
+  else augment_clahe_lut_kernel<1><<<grid, 256, 0, st>>>(s, index, h, w, gx, gy, table, l);
+  return check_launch("augment_clahe_luts");
+}
+
 extern "C" int embnet_augment_apply(const void* src, const int32_t* index, int n, int h, int w, int c_in, int c_out,
                                     const float* table, uint64_t seed, uint64_t batch_no, float* dst, void* stream) {
   EMBNET_CHECK_ARG(src && table && dst, "augment_apply: null pointer");
@@ -448,7 +751,8 @@ extern "C" int embnet_augment_apply(const void* src, const int32_t* index, int n
   const dim3 grid((unsigned)(cdiv(w, AUG_TILE) * cdiv(h, AUG_TILE)), (unsigned)n);
   const unsigned char* s = (const unsigned char*)src;
   const bool vec = (w & 3) == 0 && ((uintptr_t)dst & 15) == 0;
-#define AUG_LAUNCH(CI, CO, V) augment_apply_kernel<CI, CO, V><<<grid, 256, 0, st>>>(s, index, h, w, c_out, table, seed, batch_no, dst)
+#define AUG_LAUNCH(CI, CO, V) \
+  augment_apply_kernel<CI, CO, V, false><<<grid, 256, 0, st>>>(s, index, h, w, c_out, table, seed, batch_no, dst, nullptr, 0, 0)
   if (vec && c_in == 3 && c_out == 3) AUG_LAUNCH(3, 3, true);
   else if (vec && c_in == 3 && c_out == 4) AUG_LAUNCH(3, 4, true);
   else if (vec && c_in == 4 && c_out == 4) AUG_LAUNCH(4, 4, true);
@@ -459,4 +763,33 @@ extern "C" int embnet_augment_apply(const void* src, const int32_t* index, int n
   else AUG_LAUNCH(4, 0, false);
 #undef AUG_LAUNCH
   return check_launch("augment_apply");
+}
+
+extern "C" int embnet_augment_apply_clahe(const void* src, const int32_t* index, int n, int h, int w, int c_in, int c_out,
+                                          const float* table, const void* luts, int gx, int gy, uint64_t seed, uint64_t batch_no,
+                                          float* dst, void* stream) {
+  EMBNET_CHECK_ARG(src && table && luts && dst, "augment_apply_clahe: null pointer");
+  EMBNET_CHECK_ARG(n > 0 && n <= 65535 && h >= 4 && w >= 4 && h <= 16384 && w <= 16384,
+                   "augment_apply_clahe: n=%d h=%d w=%d (1 <= n <= 65535, 4 <= h, w <= 16384)", n, h, w);
+  EMBNET_CHECK_ARG((c_in == 1 || c_in == 3) && c_out >= c_in && c_out <= 16,
+                   "augment_apply_clahe: c_in=%d c_out=%d (c_in 1 or 3: clahe takes gray or BGR images; c_in <= c_out <= 16)",
+                   c_in, c_out);
+  const int rc = check_clahe_grid("augment_apply_clahe", gx, gy, h, w);
+  if (rc != EMBNET_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const long pixels = (long)h * w;
+  EMBNET_TRACE("embnet::augment_apply_clahe_kernel", TRACE_BYTES, (double)n * pixels * (c_in + 4.0 * c_out), st);
+  const dim3 grid((unsigned)(cdiv(w, AUG_TILE) * cdiv(h, AUG_TILE)), (unsigned)n);
+  const unsigned char* s = (const unsigned char*)src;
+  const unsigned char* l = (const unsigned char*)luts;
+  const bool vec = (w & 3) == 0 && ((uintptr_t)dst & 15) == 0;
+#define AUG_LAUNCH(CI, CO, V) \
+  augment_apply_kernel<CI, CO, V, true><<<grid, 256, 0, st>>>(s, index, h, w, c_out, table, seed, batch_no, dst, l, gx, gy)
+  if (vec && c_in == 3 && c_out == 3) AUG_LAUNCH(3, 3, true);
+  else if (vec && c_in == 3 && c_out == 4) AUG_LAUNCH(3, 4, true);
+  else if (vec && c_in == 1 && c_out == 1) AUG_LAUNCH(1, 1, true);
+  else if (c_in == 1) AUG_LAUNCH(1, 0, false);
+  else AUG_LAUNCH(3, 0, false);
+#undef AUG_LAUNCH
+  return check_launch("augment_apply_clahe");
 }

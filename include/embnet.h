@@ -436,6 +436,7 @@ int embnet_u8_to_f32(const void* src, const int32_t* index, int n, long pixels, 
  *   8 hue_saturation_value a0, a1, a2 = hue, sat, val shift limits: OpenCV 8-bit float HSV of the BGR pixel (H wraps at 180)
  *   9 blur                 a0 = blur_limit (1..7): k x k box, odd k uniform in [3, max(3, limit)], reflect-101 borders
  *  10 gauss_noise          a0, a1 = var_limit (lo, hi): sigma = sqrt(U(lo, hi)), one normal draw per element
+ *  (11 clahe is not an op record: embnet_augment_params_clahe below takes it apart from the list)
  * Only 6-8 may repeat.  Application order is fixed: geometry (every crop in list order, each inside the previous box, then
  * rot90, hflip, vflip composed into one output -> source map, bilinear with half-pixel centres and clamped borders; a map
  * without a crop is integer and reads one texel), the pixel ops 6-8 in list order, blur, noise, then v / 255.f.  Float32 on
@@ -446,18 +447,54 @@ int embnet_u8_to_f32(const void* src, const int32_t* index, int n, long pixels, 
  *   (cos for even e, sin for odd).  A row's values depend on (seed, batch_no, row) only.
  * TABLE: float32 [n][embnet_augment_param_floats() = 48], 16-byte aligned:
  *   0-3 crop box x0, y0, w, h in source pixels ((0, 0, w, h) = no crop); 4 hflip; 5 vflip; 6 rot90 k; 7 blur k (0 = off);
- *   8 noise sigma; 9 noise fired; 10 number of ops fired; 11-15 zero;
+ *   8 noise sigma; 9 noise fired; 10 number of ops fired; 11-14 CLAHE's (below; zero unless it fired); 15 zero;
  *   16 + 4 i .. 19 + 4 i, op i: { opcode if it fired else 0, s0, s1, s2 }: rrc (w, h, attempt 1-10 or 0 = fallback),
  *   center_crop (w, h), rot90 (k), brightness_contrast (alpha, beta), gamma (gamma), hsv (dh, ds, dv), blur (k),
  *   gauss_noise (sigma, variance); zeros for ops not fired or beyond n_ops.
  * APPLY: src uint8 [*, h, w, c_in] (1 <= c_in <= 4), index as embnet_u8_to_f32, dst float32 [n, h, w, c_out] (c_out <= 16,
  *   zero padding), table from embnet_augment_params for the same (n, h, w).  seed and batch_no key the noise.  An image with
- *   no op fired is bit for bit what embnet_u8_to_f32(denom = 255) writes.  n <= 65535, 4 <= h, w <= 16384. */
+ *   no op fired is bit for bit what embnet_u8_to_f32(denom = 255) writes.  n <= 65535, 4 <= h, w <= 16384.
+ *   embnet_augment_apply ignores table fields 11-14: given a table with CLAHE it writes the output without CLAHE. */
 size_t embnet_augment_param_floats(void);
 int embnet_augment_params(const float* ops, int n_ops, uint64_t seed, uint64_t batch_no, int n, int h, int w, float* table,
                           void* stream);
 int embnet_augment_apply(const void* src, const int32_t* index, int n, int h, int w, int c_in, int c_out, const float* table,
                          uint64_t seed, uint64_t batch_no, float* dst, void* stream);
+/* CLAHE (opcode 11): OpenCV's 8-bit CLAHE (cv::createCLAHE(clip, grid).apply, what albumentations' A.CLAHE calls), kept out of
+ * the 8 op slots so that no other op's record, draw or table field moves.
+ * RECORD: { 11, p, clip_lo, clip_hi, gx, gy, 0, 0 } (tile_grid_size = (gx columns, gy rows), cv::Size order) plus pos = the
+ *   number of other ops listed before it.  Rejected before a launch: p outside [0, 1], not 0 < clip_lo <= clip_hi, gx or gy not
+ *   an integer in 1..16, 2 gx > w or 2 gy > h (the pad stays below the image size), pos outside [0, n_ops], c_in not 1 or 3.
+ * DRAWS: RNG op index 8 (no slot uses it, so every other op draws what it draws without CLAHE): fires if u(8, 0) < p (b = 256);
+ *   clip = clip_lo + (clip_hi - clip_lo) u(8, 1) in float32 (b = 257).  Only when it fires: field 10 counts it, 11 = clip,
+ *   12 = pos, 13 = gx, 14 = gy; a row where it did not fire is bit for bit the row of the list without it.
+ * ORDER: geometry -> pixel ops in slots < pos -> CLAHE -> pixel ops in slots >= pos -> blur -> noise -> / 255.
+ * VALUE equalised: 1 channel: v itself.  3 channels: L* of the pixel read as BGR (as the HSV op reads it; albumentations calls
+ *   COLOR_RGB2LAB on cv2's BGR arrays, so the two differ as for HSV), scaled by 255/100.  OpenCV's float Lab: c = v / 255,
+ *   linear = c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4, OpenCV's D65 sRGB->XYZ matrix, X /= 0.950456, Z /= 1.088754,
+ *   f(t) = t > 0.008856 ? cbrt(t) : 7.787 t + 16/116, L = Y > 0.008856 ? 116 cbrt(Y) - 16 : 903.3 Y, a = 500 (f(X) - f(Y)),
+ *   b = 200 (f(Y) - f(Z)).  bin = rint(clamp(L8, 0, 255)).
+ * TILES: if w % gx or h % gy is non-zero, BOTH axes are padded at the bottom / right with reflect-101 by g - size % g (an axis
+ *   that divides gains a full g: OpenCV's copyMakeBorder quirk); tw = padded_w / gx, th = padded_h / gy; padded pixels count.
+ * LUT per tile: clip = max(1, (int)((double)clip * tw th / 256)); each bin is clipped at clip and the excess summed; excess / 256
+ *   is added to every bin, then 1 to bins 0, step, 2 step, ... until excess % 256 is used up (step = max(256 / remainder, 1));
+ *   LUT[i] = saturate(rint((float)cumsum_i * (255.f / (tw th)))), round half even, bytes.
+ * MAPPING of output pixel (y, x): txf = x (1.f / tw) - 0.5f, tx1 = floor(txf), xa = txf - tx1, tx2 = min(tx1 + 1, gx - 1),
+ *   tx1 = max(tx1, 0), the same for y; res = (L11 (1 - xa) + L12 xa)(1 - ya) + (L21 (1 - xa) + L22 xa) ya, each L that tile's
+ *   LUT at the pixel's bin, float32, not rounded.  1 channel: v = res.  3 channels: L* = res 100/255 with the pixel's own a*, b*
+ *   back through OpenCV's float Lab -> XYZ -> BGR (linear values clipped to [0, 1], then the inverse companding), * 255, clipped.
+ *   Halo pixels of a blur get CLAHE at their own (reflected) coordinates.
+ * ENTRY POINTS: embnet_augment_params_clahe = embnet_augment_params plus the CLAHE draws (clahe_rec NULL: exactly
+ *   embnet_augment_params).  embnet_augment_clahe_luts writes uint8 luts[n][gy][gx][256] (embnet_augment_clahe_lut_bytes,
+ *   4-byte aligned) for the rows where CLAHE fired and leaves the other rows untouched; gx, gy are the record's.
+ *   embnet_augment_apply_clahe = embnet_augment_apply with the CLAHE stage, reading those LUTs; c_in 1 or 3. */
+int embnet_augment_params_clahe(const float* ops, int n_ops, const float* clahe_rec, int clahe_pos, uint64_t seed,
+                                uint64_t batch_no, int n, int h, int w, float* table, void* stream);
+size_t embnet_augment_clahe_lut_bytes(int n, int gx, int gy);
+int embnet_augment_clahe_luts(const void* src, const int32_t* index, int n, int h, int w, int c_in, int gx, int gy,
+                              const float* table, void* luts, void* stream);
+int embnet_augment_apply_clahe(const void* src, const int32_t* index, int n, int h, int w, int c_in, int c_out, const float* table,
+                               const void* luts, int gx, int gy, uint64_t seed, uint64_t batch_no, float* dst, void* stream);
 
 /* Dense (backbones.py:35,72,75,114,116; models.py:44): x[m,in], w[in,out], y[m,out].
  * workspace (optional, may be NULL/0): >= embnet_dense_fwd_workspace_bytes lets a forward with few output tiles and a long
