@@ -680,39 +680,7 @@ __global__ __launch_bounds__(256, VEC ? CONV_OCC<G> : 1) void conv_dgrad_kernel(
 template <class G>
 __global__ __launch_bounds__(256, CONV_OCC_H<G>) void conv_dgrad_h_kernel(ConvDgradParams p) { conv_dgrad_body<G, true, true>(p); }
 
-struct ConvWgradParams { const float* x; const float* dy; float* out; ConvGeom g; int kt_per_split, splits, xcd_order; InputTransform tf; int fair_from; int stagger; Ranges rg; };
-
-// The weight gradient on the 16x16x32 MFMA shape (gemm_engine.h, "K32"): same tiles, loaders, slabs and summation order per
-// output element over k tiles; inside a k tile the 32 pixels are summed by one instruction per term instead of two.
-template <class G, bool TF>
-__device__ __forceinline__ void conv_wgrad_k32_body(const ConvWgradParams& p) {
-  using TA = TileKM<G::BM>;
-  using TB = TileKM<G::BN>;
-  __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS<G, TA, TB>];
-  prio_hi();
-  const int M = p.g.R * p.g.S * p.g.C, Kg = p.g.N * p.g.OH * p.g.OW;
-  const int tiles_n = (p.g.K + G::BN - 1) / G::BN;
-  const int tiles = ((M + G::BM - 1) / G::BM) * tiles_n;
-  const int split = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-  if (split >= p.splits) return;
-  const int m0 = (tile / tiles_n) * G::BM, n0 = (tile % tiles_n) * G::BN;
-  const int kt_total = (Kg + BK - 1) / BK;
-  const int kt0 = split * p.kt_per_split, kt1 = min(kt0 + p.kt_per_split, kt_total);
-  LoadConvWgradA<G::BM, true, TF> la; la.init(p.x, p.g, m0, threadIdx.x, p.tf);
-  LoadRowsKM<G::BN, true> lb; lb.init(p.dy, p.g.K, p.g.K, Kg, n0, threadIdx.x);
-  f32x4 acc[G::TM][G::TN][4];
-  gemm_mainloop3_k32<G, TA, TB>(la, lb, kt0, kt1, reinterpret_cast<unsigned char*>(smem), acc, (int)blockIdx.x >= p.fair_from);
-  float* out = p.out + (long)split * M * p.g.K;
-  for_each_acc16_row4<G>(acc, smem, [&](int r, int c, float4 v) {
-    const int row = m0 + r, col = n0 + c;
-    if (row < M && col < p.g.K) *reinterpret_cast<float4*>(out + (long)row * p.g.K + col) = v;
-  });
-}
-template <class G>
-__global__ __launch_bounds__(256, CONV_OCC<G>) void conv_wgrad_k32_kernel(ConvWgradParams p) { conv_wgrad_k32_body<G, false>(p); }
-// (the input-transform form: x is the INPUT of the BatchNormalization in front, act(x*scale + shift) applied in the loader)
-template <class G>
-__global__ __launch_bounds__(256) void conv_wgrad_k32_tf_kernel(ConvWgradParams p) { conv_wgrad_k32_body<G, true>(p); }
+struct ConvWgradParams { const float* x; const float* dy; float* out; ConvGeom g; int kt_per_split, splits; InputTransform tf; int fair_from; Ranges rg; };
 
 // VA: 16-byte gathers of X (C % 4 == 0); VB: 16-byte loads of dY (K % 4 == 0)
 template <class G, bool VA, bool VB, bool TF, bool H = false>
@@ -723,15 +691,10 @@ __device__ __forceinline__ void conv_wgrad_body(const ConvWgradParams& p) {
   prio_hi();                                             // prologue at raised issue priority (gemm_engine.h)
   const int M = p.g.R * p.g.S * p.g.C, Kg = p.g.N * p.g.OH * p.g.OW;
   const int tiles_n = (p.g.K + G::BN - 1) / G::BN;
-  // Two workgroup orders (speed only; results identical).  Default: tiles of one K-split on consecutive
-  // ids, i.e. spread over the 8 XCDs.  xcd_order=1 (EMBNET_WGRAD_XCD=1) puts all tiles of a split on ONE
-  // XCD so its L2 serves the shared X/dY pixels — HBM traffic drops ~4x on the 3x3 layers, but measured
-  // 20-25 % SLOWER (A/B in one process, tools/kernel_bench.py): the tiles hit the same L2 lines at the
-  // same instant; spreading them over eight L2s + the 256 MB Infinity Cache is faster.  Kept as a knob.
+  // The tiles of one K-split sit on consecutive ids, i.e. spread over the 8 XCDs: faster than all tiles of a split
+  // on one XCD, whose L2 would serve the shared X/dY pixels (HBM traffic ~4x lower, 20-25 % slower).
   const int tiles = ((M + G::BM - 1) / G::BM) * tiles_n;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int split = p.xcd_order ? (slot / tiles) * 8 + xcd : blockIdx.x / tiles;
-  const int tile = p.xcd_order ? slot % tiles : blockIdx.x % tiles;
+  const int split = blockIdx.x / tiles, tile = blockIdx.x % tiles;
   if (split >= p.splits) return;
   const int m0 = (tile / tiles_n) * G::BM, n0 = (tile % tiles_n) * G::BN;
   const int kt_total = (Kg + BK - 1) / BK;
@@ -741,18 +704,12 @@ __device__ __forceinline__ void conv_wgrad_body(const ConvWgradParams& p) {
   LoadRowsKM<G::BN, VB> lb; lb.init(p.dy, p.g.K, p.g.K, Kg, n0, threadIdx.x);
   f32x16 acc[G::TM][G::TN];
   stamp(2);
-  // stagger > 0 (with xcd_order): the tiles of one split, co-resident on one XCD, start their K ranges `stagger`
-  // tiles apart (wrapping around), so they want different L2 lines at any instant but the same ones within a few
-  // tiles' time.  Two passes over the rotated range; the accumulators carry over.
-  const int rot = p.stagger > 0 ? min((tile * p.stagger) % max(kt1 - kt0, 1), kt1 - kt0) : 0;
   if constexpr (H) {                                     // x = operand a, dy = operand b
     const float2 sa = range_scale(p.rg.a), sb = range_scale(p.rg.b);
-    conv_mainloop<G, TA, TB, decltype(la), decltype(lb), true>(la, lb, kt0 + rot, kt1, smem, acc, (int)blockIdx.x >= p.fair_from, true, sa.x, sb.x);
-    if (rot > 0) { prio_lo(); conv_mainloop<G, TA, TB, decltype(la), decltype(lb), true>(la, lb, kt0, kt0 + rot, smem, acc, false, false, sa.x, sb.x); }
+    conv_mainloop<G, TA, TB, decltype(la), decltype(lb), true>(la, lb, kt0, kt1, smem, acc, (int)blockIdx.x >= p.fair_from, true, sa.x, sb.x);
     scale_acc<G>(acc, sa.y, sb.y);
   } else {
-    conv_mainloop<G, TA, TB>(la, lb, kt0 + rot, kt1, smem, acc, (int)blockIdx.x >= p.fair_from);
-    if (rot > 0) { prio_lo(); conv_mainloop<G, TA, TB>(la, lb, kt0, kt0 + rot, smem, acc, false, false); }
+    conv_mainloop<G, TA, TB>(la, lb, kt0, kt1, smem, acc, (int)blockIdx.x >= p.fair_from);
   }
   stamp(4);
   float* out = p.out + (long)split * M * p.g.K;
@@ -916,11 +873,6 @@ using G128x64 = Geom<128, 64, 2, 2>;
 using G128x32 = Geom<128, 32, 4, 1>;
 using G64x64 = Geom<64, 64, 2, 2>;
 using G192x64 = Geom<192, 64, 2, 2>;        // wgrad only: 3x3xC64 kernels have 576 = 3*192 rows (4.5 tiles of 128)
-// three-product wgrad only (EMBNET_WGRAD_256=1, measured slower, off): a gradient of 129 .. 256 rows x <= 64 filters as ONE row tile —
-// the ResNet stem's 7x7x4 x 64 = 196 rows takes two 128-row tiles, each streaming all of dy: 1 136 MB per launch against 514 MB
-// algorithmic (profiles/r05_pmc_traffic_c2.txt)
-using G256x64 = Geom<256, 64, 4, 1>;
-
 
 // pick the widest N tile that the channel count fills, shrink M tile when the grid would not cover the chip
 static int pick_tile(long m, int ncols, bool strided_dgrad = false, long kdepth = 0) {
@@ -937,11 +889,6 @@ static int pick_tile(long m, int ncols, bool strided_dgrad = false, long kdepth 
   // In the training step (bench.py, EMBNET_BENCH_DETAIL, per layer): 14x14x256 -> 256 195 us vs 221 forward and
   // 198 vs 235 data gradient, 28x28x128 s2 -> 256 105 vs 117; 128-wide layers are neutral, and the stride classes of
   // a strided data gradient (unequal K per class) lose with the big tile (162 vs 114 us) -> they keep the old rule.
-  // short reductions (EfficientNet's 1x1 convs at 14x14 / 7x7: 3-6 K tiles): the loop is a few gather round trips whatever the
-  // tile; EMBNET_CONV_SHORTK = 1 / 3 picks 128x64 / 64x64 tiles for them (more workgroups per CU to hide the trips) — experiment
-  static const int shortk = (int)env_long("EMBNET_CONV_SHORTK", 0);
-  static const long shortk_max = env_long("EMBNET_CONV_SHORTK_MAX", 8);
-  if (shortk && kdepth > 0 && kdepth <= shortk_max * BK && !strided_dgrad && ncols >= 64) return shortk;
   static const long t128_min = env_long("EMBNET_CONV_T128_MIN", 384);
   const long t128 = cdiv(m, 128) * cdiv(ncols, 128);
   if ((ncols >= 256 && !strided_dgrad && t128 >= t128_min) || (ncols >= 128 && t128 >= 4 * 768)) return 0;
@@ -956,12 +903,12 @@ static int pick_tile(long m, int ncols, bool strided_dgrad = false, long kdepth 
   if (!strided_dgrad && kdepth >= 32 * BK && cdiv(m, 64) * cdiv(ncols, 64) < 512) return 1;
   return (cdiv(m, 128) * cdiv(ncols, 64) >= need) ? 1 : 3;
 }
-static const int TILE_BM[6] = {128, 128, 128, 64, 192, 256}, TILE_BN[6] = {128, 64, 32, 64, 64, 64}, TILE_WTM[6] = {64, 64, 32, 32, 96, 64};
+static const int TILE_BM[5] = {128, 128, 128, 64, 192}, TILE_BN[5] = {128, 64, 32, 64, 64}, TILE_WTM[5] = {64, 64, 32, 32, 96};
 // workgroups of each tile type a CU holds at once (registers / LDS; measured with in-kernel stamps)
 #if EMBNET_CONV_SPLIT
-static const int TILE_RESIDENT[6] = {2, 3, 4, 4, 2, 2};
+static const int TILE_RESIDENT[5] = {2, 3, 4, 4, 2};
 #else
-static const int TILE_RESIDENT[6] = {3, 4, 5, 7, 3, 3};
+static const int TILE_RESIDENT[5] = {3, 4, 5, 7, 3};
 #endif
 // Progress-ordered priority (gemm_engine.h: `fair`) for launches whose workgroups are all resident at once.  Measured
 // A/B, one process (tools/exp/ab_conv.py, ResNet18 layers at batch 128): 64x64-tile forward / data-gradient launches
@@ -1032,7 +979,7 @@ static void plan_tail(long tiles, int kt, int bm, int bn, size_t ws_bytes, Split
 }
 
 // kernel name as rocprofv3 prints it, for the trace log (and embnet_conv2d_kernel_name)
-static const char* GEOM_NAME[6] = {"128, 128, 2, 2", "128, 64, 2, 2", "128, 32, 4, 1", "64, 64, 2, 2", "192, 64, 2, 2", "256, 64, 4, 1"};
+static const char* GEOM_NAME[5] = {"128, 128, 2, 2", "128, 64, 2, 2", "128, 32, 4, 1", "64, 64, 2, 2", "192, 64, 2, 2"};
 static const char* conv_kernel_name(const char* kernel, const char* params, int tile, const char* flags) {
   static thread_local char buf[160];
   snprintf(buf, sizeof buf, "void embnet::%s<embnet::Geom<%s>, %s>(embnet::%s)", kernel, GEOM_NAME[tile], flags, params);
@@ -1057,7 +1004,6 @@ static const char* conv_kernel_name(const char* kernel, const char* params, int 
 #define LAUNCH_WGRAD_H(KERNEL, tile, grid, st, p)          /* + the 192-row tile only the weight gradient plans */ \
   switch (tile) {                                                                     \
     case 4: KERNEL<G192x64><<<grid, 256, 0, st>>>(p); break;                          \
-    case 5: KERNEL<G256x64><<<grid, 256, 0, st>>>(p); break;                          \
     default: LAUNCH_TILED_H(KERNEL, tile, grid, st, p)                                \
   }
 static const char* conv_h_kernel_name(const char* kernel, const char* params, int tile) {
@@ -1115,10 +1061,6 @@ extern "C" int embnet_range_multi(const void* table, int n_tensors, const int32_
   return check_launch("range_multi");
 }
 
-// Off by default: 1-6 % faster per layer back to back (profiles/r04_exp_wgrad_k32.txt), 2 % SLOWER inside the training step
-// (same box, alternating runs: 123.9-124.9 vs 121.7-122.1 us for the 128x128 tile, step time equal) — see DESIGN 3.12.
-static bool wgrad_k32() { static const bool v = env_long("EMBNET_WGRAD_K32", 0) != 0; return v; }
-
 extern "C" int embnet_conv_mfma_terms(void) { return EMBNET_CONV_SPLIT ? 6 : 1; }
 // ... of the kernels that read pre-split planes (conv_patch.hip, conv_wgrad_planes.hip): 3 in the two-piece fp16 format
 extern "C" int embnet_conv_planes_mfma_terms(void) { return planes_f16() ? 3 : 6; }
@@ -1164,14 +1106,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
   }
   const bool vec = (c & 3) == 0 && (k & 3) == 0 && aligned16(x) && aligned16(w) && (!bias || aligned16(bias));
   const bool hform = ranged && vec && !in_scale;
-  int tile = pick_tile(M, k, false, (long)r * s * c);
-  // EMBNET_FWD_256=1 (experiment, off): a short reduction into <= 64 filters over very many pixels (the zoo ResNets' 7x7x4 stem: 7 K
-  // tiles, 12 544 tiles of 128 x 64 at batch 128) on 256 x 64 tiles — if the launch were (rounds) x (K tiles) x (a gather round trip),
-  // half the rounds would halve it; measured 244 -> 271 us: it is the rate at which the L1 takes the 49 16-byte requests per output
-  // pixel, and fewer, fatter workgroups hide less of it.  Only the three-product form has the instantiation; M % 256 == 0 keeps the
-  // statistics' row count what embnet_conv2d_fwd_stats_rows says.
-  static const int fwd256 = (int)env_long("EMBNET_FWD_256", 0);     // measured slower (244 -> 271 us, profiles/r06_exp_fwd256.txt): off
-  if (fwd256 && hform && tile == 1 && k <= 64 && M % 256 == 0 && cdiv((long)r * s * c, BK) <= 8 && M / 256 >= 4 * 512) tile = 5;
+  const int tile = pick_tile(M, k, false, (long)r * s * c);
   const long tiles = (long)cdiv(M, TILE_BM[tile]) * cdiv(k, TILE_BN[tile]);
   EMBNET_CHECK_ARG(!in_scale || (vec && aligned16(in_scale) && aligned16(in_shift)),
                    "conv2d_fwd: the fused input transform needs channel counts that are multiples of 4 and aligned pointers");
@@ -1191,8 +1126,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
                       conv_kernel_name(in_scale ? "conv_fwd_tf_kernel" : "conv_fwd_kernel", "ConvFwdParams", tile,
                                        (vec || in_scale) ? "true" : "false"), flop,
                       4.0 * ((double)n * h * wd * c + (double)r * s * c * k + (double)M * k * (residual ? 2 : 1)), st);
-    if (hform && tile == 5) conv_fwd_h_kernel<G256x64><<<grid, 256, 0, st>>>(p);
-    else if (hform) { LAUNCH_TILED_H(conv_fwd_h_kernel, tile, grid, st, p) }
+    if (hform) { LAUNCH_TILED_H(conv_fwd_h_kernel, tile, grid, st, p) }
     else if (in_scale) { LAUNCH_TILED(conv_fwd_tf_kernel, true, tile, grid, st, p) }
     else if (vec) { LAUNCH_TILED(conv_fwd_kernel, true, tile, grid, st, p) }
     else { LAUNCH_TILED(conv_fwd_kernel, false, tile, grid, st, p) }
@@ -1365,8 +1299,7 @@ static void wgrad_plan(int rows, int k, long kg, int& tile, int& splits, int& kt
   // few gradient rows (1x1 convs on 16..64 channels, EfficientNet): 64-row tiles, whatever the width
   tile = (rows <= 64 && k > 32) ? 3 : (k <= 32 ? 2 : (k <= 64 ? 1 : 0));
   // 128-row tiles waste the last half tile of a 576-row (3x3x64) gradient; 192-row tiles fit it exactly
-  static const bool no192 = env_long("EMBNET_WGRAD_NO192", 0) != 0;
-  if (tile == 1 && rows % 192 == 0 && rows % 128 != 0 && !no192) tile = 4;
+  if (tile == 1 && rows % 192 == 0 && rows % 128 != 0) tile = 4;
   const int forced_tile = (int)env_long("EMBNET_WGRAD_TILE", -1);
   if (forced_tile >= 0) tile = forced_tile;
   const long tiles = (long)cdiv(rows, TILE_BM[tile]) * cdiv(k, TILE_BN[tile]);
@@ -1418,17 +1351,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspac
   const bool ranged = ranges_ok(rg);
   EMBNET_CHECK_ARG(x && dy && dw, "conv2d_wgrad: null pointer");
   EMBNET_CHECK_ARG(aligned16(dw) && aligned16(workspace), "conv2d_wgrad: dw and workspace must be 16-byte aligned");
-  ConvWgradParams p{x, dy, dw, {}, 0, 1, 0};
-#ifndef EMBNET_WGRAD_XCD_DEFAULT
-#define EMBNET_WGRAD_XCD_DEFAULT 0
-#endif
-#ifndef EMBNET_WGRAD_STAGGER_DEFAULT
-#define EMBNET_WGRAD_STAGGER_DEFAULT 0
-#endif
-  static const int xcd_order = (int)env_long("EMBNET_WGRAD_XCD", EMBNET_WGRAD_XCD_DEFAULT);
-  static const int stagger = (int)env_long("EMBNET_WGRAD_STAGGER", EMBNET_WGRAD_STAGGER_DEFAULT);
-  p.xcd_order = xcd_order;
-  p.stagger = xcd_order ? stagger : 0;
+  ConvWgradParams p{x, dy, dw, {}, 0, 1};
   if (int rc = make_geom(p.g, n, h, wd, c, r, s, k, stride, pad_t, pad_l, oh, ow, "conv2d_wgrad")) return rc;
   int tile;
   const int rows = r * s * c;
@@ -1453,7 +1376,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspac
     }
     return check_launch("conv2d_wgrad");
   }
-  dim3 grid(cdiv(rows, TILE_BM[tile]) * cdiv(k, TILE_BN[tile]) * ((p.splits + 7) / 8 * 8));
+  const dim3 grid(cdiv(rows, TILE_BM[tile]) * cdiv(k, TILE_BN[tile]) * ((p.splits + 7) / 8 * 8));
   p.fair_from = fair_from(grid.x, tile, true);
   const bool va = (c & 3) == 0 && aligned16(x), vb = (k & 3) == 0 && aligned16(dy);
   EMBNET_CHECK_ARG(!in_scale == !in_shift, "conv2d_wgrad: in_scale and in_shift go together");
@@ -1461,50 +1384,15 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspac
                    "conv2d_wgrad: the fused input transform needs channel counts that are multiples of 4 and aligned pointers");
   p.tf = InputTransform{in_scale, in_shift, in_act};
   if (do_main) {
-    // 16x16x32 MFMA shape for the weight gradient (both operands k-major: same fragment reads and matrix cycles as
-    // 32x32x16): EMBNET_WGRAD_K32=1 (experiment; see wgrad_k32()).
-    // (not the 128x64 tile: at three workgroups per CU its K32 form spills 9 registers in the loop — the ResNet stem's
-    // weight gradient ran 455-472 us on it against 300-320, profiles/r04_bench_kernel_stats.md)
-    const bool k32 = wgrad_k32() && tile != 1;
-    const bool hform = ranged && va && vb && !in_scale && !(k32 && !p.xcd_order);
+    const bool hform = ranged && va && vb && !in_scale;
     p.rg = rg;
-    // one 256-row tile where two 128-row tiles would each stream all of dy (three-product kernels only; the split count — the slab
-    // layout every caller planned with — stays the plan's).  EMBNET_WGRAD_256=1; OFF by default: the stem's weight gradient moves half
-    // the bytes (1 130 -> 554 MB per launch, profiles/r06_pmc_traffic_c2_xcd0.txt) and takes 256 -> 321-330 us: half as many
-    // workgroups, and the loop is bound by its gather round trips, not by bytes (profiles/r06_exp_xcd_rows.txt)
-    static const bool use256 = env_long("EMBNET_WGRAD_256", 0) != 0;
-    if (hform && tile == 1 && rows > 128 && rows <= 256 && use256) {
-      tile = 5;
-      grid = dim3(cdiv(k, TILE_BN[5]) * ((p.splits + 7) / 8 * 8));
-      p.fair_from = fair_from(grid.x, tile, true);
-    }
-    char k32name[160];
-    snprintf(k32name, sizeof k32name, "void embnet::conv_wgrad_k32_kernel<embnet::Geom<%s> >(embnet::ConvWgradParams)", GEOM_NAME[tile]);
-    if (in_scale) snprintf(k32name, sizeof k32name, "void embnet::conv_wgrad_k32_tf_kernel<embnet::Geom<%s> >(embnet::ConvWgradParams)", GEOM_NAME[tile]);
     EMBNET_TRACE_FLOP(hform ? conv_h_kernel_name("conv_wgrad_h_kernel", "ConvWgradParams", tile) :
-                      ((in_scale || (va && vb)) && k32 && !p.xcd_order) ? k32name :
                       conv_kernel_name(in_scale ? "conv_wgrad_tf_kernel" : "conv_wgrad_kernel", "ConvWgradParams", tile,
                                        (in_scale || (va && vb)) ? "true, true" : (vb ? "false, true" : "false, false")),
                       2.0 * n * oh * ow * (double)k * rows,
                       4.0 * ((double)n * h * wd * c + (double)n * oh * ow * k + (double)rows * k * p.splits), st);
     if (hform) { LAUNCH_WGRAD_H(conv_wgrad_h_kernel, tile, grid, st, p) }
-    else if (in_scale && k32 && !p.xcd_order) {         // same arithmetic as the plain K32 kernels: deferred BN stays bit-identical
-      switch (tile) {
-        case 0: conv_wgrad_k32_tf_kernel<G128x128><<<grid, 256, 0, st>>>(p); break;
-        case 2: conv_wgrad_k32_tf_kernel<G128x32><<<grid, 256, 0, st>>>(p); break;
-        case 4: conv_wgrad_k32_tf_kernel<G192x64><<<grid, 256, 0, st>>>(p); break;
-        default: conv_wgrad_k32_tf_kernel<G64x64><<<grid, 256, 0, st>>>(p); break;
-      }
-    }
     else if (in_scale) { LAUNCH_WGRAD(conv_wgrad_tf_kernel, true, true) }
-    else if (va && vb && k32 && !p.xcd_order) {
-      switch (tile) {
-        case 0: conv_wgrad_k32_kernel<G128x128><<<grid, 256, 0, st>>>(p); break;
-        case 2: conv_wgrad_k32_kernel<G128x32><<<grid, 256, 0, st>>>(p); break;
-        case 4: conv_wgrad_k32_kernel<G192x64><<<grid, 256, 0, st>>>(p); break;
-        default: conv_wgrad_k32_kernel<G64x64><<<grid, 256, 0, st>>>(p); break;
-      }
-    }
     else if (va && vb) { LAUNCH_WGRAD(conv_wgrad_kernel, true, true) }
     else if (vb) { LAUNCH_WGRAD(conv_wgrad_kernel, false, true) }
     else { LAUNCH_WGRAD(conv_wgrad_kernel, false, false) }
@@ -1608,8 +1496,6 @@ extern "C" const char* embnet_conv2d_kernel_name(int kind, int n, int h, int wd,
     int tile, sp, kt;
     wgrad_plan(r * s * c, k, (long)n * oh * ow, tile, sp, kt, r == 1 && s == 1);
     if (tile < 0) snprintf(buf, sizeof buf, "embnet::thinw::thin_wgrad_kernel");
-    else if (((c | k) & 3) == 0 && wgrad_k32() && tile != 1)
-      snprintf(buf, sizeof buf, "void embnet::conv_wgrad_k32_kernel<embnet::Geom<%s> >(embnet::ConvWgradParams)", geoms[tile]);
     else
       snprintf(buf, sizeof buf, "void embnet::conv_wgrad_kernel<embnet::Geom<%s>, %s, %s>(embnet::ConvWgradParams)",
                geoms[tile], ((k & 3) == 0) ? t : "false", tk);

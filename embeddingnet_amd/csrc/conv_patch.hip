@@ -50,7 +50,6 @@ struct PatchParams {
   int PH, PW; FastDiv dPHW, dPW;
   int LR;                        // LDS patch rows (multiple of 32)
   int n_full, parts, cc_part, n_pieces, grid; float* ws;
-  int xcd_rows;                  // work_item: the column tiles of a tile row on one XCD (EMBNET_PATCH_XCD_ROWS=1; off by default)
   BnSums bn;                     // data-gradient use: the BatchNorm-backward sums of the layer in front (bn.x == NULL: off)
   // conv1x1_a32_kernel: the activation operand is the fp32 tensor itself (xp points at floats [pixels][C]), split in the matrix
   // waves; its scale comes from its range slot
@@ -74,17 +73,9 @@ __device__ __forceinline__ Item work_item(int item, int n_mine) {
   const int b = blockIdx.x, NCC = pp->g.C / CCH, tiles_n = (pp->g.K + BN - 1) / BN;
   Item t; int id;
   if (item < n_mine) {
-    // whole rounds of `grid` tiles.  Workgroups b, b + 8, b + 16 ... share an XCD (observed placement; speed only): where a row
-    // of tiles has T = 2, 4, ... column tiles (256 / 512 filters) they go to T consecutive workgroups OF ONE XCD, so the input
-    // patch they all read is fetched into one L2 once instead of into T of them (profiles/r05_pmc_traffic_c2.txt: 1.58 x the
-    // algorithmic bytes per launch).  A bijection of the round's positions when T divides grid / 8; other T keep the plain order.
-    int pos = b;
-    const int per_xcd = pp->grid >> 3;
-    if (pp->xcd_rows && tiles_n > 1 && (pp->grid & 7) == 0 && per_xcd % tiles_n == 0 && (item + 1) * pp->grid <= pp->n_full) {   // (whole rounds only)
-      const int xcd = b & 7, slot = b >> 3;
-      pos = ((slot / tiles_n) * 8 + xcd) * tiles_n + slot % tiles_n;
-    }
-    id = pos + item * pp->grid; t.cc_b = 0; t.cc_e = NCC; t.part = nullptr;
+    // whole rounds of `grid` tiles in plain order (putting the column tiles of a tile row on one XCD saved HBM traffic but no time;
+    // DESIGN 3.14)
+    id = b + item * pp->grid; t.cc_b = 0; t.cc_e = NCC; t.part = nullptr;
   }
   else {
     id = pp->n_full + b / pp->parts;
@@ -1056,10 +1047,6 @@ extern "C" int embnet_conv_weight_planes(const void* table, int n_tensors, const
   return check_launch("conv_weight_planes");
 }
 
-// (off: measured on C2, three alternating pairs — 85.5 us either way, FETCH + WRITE 117.0 -> 109.2 MB per launch: the layers with several
-// column tiles per row have fewer tiles than the grid, i.e. no whole round; profiles/r06_exp_xcd_rows.txt)
-static int patch_xcd_rows() { static const int v = env_long("EMBNET_PATCH_XCD_ROWS", 0) != 0; return v; }
-static bool patch_pipe() { static const bool v = env_long("EMBNET_PATCH_PIPE", 1) != 0; return v; }   // 0: the plain loop (A/B)
 template <int BN, int TPS, int NBS>
 static void launch_patch(const PatchParams& p, size_t lds, hipStream_t st) {
   static bool once = false;
@@ -1067,14 +1054,12 @@ static void launch_patch(const PatchParams& p, size_t lds, hipStream_t st) {
     (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     once = true;
   }
   if (planes_f16()) {
     if (p.bn.x) conv_patch_kernel<BN, 3, 3, TPS, NBS, true, true><<<p.grid, 640, lds, st>>>(p);
-    else if (patch_pipe()) conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true><<<p.grid, 640, lds, st>>>(p);
-    else conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true><<<p.grid, 640, lds, st>>>(p);
+    else conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true><<<p.grid, 640, lds, st>>>(p);
     return;
   }
   if (p.bn.x) conv_patch_kernel<BN, 3, 3, TPS, NBS, true, false><<<p.grid, 640, lds, st>>>(p);
@@ -1102,13 +1087,12 @@ static int conv2d_patch_impl(const void* xp, const void* wp, const float* bias, 
   p.grid = pl.grid;
   if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
   p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  p.xcd_rows = patch_xcd_rows();
   hipStream_t st = (hipStream_t)stream;
   {
     // (the names rocprofv3 prints: bench.py looks the kernel's measured HBM traffic up by them)
     static thread_local char kname[160];
     snprintf(kname, sizeof kname, "void embnet::patch::conv_patch_kernel<%d, 3, 3, %d, %d, %s%s>(embnet::patch::PatchParams)", pl.bn, pl.tps, pl.nbs,
-             p.bn.x ? "true" : "false", planes_f16() ? ((patch_pipe() && !p.bn.x) ? ", true, true" : ", true") : "");
+             p.bn.x ? "true" : "false", planes_f16() ? (p.bn.x ? ", true" : ", true, true") : "");
     EMBNET_TRACE_FLOP(kname,
                       2.0 * M * k * r * s * c,
                       (planes_f16() ? 4.0 : 6.0) * ((double)n * h * wd * c + (double)r * s * c * k) + 4.0 * (double)M * k * (residual ? 2 : 1), st);
@@ -1160,7 +1144,6 @@ extern "C" int embnet_conv2d_planes1x1_f32(const void* xp, const void* wp, const
   p.grid = pl.grid;
   if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
   p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  p.xcd_rows = patch_xcd_rows();
   hipStream_t st = (hipStream_t)stream;
   {
     static thread_local char kname[160];
@@ -1213,7 +1196,6 @@ extern "C" int embnet_conv2d_dma1x1_f32(const float* x, const void* wp, const fl
   p.grid = pl.grid;
   if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
   p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  p.xcd_rows = patch_xcd_rows();
   hipStream_t st = (hipStream_t)stream;
   {
     static thread_local char kname[160];

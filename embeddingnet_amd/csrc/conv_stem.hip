@@ -5,7 +5,7 @@
 // Why: on the implicit-GEMM loop (conv.hip) this layer is 12 544 tiles of 128 pixels x 64 filters with a reduction of seven 32-deep K
 // tiles; every output pixel issues 49 sixteen-byte gathers for its 196 multiply-adds x 64 filters, the loop runs at the rate the L1
 // takes those requests (244 us at batch 128, 0.16 of what the matrix pipe could do), and neither more resident workgroups nor fatter
-// tiles help (EMBNET_FWD_256).  Here every input pixel is fetched ONCE per tile:
+// tiles help (256-row tiles).  Here every input pixel is fetched ONCE per tile:
 //  * a workgroup (persistent) takes 16 x 16 output pixels of one image x all 64 filters; the input PATCH those outputs read
 //    (37 x 37 pixels x 16 B, fp32, zero outside the image) reaches LDS by LDS-DMA from a loader wave, two tiles ahead (three
 //    buffers, one s_barrier per tile);

@@ -64,7 +64,6 @@ struct Params {
   unsigned x_plane_bytes, dy_plane_bytes, x_chunk_bytes, dy_chunk_bytes;
   int tiles_k, tiles, splits, stages_total, stages_per_split, HB;
   long slab_elems;
-  int knobs;                   // experiments (EMBNET_WGP_KNOBS): bit 0 = s_setprio 1 for waves 4-7, bit 1 = for the x loaders (0-3), bit 2 = stagger
 };
 
 // F16: the planes hold two fp16 pieces + a scale (gemm_engine.h, EMBNET_PLANES_F16): a loader wave places two (plane, chunk) images
@@ -137,13 +136,13 @@ __global__ __launch_bounds__(512) void conv_wgrad_planes_kernel(const Params p) 
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  if (((p.knobs & 1) && wave >= 4) || ((p.knobs & 2) && wave < 4)) __builtin_amdgcn_s_setprio(1);
 
   // STAG: waves 4-7 run HALF A STAGE behind waves 0-3 (the partner waves of a SIMD then alternate between the barrier / DMA-issue
   // / fragment-read phase and the MFMA phase instead of meeting in both: microarchitecture guide, 'Two waves per SIMD', item 9).
   // A stage becomes two ticks with a barrier each; the early waves' stage start is the late waves' stage middle.  The x loaders
   // (early) issue at their stage MIDDLE (the block they overwrite is read by the late waves until then), the dy loaders (late) at
   // their stage START; each group waits for its own requests in front of the barrier that starts the OTHER group's stage.
+  // (Measured slower, DESIGN 3.13: only STAG = false is instantiated.)
   const bool late = STAG && wave >= 4;
   for (int u = 0; u < HB + D; ++u) issue(u);
   if (late) {                                                    // tick 0 belongs to the early waves' first half stage
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_planes_kernel(const Params p) 
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[t & 1][FA[e]]), __builtin_bit_cast(f16x8, b[FB[e]]), acc[t], 0, 0, 0);
       } else {
 #pragma unroll
-        for (int e = 6 - EMBNET_EXP_TERMS; e < 6; ++e)      // (EMBNET_EXP_TERMS: gemm_engine.h; 6 in the product)
+        for (int e = 0; e < 6; ++e)
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[t & 1][PA[e]], b[PB[e]], acc[t], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);          // one tap's fragments ahead, not all nine (registers)
@@ -289,25 +288,20 @@ extern "C" int embnet_conv2d_wgrad_planes_f32(const void* x_planes, const void* 
   p.x_chunk_bytes = p.dy_chunk_bytes = (unsigned)((size_t)n * h * wd * 32);
   p.tiles_k = pl.tiles_k; p.tiles = pl.tiles; p.splits = pl.splits; p.stages_total = pl.stages_total;
   p.stages_per_split = pl.stages_per_split; p.HB = pl.HB; p.slab_elems = 9l * c * k;
-  static const int knobs = (int)env_long("EMBNET_WGP_KNOBS", 0);
-  p.knobs = knobs;
   hipStream_t st = (hipStream_t)stream;
   static bool once = false;
   if (!once) {
     (void)hipFuncSetAttribute((const void*)conv_wgrad_planes_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_planes_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv_wgrad_planes_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     once = true;
   }
   const int grid = (pl.tiles * pl.splits + 7) / 8 * 8;
   {
     const double m = (double)n * h * wd;
-    EMBNET_TRACE_FLOP(planes_f16() ? "void embnet::wgp::conv_wgrad_planes_kernel<false, true>(embnet::wgp::Params)" :
-                      (knobs & 4) ? "void embnet::wgp::conv_wgrad_planes_kernel<true>(embnet::wgp::Params)"
-                                  : "void embnet::wgp::conv_wgrad_planes_kernel<false>(embnet::wgp::Params)", 2.0 * m * k * 9.0 * c,
+    EMBNET_TRACE_FLOP(planes_f16() ? "void embnet::wgp::conv_wgrad_planes_kernel<false, true>(embnet::wgp::Params)"
+                                   : "void embnet::wgp::conv_wgrad_planes_kernel<false>(embnet::wgp::Params)", 2.0 * m * k * 9.0 * c,
                       (planes_f16() ? 4.0 : 6.0) * m * (c + k) + 4.0 * 9.0 * c * k * pl.splits, st);
     if (planes_f16()) conv_wgrad_planes_kernel<false, true><<<grid, 512, LDS_BYTES, st>>>(p);
-    else if (knobs & 4) conv_wgrad_planes_kernel<true><<<grid, 512, LDS_BYTES, st>>>(p);
     else conv_wgrad_planes_kernel<false><<<grid, 512, LDS_BYTES, st>>>(p);
   }
   if (pl.splits > 1 && reduce) launch_slab_reduce((const float*)workspace, pl.splits, 9l * c * k, dw, st);

@@ -25,16 +25,7 @@
 // steps from a single ds_read_b128 (conflict-free with the +4 pad), a KM tile
 // from four ds_read_b32 of 32 consecutive floats.  Summation order inside a
 // tile differs from plain k order; results are f32-rounding-equivalent.
-//
-// Diagnostic / ablation builds (tools/build_variant.sh -DEMBNET_DIAG_ENGINE=1 ...): the same engine with the round-1/2
-// experiment switches threaded through its main loops (EMBNET_ABLATE, _INTERLEAVE, _PIN, _SETPRIO, _SPLIT_DIST,
-// _SPLIT_ABLATE, _LDS_STAGES, in-loop stamps) lives in tools/exp/gemm_engine_diag.h; this file is the product.
 #pragma once
-#if defined(EMBNET_DIAG_ENGINE)
-// The diagnostic copy of this header (round-1/2 experiment switches) is frozen at round 3: it lacks the K32 main loop and the
-// k-major swizzle bit conv.hip needs since round 4.  To rebuild those experiment variants check out a round-3 tree (f78adeb).
-#error "tools/exp/gemm_engine_diag.h is the round-3 engine; build the diagnostic variants from a round-3 checkout"
-#else
 #include "common.h"
 #include <type_traits>
 
@@ -258,7 +249,7 @@ __device__ __forceinline__ void mfma_step(const float (&a)[G::TM][4], const floa
 // before they go to LDS (one load outstanding per loader, so it may use state load() left); TA/TB: their LDS tile
 // types.  smem holds MAIN_FLOATS<TA,TB> floats: one LDS buffer, the next K tile prefetched into registers under the MFMAs
 // of the current one, two barriers per tile.  (A two-stage LDS, software-pipelined variant measured 3-5 % slower: it
-// costs a resident workgroup per CU; tools/exp/gemm_engine_diag.h keeps it.)
+// costs a resident workgroup per CU; git history keeps it.)
 // `fair` (wave-uniform): lower this wave's issue priority as it progresses through its K range (3, 2, 1, 0 by
 // quarter) instead of running the loop at 0.  The SIMD arbitrates oldest-first, so workgroups that start together
 // finish one after the other (4 co-resident 128x64 tiles: 68, 78, 91, 105 us) — fine while new workgroups keep
@@ -463,7 +454,7 @@ struct TileKM3 {
   static constexpr int PLANE = BK * PITCH, BYTES = 3 * PLANE;
   // byte offset of row `row` (a multiple of 4) of k-row k.  128-byte rows: k-rows 0..3 -> slots (0|1) of the windows
   // [0,128) and [128,256): flip the 64-byte half with bit 1 of k; 256-byte rows: XOR the 64-byte slot with k & 3.
-  // (bit 3 of k also flips the 32-byte half: the K = 32 fragments of frag16 read k-rows 8 apart in one 32-lane pass; the
+  // (bit 3 of k also flips the 32-byte half, for K = 32 fragment reads of k-rows 8 apart in one 32-lane pass; the
   // K = 16 fragments never mix the two values of bit 3 in a pass, so they do not notice)
   __device__ static __forceinline__ int off(int k, int row) {
     const int b = (row * 2) ^ (((k >> 3) & 1) << 5);
@@ -495,22 +486,6 @@ struct TileKM3 {
       v[q] = __builtin_bit_cast(V, w);
     }
   }
-  // the A/B operand of v_mfma_f32_16x16x32_bf16 for rows r0 .. r0+15 over ALL 32 k of the tile: lane (i = lane & 15,
-  // g = lane >> 4) receives k = 8g .. 8g+7 of row r0 + i, again from two transposed reads per plane (k-rows 8g+0..3, 8g+4..7)
-  __device__ static __forceinline__ void frag16(const unsigned char* s, int r0, int lane, bf16x8 (&v)[3]) {
-    const int k = 8 * (lane >> 4) + ((lane & 15) >> 2);
-    const int row = r0 + 4 * (lane & 3);
-    const unsigned char* a = s + off(k, row);
-    const unsigned char* a4 = s + off(k + 4, row);
-    typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a + q * PLANE));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a4 + q * PLANE));
-      const s16x8 w = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-      v[q] = __builtin_bit_cast(bf16x8, w);
-    }
-  }
 };
 
 template <class T> struct SplitTile;
@@ -520,12 +495,6 @@ template <int R> struct SplitTile<TileKM<R>> { using type = TileKM3<R>; };
 template <class TA, class TB>
 constexpr int MAIN3_BYTES = SplitTile<TA>::type::BYTES + SplitTile<TB>::type::BYTES;
 
-// EMBNET_EXP_TERMS (build-time experiment, tools/exp/run_r05_terms3.sh): 3 executes only the three largest of the six terms —
-// NOT the product's arithmetic (16-bit products) — to measure what a three-term scheme (an fp16 x 2 split) would
-// run at.  The product is built with 6.
-#ifndef EMBNET_EXP_TERMS
-#define EMBNET_EXP_TERMS 6
-#endif
 // one k16-step: six terms per accumulator, smallest first; the accumulators of a wave alternate inside a term so
 // consecutive MFMAs are independent
 template <class G>
@@ -533,7 +502,7 @@ __device__ __forceinline__ void mfma_step3(const bf16x8 (&a)[G::TM][3], const bf
                                            f32x16 (&acc)[G::TM][G::TN]) {
   constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
-  for (int t = 6 - EMBNET_EXP_TERMS; t < 6; ++t)
+  for (int t = 0; t < 6; ++t)
 #pragma unroll
     for (int im = 0; im < G::TM; ++im)
 #pragma unroll
@@ -546,7 +515,7 @@ __device__ __forceinline__ void mfma_step3(const bf16x8 (&a)[G::TM][3], const bf
 // only the 8-byte LDS stores.  TA/TB are the fp32 tile types the loaders were written for.
 // The registers are free as soon as they are split, so tile kt+2 is requested right behind the split of tile kt+1
 // (before the barrier pair and the LDS stores of the next iteration), not after them (+1.5 %).
-// Measured and not adopted (tools/exp/gemm_engine_diag.h, profiles/r02_exp_ab_split_*.txt): two register sets in flight
+// Measured and not adopted (git history, profiles/r02_exp_ab_split_*.txt): two register sets in flight
 // (EMBNET_SPLIT_DIST=2: +48..130 registers, a workgroup per CU fewer, 5-30 % slower), rounded instead of truncated
 // pieces (same error, 6-7 % slower).  Round 3: what bounds this loop is the per-CU gather rate / latency.
 // H = true: the operands are split into the TWO fp16 pieces of x * s (split4h; sa / sb: each operand's power-of-two scale, chosen by
@@ -624,128 +593,6 @@ __device__ __forceinline__ void gemm_mainloop3(const LA& la, const LB& lb, int k
     lb.load(kt + 2 < kt_end ? kt + 2 : PAST, rb);
   }
   prio_hi();                                 // epilogue
-}
-
-// ---- the same six-term products on v_mfma_f32_16x16x32_bf16 ("K32") ------------------------------------------------------
-// Same matrix-pipe cycles per FLOP as the 32x32x16 form, same fragment-read count when BOTH operands are k-major (two
-// transposed reads per 16 rows x 32 k and plane, against two per 32 rows x 16 k), but the chip holds a higher clock on this
-// shape under load (HIP guide rule 28 / microarchitecture guide 'DVFS give-back' item 7: 1.12-1.15 x on random data in bare
-// loops).  A wave's WTM x WTN tile is (2 TM) x (2 TN) blocks of 16 x 16, four accumulator registers each:
-// acc[im][in][sm * 2 + sn] is the block at rows 32 im + 16 sm, columns 32 in + 16 sn; C/D map: col = lane & 15,
-// row = 4 * (lane >> 4) + r.  One K tile (32 k) is one step.
-template <class G>
-using Acc16 = f32x4[G::TM][G::TN][4];
-
-template <class G, class SA, class SB>
-__device__ __forceinline__ void mfma_tile3_k32(const unsigned char* sA, const unsigned char* sB, int wm, int wn, int lane,
-                                               f32x4 (&acc)[G::TM][G::TN][4]) {
-  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-  bf16x8 a[2 * G::TM][3];
-#pragma unroll
-  for (int i = 0; i < 2 * G::TM; ++i) SA::frag16(sA, wm + 16 * i, lane, a[i]);
-#pragma unroll
-  for (int j = 0; j < 2 * G::TN; ++j) {
-    bf16x8 b[3];
-    SB::frag16(sB, wn + 16 * j, lane, b);
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int i = 0; i < 2 * G::TM; ++i)
-        acc[i >> 1][j >> 1][(i & 1) * 2 + (j & 1)] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][PA[t]], b[PB[t]], acc[i >> 1][j >> 1][(i & 1) * 2 + (j & 1)], 0, 0, 0);
-  }
-}
-
-// gemm_mainloop3 on the K32 form; both tiles k-major (the weight-gradient GEMM).
-template <class G, class TA, class TB, class LA, class LB>
-__device__ __forceinline__ void gemm_mainloop3_k32(const LA& la, const LB& lb, int kt_begin, int kt_end,
-                                                   unsigned char* smem, f32x4 (&acc)[G::TM][G::TN][4], bool fair = false,
-                                                   bool zero_acc = true) {
-  using SA = typename SplitTile<TA>::type;
-  using SB = typename SplitTile<TB>::type;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
-  constexpr int PAST = 1 << 24;
-  if (zero_acc) {
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-      for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][b][r] = 0.f;
-  }
-  if (kt_begin >= kt_end) { prio_hi(); return; }
-  Split4 pa[TA::PASSES], pb[TB::PASSES];
-  unsigned char* sA = smem;
-  unsigned char* sB = smem + SA::BYTES;
-  float4 ra[TA::PASSES], rb[TB::PASSES];
-  auto split_all = [&]() {
-#pragma unroll
-    for (int p = 0; p < TA::PASSES; ++p) pa[p] = split4(ra[p]);
-#pragma unroll
-    for (int p = 0; p < TB::PASSES; ++p) pb[p] = split4(rb[p]);
-  };
-  la.load(kt_begin, ra); lb.load(kt_begin, rb); la.fix(ra); lb.fix(rb);
-  split_all();
-  la.load(kt_begin + 1 < kt_end ? kt_begin + 1 : PAST, ra);
-  lb.load(kt_begin + 1 < kt_end ? kt_begin + 1 : PAST, rb);
-  for (int kt = kt_begin; kt < kt_end; ++kt) {
-    __syncthreads();
-    SA::store(sA, pa, tid);
-    SB::store(sB, pb, tid);
-    __syncthreads();
-    prio_by_progress(fair, kt, kt_begin, kt_end);
-    mfma_tile3_k32<G, SA, SB>(sA, sB, wm, wn, lane, acc);
-    la.fix(ra); lb.fix(rb);
-    if (kt + 1 < kt_end) split_all();
-    la.load(kt + 2 < kt_end ? kt + 2 : PAST, ra);
-    lb.load(kt + 2 < kt_end ? kt + 2 : PAST, rb);
-  }
-  prio_hi();
-}
-
-// for_each_acc_row4 for the K32 accumulators (same staging, same callback)
-template <class G, class F>
-__device__ __forceinline__ void for_each_acc16_row4(const f32x4 (&acc)[G::TM][G::TN][4], float* smem, F&& f) {
-  constexpr int LDW = G::WTN + 4, LPR = G::WTN / 4, RPI = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
-  float* s = smem + wave * 32 * LDW;
-  __syncthreads();
-#pragma unroll
-  for (int im = 0; im < G::TM; ++im) {
-#pragma unroll
-    for (int in = 0; in < G::TN; ++in)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          s[((b >> 1) * 16 + 4 * (lane >> 4) + r) * LDW + in * 32 + (b & 1) * 16 + (lane & 15)] = acc[im][in][b][r];
-#pragma unroll
-    for (int rr = 0; rr < 32; rr += RPI) {
-      const int row = rr + lane / LPR, c4 = (lane % LPR) * 4;
-      const float4 v = *reinterpret_cast<const float4*>(&s[row * LDW + c4]);
-      f(wm + 32 * im + row, wn + c4, v);
-    }
-  }
-}
-
-template <class G, class F>
-__device__ __forceinline__ void for_each_acc16(const f32x4 (&acc)[G::TM][G::TN][4], F&& f) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
-#pragma unroll
-  for (int im = 0; im < G::TM; ++im)
-#pragma unroll
-    for (int in = 0; in < G::TN; ++in)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          f(wm + 32 * im + (b >> 1) * 16 + 4 * (lane >> 4) + r, wn + 32 * in + (b & 1) * 16 + (lane & 15), acc[im][in][b][r]);
 }
 
 // Walk the accumulators: f(row_in_tile, col_in_tile, value) for this lane's elements.
@@ -868,4 +715,3 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace embnet
-#endif  // EMBNET_DIAG_ENGINE

@@ -477,7 +477,7 @@ __global__ __launch_bounds__(256) void dwconv_dgrad4_s2_row_kernel(const float* 
 template <int KS, int ST>
 __global__ __launch_bounds__(64 * KS) void dwconv_wgrad4_wave_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                      DwGeom g, int cq_lanes, int units_per_block,
-                                                                     float* __restrict__ partial, int colmajor) {
+                                                                     float* __restrict__ partial) {
   constexpr int TW = DW_TW, NX = (TW - 1) * ST + KS, TAPS = KS * KS;
   // the TW dy quads of a unit are the same for the KS waves: each is fetched by ONE wave and handed over through LDS (two
   // buffers, one barrier per trip) — 4 instead of 4*KS of the workgroup's (4 + NX)*KS wave-wide L1 requests per unit
@@ -501,18 +501,12 @@ __global__ __launch_bounds__(64 * KS) void dwconv_wgrad4_wave_kernel(const float
       const int uu = u0 + it * unit_lanes + ul;
       const bool live = cok && uu < u1;
       const int u = min(uu, u1 - 1);
-      // colmajor: consecutive units run DOWN a 4-column block of an image, so the image row wave r reads for unit oh + 1
-      // is the one wave r + 1 read for unit oh a moment ago (L1 hit) — row-major, the KS reads of an image row are a whole
-      // row of units apart and each comes from L2: (KS + 1) / 2 x the compulsory bytes on the L2 -> L1 path
-      int row, ow0, n, oh;
-      if (colmajor) {
-        const int per_img = g.OH * wb_n;
-        n = u / per_img; const int rem = u - n * per_img, wb = rem / g.OH;
-        oh = rem - wb * g.OH; ow0 = wb * TW; row = n * g.OH + oh;
-      } else {
-        row = u / wb_n; ow0 = (u - row * wb_n) * TW;
-        n = row / g.OH; oh = row - n * g.OH;
-      }
+      // consecutive units run DOWN a 4-column block of an image, so the image row wave r reads for unit oh + 1 is the one
+      // wave r + 1 read for unit oh a moment ago (L1 hit) — row-major, the KS reads of an image row are a whole row of units
+      // apart and each comes from L2: (KS + 1) / 2 x the compulsory bytes on the L2 -> L1 path
+      const int per_img = g.OH * wb_n;
+      const int n = u / per_img, rem = u - n * per_img, wb = rem / g.OH;
+      const int oh = rem - wb * g.OH, ow0 = wb * TW, row = n * g.OH + oh;
       const int iw0 = ow0 * ST - g.pad_l, ih = oh * ST + r - g.pad_t;
       const bool rok = live && (unsigned)ih < (unsigned)g.H;
       const long rbase = ((long)n * g.H + (rok ? ih : 0)) * g.W;
@@ -828,9 +822,8 @@ static int make_dw(DwGeom& g, int n, int h, int w, int c, int r, int s, int stri
 }
 
 static bool dw_wide(const DwGeom& g) {
-  static const int forced = (int)env_long("EMBNET_DW_TW", 0);            // 4 / 8: A/B
   // eight columns per thread unless that wastes more than an eighth of a row the four-column blocks tile exactly
-  return forced ? forced == 8 : (g.OW >= 7 && cdiv(g.OW, 8) * 8 <= cdiv(g.OW, 4) * 4 + g.OW / 8);
+  return g.OW >= 7 && cdiv(g.OW, 8) * 8 <= cdiv(g.OW, 4) * 4 + g.OW / 8;
 }
 static bool dw_rows2(const DwGeom& g) { static const int rows2 = (int)env_long("EMBNET_DW_ROWS2", 1); return rows2 && g.OH >= 2; }
 // statistics variants: 256-thread chunks per workgroup, so that a launch writes at most ~2048 rows of partials (dw_block_accumulate)
@@ -1045,10 +1038,9 @@ static int dw_wave_slabs(long nunits, int c, int& cq_lanes, int& cgroups, int& u
   // kernel runs at the rate the L1 takes wave-wide requests): take the widest group of >= 8 lanes (one 128-byte line per
   // pixel) that wastes the fewest lanes.  Measured per layer (profiles/r04_exp_dw_wgrad_lanes.txt): C = 96, 480, 672, 1152 gain
   // 9 - 29 %; C = 144 (36 quads) loses 30 % in 8-lane groups and more in 4-lane groups, so a C/4 that fits one wave stays whole.
-  static const int pack = (int)env_long("EMBNET_DW_WGRAD_PACK", 1);
   const int c4 = c / 4;
   cq_lanes = 1; while (cq_lanes < c4 && cq_lanes < 64) cq_lanes <<= 1;
-  if (pack && !(c4 > 32 && c4 <= 64)) {                    // (33..64 quads: one masked 64-lane group is the fastest form measured)
+  if (!(c4 > 32 && c4 <= 64)) {                           // (33..64 quads: one masked 64-lane group is the fastest form measured)
     auto use = [&](int l) { return (double)c4 / ((double)l * cdiv(c4, l)); };
     int best = cq_lanes;
     for (int l = cq_lanes >> 1; l >= 8; l >>= 1) if (use(l) > use(best) + 1e-9) best = l;
@@ -1093,13 +1085,12 @@ extern "C" int embnet_dwconv2d_wgrad_f32(const float* x, const float* dy, float*
     int upb, cql, cgroups;
     const int blocks = dw_wave_slabs((long)n * oh * cdiv(ow, DW_TW), c, cql, cgroups, upb);
     const dim3 grid(blocks, cgroups);
-    static const int colmajor = (int)env_long("EMBNET_DW_WGRAD_COLMAJOR", 1);
     {
       EMBNET_TRACE("embnet::dwconv_wgrad4_wave_kernel", TRACE_BYTES, 4.0 * n * c * ((double)h * wd + (double)oh * ow), stream);
-      if (r == 3 && stride == 1) dwconv_wgrad4_wave_kernel<3, 1><<<grid, 192, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace, colmajor);
-      else if (r == 3) dwconv_wgrad4_wave_kernel<3, 2><<<grid, 192, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace, colmajor);
-      else if (stride == 1) dwconv_wgrad4_wave_kernel<5, 1><<<grid, 320, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace, colmajor);
-      else dwconv_wgrad4_wave_kernel<5, 2><<<grid, 320, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace, colmajor);
+      if (r == 3 && stride == 1) dwconv_wgrad4_wave_kernel<3, 1><<<grid, 192, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace);
+      else if (r == 3) dwconv_wgrad4_wave_kernel<3, 2><<<grid, 192, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace);
+      else if (stride == 1) dwconv_wgrad4_wave_kernel<5, 1><<<grid, 320, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace);
+      else dwconv_wgrad4_wave_kernel<5, 2><<<grid, 320, 0, S(stream)>>>(x, dy, g, cql, upb, (float*)workspace);
     }
     const long cnt = (long)r * s * c;
     { EMBNET_TRACE("embnet::dw_slab_sum_kernel", TRACE_BYTES, 4.0 * cnt * (blocks + 1), stream); dw_slab_sum_kernel<<<cdiv(cnt, 16), 256, 0, S(stream)>>>((const float*)workspace, blocks, cnt, dw); }

@@ -30,8 +30,6 @@ __device__ __forceinline__ float4 drop4(const DropArg& d, uint64_t seed, long i4
   return v;
 }
 
-static bool bn_scalar() { static const bool v = env_long("EMBNET_BN_SCALAR", 0) != 0; return v; }   // A/B knob
-
 // ---------------------------------------------------------------- column reductions over [M, C]
 // Layout of a 256-thread workgroup: cl channel lanes x rl row lanes (cl*rl = 256, cl a power of 2),
 // consecutive threads on consecutive channels -> coalesced rows.  Each workgroup reduces a slab of
@@ -475,8 +473,7 @@ static PixGeom pix_geom(int n, int hw, int c4) {
   g.cls_log2 = 4;
   while (g.cls_log2 > 0 && (1 << (g.cls_log2 - 1)) >= c4) --g.cls_log2;
   g.xblocks = (c4 + (1 << g.cls_log2) - 1) >> g.cls_log2;
-  static const long wide = env_long("EMBNET_PIX_WIDE", 1);               // A/B knob: 0 = 256 threads everywhere
-  g.threads = (wide && (long)g.xblocks * n < 2048 && hw >= 256) ? 1024 : 256;
+  g.threads = ((long)g.xblocks * n < 2048 && hw >= 256) ? 1024 : 256;
   return g;
 }
 template <int Q, class F>
@@ -1534,7 +1531,7 @@ static int bn_train_fwd_impl(const float* x, long m, int c, const float* gamma, 
   if (partial_in) {                         // sum / sum-of-squares partials [2][c][rows] already produced (conv epilogue)
     EMBNET_CHECK_ARG(partial_rows > 0, "bn_train_fwd: partial_rows=%d", partial_rows);
     partial = partial_in; nblocks = partial_rows;
-  } else if ((c & 3) == 0 && !bn_scalar()) {
+  } else if ((c & 3) == 0) {
     const ColGeom g4 = col_geom(m, c / 4);
     nblocks = g4.blocks;
     { EMBNET_TRACE("embnet::bn_stats4_kernel", TRACE_BYTES, 4.0 * m * c, stream); bn_stats4_kernel<<<g4.blocks, 256, 0, S(stream)>>>(x, m, c / 4, g4, (float*)workspace); }
@@ -1687,12 +1684,12 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
                        const float* dx_add, float* dx, float* dgamma, float* dbeta, void* dx_planes, void* workspace,
                        size_t workspace_bytes, uint32_t* emit, void* stream, const float* xhat_bound = nullptr,
                        const uint32_t* dx_add_range = nullptr) {
-  EMBNET_CHECK_ARG(!emit || (dx && (!dx_planes || planes_f16()) && (c & 3) == 0 && !bn_scalar() && save_mean && save_rstd &&
+  EMBNET_CHECK_ARG(!emit || (dx && (!dx_planes || planes_f16()) && (c & 3) == 0 && save_mean && save_rstd &&
                              !(reinterpret_cast<uintptr_t>(emit) & 3)),
                    "bn_bwd: a range of dx was requested but this call cannot emit one (an fp32 dx — beside planes only in the two-piece "
                    "format —, c %% 4 == 0, saved statistics, a 4-byte aligned slot)");
   EMBNET_CHECK_ARG(dy && x && scale && shift && (dx || dx_planes) && dgamma && dbeta && workspace, "bn_bwd: null pointer");
-  EMBNET_CHECK_ARG(dx || ((c & 3) == 0 && !bn_scalar()), "bn_bwd: dx = NULL (planes only) needs the four-channel kernels");
+  EMBNET_CHECK_ARG(dx || (c & 3) == 0, "bn_bwd: dx = NULL (planes only) needs the four-channel kernels");
   EMBNET_CHECK_ARG(!dx_planes || ((c & 15) == 0 && (size_t)m * c * 2 < 0x7FFFFFF0ull / 3), "bn_bwd: dx_planes needs c %% 16 == 0");
   EMBNET_CHECK_ARG(!training || (save_mean && save_rstd), "bn_bwd: training needs saved statistics");
   EMBNET_CHECK_ARG(m > 0 && c > 0, "bn_bwd: m=%ld c=%d", m, c);
@@ -1705,12 +1702,11 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
   // save_mean/save_rstd when given, else zeros.
   // planes in the two-piece format need dx's range before the apply pass: from the bound (the reduction's max |dz|, the forward's
   // max |xhat|, the range of what is added) where all of it is at hand, else from a dry run of the pass (launch_bn_bwd_apply4)
-  static const bool no_dry = env_long("EMBNET_BN_BWD_BOUND", 1) != 0;          // 0: round 5's dry run (A/B)
-  const bool bound = no_dry && dx_planes && planes_f16() && (c & 3) == 0 && !bn_scalar() && save_mean && save_rstd &&
+  const bool bound = dx_planes && planes_f16() && (c & 3) == 0 && save_mean && save_rstd &&
                      (xhat_bound || !training) && (!dx_add || dx_add_range);
   float* dx_bound = nullptr;
   if (save_mean && save_rstd) {
-    if ((c & 3) == 0 && !bn_scalar()) {
+    if ((c & 3) == 0) {
       const ColGeom g4 = col_geom(m, c / 4);
       float* pmax = bound ? partial + (size_t)g4.blocks * 2 * c : nullptr;
       if (bound) dx_bound = pmax + (size_t)g4.blocks * c;
@@ -1724,7 +1720,7 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
   } else {
     zero2_kernel<<<cdiv(c, 256), 256, 0, S(stream)>>>(dbeta, dgamma, c);
   }
-  if ((c & 3) == 0 && !bn_scalar())
+  if ((c & 3) == 0)
     { EMBNET_TRACE(dx_bound ? "void embnet::bn_bwd_apply4_kernel<4>" : emit && !dx_planes ? "void embnet::bn_bwd_apply4_kernel<3>" : dx_planes && planes_f16() ? "void embnet::bn_bwd_apply4_kernel<1>" : "void embnet::bn_bwd_apply4_kernel<0>", TRACE_BYTES, ((dx_add ? 16.0 : 12.0) + (dx_planes && planes_f16() && !dx_bound ? 8.0 : 0.0)) * m * c, stream);   // (<1>: + the dry run <2>; the names rocprofv3 prints)
       launch_bn_bwd_apply4(dy, x, m, c, save_mean, save_rstd, scale, shift, dbeta, dgamma, relu, training, dx_add, dx, dx_planes, S(stream), emit, dx_bound, dx_add_range); }
   else
@@ -1854,9 +1850,8 @@ static int bn_bwd_partials_impl(const float* dy, const float* x, long m, int c, 
   EMBNET_CHECK_ARG(m > 0 && c > 0 && (c & 3) == 0 && rows > 0, "bn_bwd_partials: m=%ld c=%d rows=%d (c %% 4 == 0)", m, c, rows);
   EMBNET_CHECK_ARG(!dx_planes || ((c & 15) == 0 && (size_t)m * c * 2 < 0x7FFFFFF0ull / 3), "bn_bwd_partials: dx_planes needs c %% 16 == 0");
   // the planes' scale from the bound where the partials carry the max |dz| plane (the per-channel bounds live behind the planes' slot)
-  static const bool no_dry = env_long("EMBNET_BN_BWD_BOUND", 1) != 0;
   const long total4 = m * c / 4;
-  const bool bound = no_dry && dx_planes && planes_f16() && partial_kinds == 3 && xhat_bound && (!dx_add || dx_add_range) && 2 * total4 >= 2 + c;
+  const bool bound = dx_planes && planes_f16() && partial_kinds == 3 && xhat_bound && (!dx_add || dx_add_range) && 2 * total4 >= 2 + c;
   float* dx_bound = bound ? planes_scale_slot(dx_planes, total4 * 4) + 2 : nullptr;
   bn_bwd_finalize_kernel<<<c, 256, 0, S(stream)>>>(partials, rows, c, dbeta, dgamma, 1, bound ? nullptr : emit,
                                                    bound ? partials + (size_t)2 * c * rows : nullptr, scale, xhat_bound, 1.f / (float)m, 1, dx_bound);

@@ -24,22 +24,6 @@ from ._lib import check, ptr, stream
 _WS = {}
 
 
-# Knob (off): run each conv's wgrad on a side stream beside its dgrad.  Measured on ResNet18/MI355X: +-0 % when
-# joined right after the dgrad (both are MFMA-bound), +1.8 % when the join is deferred to the end of backward so
-# wgrad overlaps the HBM-bound BN-backward kernels — not worth per-kernel timings that no longer mean anything
-# (co-running doubles the wgrad kernel's own duration) and hand-made gradient hand-over (autograd clones dW on
-# the main stream as soon as backward() returns it).
-OVERLAP_WGRAD = _os.environ.get("EMBNET_OVERLAP_WGRAD", "0") == "1"
-_SIDE = {}
-
-
-def _side_stream(device):
-    key = (device.type, device.index)
-    if key not in _SIDE:
-        _SIDE[key] = torch.cuda.Stream(device=device)
-    return _SIDE[key]
-
-
 _WS_RETIRED = []
 _WS_POISON = _os.environ.get("EMBNET_WS_POISON", "0") == "1"
 
@@ -587,9 +571,6 @@ def _emit_dx_range(dx):
     return slot
 
 
-_BN_SCALAR = _os.environ.get("EMBNET_BN_SCALAR", "0") not in ("0", "")
-
-
 def _planes_range_ok(x):
     """A BatchNorm backward that writes dx as planes AND as fp32 can leave dx's range too: in the two-piece format its dry run
     finds the maximum anyway."""
@@ -779,20 +760,9 @@ class _Conv2dFn(torch.autograd.Function):
             dy_planes = torch.empty(3 * dz.numel(), device=dz.device, dtype=torch.int16)
             check(lib.embnet_planes_from_f32(ptr(dz), dz.numel() // k, k, ptr(dy_planes), stream()))
 
-        def run_wgrad():
-            conv_wgrad(lib, x, dz, dw, w, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, in_scale, in_shift, ctx.in_act,
-                       getattr(ctx, "x_planes", None), dy_planes, dy_range, getattr(ctx, "x_range", None))
-
         dw_note = None
         if need_dw:
             dw, dw_note = _sink(w)
-        overlap = OVERLAP_WGRAD and need_dx and need_dw
-        if overlap:
-            main = torch.cuda.current_stream()
-            side = _side_stream(x.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                run_wgrad()
         if need_dx:
             dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
             if dy_planes is not None and patch_ok(n, oh, ow, k, r, s, c, 1, h, wd):
@@ -808,7 +778,6 @@ class _Conv2dFn(torch.autograd.Function):
                 check(lib.embnet_conv2d_dma1x1_f32(ptr(dz), ptr(weight_planes(w, 1)), None, ptr(dx), n, oh, ow, k, c, 1, h, wd, 0,
                                                    ptr(dskip), None, _rptr(dy_range), ptr(dws), dws.numel() * 4, stream()))
             else:
-                # its own scratch: with OVERLAP_WGRAD the wgrad slabs are in flight on the side stream's buffer
                 dws = workspace(lib.embnet_conv2d_dgrad_workspace_bytes(n, h, wd, c, r, s, k, stride), x.device)
                 bn_src = getattr(ctx, "bn_src", None) if dskip is None else None
                 rows = lib.embnet_conv2d_dgrad_bnsums_rows(n, h, wd, c, r, s, k, stride) if bn_src is not None else 0
@@ -827,11 +796,9 @@ class _Conv2dFn(torch.autograd.Function):
                     check(lib.embnet_conv2d_dgrad_f32_ex(
                         ptr(dz), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, 0, ptr(dskip), ptr(dws),
                         dws.numel() * 4, _rptr(dy_range), _rptr(w_range) if dy_range is not None else None, stream()))
-        if overlap:
-            torch.cuda.current_stream().wait_stream(side)
-        elif need_dw:
-            run_wgrad()
         if need_dw:
+            conv_wgrad(lib, x, dz, dw, w, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, in_scale, in_shift, ctx.in_act,
+                       getattr(ctx, "x_planes", None), dy_planes, dy_range, getattr(ctx, "x_range", None))
             dw = _done(dw, dw_note)
         if want_db:
             db, db_note = _sink(ctx.bias_ref)
@@ -1064,7 +1031,7 @@ class Conv2D(nn.Module):
         if _range_of(x) is None:
             return None
         kernel = self.kernel if kernel is None else kernel
-        if kernel.shape[2] % 4 or kernel.shape[3] % 4 or x.shape[-1] % 4 or _BN_SCALAR:
+        if kernel.shape[2] % 4 or kernel.shape[3] % 4 or x.shape[-1] % 4:
             return None
         return weight_range(self.kernel)
 
@@ -1100,7 +1067,7 @@ class Conv2D(nn.Module):
                 and (kernel.shape[0] * kernel.shape[1] * kernel.shape[2] >= 128 or x.numel() // x.shape[-1] >= (1 << 20))
                 and residual is None and not with_skip):
             cp = (x.shape[-1] + 3) // 4 * 4           # image input, large kernel: 4-channel copy, 16-byte gathers
-            x = pad_channels(x, cp, with_range=bool(CONV_F16[0] and getattr(self, "f16", False) and not _BN_SCALAR))
+            x = pad_channels(x, cp, with_range=bool(CONV_F16[0] and getattr(self, "f16", False)))
             kernel = _PadKernelFn.apply(kernel, cp)
         planes = getattr(x, "_planes", None) if in_stats is None else None
         if planes is not None and not self.patch_capable(x.shape):
@@ -1362,7 +1329,7 @@ class _BatchNormFn(torch.autograd.Function):
         planes_only = bool(planes_only and emit_planes and not dropout)
         y = _placeholder(x.shape, x.device) if planes_only else torch.empty_like(x)
         # mean, rstd, scale, shift; in training also row 4 = the per-channel bounds of |y| and row 5 = y's range slot (first word)
-        ranged = bool(training and c % 4 == 0 and not _BN_SCALAR)
+        ranged = bool(training and c % 4 == 0)
         stats = torch.empty((7 if ranged else 4, c), device=x.device, dtype=torch.float32)     # (row 6: the bounds of |xhat|, for backward)
         yk = None if (emit_planes or dropout) else y                         # planes / dropout: statistics first, then one pass
         if training:
@@ -1393,7 +1360,7 @@ class _BatchNormFn(torch.autograd.Function):
             if len(_BN_FWD_STATS) > 64:
                 _BN_FWD_STATS.clear()
             _BN_FWD_STATS[y.data_ptr()] = (x, stats, int(relu))
-        ctx.emit_dx_range = bool(emit_dx_range) and c % 4 == 0 and training and not _BN_SCALAR
+        ctx.emit_dx_range = bool(emit_dx_range) and c % 4 == 0 and training
         ctx.emit_dx_planes = bool(emit_dx_planes) and c % 16 == 0
         ctx.dx_planes_only = bool(dx_planes_only) and ctx.emit_dx_planes and not with_skip
         ctx.in_relu_bias = in_relu_bias if (in_relu_bias is not None and not with_skip and c % 4 == 0) else None
@@ -2007,7 +1974,7 @@ def input_bn_conv(x, bn, conv, emit_stats=False, zero_sum_dy=False):
     r, s, c, k = conv.kernel.shape
     cp = c if c % 4 == 0 else c + 4 - c % 4                         # the fused stem pads the image channels
     w_range = None
-    if CONV_F16[0] and getattr(conv, "f16", False) and conv.kernel.shape[3] % 4 == 0 and not _BN_SCALAR:
+    if CONV_F16[0] and getattr(conv, "f16", False) and conv.kernel.shape[3] % 4 == 0:
         w_range = weight_range(conv.kernel)
     # the zoo ResNets' 7x7 / 2 stem on its own kernel (csrc/conv_stem.hip: every input pixel once per tile instead of 49 gathers per
     # output pixel) when both operands carry a range
@@ -2094,7 +2061,7 @@ class MaxPool2D(nn.Module):
         rc = getattr(x, "_relu_conv", None) if (FUSE_RELU_POOL[0] and torch.is_grad_enabled() and x.requires_grad) else None
         fused = rc is not None and x.shape[3] % 4 == 0 and x.shape[0] * x.shape[1] * x.shape[2] < 2 ** 31
         slot = None
-        if _range_of(x) is None and self.emit_range and CONV_F16[0] and x.shape[3] % 4 == 0 and not _BN_SCALAR:
+        if _range_of(x) is None and self.emit_range and CONV_F16[0] and x.shape[3] % 4 == 0:
             slot = _new_range_slot(x.device)
         want = bool(fused and getattr(x, "_wants_dy_range", False))
         y = _MaxPoolFn.apply(x, self.k, self.s, self.p, rc[0] if fused else None, slot, want)

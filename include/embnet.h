@@ -540,7 +540,7 @@ int embnet_bn_bwd(const float* dy, const float* x, long m, int c, const float* s
  * two-piece format the planes' scale then comes from an upper bound of |dx| —
  *   |scale_c| (max |dz| + |dbeta_c| / m + xhat_bound_c |dgamma_c| / m)  [+ the range of dx_add],
  * max |dz| per channel being a third output of the reduction pass — instead of from a DRY RUN of the apply pass (8 B per element
- * read once more: round 5's form, still taken when either pointer is missing; EMBNET_BN_BWD_BOUND=0 forces it). */
+ * read once more: round 5's form, still taken when either pointer is missing). */
 int embnet_bn_bwd_ex(const float* dy, const float* x, long m, int c, const float* save_mean, const float* save_rstd,
                      const float* scale, const float* shift, int relu, int training, const float* dx_add, float* dx,
                      float* dgamma, float* dbeta, void* dx_planes, void* workspace, size_t workspace_bytes, uint32_t* dx_range,
