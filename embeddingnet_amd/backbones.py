@@ -137,8 +137,8 @@ def _simple2(gen):
 
 
 RN_EPS = 2e-5
-DEFER_BN = __import__("os").environ.get("EMBNET_DEFER_BN", "0") == "1"
-EPILOGUE_STATS = __import__("os").environ.get("EMBNET_EPILOGUE_STATS", "1") == "1"
+DEFER_BN = L.env_switch("EMBNET_DEFER_BN", False)
+EPILOGUE_STATS = L.env_switch("EMBNET_EPILOGUE_STATS", True)
 RESNET = {"resnet18": ("basic", (2, 2, 2, 2)), "resnet34": ("basic", (3, 4, 6, 3)),
           "resnet50": ("bottleneck", (3, 4, 6, 3))}
 

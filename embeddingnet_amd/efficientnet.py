@@ -43,7 +43,7 @@ def block_list(name):
     return out, round_filters(32, width), round_filters(1280, width)
 
 
-EFFNET_F16 = __import__("os").environ.get("EMBNET_EFFNET_F16", "1") != "0"
+EFFNET_F16 = L.env_switch("EMBNET_EFFNET_F16", True)
 
 
 def _conv(cin, cout, k, stride, gen):

@@ -12,6 +12,7 @@ glorot_uniform; 'same' pads extra on the bottom/right; BatchNormalization
 momentum .99, eps 1e-3, biased batch variance in training; MaxPool2D() 2x2/2;
 Dropout inverted scaling; l2(lambda) = lambda * sum(w^2) on kernels.
 """
+import contextlib
 import math
 import os as _os
 
@@ -21,11 +22,28 @@ from torch import nn
 from . import _lib
 from ._lib import check, ptr, stream
 
+
+def env_switch(var, default):
+    """A run-time switch: "0" in its environment variable is off, "1" is on, unset or anything else is `default`."""
+    return {"0": False, "1": True}.get(_os.environ.get(var), default)
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """`with switches(PATCH_CONV=False, ...):` sets those list-valued switches of this module and restores what they held."""
+    old = {name: globals()[name][0] for name in values}
+    try:
+        for name, v in values.items():
+            globals()[name][0] = v
+        yield
+    finally:
+        for name, v in old.items():
+            globals()[name][0] = v
+
+
 _WS = {}
-
-
 _WS_RETIRED = []
-_WS_POISON = _os.environ.get("EMBNET_WS_POISON", "0") == "1"
+_WS_POISON = env_switch("EMBNET_WS_POISON", False)
 
 
 def workspace(nbytes, device):
@@ -137,10 +155,23 @@ class _CtxDict:
         return getattr(_CONTEXTS[-1], self._n)
 
     def __setitem__(self, k, v):
-        ctx = _CONTEXTS[-1]
+        cur = _CONTEXTS[-1]
         if self._n in StepContext.BACKWARD:
-            _arm_cleanup(ctx)
-        getattr(ctx, self._n)[k] = v
+            _arm_cleanup(cur)
+        getattr(cur, self._n)[k] = v
+
+    def put(self, k, v, cap, drop):
+        """self[k] = v under a size cap: an entry whose consumer never comes (the gradient got a second contribution and is another
+        tensor; the consumer fell back to its fp32 kernel) pins its tensors until the backward ends, or for good outside one.
+        drop="all": beyond `cap` entries drop them all (entries normally claimed at once); "oldest": from `cap` entries on evict
+        the oldest first (some go unclaimed in ordinary use: keep few)."""
+        assert drop in ("all", "oldest"), drop
+        d = self._d()
+        if drop == "all" and len(d) > cap:
+            d.clear()
+        while drop == "oldest" and len(d) >= cap:
+            d.pop(next(iter(d)))
+        self[k] = v
 
     def __getitem__(self, k):
         return self._d()[k]
@@ -194,12 +225,12 @@ class _CtxList:
 
 
 SLAB_DEFER = [False]
-SLAB_DEFER_ENABLED = [_os.environ.get("EMBNET_SLAB_DEFER", "1") != "0"]      # [False]: per-layer slab sums everywhere (A/B)
+SLAB_DEFER_ENABLED = [env_switch("EMBNET_SLAB_DEFER", True)]      # [False]: per-layer slab sums everywhere (A/B)
 _SLAB_PENDING = _CtxList("slab_pending")          # (slab buffer, dw, elements, splits, kernel) of the current context
 _SLAB_BUFS = {}             # kernel storage address -> slab buffer (scratch: any stale content is overwritten before use)
 
 
-WGRAD_PLANES = [_os.environ.get("EMBNET_WGRAD_PLANES", "1") != "0"]   # [False]: every weight gradient on the gather loop (A/B)
+WGRAD_PLANES = [env_switch("EMBNET_WGRAD_PLANES", True)]   # [False]: every weight gradient on the gather loop (A/B)
 _SLAB_RETIRED = []          # replaced slab buffers: a captured graph may still write into them, so they are never freed
 
 
@@ -332,46 +363,46 @@ def _done(out, notify):
 # embnet_conv2d_dgrad_bnsums_f32 and leaves the partial sums here under its dx's address; the BatchNormalization backward that
 # receives exactly that tensor starts at its finalize kernel.  (The entry keeps an alias of dx: autograd then never
 # accumulates a second consumer's gradient into it in place, so a hit means dy IS that data gradient.)
-FUSE_BN_SUMS = [__import__("os").environ.get("EMBNET_FUSE_BN_SUMS", "1") == "1"]
+FUSE_BN_SUMS = [env_switch("EMBNET_FUSE_BN_SUMS", True)]
 # ... and a stride-1 3x3 Conv2D on the patch kernel to embnet_conv2d_patch_bnsums_f32 (the same sums from that kernel's epilogue).
 # OFF by default: the epilogue's reads of the BatchNormalization's input cost the data-gradient launches more (+0.5 ms per
 # ResNet18 step) than the thirteen reduction launches they replace (0.3 ms): C2 10.75 -> 10.97 ms, C3 106.1 -> 107.1
 # (profiles/r05_exp_patch_bnsums.txt).
-PATCH_BN_SUMS = [__import__("os").environ.get("EMBNET_PATCH_BN_SUMS", "0") == "1"]
-# the pooled branch's gradient (squeeze-and-excite) added inside the BatchNorm-backward passes instead of by a pass of its own
-# the squeeze-and-excite multiply's backward (dy * gate) applied inside the BatchNorm backward too (MBConv opts in: lazy_scale)
+PATCH_BN_SUMS = [env_switch("EMBNET_PATCH_BN_SUMS", False)]
 # BatchNorm apply + DropConnect + Add of an MBConv tail as one pass, the drop factor applied inside the BatchNorm backward
-FUSE_DROP_ADD = [__import__("os").environ.get("EMBNET_FUSE_DROP_ADD", "1") == "1"]
-DW_EMIT_STATS = [__import__("os").environ.get("EMBNET_DW_EMIT_STATS", "1") == "1"]     # depthwise forward emits the next BN's statistics
-DW_BN_SUMS = [__import__("os").environ.get("EMBNET_DW_BN_SUMS", "1") == "1"]   # ... and its stride-1 data gradient the previous BN's backward sums
-SE_TWO_STAGE = [__import__("os").environ.get("EMBNET_SE_TWO_STAGE", "1") == "1"]  # ... and the activated tensor is never written (se_gate)
+FUSE_DROP_ADD = [env_switch("EMBNET_FUSE_DROP_ADD", True)]
+DW_EMIT_STATS = [env_switch("EMBNET_DW_EMIT_STATS", True)]     # depthwise forward emits the next BN's statistics
+DW_BN_SUMS = [env_switch("EMBNET_DW_BN_SUMS", True)]   # ... and its stride-1 data gradient the previous BN's backward sums
+SE_TWO_STAGE = [env_switch("EMBNET_SE_TWO_STAGE", True)]  # ... and the activated tensor is never written (se_gate)
 POOL_PENDING = _CtxDict("pool_pending")
-SE_BN_SUMS = [__import__("os").environ.get("EMBNET_SE_BN_SUMS", "1") == "1"]      # ... and its reduction pass rides on the gate's gradient pass
-FUSE_GATE_BN = [__import__("os").environ.get("EMBNET_FUSE_GATE_BN", "1") == "1"]
+SE_BN_SUMS = [env_switch("EMBNET_SE_BN_SUMS", True)]      # ... and its reduction pass rides on the gate's gradient pass
+# the squeeze-and-excite multiply's backward (dy * gate) applied inside the BatchNorm backward too (MBConv opts in: lazy_scale)
+FUSE_GATE_BN = [env_switch("EMBNET_FUSE_GATE_BN", True)]
 GATE_PENDING = _CtxDict("gate_pending")
-FUSE_GAP_BN = [__import__("os").environ.get("EMBNET_FUSE_GAP_BN", "1") == "1"]
+# the pooled branch's gradient (squeeze-and-excite) added inside the BatchNorm-backward passes instead of by a pass of its own
+FUSE_GAP_BN = [env_switch("EMBNET_FUSE_GAP_BN", True)]
 BN_SUMS = _CtxDict("bn_sums")
 _BN_FWD_STATS = _CtxDict("bn_fwd_stats")
 
 # a Dropout directly behind a BatchNormalization rides on the BatchNormalization's kernels (backbones.Seq); 0: separate passes
-FUSE_DROPOUT_BN = [__import__("os").environ.get("EMBNET_FUSE_DROPOUT_BN", "1") == "1"]
-FUSE_RELU_BN = [_os.environ.get("EMBNET_FUSE_RELU_BN", "1") != "0"]
+FUSE_DROPOUT_BN = [env_switch("EMBNET_FUSE_DROPOUT_BN", True)]
+FUSE_RELU_BN = [env_switch("EMBNET_FUSE_RELU_BN", True)]
 # conv -> ReLU -> MaxPool (the 'simple' backbone): the same hand-over from MaxPool2D's backward (embnet_maxpool_relu_bwd_colsum)
-FUSE_RELU_POOL = [_os.environ.get("EMBNET_FUSE_RELU_POOL", "1") != "0"]
+FUSE_RELU_POOL = [env_switch("EMBNET_FUSE_RELU_POOL", True)]
 RELU_DONE = _CtxDict("relu_done")
-PATCH_CONV = [_os.environ.get("EMBNET_CONV_PATCH", "1") != "0"]      # [False]: every conv on the gather kernels (A/B)
+PATCH_CONV = [env_switch("EMBNET_CONV_PATCH", True)]      # [False]: every conv on the gather kernels (A/B)
 # 1x1 convs marked `planes1x1` (backbones: the bottleneck's conv3, whose input is the thin tensor) run their FORWARD on the planes GEMM
 # (csrc/conv_patch.hip conv1x1_planes_kernel).  OFF by default: back to back the kernel beats the ranged gather kernel on every
 # stride-1 ResNet50 layer (profiles/r06_exp_conv1x1_planes.txt: 1024 -> 256 at 14x14 150 -> 81 us), but in the step the
 # BatchNormalization in front must write the planes BESIDE the fp32 copy the gather weight gradient still reads: C3 86.8 -> 87.8 ms
 # (profiles/r06_exp_conv1x1_step.txt).  It pays once a 1x1 planes weight gradient lets that tensor exist as planes only.
-CONV1X1_PLANES = [_os.environ.get("EMBNET_CONV_1X1_PLANES", "0") != "0"]
+CONV1X1_PLANES = [env_switch("EMBNET_CONV_1X1_PLANES", False)]
 # 1x1 convs whose operands both carry a range: the activation operand read as fp32 by LDS-DMA and split in the matrix waves
 # (csrc/conv_patch.hip conv1x1_a32_kernel) instead of the gather loop — forward, and the stride-1 data gradients that do not carry
 # BatchNorm-backward sums; output width >= 128.  Built, tested (tests/test_conv1x1_dma_gpu.py), OFF: 1.1 - 1.3 x the gather kernel
 # back to back, 86.0 -> 86.2 ms in the C3 step (profiles/r06_exp_conv1x1_dma_step.txt) — ResNet50's 1x1 layers are HBM-bound there.
-CONV1X1_DMA = [int(_os.environ.get("EMBNET_CONV_1X1_DMA_MODE", "0"))]
-STEM_CONV = [_os.environ.get("EMBNET_STEM_CONV", "1") != "0"]        # [False]: the ResNet stem's forward on the gather kernel (A/B)
+CONV1X1_DMA = [int(env_switch("EMBNET_CONV_1X1_DMA_MODE", 0))]          # (an integer mode: 0 off, 1 on)
+STEM_CONV = [env_switch("EMBNET_STEM_CONV", True)]        # [False]: the ResNet stem's forward on the gather kernel (A/B)
 
 
 def _dma1x1_ok(n, h, wd, c, k, stride, oh, ow):
@@ -487,7 +518,7 @@ def refresh_tensors(tensors, holder):
 # A pass that lacks either operand's range (an inference-mode BatchNormalization, a gradient that reaches the conv from anywhere
 # else) runs the six-term kernel.  Entries a backward leaves unclaimed are dropped — and counted — by the step context's
 # end-of-backward sweep (StepContext.unclaimed['dy_range']); nothing is ever dropped by size.
-CONV_F16 = [_os.environ.get("EMBNET_CONV_F16", "1") != "0"]           # [False]: six-term products everywhere (A/B)
+CONV_F16 = [env_switch("EMBNET_CONV_F16", True)]           # [False]: six-term products everywhere (A/B)
 DY_RANGE = _CtxDict("dy_range")
 
 
@@ -577,7 +608,7 @@ def _planes_range_ok(x):
     return _lib.lib().embnet_conv_planes_mfma_terms() == 3
 
 
-PLANES_ONLY = [_os.environ.get("EMBNET_PLANES_ONLY", "1") != "0"]     # [False]: every planes tensor keeps its fp32 copy (A/B)
+PLANES_ONLY = [env_switch("EMBNET_PLANES_ONLY", True)]     # [False]: every planes tensor keeps its fp32 copy (A/B)
 
 
 def _placeholder(shape, device):
@@ -614,16 +645,42 @@ def _patch_dgrad(dy_planes, w, dx, n, h, wd, c, r, s, k, pt, pl, oh, ow, dx_add,
         bn_x, bn_stats, bn_act = bn_src
         rows = lib.embnet_conv2d_patch_stats_rows(n, h, wd)
         partial = torch.empty((2, c, rows), device=dx.device, dtype=torch.float32)
-        sp = bn_stats.data_ptr()
+        st = _StatsRows(bn_stats)
         check(lib.embnet_conv2d_patch_bnsums_f32(ptr(dy_planes), ptr(weight_planes(w, 1)), ptr(dx), n, oh, ow, k, r, s, c,
-                                                 r - 1 - pt, s - 1 - pl, h, wd, ptr(bn_x), sp + 8 * c, sp + 12 * c, sp, sp + 4 * c,
+                                                 r - 1 - pt, s - 1 - pl, h, wd, ptr(bn_x), st.scale, st.shift, st.mean, st.rstd,
                                                  int(bn_act), ptr(partial), rows, ptr(ws), ws.numel() * 4, stream()))
-        while len(BN_SUMS) >= 8:     # unclaimed entries (the gradient got a second contribution) pin a dx each: keep few
-            BN_SUMS.pop(next(iter(BN_SUMS)))
-        BN_SUMS[dx.data_ptr()] = (partial, rows, bn_x.data_ptr(), dx.detach())
+        BN_SUMS.put(dx.data_ptr(), (partial, rows, bn_x.data_ptr(), dx.detach()), 8, "oldest")
         return
     check(lib.embnet_conv2d_patch_f32(ptr(dy_planes), ptr(weight_planes(w, 1)), None, ptr(dx), n, oh, ow, k, r, s, c,
                                       r - 1 - pt, s - 1 - pl, h, wd, 0, ptr(dx_add), None, ptr(ws), ws.numel() * 4, stream()))
+
+
+# ---- the BatchNormalization statistics tensor ----------------------------------------------------------------------------
+# Every BatchNorm forward writes a [height, C] fp32 tensor `stats`, saves it for its backward and lends it to the fused kernels
+# around the layer (Deferred, `_bn_src`, `_lazy_scale_ok`); the C entry points take its rows as separate addresses.  The rows:
+# mean, rstd (the batch statistics: training mode only), scale, shift (y = act(x * scale + shift)), bound (per-channel bounds of
+# |y|, nn_kernels.hip channel_bound), range (first word: the range slot of y, handed on as (stats, address): _rptr) and xhat
+# (per-channel bounds of |xhat|: what the backward needs to bound its dx without a dry run).  A layer allocates one of three
+# heights: 4 (mean .. shift), 6 (.. range: the output carries a range) or 7 (.. xhat: _BatchNormFn in training mode, C % 4 == 0).
+STATS_ROWS = ("mean", "rstd", "scale", "shift", "bound", "range", "xhat")
+STATS_HEIGHTS = (4, 6, 7)
+
+
+class _StatsRows:
+    """The row addresses of a statistics tensor by name, None (NULL to the C entry points) for a row it lacks.  Plain integers."""
+    __slots__ = STATS_ROWS
+
+    def __init__(self, stats):
+        p, height, row = stats.data_ptr(), stats.shape[0], 4 * stats.shape[1]
+        self.mean, self.rstd, self.scale, self.shift = p, p + row, p + 2 * row, p + 3 * row
+        self.bound, self.range = (p + 4 * row, p + 5 * row) if height >= 6 else (None, None)
+        self.xhat = p + 6 * row if height >= 7 else None
+
+
+def _in_affine(in_stats):
+    """(in_scale, in_shift) of the conv entry points — the rows of the Deferred BatchNormalization in front — or (None, None)."""
+    st = _StatsRows(in_stats) if in_stats is not None else None
+    return (st.scale, st.shift) if st is not None else (None, None)
 
 
 def _c(t):
@@ -639,6 +696,25 @@ def same_pad(n, k, s):
 
 
 # ----------------------------------------------------------------------------- conv
+def _gather_fwd(lib, x, w, bias, y, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, x_range, w_range, out_stats=None, relu=0,
+                residual=None, in_scale=None, in_shift=None, in_act=0):
+    """y = conv(x, w) on the gather kernel — on three products when BOTH operands' range slots are given and no in_scale, as conv_wgrad."""
+    ws = workspace(lib.embnet_conv2d_fwd_workspace_bytes(n, c, r, s, k, oh, ow), x.device)
+    xr, wr = (_rptr(x_range), _rptr(w_range)) if (x_range is not None and w_range is not None and in_scale is None) else (None, None)
+    check(lib.embnet_conv2d_fwd_f32_ex(
+        ptr(x), ptr(w), ptr(bias), ptr(y), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, int(relu), ptr(residual),
+        in_scale, in_shift, int(in_act), ptr(out_stats), ptr(ws), ws.numel() * 4, xr, wr, stream()))
+
+
+def _gather_dgrad(lib, dy, w, dx, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, dy_range, w_range, accumulate=0, dx_add=None):
+    """dx (accumulate: +=; dx_add: + that tensor) = the data gradient on the gather kernel — on three products as _gather_fwd."""
+    ws = workspace(lib.embnet_conv2d_dgrad_workspace_bytes(n, h, wd, c, r, s, k, stride), dx.device)
+    dr, wr = (_rptr(dy_range), _rptr(w_range)) if (dy_range is not None and w_range is not None) else (None, None)
+    check(lib.embnet_conv2d_dgrad_f32_ex(
+        ptr(dy), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, accumulate, ptr(dx_add), ptr(ws), ws.numel() * 4,
+        dr, wr, stream()))
+
+
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, geom, relu, residual=None, in_stats=None, in_act=0, out_stats=None, with_skip=False,
@@ -656,10 +732,7 @@ class _Conv2dFn(torch.autograd.Function):
         if c2 != c:
             raise _lib.EmbnetError(f"conv2d: input has {c} channels, kernel expects {c2}")
         stride, pt, pl, oh, ow = geom
-        # in_stats [4,C] (mean, rstd, scale, shift of the BatchNormalization in front): the kernels read
-        # act(x*scale + shift) on the fly, x being the BN's INPUT (layers.Deferred)
-        in_scale = (in_stats.data_ptr() + 8 * in_stats.shape[1]) if in_stats is not None else None
-        in_shift = (in_stats.data_ptr() + 12 * in_stats.shape[1]) if in_stats is not None else None
+        in_scale, in_shift = _in_affine(in_stats)
         if residual is not None:
             if relu:
                 raise _lib.EmbnetError("conv2d: a fused residual add goes with a linear conv (no fused ReLU)")
@@ -682,12 +755,8 @@ class _Conv2dFn(torch.autograd.Function):
             check(lib.embnet_conv2d_dma1x1_f32(ptr(x), ptr(weight_planes(w, 0)), ptr(bias), ptr(y), n, h, wd, c, k, stride, oh, ow,
                                                int(relu), ptr(residual), ptr(out_stats), _rptr(x_range), ptr(ws), ws.numel() * 4, stream()))
         else:
-            ws = workspace(lib.embnet_conv2d_fwd_workspace_bytes(n, c, r, s, k, oh, ow), x.device)
-            fr = w_range is not None and x_range is not None and in_stats is None
-            check(lib.embnet_conv2d_fwd_f32_ex(
-                ptr(x), ptr(w), ptr(bias), ptr(y), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, int(relu), ptr(residual),
-                in_scale, in_shift, int(in_act), ptr(out_stats), ptr(ws), ws.numel() * 4,
-                _rptr(x_range) if fr else None, _rptr(w_range) if fr else None, stream()))
+            _gather_fwd(lib, x, w, bias, y, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, x_range, w_range, out_stats, relu, residual,
+                        in_scale, in_shift, in_act)
         one = planes is not None and r == 1         # (a 1x1 planes forward: data and weight gradient run the gather kernels, on their ranges)
         ctx.patch = planes is not None and not one
         ctx.w_range = w_range if ((planes is None or one) and in_stats is None) else None
@@ -716,7 +785,7 @@ class _Conv2dFn(torch.autograd.Function):
         dskip = _c(dskip) if dskip is not None else None
         dx = dw = db = None
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        w_range = getattr(ctx, "w_range", None)
+        w_range = ctx.w_range
         dz_range = None                      # (fused ReLU) the range of dz, from the pass that applied the mask
         done = RELU_DONE.pop(dy.data_ptr(), None) if (ctx.relu and RELU_DONE) else None
         if done is not None and done[0].shape == dy.shape:
@@ -741,8 +810,7 @@ class _Conv2dFn(torch.autograd.Function):
                 check(lib.embnet_relu_bwd(ptr(dy), ptr(y), dy.numel(), ptr(dz), stream()))
         else:
             dz = dy
-        in_scale = (in_stats.data_ptr() + 8 * in_stats.shape[1]) if in_stats is not None else None
-        in_shift = (in_stats.data_ptr() + 12 * in_stats.shape[1]) if in_stats is not None else None
+        in_scale, in_shift = _in_affine(in_stats)
 
         # planes of dy left by the BatchNormalization behind this conv (only usable when dz IS dy: no fused ReLU)
         dy_planes = _take_dy_planes(dy) if (ctx.patch and not ctx.relu) else None
@@ -766,11 +834,10 @@ class _Conv2dFn(torch.autograd.Function):
         if need_dx:
             dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
             if dy_planes is not None and patch_ok(n, oh, ow, k, r, s, c, 1, h, wd):
-                _patch_dgrad(dy_planes, w, dx, n, h, wd, c, r, s, k, pt, pl, oh, ow, dskip,
-                             getattr(ctx, "bn_src", None) if dskip is None else None)
+                _patch_dgrad(dy_planes, w, dx, n, h, wd, c, r, s, k, pt, pl, oh, ow, dskip, ctx.bn_src if dskip is None else None)
             elif (r == 1 and s == 1 and stride == 1 and dy_range is not None and w_range is not None and w.shape[3] % 16 == 0
                   and _dma1x1_ok(n, oh, ow, k, c, 1, h, wd)
-                  and (dskip is not None or getattr(ctx, "bn_src", None) is None
+                  and (dskip is not None or ctx.bn_src is None
                        or lib.embnet_conv2d_dgrad_bnsums_rows(n, h, wd, c, r, s, k, stride) <= 0)):
                 # 1x1 stride-1 data gradient without BatchNorm sums: dz by LDS-DMA as fp32 against the flipped kernel planes (c and k
                 # swap roles)
@@ -778,27 +845,23 @@ class _Conv2dFn(torch.autograd.Function):
                 check(lib.embnet_conv2d_dma1x1_f32(ptr(dz), ptr(weight_planes(w, 1)), None, ptr(dx), n, oh, ow, k, c, 1, h, wd, 0,
                                                    ptr(dskip), None, _rptr(dy_range), ptr(dws), dws.numel() * 4, stream()))
             else:
-                dws = workspace(lib.embnet_conv2d_dgrad_workspace_bytes(n, h, wd, c, r, s, k, stride), x.device)
-                bn_src = getattr(ctx, "bn_src", None) if dskip is None else None
+                bn_src = ctx.bn_src if dskip is None else None
                 rows = lib.embnet_conv2d_dgrad_bnsums_rows(n, h, wd, c, r, s, k, stride) if bn_src is not None else 0
                 if rows > 0:
                     bn_x, bn_stats, bn_act = bn_src
+                    dws = workspace(lib.embnet_conv2d_dgrad_workspace_bytes(n, h, wd, c, r, s, k, stride), x.device)
                     partial = torch.empty((3, c, rows), device=x.device, dtype=torch.float32)      # sums, and max |dz| per band
-                    sp = bn_stats.data_ptr()
+                    st = _StatsRows(bn_stats)
                     check(lib.embnet_conv2d_dgrad_bnsums_f32_ex(
-                        ptr(dz), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, ptr(bn_x), sp + 8 * c, sp + 12 * c,
-                        sp, sp + 4 * c, int(bn_act), ptr(partial), rows, ptr(dws), dws.numel() * 4,
+                        ptr(dz), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, ptr(bn_x), st.scale, st.shift,
+                        st.mean, st.rstd, int(bn_act), ptr(partial), rows, ptr(dws), dws.numel() * 4,
                         _rptr(dy_range), _rptr(w_range) if dy_range is not None else None, stream()))
-                    while len(BN_SUMS) >= 8:     # unclaimed entries (the gradient got a second contribution) pin a dx each: keep few
-                        BN_SUMS.pop(next(iter(BN_SUMS)))
-                    BN_SUMS[dx.data_ptr()] = (partial, rows, bn_x.data_ptr(), dx.detach())
+                    BN_SUMS.put(dx.data_ptr(), (partial, rows, bn_x.data_ptr(), dx.detach()), 8, "oldest")
                 else:
-                    check(lib.embnet_conv2d_dgrad_f32_ex(
-                        ptr(dz), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, 0, ptr(dskip), ptr(dws),
-                        dws.numel() * 4, _rptr(dy_range), _rptr(w_range) if dy_range is not None else None, stream()))
+                    _gather_dgrad(lib, dz, w, dx, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, dy_range, w_range, 0, dskip)
         if need_dw:
             conv_wgrad(lib, x, dz, dw, w, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, in_scale, in_shift, ctx.in_act,
-                       getattr(ctx, "x_planes", None), dy_planes, dy_range, getattr(ctx, "x_range", None))
+                       ctx.x_planes, dy_planes, dy_range, ctx.x_range)
             dw = _done(dw, dw_note)
         if want_db:
             db, db_note = _sink(ctx.bias_ref)
@@ -827,8 +890,7 @@ class _ConvPairFn(torch.autograd.Function):
         x, w1, w2 = _c(x), _c(w1), _c(w2)
         lib = _lib.lib()
         n, h, wd, c = x.shape
-        in_scale = (in_stats.data_ptr() + 8 * in_stats.shape[1]) if in_stats is not None else None
-        in_shift = (in_stats.data_ptr() + 12 * in_stats.shape[1]) if in_stats is not None else None
+        in_scale, in_shift = _in_affine(in_stats)
         ys = []
         for w, geom, st in ((w1, geom1, out_stats1), (w2, geom2, None)):
             r, s, c2, k = w.shape
@@ -841,11 +903,8 @@ class _ConvPairFn(torch.autograd.Function):
                 check(lib.embnet_conv2d_patch_f32(ptr(planes), ptr(weight_planes(w, 0)), None, ptr(y), n, h, wd, c, r, s, k,
                                                   pt, pl, oh, ow, 0, None, ptr(st), ptr(ws), ws.numel() * 4, stream()))
             else:
-                ws = workspace(lib.embnet_conv2d_fwd_workspace_bytes(n, c, r, s, k, oh, ow), x.device)
-                wr = w_ranges[0 if w is w1 else 1]
-                check(lib.embnet_conv2d_fwd_f32_ex(
-                    ptr(x), ptr(w), None, ptr(y), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, 0, None, in_scale, in_shift,
-                    int(in_act), ptr(st), ptr(ws), ws.numel() * 4, _rptr(x_range) if wr is not None else None, _rptr(wr), stream()))
+                _gather_fwd(lib, x, w, None, y, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, x_range, w_ranges[0 if w is w1 else 1],
+                            st, 0, None, in_scale, in_shift, in_act)
             ys.append(y)
         ctx.patch = planes is not None
         ctx.w_ranges = (w_ranges[0] if planes is None else None, w_ranges[1])
@@ -860,8 +919,7 @@ class _ConvPairFn(torch.autograd.Function):
         x, w1, w2, in_stats = ctx.saved_tensors
         lib = _lib.lib()
         n, h, wd, c = x.shape
-        in_scale = (in_stats.data_ptr() + 8 * in_stats.shape[1]) if in_stats is not None else None
-        in_shift = (in_stats.data_ptr() + 12 * in_stats.shape[1]) if in_stats is not None else None
+        in_scale, in_shift = _in_affine(in_stats)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dws, first = [], True
         for w, geom, dy, need_dw in ((w1, ctx.geoms[0], dy1, ctx.needs_input_grad[1]),
@@ -876,23 +934,19 @@ class _ConvPairFn(torch.autograd.Function):
             dy_planes = _take_dy_planes(dy) if (ctx.patch and w is w1) else None
             if _is_placeholder(dy) and dy_planes is None:
                 raise _lib.EmbnetError("conv_pair backward: the gradient exists only as planes and they are gone (DY_PLANES)")
-            w_range = getattr(ctx, "w_ranges", (None, None))[0 if w is w1 else 1]
+            w_range = ctx.w_ranges[0 if w is w1 else 1]
             dy_range = _take_dy_range(dy) if (w_range is not None and not _is_placeholder(dy)) else None
             if dx is not None:
                 if dy_planes is not None and first and patch_ok(n, oh, ow, k, r, s, c, 1, h, wd):
                     _patch_dgrad(dy_planes, w, dx, n, h, wd, c, r, s, k, pt, pl, oh, ow, None)
-                else:
-                    sc = workspace(lib.embnet_conv2d_dgrad_workspace_bytes(n, h, wd, c, r, s, k, stride), x.device)
-                    check(lib.embnet_conv2d_dgrad_f32_ex(
-                        ptr(dy), ptr(w), ptr(dx), n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, 0 if first else 1, None,
-                        ptr(sc), sc.numel() * 4, _rptr(dy_range), _rptr(w_range) if dy_range is not None else None, stream()))
+                else:       # (the second data gradient adds into the first one's dx)
+                    _gather_dgrad(lib, dy, w, dx, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, dy_range, w_range, 0 if first else 1)
                 first = False
             dw = None
             if need_dw:
                 dw, note = _sink(w)
                 conv_wgrad(lib, x, dy, dw, w, n, h, wd, c, r, s, k, stride, pt, pl, oh, ow, in_scale, in_shift, ctx.in_act,
-                           getattr(ctx, "x_planes", None) if w is w1 else None, dy_planes, dy_range,
-                           getattr(ctx, "x_range", None) if w_range is not None else None)
+                           ctx.x_planes if w is w1 else None, dy_planes, dy_range, ctx.x_range if w_range is not None else None)
                 dw = _done(dw, note)
             dws.append(dw)
         if dx is not None and first:
@@ -1002,7 +1056,7 @@ def pad_channels(x, cp, with_range=False):
 # a first-layer conv on a 3-channel image with a large kernel (the `simple` backbone's 10x10x3 -> 64,
 # /root/reference/embedding_net/backbones.py:21-22) or on a large batch of large images (EfficientNet's 3x3 stride-2 stem at
 # 224x224 x 256: 234 + 309 us forward + weight gradient) runs the scalar-gather kernels: 18-82 TFLOP/s
-PAD_INPUT_CONV = [_os.environ.get("EMBNET_PAD_INPUT_CONV", "1") != "0"]
+PAD_INPUT_CONV = [env_switch("EMBNET_PAD_INPUT_CONV", True)]
 
 
 class Conv2D(nn.Module):
@@ -1203,7 +1257,7 @@ class _DenseFn(torch.autograd.Function):
 
 # The squeeze-and-excite gate sigmoid(Dense(swish(Dense(pooled)))) as one forward and two backward launches (csrc/se_mlp.hip)
 # instead of twelve dense / activation / column-sum launches of 6-16 us each (EMBNET_SE_MLP=0: the composed form).
-SE_MLP = [__import__("os").environ.get("EMBNET_SE_MLP", "1") == "1"]
+SE_MLP = [env_switch("EMBNET_SE_MLP", True)]
 
 
 class _SEMlpFn(torch.autograd.Function):
@@ -1264,30 +1318,27 @@ class Dense(nn.Module):
 
 
 # ----------------------------------------------------------------------------- batch norm
-def _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, act, y, stats, moving_mean, moving_var, partials=None, with_range=False):
-    """embnet_bn_train_fwd_ex; partials [2,C,P] = sums / sums of squares of x by row band from the producing conv's
-    epilogue (Conv2D(..., emit_stats=True)), which then replace the statistics pass over x.
-    stats with >= 5 rows: row 4 receives the per-channel bounds of |act(BN(x))| (nn_kernels.hip channel_bound); with_range (needs a
-    sixth row and y): the apply pass folds them into the range slot of y — the first word of row 5 (_stats_range); a seventh row
-    receives the per-channel bounds of |xhat| (what the backward needs to bound its dx without a dry run)."""
+def _bn_stats(x, m, c, height, gamma, beta, eps, momentum, act, training, moving_mean, moving_var, partials=None, y=None,
+              with_range=False):
+    """-> (stats [height, C], its _StatsRows): the first pass of every BatchNorm forward; y: it also writes act(BN(x)).  training:
+    partials [2,C,P] = sums / sums of squares of x by row band from the producing conv's epilogue (Conv2D(..., emit_stats=True))
+    replace the statistics pass over x; the `bound` and `xhat` rows, where stats has them, receive the per-channel bounds of
+    |act(BN(x))| and |xhat|; with_range (needs y): the apply pass folds the former into the range slot of y.  Else: moving statistics."""
     lib = _lib.lib()
+    stats = torch.empty((height, c), device=x.device, dtype=torch.float32)
+    st = _StatsRows(stats)
+    if not training:
+        check(lib.embnet_bn_infer_fwd(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), eps, int(act), ptr(y),
+                                      st.scale, st.shift, stream()))
+        return stats, st
     ws = workspace(lib.embnet_bn_workspace_bytes(m, c), x.device)
     if partials is not None and tuple(partials.shape[:2]) != (2, c):
         raise _lib.EmbnetError(f"BatchNormalization: statistics partials {tuple(partials.shape)} for {c} channels")
-    sp, sc = stats.data_ptr(), stats.shape[1]
-    bound = sp + 16 * sc if stats.shape[0] >= 5 else None
-    yr = sp + 20 * sc if (with_range and y is not None and stats.shape[0] >= 6) else None
-    xh = sp + 24 * sc if stats.shape[0] >= 7 else None
-    check(lib.embnet_bn_train_fwd_ex(ptr(x), m, c, ptr(gamma), ptr(beta), eps, momentum, int(act), ptr(y),
-                                     sp, sp + 4 * sc, sp + 8 * sc, sp + 12 * sc,
-                                     ptr(moving_mean), ptr(moving_var), ptr(partials),
-                                     partials.shape[2] if partials is not None else 0, ptr(ws), ws.numel() * 4, bound, yr, xh, stream()))
-
-
-def _stats_range(stats):
-    """The range slot inside a BatchNormalization's statistics tensor (rows: mean, rstd, scale, shift, bound, [range word]): (owner,
-    address) — see _rptr."""
-    return (stats, stats.data_ptr() + 20 * stats.shape[1])
+    check(lib.embnet_bn_train_fwd_ex(ptr(x), m, c, ptr(gamma), ptr(beta), eps, momentum, int(act), ptr(y), st.mean, st.rstd,
+                                     st.scale, st.shift, ptr(moving_mean), ptr(moving_var), ptr(partials),
+                                     partials.shape[2] if partials is not None else 0, ptr(ws), ws.numel() * 4, st.bound,
+                                     st.range if (with_range and y is not None) else None, st.xhat, stream()))
+    return stats, st
 
 
 def _partials_of(x, training):
@@ -1328,38 +1379,28 @@ class _BatchNormFn(torch.autograd.Function):
         m = x.numel() // c
         planes_only = bool(planes_only and emit_planes and not dropout)
         y = _placeholder(x.shape, x.device) if planes_only else torch.empty_like(x)
-        # mean, rstd, scale, shift; in training also row 4 = the per-channel bounds of |y| and row 5 = y's range slot (first word)
         ranged = bool(training and c % 4 == 0)
-        stats = torch.empty((7 if ranged else 4, c), device=x.device, dtype=torch.float32)     # (row 6: the bounds of |xhat|, for backward)
         yk = None if (emit_planes or dropout) else y                         # planes / dropout: statistics first, then one pass
-        if training:
-            _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, relu, yk, stats, moving_mean, moving_var, partials, with_range=ranged)
-        else:
-            check(lib.embnet_bn_infer_fwd(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), eps,
-                                          int(relu), ptr(yk), (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]), stream()))
+        stats, st = _bn_stats(x, m, c, 7 if ranged else 4, gamma, beta, eps, momentum, relu, training, moving_mean, moving_var,
+                              partials, yk, with_range=ranged)
         if emit_planes:
             planes = torch.empty(3 * x.numel(), device=x.device, dtype=torch.int16)
             # the planes' scale: from the bounds (training) — or, without them (inference statistics), from a dry run of the pass
-            check(lib.embnet_affine_act_planes_ex(ptr(x), m, c, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c), int(relu),
-                                                  None if planes_only else ptr(y), ptr(planes),
-                                                  (stats.data_ptr() + 16 * c) if ranged else None,
-                                                  (stats.data_ptr() + 20 * c) if (ranged and not planes_only) else None, stream()))
+            check(lib.embnet_affine_act_planes_ex(ptr(x), m, c, st.scale, st.shift, int(relu), None if planes_only else ptr(y),
+                                                  ptr(planes), st.bound, None if planes_only else st.range, stream()))
             _ACT_PLANES[y.data_ptr()] = planes
         ctx.dropout = None
         if dropout:
             rate, seed = dropout
             ctx.dropout = (rate, seed, GRAPH_TICK)
-            check(lib.embnet_affine_act_dropout(ptr(x), m, c, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c), int(relu),
+            check(lib.embnet_affine_act_dropout(ptr(x), m, c, st.scale, st.shift, int(relu),
                                                 rate, seed, GRAPH_TICK, ptr(y), stream()))
             if ranged:       # |dropout(a)| <= |a| / (1 - rate): the range word from the channel bounds (no apply pass folded them)
-                check(lib.embnet_range_from_bound(stats.data_ptr() + 16 * c, c, 1.0 / (1.0 - float(rate)), None,
-                                                  stats.data_ptr() + 20 * c, stream()))
+                check(lib.embnet_range_from_bound(st.bound, c, 1.0 / (1.0 - float(rate)), None, st.range, stream()))
         if ranged and not planes_only:
-            _ACT_RANGE[y.data_ptr()] = _stats_range(stats)
+            _ACT_RANGE[y.data_ptr()] = (stats, st.range)
         if training and FUSE_BN_SUMS[0] and c % 4 == 0 and not dropout:
-            if len(_BN_FWD_STATS) > 64:
-                _BN_FWD_STATS.clear()
-            _BN_FWD_STATS[y.data_ptr()] = (x, stats, int(relu))
+            _BN_FWD_STATS.put(y.data_ptr(), (x, stats, int(relu)), 64, "all")
         ctx.emit_dx_range = bool(emit_dx_range) and c % 4 == 0 and training
         ctx.emit_dx_planes = bool(emit_dx_planes) and c % 16 == 0
         ctx.dx_planes_only = bool(dx_planes_only) and ctx.emit_dx_planes and not with_skip
@@ -1387,32 +1428,27 @@ class _BatchNormFn(torch.autograd.Function):
             e = DY_RANGE.pop(dskip.data_ptr(), None)
             if e is not None and e[1].shape == dskip.shape:
                 dskip_range = e[0]
-        xh = (stats.data_ptr() + 24 * c) if stats.shape[0] >= 7 else None     # bounds of |xhat| from the forward statistics
-        only = getattr(ctx, "dx_planes_only", False) and dskip is None
+        st = _StatsRows(stats)              # (st.xhat: the bounds of |xhat| from the forward statistics, when it left them)
+        only = ctx.dx_planes_only and dskip is None
         dx = _placeholder(x.shape, x.device) if only else torch.empty_like(x)
         dxp = None if only else ptr(dx)
         tg, tb, finish = _bn_grad_targets(ctx, c, x.device)
         ws = workspace(lib.embnet_bn_workspace_bytes(m, c), x.device)
-        mean = stats.data_ptr() if ctx.training else None
-        rstd = (stats.data_ptr() + 4 * stats.shape[1]) if ctx.training else None
+        mean, rstd = (st.mean, st.rstd) if ctx.training else (None, None)
         planes = None
-        if getattr(ctx, "emit_dx_planes", False):
+        if ctx.emit_dx_planes:
             planes = torch.empty(3 * x.numel(), device=x.device, dtype=torch.int16)
-            if len(DY_PLANES) > 64:                  # entries nobody collected (a consumer fell back to the fp32 kernel)
-                DY_PLANES.clear()
-            DY_PLANES[dx.data_ptr()] = (planes, dx)
-        drop = getattr(ctx, "dropout", None)
-        inrelu = getattr(ctx, "in_relu_bias", None) is not None and planes is None and dskip is None
+            DY_PLANES.put(dx.data_ptr(), (planes, dx), 64, "all")
+        drop = ctx.dropout
+        inrelu = ctx.in_relu_bias is not None and planes is None and dskip is None
         hit = BN_SUMS.pop(dy.data_ptr(), None) if BN_SUMS else None
         if (hit is not None and hit[2] == x.data_ptr() and hit[3].shape == dy.shape and ctx.training and c % 4 == 0
                 and not inrelu and drop is None):
             # dy is the data gradient of the conv behind this layer, which already produced the column sums
-            dxr = None
-            if getattr(ctx, "emit_dx_range", False) and not only and (planes is None or _planes_range_ok(x)):
-                dxr = _emit_dx_range(dx)
-            check(lib.embnet_bn_bwd_partials_ex(ptr(dy), ptr(x), m, c, mean, rstd, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c),
+            dxr = _emit_dx_range(dx) if (ctx.emit_dx_range and not only and (planes is None or _planes_range_ok(x))) else None
+            check(lib.embnet_bn_bwd_partials_ex(ptr(dy), ptr(x), m, c, mean, rstd, st.scale, st.shift,
                                                 int(ctx.relu), ptr(hit[0]), hit[1], ptr(dskip), dxp, ptr(tg), ptr(tb), ptr(planes),
-                                                ptr(dxr), int(hit[0].shape[0]), xh, ptr(dskip_range), stream()))
+                                                ptr(dxr), int(hit[0].shape[0]), st.xhat, ptr(dskip_range), stream()))
             dgamma, dbeta = finish()
             return (dx, dgamma, dbeta) + (None,) * 15
         if drop is not None and not inrelu:      # the Dropout's backward as a pass of its own in front of the BN backward
@@ -1424,26 +1460,21 @@ class _BatchNormFn(torch.autograd.Function):
             (bias,) = ctx.in_relu_bias
             db, db_note = _sink(bias)
             # (the conv in front tagged its output `_wants_dy_range`: the exact range of dz rides on the pass, for its two gradients)
-            dzr = _emit_dx_range(dx) if getattr(ctx, "emit_dx_range", False) else None
+            dzr = _emit_dx_range(dx) if ctx.emit_dx_range else None
             if drop is not None:
-                check(lib.embnet_bn_bwd_inrelu_dropout_ex(ptr(dy), ptr(x), m, c, mean, rstd, (stats.data_ptr() + 8 * stats.shape[1]),
-                                                          (stats.data_ptr() + 12 * stats.shape[1]), int(ctx.relu), int(ctx.training),
-                                                          drop[0], drop[1], drop[2], ptr(dx), ptr(tg), ptr(tb), ptr(db), ptr(ws),
-                                                          ws.numel() * 4, ptr(dzr), stream()))
+                check(lib.embnet_bn_bwd_inrelu_dropout_ex(ptr(dy), ptr(x), m, c, mean, rstd, st.scale, st.shift, int(ctx.relu),
+                                                          int(ctx.training), drop[0], drop[1], drop[2], ptr(dx), ptr(tg), ptr(tb),
+                                                          ptr(db), ptr(ws), ws.numel() * 4, ptr(dzr), stream()))
             else:
-                check(lib.embnet_bn_bwd_inrelu_ex(ptr(dy), ptr(x), m, c, mean, rstd, (stats.data_ptr() + 8 * stats.shape[1]),
-                                                  (stats.data_ptr() + 12 * stats.shape[1]), int(ctx.relu), int(ctx.training), ptr(dx),
+                check(lib.embnet_bn_bwd_inrelu_ex(ptr(dy), ptr(x), m, c, mean, rstd, st.scale, st.shift,
+                                                  int(ctx.relu), int(ctx.training), ptr(dx),
                                                   ptr(tg), ptr(tb), ptr(db), ptr(ws), ws.numel() * 4, ptr(dzr), stream()))
-            if len(RELU_DONE) > 64:
-                RELU_DONE.clear()
-            RELU_DONE[dx.data_ptr()] = (dx.detach(), db, db_note)
+            RELU_DONE.put(dx.data_ptr(), (dx.detach(), db, db_note), 64, "all")
         else:
-            dxr = None
-            if getattr(ctx, "emit_dx_range", False) and not only and (planes is None or _planes_range_ok(x)):
-                dxr = _emit_dx_range(dx)
-            check(lib.embnet_bn_bwd_ex(ptr(dy), ptr(x), m, c, mean, rstd, (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]),
+            dxr = _emit_dx_range(dx) if (ctx.emit_dx_range and not only and (planes is None or _planes_range_ok(x))) else None
+            check(lib.embnet_bn_bwd_ex(ptr(dy), ptr(x), m, c, mean, rstd, st.scale, st.shift,
                                        int(ctx.relu), int(ctx.training), ptr(dskip), dxp, ptr(tg), ptr(tb), ptr(planes), ptr(ws),
-                                       ws.numel() * 4, ptr(dxr), xh, ptr(dskip_range), stream()))
+                                       ws.numel() * 4, ptr(dxr), st.xhat, ptr(dskip_range), stream()))
         dgamma, dbeta = finish()
         return (dx, dgamma, dbeta) + (None,) * 15
 
@@ -1462,16 +1493,10 @@ class _BNGapFn(torch.autograd.Function):
         n, c = x.shape[0], x.shape[-1]
         m = x.numel() // c
         ctx.lazy_scale = bool(lazy_scale)
-        stats = torch.empty((4, c), device=x.device, dtype=torch.float32)   # mean, rstd, scale, shift
-        if training:
-            _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, act, None, stats, moving_mean, moving_var, partials)
-        else:
-            check(lib.embnet_bn_infer_fwd(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), eps,
-                                          int(act), None, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c), stream()))
+        stats, st = _bn_stats(x, m, c, 4, gamma, beta, eps, momentum, act, training, moving_mean, moving_var, partials)
         y = torch.empty_like(x)
         g = torch.empty((n, c), device=x.device, dtype=torch.float32)
-        check(lib.embnet_affine_act_gap(ptr(x), n, m // n, c, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c), int(act),
-                                        ptr(y), ptr(g), stream()))
+        check(lib.embnet_affine_act_gap(ptr(x), n, m // n, c, st.scale, st.shift, int(act), ptr(y), ptr(g), stream()))
         ctx.relu, ctx.training, ctx.has_gamma = act, training, gamma is not None
         ctx.gamma_ref, ctx.beta_ref = gamma, beta
         ctx.save_for_backward(x, stats)
@@ -1489,8 +1514,9 @@ class _BNGapFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         tg, tb, finish = _bn_grad_targets(ctx, c, x.device)
         ws = workspace(lib.embnet_bn_workspace_bytes(m, c), x.device)
+        st = _StatsRows(stats)
         gate = None
-        if getattr(ctx, "lazy_scale", False):
+        if ctx.lazy_scale:
             ent = GATE_PENDING.pop(dy.data_ptr(), None)
             if ent is None or ent[1].shape != dy.shape:
                 raise _lib.EmbnetError("BatchNormalization(lazy_scale=True): the gradient of the gated tensor did not arrive "
@@ -1500,16 +1526,14 @@ class _BNGapFn(torch.autograd.Function):
                 dg = torch.zeros((n, c), device=x.device, dtype=torch.float32)
             if ent[2] is not None and ctx.training and m * (c // 4) < 2 ** 31 - 1:
                 # channel_scale's backward already summed everything this layer's dbeta / dgamma need (embnet_se_bn_sums)
-                check(lib.embnet_bn_bwd_gap_sums(ptr(dy), ptr(_c(dg)), ptr(gate), ptr(ent[2]), n, m // n, ptr(x), c, stats.data_ptr(),
-                                                 stats.data_ptr() + 4 * c, stats.data_ptr() + 8 * c, stats.data_ptr() + 12 * c,
-                                                 int(ctx.relu), ptr(dx), ptr(tg), ptr(tb), stream()))
+                check(lib.embnet_bn_bwd_gap_sums(ptr(dy), ptr(_c(dg)), ptr(gate), ptr(ent[2]), n, m // n, ptr(x), c, st.mean,
+                                                 st.rstd, st.scale, st.shift, int(ctx.relu), ptr(dx), ptr(tg), ptr(tb), stream()))
                 dgamma, dbeta = finish()
                 return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
         if dg is not None and ctx.training and (FUSE_GAP_BN[0] or gate is not None) and m * (c // 4) < 2 ** 31 - 1:
             # d(output) = dy (* gate) + dg / hw formed inside the two BatchNorm-backward passes: the summed tensor is never written
-            check(lib.embnet_bn_bwd_gap(ptr(dy), ptr(_c(dg)), ptr(gate), n, m // n, ptr(x), c, stats.data_ptr(), stats.data_ptr() + 4 * c,
-                                        stats.data_ptr() + 8 * c, stats.data_ptr() + 12 * c, int(ctx.relu), ptr(dx), ptr(tg), ptr(tb),
-                                        ptr(ws), ws.numel() * 4, stream()))
+            check(lib.embnet_bn_bwd_gap(ptr(dy), ptr(_c(dg)), ptr(gate), n, m // n, ptr(x), c, st.mean, st.rstd,
+                                        st.scale, st.shift, int(ctx.relu), ptr(dx), ptr(tg), ptr(tb), ptr(ws), ws.numel() * 4, stream()))
             dgamma, dbeta = finish()
             return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
         if gate is not None:                                # (not reached: lazy_scale is only granted in training mode)
@@ -1518,11 +1542,9 @@ class _BNGapFn(torch.autograd.Function):
             dz = torch.empty_like(dy)
             check(lib.embnet_gap_bwd(ptr(_c(dg)), n, m // n, c, ptr(dy), ptr(dz), stream()))
             dy = dz
-        mean = stats.data_ptr() if ctx.training else None
-        rstd = (stats.data_ptr() + 4 * c) if ctx.training else None
-        check(lib.embnet_bn_bwd(ptr(dy), ptr(x), m, c, mean, rstd, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c),
-                                int(ctx.relu), int(ctx.training), None, ptr(dx), ptr(tg), ptr(tb), None, ptr(ws),
-                                ws.numel() * 4, stream()))
+        mean, rstd = (st.mean, st.rstd) if ctx.training else (None, None)
+        check(lib.embnet_bn_bwd(ptr(dy), ptr(x), m, c, mean, rstd, st.scale, st.shift, int(ctx.relu), int(ctx.training), None,
+                                ptr(dx), ptr(tg), ptr(tb), None, ptr(ws), ws.numel() * 4, stream()))
         dgamma, dbeta = finish()
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
 
@@ -1538,11 +1560,10 @@ class _BNPoolFn(torch.autograd.Function):
         lib = _lib.lib()
         n, c = x.shape[0], x.shape[-1]
         m = x.numel() // c
-        stats = torch.empty((6 if c % 4 == 0 else 4, c), device=x.device, dtype=torch.float32)   # mean, rstd, scale, shift [, bound of |act(BN(x))|, range word]
-        _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, act, None, stats, moving_mean, moving_var, partials)
+        stats, st = _bn_stats(x, m, c, 6 if c % 4 == 0 else 4, gamma, beta, eps, momentum, act, True, moving_mean, moving_var,
+                              partials)             # (height 6: _BNScaleFn gives the gated output a range)
         g = torch.empty((n, c), device=x.device, dtype=torch.float32)
-        check(lib.embnet_affine_act_gap(ptr(x), n, m // n, c, (stats.data_ptr() + 8 * c), (stats.data_ptr() + 12 * c), int(act),
-                                        None, ptr(g), stream()))
+        check(lib.embnet_affine_act_gap(ptr(x), n, m // n, c, st.scale, st.shift, int(act), None, ptr(g), stream()))
         ctx.relu, ctx.has_gamma, ctx.token = act, gamma is not None, token
         ctx.gamma_ref, ctx.beta_ref = gamma, beta
         ctx.save_for_backward(x, stats)
@@ -1562,9 +1583,9 @@ class _BNPoolFn(torch.autograd.Function):
         dg, gate, sums = ent
         dx = torch.empty_like(x)
         tg, tb, finish = _bn_grad_targets(ctx, c, x.device)
-        sp = stats.data_ptr()
-        check(lib.embnet_bn_bwd_gap_sums(ptr(dg), ptr(_c(dpool)), ptr(gate), ptr(sums), n, m // n, ptr(x), c, sp, sp + 4 * c, sp + 8 * c,
-                                         sp + 12 * c, int(ctx.relu), ptr(dx), ptr(tg), ptr(tb), stream()))
+        st = _StatsRows(stats)
+        check(lib.embnet_bn_bwd_gap_sums(ptr(dg), ptr(_c(dpool)), ptr(gate), ptr(sums), n, m // n, ptr(x), c, st.mean, st.rstd, st.scale,
+                                         st.shift, int(ctx.relu), ptr(dx), ptr(tg), ptr(tb), stream()))
         dgamma, dbeta = finish()
         return dx, dgamma, dbeta, None, None, None, None, None, None, None
 
@@ -1580,11 +1601,11 @@ class _BNScaleFn(torch.autograd.Function):
         hw = x.numel() // (n * c)
         s = _c(s)
         y = torch.empty_like(x)
-        sp = stats.data_ptr()
-        check(_lib.lib().embnet_affine_act_scale(ptr(x), n, hw, c, sp + 8 * c, sp + 12 * c, int(act), ptr(s), ptr(y), stream()))
-        if stats.shape[0] >= 6:              # |act(BN(x)) * gate| <= the BatchNorm's output bound (the gate is a sigmoid): y's range slot
-            check(_lib.lib().embnet_range_from_bound(sp + 16 * c, c, 1.0, None, sp + 20 * c, stream()))
-            _ACT_RANGE[y.data_ptr()] = _stats_range(stats)
+        st = _StatsRows(stats)
+        check(_lib.lib().embnet_affine_act_scale(ptr(x), n, hw, c, st.scale, st.shift, int(act), ptr(s), ptr(y), stream()))
+        if st.range is not None:             # |act(BN(x)) * gate| <= the BatchNorm's output bound (the gate is a sigmoid): y's range slot
+            check(_lib.lib().embnet_range_from_bound(st.bound, c, 1.0, None, st.range, stream()))
+            _ACT_RANGE[y.data_ptr()] = (stats, st.range)
         ctx.act, ctx.token = int(act), token
         ctx.save_for_backward(x, s, stats)
         return y
@@ -1596,11 +1617,9 @@ class _BNScaleFn(torch.autograd.Function):
         hw = x.numel() // (n * c)
         dg = _c(dg)
         sums = torch.empty((n, 5, c), device=x.device, dtype=torch.float32)
-        sp = stats.data_ptr()
-        check(_lib.lib().embnet_se_bn_sums(ptr(dg), ptr(x), n, hw, c, sp, sp + 4 * c, sp + 8 * c, sp + 12 * c, ctx.act, ptr(sums), stream()))
-        while len(POOL_PENDING) >= 8:
-            POOL_PENDING.pop(next(iter(POOL_PENDING)))
-        POOL_PENDING[ctx.token] = (dg, s, sums)
+        st = _StatsRows(stats)
+        check(_lib.lib().embnet_se_bn_sums(ptr(dg), ptr(x), n, hw, c, st.mean, st.rstd, st.scale, st.shift, ctx.act, ptr(sums), stream()))
+        POOL_PENDING.put(ctx.token, (dg, s, sums), 8, "oldest")
         return None, sums[:, 0, :], None, None, None
 
 
@@ -1616,16 +1635,15 @@ class _BNDropAddFn(torch.autograd.Function):
         lib = _lib.lib()
         n, c = x.shape[0], x.shape[-1]
         m = x.numel() // c
-        stats = torch.empty((6 if skip_range is not None else 4, c), device=x.device, dtype=torch.float32)   # mean, rstd, scale, shift [, bound, range word]
-        _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, 0, None, stats, moving_mean, moving_var, partials)
+        stats, st = _bn_stats(x, m, c, 6 if skip_range is not None else 4, gamma, beta, eps, momentum, 0, True, moving_mean,
+                              moving_var, partials)
         y = torch.empty_like(x)
         factor = torch.empty((n, c), device=x.device, dtype=torch.float32)
-        check(lib.embnet_affine_drop_add(ptr(x), n, m // n, c, stats.data_ptr() + 8 * c, stats.data_ptr() + 12 * c, float(rate), seed,
+        check(lib.embnet_affine_drop_add(ptr(x), n, m // n, c, st.scale, st.shift, float(rate), seed,
                                          GRAPH_TICK, ptr(skip), ptr(y), ptr(factor), stream()))
         if skip_range is not None:
-            sp = stats.data_ptr()
-            check(lib.embnet_range_from_bound(sp + 16 * c, c, 1.0 / (1.0 - float(rate)), _rptr(skip_range), sp + 20 * c, stream()))
-            _ACT_RANGE[y.data_ptr()] = _stats_range(stats)
+            check(lib.embnet_range_from_bound(st.bound, c, 1.0 / (1.0 - float(rate)), _rptr(skip_range), st.range, stream()))
+            _ACT_RANGE[y.data_ptr()] = (stats, st.range)
         ctx.has_gamma, ctx.gamma_ref, ctx.beta_ref = gamma is not None, gamma, beta
         ctx.save_for_backward(x, stats, factor)
         return y
@@ -1641,8 +1659,8 @@ class _BNDropAddFn(torch.autograd.Function):
         tg, tb, finish = _bn_grad_targets(ctx, c, x.device)
         ws = workspace(lib.embnet_bn_workspace_bytes(m, c), x.device)
         zero = torch.zeros((n, c), device=x.device, dtype=torch.float32)
-        sp = stats.data_ptr()
-        check(lib.embnet_bn_bwd_gap(ptr(dy), ptr(zero), ptr(factor), n, m // n, ptr(x), c, sp, sp + 4 * c, sp + 8 * c, sp + 12 * c, 0,
+        st = _StatsRows(stats)
+        check(lib.embnet_bn_bwd_gap(ptr(dy), ptr(zero), ptr(factor), n, m // n, ptr(x), c, st.mean, st.rstd, st.scale, st.shift, 0,
                                     ptr(dx), ptr(tg), ptr(tb), ptr(ws), ws.numel() * 4, stream()))
         dgamma, dbeta = finish()
         return dx, dgamma, dbeta, None, None, None, None, None, dy, None, None, None
@@ -1672,8 +1690,8 @@ class _AffineActFn(torch.autograd.Function):
     def forward(ctx, raw, stats, act):
         y = torch.empty_like(raw)
         c = raw.shape[-1]
-        check(_lib.lib().embnet_affine_act(ptr(raw), raw.numel() // c, c, (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]),
-                                           int(act), ptr(y), stream()))
+        st = _StatsRows(stats)
+        check(_lib.lib().embnet_affine_act(ptr(raw), raw.numel() // c, c, st.scale, st.shift, int(act), ptr(y), stream()))
         return y
 
     @staticmethod
@@ -1687,17 +1705,12 @@ class _BNDeferFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, moving_mean, moving_var, eps, momentum, act, training, partials=None):
         x = _c(x)
-        lib = _lib.lib()
         c = x.shape[-1]
-        m = x.numel() // c
-        stats = torch.empty((4, c), device=x.device, dtype=torch.float32)   # mean, rstd, scale, shift
-        if training:
-            _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, act, None, stats, moving_mean, moving_var, partials)
-        else:
-            check(lib.embnet_bn_infer_fwd(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), eps,
-                                          int(act), None, (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]), stream()))
+        stats, _ = _bn_stats(x, x.numel() // c, c, 4, gamma, beta, eps, momentum, act, training, moving_mean, moving_var, partials)
         ctx.relu, ctx.training, ctx.has_gamma = int(act), training, gamma is not None
         ctx.gamma_ref, ctx.beta_ref = gamma, beta
+        ctx.emit_dx_range = ctx.emit_dx_planes = ctx.dx_planes_only = False    # (backward is _BatchNormFn's, without its fused extras)
+        ctx.in_relu_bias = ctx.dropout = None
         ctx.save_for_backward(x, stats)
         ctx.mark_non_differentiable(stats)
         return x.view_as(x), stats
@@ -1895,9 +1908,8 @@ class _InputBNConvFn(torch.autograd.Function):
             xp, beta_p, mm_p, mv_p, w_p = x, beta, moving_mean, moving_var, w
         a = torch.empty_like(xp)
         ranged = w_range is not None and cp % 4 == 0
-        stats = torch.empty((6 if ranged else 4, cp), device=x.device, dtype=torch.float32)
-        _bn_train_fwd(xp, m, cp, None, beta_p, eps, momentum, 0, a, stats, mm_p, mv_p, with_range=ranged)
-        a_range = _stats_range(stats) if ranged else None
+        stats, st = _bn_stats(xp, m, cp, 6 if ranged else 4, None, beta_p, eps, momentum, 0, True, mm_p, mv_p, None, a, ranged)
+        a_range = (stats, st.range) if ranged else None
         if cp != c:                                # the pad channel is identically 0 after BN (x=0, beta=0)
             moving_mean.copy_(mm_p[:c])
             moving_var.copy_(mv_p[:c])
@@ -1908,10 +1920,7 @@ class _InputBNConvFn(torch.autograd.Function):
             check(lib.embnet_conv2d_stem_f32(ptr(a), ptr(w_p), ptr(y), n, h, wd, pt, pl, oh, ow, ptr(out_stats), _rptr(a_range),
                                              _rptr(w_range), stream()))
         else:
-            cws = workspace(lib.embnet_conv2d_fwd_workspace_bytes(n, cp, r, s, k, oh, ow), x.device)
-            check(lib.embnet_conv2d_fwd_f32_ex(
-                ptr(a), ptr(w_p), None, ptr(y), n, h, wd, cp, r, s, k, stride, pt, pl, oh, ow, 0, None, None, None, 0,
-                ptr(out_stats), ptr(cws), cws.numel() * 4, _rptr(a_range), _rptr(w_range) if a_range is not None else None, stream()))
+            _gather_fwd(lib, a, w_p, None, y, n, h, wd, cp, r, s, k, stride, pt, pl, oh, ow, a_range, w_range, out_stats)
         ctx.w_range = w_range
         ctx.a_range = a_range
         ctx.geom, ctx.c, ctx.zero_sum_dy = geom, c, bool(zero_sum_dy)
@@ -1929,11 +1938,10 @@ class _InputBNConvFn(torch.autograd.Function):
         dy = _c(dy)
         dw_p = torch.empty((r, s, cp, k), device=a.device, dtype=torch.float32)
         ws = workspace(lib.embnet_conv2d_wgrad_workspace_bytes(n, cp, r, s, k, oh, ow), a.device)
-        a_range = getattr(ctx, "a_range", None)
-        dy_range = _take_dy_range(dy) if (getattr(ctx, "w_range", None) is not None and a_range is not None) else None
+        dy_range = _take_dy_range(dy) if (ctx.w_range is not None and ctx.a_range is not None) else None
         check(lib.embnet_conv2d_wgrad_f32_ex(
             ptr(a), ptr(dy), ptr(dw_p), ptr(ws), ws.numel() * 4, n, h, wd, cp, r, s, k, stride, pt, pl, oh, ow,
-            None, None, 0, _rptr(a_range) if dy_range is not None else None, _rptr(dy_range), stream()))
+            None, None, 0, _rptr(ctx.a_range) if dy_range is not None else None, _rptr(dy_range), stream()))
         if cp == c:
             dw = dw_p
         else:
@@ -2036,12 +2044,10 @@ class _MaxPoolFn(torch.autograd.Function):
             x = ctx.saved_tensors[1]
             db, db_note = _sink(ctx.relu_bias)
             ws = workspace(lib.embnet_bn_workspace_bytes(n * h * w, c), dy.device)
-            dzr = _emit_dx_range(dx) if getattr(ctx, "want_dz_range", False) else None
+            dzr = _emit_dx_range(dx) if ctx.want_dz_range else None
             check(lib.embnet_maxpool_relu_bwd_colsum_ex(ptr(dy), ptr(arg), ptr(x), n, h, w, c, k, stride, pad, oh, ow, ptr(dx), ptr(db),
                                                         ptr(ws), ws.numel() * 4, ptr(dzr), stream()))
-            if len(RELU_DONE) > 64:
-                RELU_DONE.clear()
-            RELU_DONE[dx.data_ptr()] = (dx.detach(), db, db_note)
+            RELU_DONE.put(dx.data_ptr(), (dx.detach(), db, db_note), 64, "all")
             return (dx,) + (None,) * 6
         check(lib.embnet_maxpool_bwd(ptr(dy), ptr(arg), n, h, w, c, k, stride, pad, oh, ow, ptr(dx), stream()))
         return (dx,) + (None,) * 6
@@ -2087,17 +2093,12 @@ class _BNActMaxPoolFn(torch.autograd.Function):
         oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
         if oh <= 0 or ow <= 0:
             raise _lib.EmbnetError(f"MaxPool {k}x{k}/{stride} does not fit a {h}x{w} input")
-        stats = torch.empty((4, c), device=x.device, dtype=torch.float32)   # mean, rstd, scale, shift
-        if training:
-            _bn_train_fwd(x, m, c, gamma, beta, eps, momentum, act, None, stats, moving_mean, moving_var, partials)
-        else:
-            check(lib.embnet_bn_infer_fwd(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), eps,
-                                          int(act), None, (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]), stream()))
+        stats, st = _bn_stats(x, m, c, 4, gamma, beta, eps, momentum, act, training, moving_mean, moving_var, partials)
         y = torch.empty((n, oh, ow, c), device=x.device, dtype=torch.float32)
         arg = torch.empty((n, oh, ow, c), device=x.device, dtype=torch.uint8)
         # training: keep the BN input at every window's winner, so backward's dgamma/dbeta sums stream instead of gathering
         xwin = torch.empty_like(y) if training else None
-        check(lib.embnet_bn_act_maxpool_fwd(ptr(x), n, h, w, c, (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]), int(act), k,
+        check(lib.embnet_bn_act_maxpool_fwd(ptr(x), n, h, w, c, st.scale, st.shift, int(act), k,
                                             stride, pad, oh, ow, ptr(y), ptr(arg), ptr(xwin) if training else None, stream()))
         ctx.cfg = (n, h, w, c, k, stride, pad, oh, ow, int(act), training, gamma is not None)
         ctx.has_gamma, ctx.gamma_ref, ctx.beta_ref = gamma is not None, gamma, beta
@@ -2117,13 +2118,12 @@ class _BNActMaxPoolFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         tg, tb, finish = _bn_grad_targets(ctx, c, x.device)
         ws = workspace(lib.embnet_bn_act_maxpool_bwd_workspace_bytes(n, oh, ow, c), x.device)
-        mean = stats.data_ptr() if training else None
-        rstd = (stats.data_ptr() + 4 * stats.shape[1]) if training else None
-        dxr = _emit_dx_range(dx) if getattr(ctx, "emit_dx_range", False) else None
-        check(lib.embnet_bn_act_maxpool_bwd_ex(ptr(dy), ptr(arg), ptr(x), n, h, w, c, k, stride, pad, oh, ow, mean, rstd,
-                                               (stats.data_ptr() + 8 * stats.shape[1]), (stats.data_ptr() + 12 * stats.shape[1]), act, int(training),
-                                               ptr(xwin) if training else None, ptr(dx),
-                                               ptr(tg), ptr(tb), ptr(ws), ws.numel() * 4, ptr(dxr), stream()))
+        st = _StatsRows(stats)
+        mean, rstd = (st.mean, st.rstd) if training else (None, None)
+        dxr = _emit_dx_range(dx) if ctx.emit_dx_range else None
+        check(lib.embnet_bn_act_maxpool_bwd_ex(ptr(dy), ptr(arg), ptr(x), n, h, w, c, k, stride, pad, oh, ow, mean, rstd, st.scale,
+                                               st.shift, act, int(training), ptr(xwin) if training else None, ptr(dx), ptr(tg),
+                                               ptr(tb), ptr(ws), ws.numel() * 4, ptr(dxr), stream()))
         dgamma, dbeta = finish()
         return (dx, dgamma, dbeta) + (None,) * 11
 
@@ -2287,18 +2287,16 @@ class _DepthwiseFn(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            bn_src = getattr(ctx, "bn_src", None)
+            bn_src = ctx.bn_src
             rows = lib.embnet_dwconv2d_dgrad_bnsums_rows(n, h, wd, c, r, s, stride) if bn_src is not None else 0
             if rows > 0:
                 bn_x, bn_stats, bn_act = bn_src
                 partial = (torch.zeros if c // 4 > 256 else torch.empty)((2, c, rows), device=x.device, dtype=torch.float32)
-                sp = bn_stats.data_ptr()
+                st = _StatsRows(bn_stats)
                 check(lib.embnet_dwconv2d_dgrad_bnsums_f32(ptr(dy), ptr(w), ptr(dx), n, h, wd, c, r, s, stride, pt, pl, oh, ow,
-                                                           ptr(bn_x), sp + 8 * c, sp + 12 * c, sp, sp + 4 * c, int(bn_act),
+                                                           ptr(bn_x), st.scale, st.shift, st.mean, st.rstd, int(bn_act),
                                                            ptr(partial), rows, stream()))
-                while len(BN_SUMS) >= 8:
-                    BN_SUMS.pop(next(iter(BN_SUMS)))
-                BN_SUMS[dx.data_ptr()] = (partial, rows, bn_x.data_ptr(), dx.detach())
+                BN_SUMS.put(dx.data_ptr(), (partial, rows, bn_x.data_ptr(), dx.detach()), 8, "oldest")
             else:
                 check(lib.embnet_dwconv2d_dgrad_f32(ptr(dy), ptr(w), ptr(dx), n, h, wd, c, r, s, stride, pt, pl, oh, ow,
                                                     stream()))
@@ -2409,15 +2407,13 @@ class _ChannelScaleFn(torch.autograd.Function):
                 # that layer's dbeta / dgamma follow: it then skips its reduction pass (embnet_se_bn_sums)
                 bn_x, bn_stats, bn_act = ctx.lazy
                 sums = torch.empty((n, 5, c), device=x.device, dtype=torch.float32)
-                sp = bn_stats.data_ptr()
-                check(_lib.lib().embnet_se_bn_sums(ptr(dy), ptr(bn_x), n, h * w, c, sp, sp + 4 * c, sp + 8 * c, sp + 12 * c, int(bn_act),
+                st = _StatsRows(bn_stats)
+                check(_lib.lib().embnet_se_bn_sums(ptr(dy), ptr(bn_x), n, h * w, c, st.mean, st.rstd, st.scale, st.shift, int(bn_act),
                                                    ptr(sums), stream()))
                 ds = sums[:, 0, :]
             else:
                 check(_lib.lib().embnet_channel_scale_dgate(ptr(x), ptr(dy), n, h * w, c, ptr(ds), stream()))
-            while len(GATE_PENDING) >= 8:
-                GATE_PENDING.pop(next(iter(GATE_PENDING)))
-            GATE_PENDING[dy.data_ptr()] = (s, dy.detach(), sums)
+            GATE_PENDING.put(dy.data_ptr(), (s, dy.detach(), sums), 8, "oldest")
             return dy, ds, None
         dx = torch.empty_like(x)
         check(_lib.lib().embnet_channel_scale_bwd(ptr(x), ptr(s), ptr(dy), n, h * w, c, ptr(dx), ptr(ds), stream()))

@@ -163,8 +163,7 @@ def test_deferred_batchnorm_into_conv(dev, shape, k, stride, act):
     res = {}
     # (the materialised path's BatchNorm-backward sums by the BatchNorm's own reduction pass, as the deferred path computes
     # them: with layers.FUSE_BN_SUMS the conv's data gradient would produce them in another summation order)
-    fuse_bn_sums, L.FUSE_BN_SUMS[0] = L.FUSE_BN_SUMS[0], False
-    try:
+    with L.switches(FUSE_BN_SUMS=False):
         for defer in (False, True):
             gen = torch.Generator().manual_seed(11)
             bn = L.BatchNormalization(cin, epsilon=2e-5, activation=act).to(dev).train()
@@ -182,8 +181,6 @@ def test_deferred_batchnorm_into_conv(dev, shape, k, stride, act):
                 with torch.no_grad():
                     bn2.gamma.copy_(bn.gamma); bn2.beta.copy_(bn.beta)
                 assert torch.equal(bn(x, defer=True).materialize(), bn2(x))
-    finally:
-        L.FUSE_BN_SUMS[0] = fuse_bn_sums
     for got, want, what in zip(res[True], res[False], ("y", "dx", "dW", "dgamma", "dbeta", "moving_mean")):
         assert torch.equal(got, want), what
 

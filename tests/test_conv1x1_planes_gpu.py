@@ -150,9 +150,7 @@ def test_bottleneck_unit_with_its_1x1_convs_on_the_planes_gemm(dev):
     from embeddingnet_amd.backbones import ResidualUnit
 
     def run(on):
-        old = L.CONV1X1_PLANES[0]
-        L.CONV1X1_PLANES[0] = on
-        try:
+        with L.switches(CONV1X1_PLANES=on):
             unit = ResidualUnit(1024, 256, 1, False, "bottleneck", torch.Generator().manual_seed(5)).to(dev).train()   # conv1 AND conv3 marked
             g = torch.Generator(device=dev).manual_seed(6)
             x = torch.randn((8, 14, 14, 1024), device=dev, generator=g).requires_grad_(True)
@@ -166,8 +164,6 @@ def test_bottleneck_unit_with_its_1x1_convs_on_the_planes_gemm(dev):
                 _lib.trace_enable(False)
             assert not L.current_context().leftovers()
             return y.detach(), x.grad, [p.grad.clone() for p in unit.parameters()], names
-        finally:
-            L.CONV1X1_PLANES[0] = old
 
     y1, dx1, g1, n1 = run(True)
     y0, dx0, g0, n0 = run(False)

@@ -177,11 +177,8 @@ def test_patch_at_bench_sizes_vs_gather_kernel_and_repeatable(dev, n, h, c, k):
     conv = L.Conv2D(c, k, 3, padding=1, use_bias=False, kernel_initializer="he_uniform", gen=gen).to(dev)
     res = torch.randn(n, h, h, k, generator=gen).to(dev)
     with torch.no_grad():
-        L.PATCH_CONV[0] = False
-        try:
+        with L.switches(PATCH_CONV=False):
             want = conv(x, residual=res, emit_stats=True)
-        finally:
-            L.PATCH_CONV[0] = True
         x._planes = planes_of(x)
         outs = [conv(x, residual=res, emit_stats=True) for _ in range(3)]
     torch.cuda.synchronize()
@@ -220,8 +217,7 @@ def test_unit_with_planes_equals_unit_on_gather_kernels(dev, n, h, c, k):
     dy = torch.randn(n, h, h, c, generator=gen).to(dev)
     out = {}
     for on in (True, False):
-        L.PATCH_CONV[0] = on
-        try:
+        with L.switches(PATCH_CONV=on):
             x = x0.clone().requires_grad_(True)
             for p in net.parameters():
                 p.grad = None
@@ -230,8 +226,6 @@ def test_unit_with_planes_equals_unit_on_gather_kernels(dev, n, h, c, k):
             y.backward(dy)
             torch.cuda.synchronize()
             out[on] = [y.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in net.parameters()]
-        finally:
-            L.PATCH_CONV[0] = True
     assert not L.DY_PLANES                         # every planes tensor left for a consumer was collected
     for a, b in zip(out[True], out[False]):
         rel = float((a - b).norm() / b.norm().clamp_min(1e-30))
@@ -281,23 +275,21 @@ def test_unit_backward_skips_the_batchnorm_reduction_pass(dev):
     x0 = torch.randn(6, 14, 14, 64, generator=gen).to(dev)
     dy = torch.randn(6, 14, 14, 64, generator=gen).to(dev)
     out, names = {}, {}
-    default = L.PATCH_BN_SUMS[0]                  # (off: the epilogue costs more than the reduction launches it replaces)
     for on in (True, False):
-        L.PATCH_BN_SUMS[0] = on
-        try:
-            x = x0.clone().requires_grad_(True)
-            for p in net.parameters():
-                p.grad = None
-            y = net(x)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y.backward(dy)
-            torch.cuda.synchronize()
-            names[on] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            out[on] = [x.grad.clone()] + [p.grad.clone() for p in net.parameters()]
-        finally:
-            L.PATCH_BN_SUMS[0] = default
-            L.BN_SUMS.clear()
+        with L.switches(PATCH_BN_SUMS=on):         # (default off: the epilogue costs more than the reduction launches it replaces)
+            try:
+                x = x0.clone().requires_grad_(True)
+                for p in net.parameters():
+                    p.grad = None
+                y = net(x)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y.backward(dy)
+                torch.cuda.synchronize()
+                names[on] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                out[on] = [x.grad.clone()] + [p.grad.clone() for p in net.parameters()]
+            finally:
+                L.BN_SUMS.clear()
     count = lambda on: sum("bn_bwd_reduce" in nm for nm in names[on])
     assert count(False) - count(True) >= 1, (names[True], names[False])
     for a, b in zip(out[True], out[False]):
@@ -316,16 +308,13 @@ def test_resnet18_patch_on_equals_off(dev):
     g = torch.randn(16, 64, generator=torch.Generator().manual_seed(2)).to(dev)
     res = {}
     for on in (True, False):
-        L.PATCH_CONV[0] = on
-        try:
+        with L.switches(PATCH_CONV=on):
             for p in base.parameters():
                 p.grad = None
             y = base(imgs)
             y.backward(g)
             torch.cuda.synchronize()
             res[on] = (y.detach().clone(), [p.grad.clone() for p in base.parameters()])
-        finally:
-            L.PATCH_CONV[0] = True
     assert not L.DY_PLANES
     assert float((res[True][0] - res[False][0]).norm() / res[False][0].norm()) < 2e-5
     rels = [float((a - b).norm() / b.norm().clamp_min(1e-30)) for a, b in zip(res[True][1], res[False][1])]

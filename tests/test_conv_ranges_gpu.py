@@ -272,9 +272,7 @@ def _resnet18_step(dev, f16):
     from embeddingnet_amd.backbones import get_backbone
     from embeddingnet_amd.train_step import TripletTrainer
     from embeddingnet_amd.optimizers import KerasOptimizer
-    old = L.CONV_F16[0]
-    L.CONV_F16[0] = f16
-    try:
+    with L.switches(CONV_F16=f16):
         torch.manual_seed(0)
         base, _ = get_backbone((64, 64, 3), encodings_len=64, backbone_name="resnet18", backbone_weights=None, seed=4, device=dev)
         base.train()
@@ -293,8 +291,6 @@ def _resnet18_step(dev, f16):
             _lib.trace_enable(False)
         left = tr.ctx.leftovers()
         return losses, names, left
-    finally:
-        L.CONV_F16[0] = old
 
 
 def test_resnet18_step_runs_its_gather_convs_on_three_products(dev):

@@ -161,9 +161,7 @@ def test_resnet18_runs_its_stem_on_the_kernel(dev):
     from embeddingnet_amd.backbones import get_backbone
 
     def run(on):
-        old = L.STEM_CONV[0]
-        L.STEM_CONV[0] = on
-        try:
+        with L.switches(STEM_CONV=on):
             torch.manual_seed(0)
             base, _ = get_backbone((96, 96, 3), encodings_len=32, backbone_name="resnet18", backbone_weights=None, seed=2, device=dev)
             base.train()
@@ -179,8 +177,6 @@ def test_resnet18_runs_its_stem_on_the_kernel(dev):
                 _lib.trace_enable(False)
             assert not L.current_context().leftovers()
             return y.detach(), [p.grad.clone() for p in base.parameters() if p.grad is not None], names
-        finally:
-            L.STEM_CONV[0] = old
 
     y1, g1, n1 = run(True)
     y0, g0, n0 = run(False)

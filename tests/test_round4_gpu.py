@@ -204,8 +204,7 @@ def test_deferred_slab_sums_are_bit_identical(dev, backbone, shape):
     x = torch.rand((12,) + shape, device=dev, generator=torch.Generator(device=dev).manual_seed(6))
     res, launches = [], []
     for defer in (False, True):
-        L.SLAB_DEFER_ENABLED[0] = defer
-        try:
+        with L.switches(SLAB_DEFER_ENABLED=defer):
             base, _ = B.get_backbone(shape, encodings_len=32, backbone_name=backbone, backbone_weights=None, seed=4, device=dev)
             for m in base.modules():
                 if hasattr(m, "enabled"):
@@ -218,8 +217,6 @@ def test_deferred_slab_sums_are_bit_identical(dev, backbone, shape):
             torch.cuda.synchronize()
             names = [r[0] for r in _lib.trace_records()]
             _lib.trace_enable(False)
-        finally:
-            L.SLAB_DEFER_ENABLED[0] = True
         launches.append((sum("slab_reduce_kernel" in n for n in names), sum("slab_reduce_multi" in n for n in names)))
         res.append((loss.clone(), [p.grad.clone() for p in params], [p.detach().clone() for p in params]))
     # (the ResNet stem's padded-kernel gradient is consumed at once and keeps its own slab sum)
@@ -241,27 +238,26 @@ def test_relu_backward_fused_into_batchnorm_backward(dev, shape, k, cout):
     x = torch.randn(shape, device=dev)
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_RELU_BN[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(3)
-            conv = L.Conv2D(shape[-1], cout, k, activation="relu", gen=gen).to(dev)
-            with torch.no_grad():
-                conv.bias.copy_(torch.linspace(-0.3, 0.3, cout))
-            bn = L.BatchNormalization(cout).to(dev).train()
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, cout)); bn.beta.copy_(torch.linspace(-0.2, 0.2, cout))
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y = bn(conv(xt, emit_stats=fuse))
-            y.backward(torch.sin(y.detach() * 2))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(y=y.detach(), dx=xt.grad, dW=conv.kernel.grad, db=conv.bias.grad, dgamma=bn.gamma.grad, dbeta=bn.beta.grad,
-                             mm=bn.moving_mean.clone())
-        finally:
-            L.FUSE_RELU_BN[0] = True
-            L.RELU_DONE.clear()
+        with L.switches(FUSE_RELU_BN=fuse):
+            try:
+                gen = torch.Generator().manual_seed(3)
+                conv = L.Conv2D(shape[-1], cout, k, activation="relu", gen=gen).to(dev)
+                with torch.no_grad():
+                    conv.bias.copy_(torch.linspace(-0.3, 0.3, cout))
+                bn = L.BatchNormalization(cout).to(dev).train()
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, cout)); bn.beta.copy_(torch.linspace(-0.2, 0.2, cout))
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y = bn(conv(xt, emit_stats=fuse))
+                y.backward(torch.sin(y.detach() * 2))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(y=y.detach(), dx=xt.grad, dW=conv.kernel.grad, db=conv.bias.grad, dgamma=bn.gamma.grad, dbeta=bn.beta.grad,
+                                 mm=bn.moving_mean.clone())
+            finally:
+                L.RELU_DONE.clear()
     assert any("relu_bwd_colsum" in n for n in names[False]) and any("bn_stats" in n for n in names[False])
     assert not any("relu_bwd" in n or "bn_stats" in n for n in names[True]), names[True]
     assert any("bn_bwd_apply_inrelu4" in n for n in names[True])
@@ -287,27 +283,24 @@ def test_dropout_behind_batchnorm_rides_on_its_kernels(dev, image, inrelu):
     x = torch.rand((6, image, image, 3), device=dev)
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_DROPOUT_BN[0] = fuse
-        L.FUSE_RELU_BN[0] = inrelu
-        try:
-            base, _ = B.get_backbone((image, image, 3), encodings_len=32, backbone_name="simple2", backbone_weights=None, seed=5)
-            base = base.to(dev).train()
-            out = []
-            _lib.trace_reset(); _lib.trace_enable(True)
-            for step in range(2):
-                for p in base.parameters():
-                    p.grad = None
-                y = base(x)
-                y.backward(torch.cos(y.detach() * 3 + step))
-                out.append([y.detach().clone()] + [p.grad.clone() for p in base.parameters()])
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = out
-        finally:
-            L.FUSE_DROPOUT_BN[0] = True
-            L.FUSE_RELU_BN[0] = True
-            L.RELU_DONE.clear()
+        with L.switches(FUSE_DROPOUT_BN=fuse, FUSE_RELU_BN=inrelu):
+            try:
+                base, _ = B.get_backbone((image, image, 3), encodings_len=32, backbone_name="simple2", backbone_weights=None, seed=5)
+                base = base.to(dev).train()
+                out = []
+                _lib.trace_reset(); _lib.trace_enable(True)
+                for step in range(2):
+                    for p in base.parameters():
+                        p.grad = None
+                    y = base(x)
+                    y.backward(torch.cos(y.detach() * 3 + step))
+                    out.append([y.detach().clone()] + [p.grad.clone() for p in base.parameters()])
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = out
+            finally:
+                L.RELU_DONE.clear()
     n_sep, n_fused = (sum("dropout_kernel" in n for n in names[f]) for f in (False, True))
     # two steps x (3 Dropout layers forward + backward); fused: only the head's Dropout (behind a Dense) keeps its kernel,
     # plus — without the fused ReLU backward — the two backward passes in front of the BN backward
@@ -335,31 +328,30 @@ def test_batchnorm_backward_sums_come_from_the_conv_data_gradient(dev, shape, k,
     x = torch.randn(shape, device=dev)
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_BN_SUMS[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(11)
-            c = shape[-1]
-            bn = L.BatchNormalization(c, relu=True).to(dev).train()
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
-            conv = L.Conv2D(c, k, ks, padding="same", use_bias=False, gen=gen).to(dev)
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            if with_skip:
-                a, skip = bn(xt, with_skip=True)
-                y = conv(a)
-                out = y.sum(dim=-1, keepdim=True) * 0.01 + skip          # a second path from the BN's input
-            else:
-                y = conv(bn(xt))
-                out = y
-            out.backward(torch.cos(out.detach() * 1.7))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(dx=xt.grad, dW=conv.kernel.grad, dgamma=bn.gamma.grad, dbeta=bn.beta.grad)
-        finally:
-            L.FUSE_BN_SUMS[0] = True
-            L.BN_SUMS.clear()
+        with L.switches(FUSE_BN_SUMS=fuse):
+            try:
+                gen = torch.Generator().manual_seed(11)
+                c = shape[-1]
+                bn = L.BatchNormalization(c, relu=True).to(dev).train()
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
+                conv = L.Conv2D(c, k, ks, padding="same", use_bias=False, gen=gen).to(dev)
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                if with_skip:
+                    a, skip = bn(xt, with_skip=True)
+                    y = conv(a)
+                    out = y.sum(dim=-1, keepdim=True) * 0.01 + skip          # a second path from the BN's input
+                else:
+                    y = conv(bn(xt))
+                    out = y
+                out.backward(torch.cos(out.detach() * 1.7))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(dx=xt.grad, dW=conv.kernel.grad, dgamma=bn.gamma.grad, dbeta=bn.beta.grad)
+            finally:
+                L.BN_SUMS.clear()
     assert any("bn_bwd_reduce" in n for n in names[False])
     assert not any("bn_bwd_reduce" in n for n in names[True]), names[True]
     assert not L.BN_SUMS
@@ -377,25 +369,24 @@ def test_batchnorm_backward_sums_are_not_used_when_the_gradient_has_a_second_con
     x = torch.randn((4, 10, 10, 32), device=dev)
     res = {}
     for fuse in (False, True):
-        L.FUSE_BN_SUMS[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(5)
-            bn = L.BatchNormalization(32, relu=True).to(dev).train()
-            c1 = L.Conv2D(32, 64, 1, use_bias=False, gen=gen).to(dev)
-            c2 = L.Conv2D(32, 64, 1, use_bias=False, gen=gen).to(dev)
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            a = bn(xt)
-            out = c1(a) + 0.5 * c2(a)
-            out.backward(torch.sin(out.detach()))
-            torch.cuda.synchronize()
-            names = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            assert any("bn_bwd_reduce" in n for n in names)
-            res[fuse] = (xt.grad.clone(), bn.gamma.grad.clone(), bn.beta.grad.clone())
-        finally:
-            L.FUSE_BN_SUMS[0] = True
-            L.BN_SUMS.clear()
+        with L.switches(FUSE_BN_SUMS=fuse):
+            try:
+                gen = torch.Generator().manual_seed(5)
+                bn = L.BatchNormalization(32, relu=True).to(dev).train()
+                c1 = L.Conv2D(32, 64, 1, use_bias=False, gen=gen).to(dev)
+                c2 = L.Conv2D(32, 64, 1, use_bias=False, gen=gen).to(dev)
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                a = bn(xt)
+                out = c1(a) + 0.5 * c2(a)
+                out.backward(torch.sin(out.detach()))
+                torch.cuda.synchronize()
+                names = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                assert any("bn_bwd_reduce" in n for n in names)
+                res[fuse] = (xt.grad.clone(), bn.gamma.grad.clone(), bn.beta.grad.clone())
+            finally:
+                L.BN_SUMS.clear()
     for a, b in zip(res[True], res[False]):
         assert torch.equal(a, b)
 
@@ -497,8 +488,7 @@ def test_pooled_gradient_is_added_inside_the_batchnorm_backward(dev, shape, act)
     x = torch.randn(shape, device=dev)
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_GAP_BN[0] = fuse
-        try:
+        with L.switches(FUSE_GAP_BN=fuse):
             c = shape[-1]
             bn = L.BatchNormalization(c, activation=act).to(dev).train()
             with torch.no_grad():
@@ -513,8 +503,6 @@ def test_pooled_gradient_is_added_inside_the_batchnorm_backward(dev, shape, act)
             names[fuse] = [r[0] for r in _lib.trace_records()]
             _lib.trace_enable(False)
             res[fuse] = (xt.grad.clone(), bn.gamma.grad.clone(), bn.beta.grad.clone())
-        finally:
-            L.FUSE_GAP_BN[0] = True
     assert any("gap_bwd" in n for n in names[False]) and not any("gap_bwd" in n for n in names[True]), names[True]
     assert any("bn_bwd_reduce4_gap" in n for n in names[True])
     for a, b in zip(res[True], res[False]):
@@ -532,28 +520,25 @@ def test_gate_multiply_backward_rides_on_the_batchnorm_backward(dev, shape):
     n, c = shape[0], shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_GATE_BN[0] = fuse
-        L.SE_BN_SUMS[0] = False                      # (the reduction pass stays: this test is about the gate multiply alone)
-        try:
-            gen = torch.Generator().manual_seed(2)
-            bn = L.BatchNormalization(c, activation="swish").to(dev).train()
-            se = L.Dense(c, c, gen=gen).to(dev)
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y, pooled = bn(xt, emit_gap=True, lazy_scale=True)
-            s = L.sigmoid(se(pooled))
-            out = L.channel_scale(y, s, lazy=True)
-            out.backward(torch.cos(out.detach() * 2.0))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = (xt.grad.clone(), bn.gamma.grad.clone(), bn.beta.grad.clone(), se.kernel.grad.clone(), se.bias.grad.clone())
-        finally:
-            L.FUSE_GATE_BN[0] = True
-            L.SE_BN_SUMS[0] = True
-            L.GATE_PENDING.clear()
+        with L.switches(FUSE_GATE_BN=fuse, SE_BN_SUMS=False):    # (the reduction pass stays: this test is about the gate multiply alone)
+            try:
+                gen = torch.Generator().manual_seed(2)
+                bn = L.BatchNormalization(c, activation="swish").to(dev).train()
+                se = L.Dense(c, c, gen=gen).to(dev)
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y, pooled = bn(xt, emit_gap=True, lazy_scale=True)
+                s = L.sigmoid(se(pooled))
+                out = L.channel_scale(y, s, lazy=True)
+                out.backward(torch.cos(out.detach() * 2.0))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = (xt.grad.clone(), bn.gamma.grad.clone(), bn.beta.grad.clone(), se.kernel.grad.clone(), se.bias.grad.clone())
+            finally:
+                L.GATE_PENDING.clear()
     assert any("chscale_bwd" in nm for nm in names[False])
     assert not any("chscale_bwd" in nm or "gap_bwd" in nm for nm in names[True]), names[True]
     assert any("chscale_dgate4" in nm for nm in names[True]) and not L.GATE_PENDING
@@ -585,26 +570,25 @@ def test_squeeze_excite_backward_needs_no_batchnorm_reduction_pass(dev, shape, a
     n, c = shape[0], shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.SE_BN_SUMS[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(2)
-            bn = L.BatchNormalization(c, activation=act).to(dev).train()
-            se = L.Dense(c, c, gen=gen).to(dev)
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y, pooled = bn(xt, emit_gap=True, lazy_scale=True)
-            out = L.channel_scale(y, L.sigmoid(se(pooled)), lazy=True)
-            out.backward(torch.cos(out.detach() * 2.0))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(dx=xt.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone(), dW=se.kernel.grad.clone(),
-                             db=se.bias.grad.clone())
-        finally:
-            L.SE_BN_SUMS[0] = True
-            L.GATE_PENDING.clear()
+        with L.switches(SE_BN_SUMS=fuse):
+            try:
+                gen = torch.Generator().manual_seed(2)
+                bn = L.BatchNormalization(c, activation=act).to(dev).train()
+                se = L.Dense(c, c, gen=gen).to(dev)
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y, pooled = bn(xt, emit_gap=True, lazy_scale=True)
+                out = L.channel_scale(y, L.sigmoid(se(pooled)), lazy=True)
+                out.backward(torch.cos(out.detach() * 2.0))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(dx=xt.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone(), dW=se.kernel.grad.clone(),
+                                 db=se.bias.grad.clone())
+            finally:
+                L.GATE_PENDING.clear()
     assert any("bn_bwd_reduce4_gap" in nm for nm in names[False]) and any("chscale_dgate4" in nm for nm in names[False])
     assert not any("bn_bwd_reduce" in nm or "chscale" in nm.replace("chscale_fwd", "") for nm in names[True]), names[True]
     assert any("se_bn_sums4" in nm for nm in names[True])
@@ -624,25 +608,24 @@ def test_se_gate_never_writes_the_activated_tensor(dev, shape, act):
     n, c = shape[0], shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.SE_TWO_STAGE[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(2)
-            bn = L.BatchNormalization(c, activation=act).to(dev).train()
-            se = L.Dense(c, c, gen=gen).to(dev)
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            out = bn.se_gate(xt, lambda g: L.sigmoid(se(g)))
-            out.backward(torch.cos(out.detach() * 2.0))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(out=out.detach().clone(), dx=xt.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone(),
-                             dW=se.kernel.grad.clone(), db=se.bias.grad.clone(), mm=bn.moving_mean.clone())
-        finally:
-            L.SE_TWO_STAGE[0] = True
-            L.GATE_PENDING.clear(); L.POOL_PENDING.clear()
+        with L.switches(SE_TWO_STAGE=fuse):
+            try:
+                gen = torch.Generator().manual_seed(2)
+                bn = L.BatchNormalization(c, activation=act).to(dev).train()
+                se = L.Dense(c, c, gen=gen).to(dev)
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                out = bn.se_gate(xt, lambda g: L.sigmoid(se(g)))
+                out.backward(torch.cos(out.detach() * 2.0))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(out=out.detach().clone(), dx=xt.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone(),
+                                 dW=se.kernel.grad.clone(), db=se.bias.grad.clone(), mm=bn.moving_mean.clone())
+            finally:
+                L.GATE_PENDING.clear(); L.POOL_PENDING.clear()
     assert any("chscale_fwd" in nm for nm in names[False])
     assert not any("chscale" in nm or "bn_bwd_reduce" in nm for nm in names[True]), names[True]
     assert any("affine_act_scale4" in nm for nm in names[True]) and not L.POOL_PENDING
@@ -664,8 +647,7 @@ def test_batchnorm_dropconnect_add_in_one_pass(dev, shape, rate):
     c = shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_DROP_ADD[0] = fuse
-        try:
+        with L.switches(FUSE_DROP_ADD=fuse):
             bn = L.BatchNormalization(c).to(dev).train()
             drop = L.DropConnect(rate, seed=9).train() if rate > 0 else None
             with torch.no_grad():
@@ -682,8 +664,6 @@ def test_batchnorm_dropconnect_add_in_one_pass(dev, shape, rate):
             names[fuse] = [r[0] for r in _lib.trace_records()]
             _lib.trace_enable(False)
             res[fuse] = outs
-        finally:
-            L.FUSE_DROP_ADD[0] = True
     assert not any("sample_dropout" in nm or nm.endswith("add_kernel") for nm in names[True]), names[True]
     assert any("affine_drop_add4" in nm for nm in names[True])
     for sa, sb in zip(res[True], res[False]):
@@ -707,8 +687,7 @@ def test_depthwise_forward_emits_the_batchnorm_statistics(dev, shape, k, stride)
     c = shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.DW_EMIT_STATS[0] = fuse
-        try:
+        with L.switches(DW_EMIT_STATS=fuse):
             gen = torch.Generator().manual_seed(4)
             dw = L.DepthwiseConv2D(c, k, strides=stride, gen=gen).to(dev)
             bn = L.BatchNormalization(c, activation="swish").to(dev).train()
@@ -723,8 +702,6 @@ def test_depthwise_forward_emits_the_batchnorm_statistics(dev, shape, k, stride)
             _lib.trace_enable(False)
             res[fuse] = dict(y=y.detach().clone(), dx=xt.grad.clone(), dw=dw.depthwise_kernel.grad.clone(), dgamma=bn.gamma.grad.clone(),
                              dbeta=bn.beta.grad.clone(), mm=bn.moving_mean.clone(), mv=bn.moving_variance.clone())
-        finally:
-            L.DW_EMIT_STATS[0] = True
     assert any("bn_stats" in nm for nm in names[False]) and not any("bn_stats" in nm for nm in names[True]), names[True]
     for key in res[True]:
         a, b = res[True][key], res[False][key]
@@ -744,24 +721,23 @@ def test_depthwise_data_gradient_emits_the_batchnorm_backward_sums(dev, shape, k
     c = shape[-1]
     res, names = {}, {}
     for fuse in (False, True):
-        L.DW_BN_SUMS[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(4)
-            bn = L.BatchNormalization(c, activation="swish").to(dev).train()
-            dw = L.DepthwiseConv2D(c, k, strides=stride, gen=gen).to(dev)
-            with torch.no_grad():
-                bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y = dw(bn(xt))
-            y.backward(torch.cos(y.detach() * 2.0))
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(dx=xt.grad.clone(), dw=dw.depthwise_kernel.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone())
-        finally:
-            L.DW_BN_SUMS[0] = True
-            L.BN_SUMS.clear()
+        with L.switches(DW_BN_SUMS=fuse):
+            try:
+                gen = torch.Generator().manual_seed(4)
+                bn = L.BatchNormalization(c, activation="swish").to(dev).train()
+                dw = L.DepthwiseConv2D(c, k, strides=stride, gen=gen).to(dev)
+                with torch.no_grad():
+                    bn.gamma.copy_(torch.linspace(0.5, 1.5, c)); bn.beta.copy_(torch.linspace(-0.3, 0.3, c))
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y = dw(bn(xt))
+                y.backward(torch.cos(y.detach() * 2.0))
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(dx=xt.grad.clone(), dw=dw.depthwise_kernel.grad.clone(), dgamma=bn.gamma.grad.clone(), dbeta=bn.beta.grad.clone())
+            finally:
+                L.BN_SUMS.clear()
     assert any("bn_bwd_reduce" in nm for nm in names[False]) and not any("bn_bwd_reduce" in nm for nm in names[True]), names[True]
     assert torch.equal(res[True]["dw"], res[False]["dw"]) and not L.BN_SUMS
     for key in res[True]:
@@ -782,24 +758,23 @@ def test_relu_backward_fused_into_maxpool_backward(dev, shape, k, cout, pool):
     x = torch.rand(shape, device=dev) - 0.3
     res, names = {}, {}
     for fuse in (False, True):
-        L.FUSE_RELU_POOL[0] = fuse
-        try:
-            gen = torch.Generator().manual_seed(5)
-            conv = L.Conv2D(shape[-1], cout, k, activation="relu", gen=gen).to(dev)
-            with torch.no_grad():
-                conv.bias.copy_(torch.linspace(-0.2, 0.2, cout))
-            mp = L.MaxPool2D(pool[0], pool[1], zero_pad=pool[2])
-            xt = x.clone().requires_grad_(True)
-            _lib.trace_reset(); _lib.trace_enable(True)
-            y = mp(conv(xt))
-            y.backward(torch.sin(y.detach() * 3) + 0.1)
-            torch.cuda.synchronize()
-            names[fuse] = [r[0] for r in _lib.trace_records()]
-            _lib.trace_enable(False)
-            res[fuse] = dict(y=y.detach(), dx=xt.grad, dW=conv.kernel.grad, db=conv.bias.grad)
-        finally:
-            L.FUSE_RELU_POOL[0] = True
-            L.RELU_DONE.clear()
+        with L.switches(FUSE_RELU_POOL=fuse):
+            try:
+                gen = torch.Generator().manual_seed(5)
+                conv = L.Conv2D(shape[-1], cout, k, activation="relu", gen=gen).to(dev)
+                with torch.no_grad():
+                    conv.bias.copy_(torch.linspace(-0.2, 0.2, cout))
+                mp = L.MaxPool2D(pool[0], pool[1], zero_pad=pool[2])
+                xt = x.clone().requires_grad_(True)
+                _lib.trace_reset(); _lib.trace_enable(True)
+                y = mp(conv(xt))
+                y.backward(torch.sin(y.detach() * 3) + 0.1)
+                torch.cuda.synchronize()
+                names[fuse] = [r[0] for r in _lib.trace_records()]
+                _lib.trace_enable(False)
+                res[fuse] = dict(y=y.detach(), dx=xt.grad, dW=conv.kernel.grad, db=conv.bias.grad)
+            finally:
+                L.RELU_DONE.clear()
     assert any("relu_bwd_colsum" in n for n in names[False]) and any("maxpool_bwd4" in n for n in names[False])
     assert not any("relu_bwd_colsum_kernel" in n or "maxpool_bwd4" in n for n in names[True]), names[True]
     assert any("maxpool_relu_bwd_colsum4" in n for n in names[True])
@@ -817,18 +792,17 @@ def test_fused_maxpool_backward_is_not_used_when_the_conv_output_has_a_second_co
     x = torch.rand((2, 12, 12, 8), device=dev) - 0.3
     res = {}
     for fuse in (False, True):
-        L.FUSE_RELU_POOL[0] = fuse
-        try:
-            conv = L.Conv2D(8, 16, 3, activation="relu", gen=torch.Generator().manual_seed(2)).to(dev)
-            with torch.no_grad():
-                conv.bias.fill_(0.05)
-            xt = x.clone().requires_grad_(True)
-            a = conv(xt)
-            y = L.MaxPool2D()(a)
-            (y.sum() * 2 + (a * a).sum()).backward()
-            res[fuse] = (xt.grad, conv.kernel.grad, conv.bias.grad)
-        finally:
-            L.FUSE_RELU_POOL[0] = True
-            L.RELU_DONE.clear()
+        with L.switches(FUSE_RELU_POOL=fuse):
+            try:
+                conv = L.Conv2D(8, 16, 3, activation="relu", gen=torch.Generator().manual_seed(2)).to(dev)
+                with torch.no_grad():
+                    conv.bias.fill_(0.05)
+                xt = x.clone().requires_grad_(True)
+                a = conv(xt)
+                y = L.MaxPool2D()(a)
+                (y.sum() * 2 + (a * a).sum()).backward()
+                res[fuse] = (xt.grad, conv.kernel.grad, conv.bias.grad)
+            finally:
+                L.RELU_DONE.clear()
     for a, b in zip(res[True], res[False]):
         assert (a - b).abs().max().item() <= 2e-6 * b.abs().max().item()

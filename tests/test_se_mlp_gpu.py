@@ -79,15 +79,12 @@ def test_fused_gate_equals_composed_gate_in_an_mbconv_block(dev):
     x0 = torch.randn(6, 14, 14, 40, device=dev)
     res = {}
     for on in (True, False):
-        L.SE_MLP[0] = on
-        try:
+        with L.switches(SE_MLP=on):
             blk = E.MBConv(5, 40, 40, 6, 1, 0.0, 7, torch.Generator().manual_seed(3)).to(dev).train()
             x = x0.clone().requires_grad_(True)
             y = blk(x)
             y.backward(torch.sin(y.detach() * 1.7))
             torch.cuda.synchronize()
             res[on] = [y.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in blk.parameters()]
-        finally:
-            L.SE_MLP[0] = True
     for a, b in zip(res[True], res[False]):
         assert float((a - b).norm() / b.norm().clamp_min(1e-30)) < 2e-5

@@ -154,9 +154,7 @@ def _base(dev, name, seed=3):
 
 def _conv_launches(dev, name, f16):
     from embeddingnet_amd import layers as L
-    old = L.CONV_F16[0]
-    L.CONV_F16[0] = f16
-    try:
+    with L.switches(CONV_F16=f16):
         base = _base(dev, name)
         g = torch.Generator().manual_seed(1)
         x = torch.rand((8,) + SHAPES[name], generator=g).to(dev)
@@ -175,8 +173,6 @@ def _conv_launches(dev, name, f16):
         left = dict(ctx.leftovers())
         left.update({"unclaimed " + k: v for k, v in ctx.unclaimed.items() if v})      # (every range a backward pass left was claimed)
         return names, left, [p.grad.clone() for p in base.parameters() if p.grad is not None]
-    finally:
-        L.CONV_F16[0] = old
 
 
 def _six(names):
