@@ -385,11 +385,14 @@ __global__ __launch_bounds__(256) void softmax_xent_fwd_kernel(const float* __re
   float se = 0.f;
   for (int j = lane; j < c; j += 64) se += __expf(zr[j] - mx);
   se = wave_sum(se);
-  const float lse = mx + __logf(se);
+  // log_softmax_j = (z_j - mx) - log(se): the difference first, so that a maximum of 100 does not cost the small
+  // terms half an ulp of 100 (mx + log(se) formed first loses 4e-6 of every probability at that spread)
+  const float lg = __logf(se);
   float l = 0.f;
   for (int j = lane; j < c; j += 64) {
-    prob[(long)row * c + j] = __expf(zr[j] - lse);
-    l += tr[j] * (lse - zr[j]);
+    const float lp = (zr[j] - mx) - lg;
+    prob[(long)row * c + j] = __expf(lp);
+    l -= tr[j] * lp;
   }
   l = wave_sum(l);
   if (lane == 0) { loss[row] = l; correct[row] = zi == ti ? 1.f : 0.f; }

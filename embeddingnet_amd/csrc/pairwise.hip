@@ -234,6 +234,8 @@ __global__ __launch_bounds__(256) void cross_dist_kernel(CrossParams p) {
 
 // k smallest entries of each row, ascending, ties to the smaller column: one wave per row, k rounds of a
 // shuffle arg-min over the columns not yet taken (k <= 64: taken columns live one per lane).
+// A NaN entry counts as +inf (and is reported as +inf): it ties with +inf by column and never precedes a finite entry, so
+// every round finds a column and every emitted index is a column of the matrix, whatever the row holds.
 __global__ __launch_bounds__(256) void topk_smallest_kernel(const float* __restrict__ d, int rows, int n, int k,
                                                             int* __restrict__ idx, float* __restrict__ val) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -242,10 +244,14 @@ __global__ __launch_bounds__(256) void topk_smallest_kernel(const float* __restr
   int taken = -1;                                         // lane j remembers the column chosen in round j
   for (int round = 0; round < k; ++round) {
     float best = INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < n; c += 64) {
-      bool used = false;
+    // the trip count is the wave's, not the lane's: a shuffle returns nothing usable from a lane that has left the loop, and
+    // with c = lane; c < n the lanes past n % 64 had left in the last trip, so a taken column there was chosen again
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int c = c0 + lane;
+      bool used = c >= n;
       for (int j = 0; j < round; ++j) used |= (__shfl(taken, j, 64) == c);
-      const float v = r[c];
+      float v = INFINITY;
+      if (c < n && r[c] == r[c]) v = r[c];
       if (!used && (v < best || (v == best && c < bi))) { best = v; bi = c; }
     }
 #pragma unroll

@@ -337,7 +337,8 @@ def cross_distances(q, x, squared=False):
 
 
 def topk_smallest(dist, k):
-    """-> (values [rows,k], indices [rows,k] int32), ascending, ties to the smaller column."""
+    """-> (values [rows,k], indices [rows,k] int32), ascending, ties to the smaller column; 0 < k <= min(64, n).
+    A NaN entry counts as +inf and is reported as +inf: it follows every finite entry, and every index is in [0, n)."""
     dist = _prep(dist)
     rows, n = dist.shape
     idx = _new((rows, k), dist, torch.int32)

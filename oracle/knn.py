@@ -13,14 +13,38 @@ def cross_distances(q, x):
     return np.sqrt(d)
 
 
-def kneighbors(q, x, k):
-    d = cross_distances(q, x)
+def cross_sqdist64(q, x):
+    """The same formula kept in float64, unclamped and unrounded: the yardstick an fp32 distance kernel is measured by.
+    -> (d2 [nq,n], |q|^2 [nq], |x|^2 [n])"""
+    q64, x64 = np.asarray(q, np.float32).astype(np.float64), np.asarray(x, np.float32).astype(np.float64)
+    qn, xn = (q64 * q64).sum(1), (x64 * x64).sum(1)
+    d = q64 @ x64.T
+    d *= -2.0
+    d += qn[:, None]
+    d += xn[None, :]
+    return d, qn, xn
+
+
+def topk_smallest(d, k):
+    """The k smallest entries of each row of a given matrix, ascending, ties to the smaller column (a stable sort).
+    NaN counts as +inf, in the order as in the reported value: it ties with +inf by column and never precedes a
+    finite entry.  -> (values, indices)"""
+    d = np.asarray(d)
+    d = np.where(np.isnan(d), np.asarray(np.inf, d.dtype), d)
     idx = np.argsort(d, axis=1, kind="stable")[:, :k]
     return np.take_along_axis(d, idx, 1), idx
+
+
+def kneighbors(q, x, k):
+    return topk_smallest(cross_distances(q, x), k)
+
+
+def vote(votes):
+    """Majority of each row of integer class ids, ties to the smallest id (scipy.stats.mode, as sklearn's predict)."""
+    return np.array([np.bincount(v).argmax() for v in np.asarray(votes)])
 
 
 def predict(q, x, labels, k):
     """labels: integer class ids [n]."""
     _, idx = kneighbors(q, x, k)
-    votes = np.asarray(labels)[idx]
-    return np.array([np.bincount(v).argmax() for v in votes])
+    return vote(np.asarray(labels)[idx])

@@ -60,6 +60,12 @@ def softmax_cross_entropy(logits, targets):
     """Keras Dense(softmax) + loss='categorical_crossentropy' (reference backbones.py:146-151; TF computes it
     from the logits of the softmax op) and metric 'accuracy'.  Third-party arithmetic (TensorFlow 2.2):
     parity unpinned, standard definition.  Returns (mean loss, accuracy, probabilities, dlogits of the mean)."""
+    rows, acc, prob, grad = softmax_cross_entropy_rows(logits, targets)
+    return rows.mean(), acc, prob, grad
+
+
+def softmax_cross_entropy_rows(logits, targets):
+    """The same with the per-row losses [b] in place of their mean.  argmax takes the first maximum on both sides."""
     z = np.asarray(logits, np.float64)
     t = np.asarray(targets, np.float64)
     zs = z - z.max(axis=1, keepdims=True)
@@ -68,4 +74,15 @@ def softmax_cross_entropy(logits, targets):
     loss = -(t * logp).sum(axis=1)
     acc = np.mean(z.argmax(1) == t.argmax(1))
     prob = np.exp(logp)
-    return loss.mean(), acc, prob, (prob * t.sum(1, keepdims=True) - t) / z.shape[0]
+    return loss, acc, prob, (prob * t.sum(1, keepdims=True) - t) / z.shape[0]
+
+
+def l2_normalize(x, dy):
+    """K.l2_normalize(x, axis=1) (reference backbones.py:38,77,118) = x * rsqrt(max(sum x^2, 1e-12)) in float64, and
+    the gradient of sum(y * dy) by autograd: on a clamped row the maximum passes nothing to the sum, so it is
+    dy * 1e6.  -> (y, dx)"""
+    import torch
+    xr = torch.tensor(np.asarray(x, np.float32), dtype=torch.float64, requires_grad=True)
+    yr = xr * torch.rsqrt(torch.clamp((xr * xr).sum(1, keepdim=True), min=1e-12))
+    (yr * torch.tensor(np.asarray(dy, np.float64))).sum().backward()
+    return yr.detach().numpy(), xr.grad.numpy()

@@ -127,3 +127,33 @@ def knn_data(n_classes, per_class, e, sigma, n_query, seed):
     pick = rs.randint(0, n_classes * 2, size=n_query)
     queries = x[:, per_class:].reshape(-1, e)[pick]
     return gallery.copy(), labels, queries.copy(), pick // 2
+
+
+# ---- evaluation path at scale (tests/test_eval_path_gpu.py) --------------------------------------------------------
+EVAL_CROSS_CASES = [  # (name, classes, per_class, E, n_query, seed): nq x (classes * per_class) x E, sigma 0.3
+    ("q1_n642_e256", 107, 6, 256, 1, 51),            # predict_knn: one valid row of a 64x64 tile
+    ("q1_n5_e64", 5, 1, 64, 1, 52),
+    ("q3_n7_e5", 7, 1, 5, 3, 53),                    # scalar loader, ragged in all three dimensions
+    ("q65_n130_e33", 13, 10, 33, 65, 54),
+    ("q130_n257_e70", 257, 1, 70, 130, 55),
+    ("q1000_n6100_e256", 305, 20, 256, 1000, 56),    # 8 x 48 = 384 tiles of 128x128: the first size on the large tiles
+    ("q1000_n6100_e508", 305, 20, 508, 1000, 57),    # vector loader, ragged last K tile
+    ("q1000_n6100_e510", 305, 20, 510, 1000, 58),    # scalar loader (510 % 4 = 2)
+    ("q2048_n50000_e128", 2500, 20, 128, 2048, 59),  # a gallery of real size
+]
+EVAL_CROSS_RAGGED = [(3, 7, 5), (65, 130, 33), (130, 257, 70)]      # also run on raw randn rows
+EVAL_CROSS_SCALES = [1e-2, 1.0, 30.0]                               # un-normalised embeddings
+
+EVAL_KNN_CASES = [  # (name, sigma, seed) on knn_data(305, 20, 256, sigma, 1000, seed)
+    ("separable_s5", 0.3, 5), ("separable_s77", 0.3, 77), ("overlapping_s5", 1.2, 5), ("overlapping_s77", 1.2, 77),
+]
+
+
+def randn_rows(seed, nq, n, e, scale):
+    rs = np.random.RandomState(seed)
+    return (scale * rs.randn(nq, e)).astype(np.float32), (scale * rs.randn(n, e)).astype(np.float32)
+
+
+def tied_matrix(seed, rows, n):
+    """Integer-valued float rows with many repeats (0..7): every selection meets ties."""
+    return np.random.RandomState(seed).randint(0, 8, size=(rows, n)).astype(np.float32)
