@@ -385,3 +385,47 @@ def softmax_cross_entropy(logits, targets):
     """Keras Dense(softmax) + 'categorical_crossentropy' + 'accuracy' from the logits:
     -> (mean loss [autograd], accuracy, probabilities)."""
     return _SoftmaxXent.apply(logits, targets)
+
+
+# --------------------------------------------------------------------------- exact t-SNE (embeddingnet_amd/tsne.py drives these)
+def tsne_workspace(n, like):
+    """The [bytes/8] float64 workspace the three t-SNE entry points share for n points."""
+    return _new((max(_lib.lib().embnet_tsne_workspace_bytes(int(n)) // 8, 1),), like, torch.float64)
+
+
+def tsne_affinities(d2, perplexity, inplace=False, ws=None):
+    """Squared distances [n,n] -> (P [n,n] joint probabilities, beta [n] precisions; sigma = sqrt(1 / (2 beta))): scikit-learn's
+    _joint_probabilities.  inplace writes P over d2 (a float32 contiguous tensor)."""
+    d2 = _prep(d2)
+    n = d2.shape[0]
+    if d2.shape != (n, n):
+        raise _lib.EmbnetError(f"tsne_affinities: distance matrix {tuple(d2.shape)} is not square")
+    ws = tsne_workspace(n, d2) if ws is None else ws
+    p = d2 if inplace else torch.empty_like(d2)
+    beta = _new((n,), d2)
+    check(_lib.lib().embnet_tsne_affinities(ptr(d2), n, f32(perplexity), ptr(p), ptr(beta), ptr(ws), ws.numel() * 8, stream()))
+    return p, beta
+
+
+def tsne_iterate(p, y, update, gains, exaggeration, momentum, learning_rate, n_iter, ws=None):
+    """n_iter gradient-descent iterations of exact t-SNE, in place on y, update, gains (float32 contiguous [n,2])."""
+    n = p.shape[0]
+    for t in (y, update, gains):
+        if t.dtype != torch.float32 or tuple(t.shape) != (n, 2):
+            raise _lib.EmbnetError(f"tsne_iterate: y, update and gains must be float32 [{n},2]")
+    ws = tsne_workspace(n, p) if ws is None else ws
+    check(_lib.lib().embnet_tsne_iterate(ptr(p), n, ptr(y), ptr(update), ptr(gains), f32(exaggeration), f32(momentum),
+                                         f32(learning_rate), int(n_iter), ptr(ws), ws.numel() * 8, stream()))
+    return y
+
+
+def tsne_kl(p, y, return_grad=False, ws=None):
+    """-> out [2] = (KL divergence, 2-norm of the gradient) at y, on the device[, gradient [n,2]]: scikit-learn's _kl_divergence."""
+    n = p.shape[0]
+    y = _prep(y)
+    ws = tsne_workspace(n, p) if ws is None else ws
+    out = _new((2,), p)
+    grad = _new((n, 2), p) if return_grad else None
+    check(_lib.lib().embnet_tsne_kl(ptr(p), n, ptr(y), out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws), ws.numel() * 8,
+                                    stream()))
+    return (out, grad) if return_grad else out

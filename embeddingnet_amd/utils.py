@@ -1,4 +1,6 @@
-"""Drop-in for the config / optimizer part of embedding_net/utils.py (reference :143-197).
+"""Drop-in for the config / optimizer part of embedding_net/utils.py (reference :143-197) and for its encodings plots
+(`load_encodings`, `plot_tsne`, `plot_tsne_interactive`, reference :29-91; the t-SNE itself is embeddingnet_amd/tsne.py,
+exact and on the device, where the reference calls scikit-learn).
 
 `parse_params` keeps the reference's YAML schema and the layout of the dict it returns (lower-case
 section keys; MODEL.input_shape mirrored into GENERATOR and SOFTMAX_PRETRAINING; the optimizer entry of a
@@ -8,6 +10,10 @@ optimizers are constructed without parameters, ours need them, so the optimizer 
 Keras update rules and defaults, one HIP launch per step).  GENERATOR keys pass through as written, among them
 `device_augmentations` / `augment_seed` (tools/train.py: on-device augmentation, embeddingnet_amd/augment.py).
 """
+import os
+import pickle
+import sys
+
 import yaml
 
 # YAML section -> key of the returned dict (reference utils.py:169-195); the last one is optional
@@ -62,3 +68,70 @@ def parse_params(filename='configs/road_signs.yml'):
     if section in cfg:
         params[key] = _finish_section(cfg[section], shape)
     return params
+
+
+# --------------------------------------------------------------------------- encodings plots (reference utils.py:29-91)
+def load_encodings(path_to_encodings):
+    """The dict EmbeddingNet.save_encodings pickled: {'encodings': [n,e], 'labels': [n]}."""
+    with open(path_to_encodings, 'rb') as f:
+        return pickle.load(f)
+
+
+def _has_display():
+    if sys.platform.startswith(("win", "darwin")):
+        return True
+    return bool(os.environ.get("DISPLAY") or os.environ.get("WAYLAND_DISPLAY"))
+
+
+def _tsne_by_label(encodings):
+    """-> (embedding [n,2], [(label, xs, ys)] in list(set(labels)) order, as the reference iterates)."""
+    import numpy as np
+    from .tsne import TSNE
+    emb = TSNE().fit_transform(np.asarray(encodings['encodings'], dtype=np.float32))
+    names = np.array(encodings['labels'])
+    return emb, [(l, emb[names == l, 0], emb[names == l, 1]) for l in list(set(encodings['labels']))]
+
+
+def plot_tsne(encodings_path, save_plot_dir, show=True):
+    """t-SNE scatter of saved encodings: one series per label, the label written above every point, legend outside the axes,
+    16 x 16 inches, saved as `save_plot_dir + 'tsne.png.png'` (the reference's file name).  Without a display the Agg
+    backend is used and `show` does nothing.  Returns the [n,2] embedding (the reference returns None)."""
+    import matplotlib
+    headless = not _has_display()
+    if headless:
+        matplotlib.use("Agg")
+    from matplotlib import pyplot as plt
+    emb, series = _tsne_by_label(load_encodings(encodings_path))
+    fig, ax = plt.subplots(figsize=(16, 16))
+    for label, xs, ys in series:
+        ax.scatter(xs, ys, label=label)
+        for x, y in zip(xs, ys):
+            ax.annotate(label, (x, y), size=8, textcoords="offset points", xytext=(0, 10), ha='center')
+    ax.legend(bbox_to_anchor=(1.05, 1), fontsize='small', ncol=2)
+    if show and not headless:
+        fig.show()
+    fig.savefig("{}{}.png".format(save_plot_dir, 'tsne.png'))
+    plt.close(fig)
+    return emb
+
+
+def plot_tsne_interactive(encodings):
+    """The same embedding as a plotly figure (markers named by label, 1000 x 1000); `encodings` is the dict or its path.
+    Returns the [n,2] embedding."""
+    try:
+        import plotly.graph_objects as go
+    except ImportError as err:
+        raise ImportError("plot_tsne_interactive needs the 'plotly' package, which is not installed") from err
+    import numpy as np
+    if isinstance(encodings, str):
+        encodings = load_encodings(encodings)
+    emb, series = _tsne_by_label(encodings)
+    fig = go.Figure()
+    for label, xs, ys in series:
+        r, g, b = (int(255 * np.random.rand()) for _ in range(3))
+        fig.add_trace(go.Scatter(x=xs, y=ys, mode='markers', marker=dict(color=f'rgba({r},{g},{b},0.8)', size=10),
+                                 text=str(label), name=str(label)))
+    fig.update_layout(title=go.layout.Title(text="t-SNE plot", xref="paper", x=0), autosize=False, width=1000, height=1000)
+    if _has_display():
+        fig.show()
+    return emb

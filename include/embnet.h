@@ -812,6 +812,38 @@ int embnet_batch_all_loss_fwd(const float* emb, int p, int k, int e, float margi
 int embnet_batch_all_loss_bwd(const float* emb, int n, int e, const float* pair_w, const int32_t* n_active,
                               const float* upstream, float* demb, void* stream);
 
+/* ------------------------------------------------------------------ t-SNE of saved encodings
+ * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
+ * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and
+ * _utils.pyx) restated for the device; embeddingnet_amd/tsne.py drives them with scikit-learn's schedule.  Additions only:
+ * the ABI version stays 22.  fp32 storage, 2 <= n <= 32768, P dense [n,n].
+ *   embnet_tsne_affinities: d2[n,n] squared distances (embnet_pairwise_dist_f32 with squared != 0) -> p[n,n], beta[n].
+ *     Row i: bisection on beta so that the entropy of p_j|i ~ exp(-beta d2_ij), j != i, equals log(perplexity): beta = 1,
+ *     at most 100 steps, stop at |H - log perplexity| <= 1e-5, beta doubles / halves while its bracket is open, a zero row
+ *     sum becomes 1e-8 (_binary_search_perplexity; the row minimum of d2 is subtracted before exp, which cancels).
+ *     sigma_i = sqrt(1 / (2 beta_i)).  Then p = (p_cond + p_cond^T) / S, S = sum of the numerator (computed, fixed order),
+ *     max(p, 2.220446e-16) off the diagonal, diagonal 0; p_ij and p_ji are bitwise equal.  p may be the same buffer as d2.
+ *     1 <= perplexity < n.
+ *   embnet_tsne_iterate: n_iter gradient-descent iterations on y[n,2] with update[n,2] and gains[n,2] (the caller starts
+ *     them at 0 and 1): w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij,
+ *       g_i = 4 sum_j (exaggeration p_ij - w_ij / Z) w_ij (y_i - y_j)
+ *       inc = (update < 0 and g > 0) or (update > 0 and g < 0)       [the sign of update * g, immune to fp32 underflow]
+ *       gains = max(inc ? gains + 0.2 : gains * 0.8, 0.01);  update = momentum update - lr gains g;  y += update
+ *     (_gradient_descent).  Two launches per iteration: row sums over p (HBM-bound: 4 n^2 bytes), then the update, whose
+ *     workgroups each add the n row sums of w in the same fixed order in f64.  n_iter >= 0.
+ *   embnet_tsne_kl: at the current y, *kl = sum_{i != j} p_ij log(max(p_ij, eps) / max(w_ij / Z, eps)) (eps = 2.220446e-16),
+ *     *grad_norm = the 2-norm of g (exaggeration 1) over all 2n components, and, when grad != NULL, grad[n,2] = g
+ *     (_kl_divergence).  Z, the KL sum and |g|^2 are accumulated in f64.
+ * No atomics, every reduction in a fixed order: bitwise reproducible.  workspace >= embnet_tsne_workspace_bytes(n) (0 outside
+ * the range of n), 16-byte aligned, no initialisation needed; a short one is refused with -3. */
+size_t embnet_tsne_workspace_bytes(int n);
+int embnet_tsne_affinities(const float* d2, int n, float perplexity, float* p, float* beta, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int embnet_tsne_iterate(const float* p, int n, float* y, float* update, float* gains, float exaggeration, float momentum,
+                        float lr, int n_iter, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_tsne_kl(const float* p, int n, const float* y, float* kl, float* grad_norm, float* grad, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ optimizer update
  * utils.py:143-153 get_optimizer(name, lr): `Adam(lr)`, `RMSprop(lr)`, `keras_radam.RAdam(lr)`, else `SGD(lr)`
  * with the library defaults — applied by Keras after train.py:160-177's compile/fit.  One launch updates every
