@@ -159,6 +159,40 @@ class EmbeddingNet:
             total += len(imgs)
         return {'top1': top1 / max(total, 1), 'top5': top5 / max(total, 1)}
 
+    def calculate_retrieval_metrics(self, data_loader, ks=(1, 5, 10), gallery='val', batch_size=256):
+        """Recall@K / MRR of data_loader.val_data (retrieval.retrieval_metrics: the rank of the nearest same-class item).
+        gallery='val': leave-one-out within the validation set; gallery='train': the validation items are searched in
+        self.encoded_training_data (generate_encodings / load_encodings), nothing excluded.  The validation items are encoded
+        class by class in batches of at most batch_size; file lists and in-memory arrays are both handled."""
+        from .datagenerators import get_image
+        from .retrieval import retrieval_metrics
+        if gallery not in ('val', 'train'):
+            raise ValueError(f"calculate_retrieval_metrics: gallery must be 'val' or 'train' (got {gallery!r})")
+        train = self.encoded_training_data
+        if gallery == 'train' and not (train and 'encodings' in train and 'labels' in train):
+            raise ValueError("calculate_retrieval_metrics: gallery='train' needs encoded_training_data "
+                             "(generate_encodings / load_encodings / fit_knn first)")
+        encodings, labels = [], []
+        for class_name, items in data_loader.val_data.items():
+            for i0 in range(0, len(items), int(batch_size)):
+                part = items[i0:i0 + int(batch_size)]
+                if isinstance(part, np.ndarray):
+                    imgs = part
+                else:
+                    imgs = np.asarray([get_image(p, self.params_model['input_shape']) for p in part], np.float32) / 255.
+                enc = np.asarray(self.base_model.predict(imgs))
+                encodings.append(enc.reshape(len(imgs), -1))
+                labels += [class_name] * len(imgs)
+        if not encodings:
+            raise ValueError("calculate_retrieval_metrics: data_loader.val_data is empty")
+        encodings = np.concatenate(encodings, axis=0)
+        dev = next(self.base_model.parameters()).device
+        if gallery == 'train':
+            g = np.asarray(train['encodings'], np.float32)
+            return retrieval_metrics(encodings, labels, ks=ks, gallery=g.reshape(len(train['labels']), -1),
+                                     gallery_labels=train['labels'], device=dev)
+        return retrieval_metrics(encodings, labels, ks=ks, device=dev)
+
 
 class _ClsHead(nn.Module):
     def __init__(self, base_model, e):

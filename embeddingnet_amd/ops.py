@@ -356,6 +356,64 @@ def knn_vote(idx, labels):
     return pred
 
 
+# --------------------------------------------------------------------------- evaluation: retrieval (Recall@K, MRR)
+def retrieval_first_positive(q, q_labels, x=None, x_labels=None):
+    """Rank of each query's nearest same-class gallery item, without the [nq,n] distance matrix (include/embnet.h).
+
+    q [nq,e], q_labels [nq] (integers); x [n,e], x_labels [n] the gallery.  x is None: leave-one-out on q (column i is skipped
+    for query i).  -> (rank int32 [nq]: 1 + negatives in front of the first positive in (d2, index) order, 0 without a positive;
+    pos_index int32 [nq]: its gallery index or -1; pos_d2 float32 [nq]: its squared distance or +inf), on the device."""
+    q = _prep(q.detach())
+    ql = q_labels.to(torch.int32).contiguous()
+    self_exclude = x is None
+    if self_exclude:
+        if x_labels is not None:
+            raise _lib.EmbnetError("retrieval_first_positive: gallery labels without a gallery")
+        x, xl = q, ql
+    else:
+        if x_labels is None:
+            raise _lib.EmbnetError("retrieval_first_positive: a gallery needs its labels")
+        x = _prep(x.detach())
+        xl = x_labels.to(torch.int32).contiguous()
+    if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
+        raise _lib.EmbnetError(f"retrieval_first_positive: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
+    nq, e = q.shape
+    n = x.shape[0]
+    if x.shape[1] != e:
+        raise _lib.EmbnetError(f"retrieval_first_positive: widths differ ({e} vs {x.shape[1]})")
+    if tuple(ql.shape) != (nq,) or tuple(xl.shape) != (n,):
+        raise _lib.EmbnetError("retrieval_first_positive: one label per row is needed")
+    lib = _lib.lib()
+    ws = _new((max(lib.embnet_retrieval_workspace_bytes(nq, n) // 8, 1),), q, torch.float64)
+    rank, pos = _new((nq,), q, torch.int32), _new((nq,), q, torch.int32)
+    d2 = _new((nq,), q)
+    check(lib.embnet_retrieval_first_positive(ptr(q), ptr(ql), nq, ptr(x), ptr(xl), n, e, int(self_exclude), ptr(rank), ptr(pos),
+                                              ptr(d2), ptr(ws), ws.numel() * 8, stream()))
+    return rank, pos, d2
+
+
+def retrieval_reduce(rank, ks):
+    """rank int32 [nq] (0 = no positive) and cut-offs ks -> (hits int32 [nk] = #{0 < rank <= K}, n_valid int32 [] = #{rank > 0},
+    sum_inv_rank float64 [] = sum 1 / rank over rank > 0), on the device; fixed summation order.  ks: a sequence of integers >= 1
+    (checked here), or an int32 device tensor whose entries the caller has checked."""
+    rank = rank.to(torch.int32).contiguous()
+    if torch.is_tensor(ks):
+        kt = ks.to(device=rank.device, dtype=torch.int32).contiguous()
+    else:
+        ks = [int(k) for k in ks]
+        if any(k < 1 for k in ks):
+            raise _lib.EmbnetError(f"retrieval_reduce: every K must be >= 1 (got {ks})")
+        kt = torch.tensor(ks, dtype=torch.int32, device=rank.device)
+    if kt.numel() == 0 or rank.numel() == 0:
+        raise _lib.EmbnetError("retrieval_reduce: empty ranks or empty ks")
+    hits = _new((kt.numel(),), rank, torch.int32)
+    n_valid = _new((), rank, torch.int32)
+    s = _new((), rank, torch.float64)
+    check(_lib.lib().embnet_retrieval_reduce(ptr(rank), rank.numel(), ptr(kt), kt.numel(), ptr(hits), ptr(n_valid), ptr(s),
+                                             stream()))
+    return hits, n_valid, s
+
+
 # --------------------------------------------------------------------------- softmax pre-training head
 class _SoftmaxXent(torch.autograd.Function):
     @staticmethod

@@ -136,6 +136,35 @@ int embnet_topk_smallest(const float* dist, int rows, int n, int k, int32_t* idx
 /* pred[rows] = majority label among labels[idx[row,:]], ties to the smallest label (KNeighborsClassifier.predict). */
 int embnet_knn_vote(const int32_t* idx, const int32_t* labels, int rows, int k, int32_t* pred, void* stream);
 
+/* ---- retrieval evaluation (Recall@K, MRR): rank of each query's nearest same-class gallery item, computed without the
+ * [nq,n] distance matrix (csrc/retrieval.hip).  Additions only: the ABI version stays 22.
+ *   Inputs: queries q[nq,e] with labels q_labels[nq], gallery x[n,e] with labels x_labels[n] (int32, any order, no layout
+ *     assumed).  self_exclude != 0: leave-one-out — nq == n is required, row i of q is row i of x, and column i is skipped
+ *     for query i (neither a positive nor counted).
+ *   Distance: the fp32 squared distance of embnet_cross_dist_f32, d2 = max(|q|^2 + |x|^2 - 2 q.x, 0), no square root (the
+ *     order is the same); a NaN d2 counts as +inf, as in embnet_topk_smallest.
+ *   Order: lexicographic on (d2, gallery index) — ties go to the smaller index (embnet_topk_smallest's rule).
+ *   Positive of query r: a non-excluded column c with x_labels[c] == q_labels[r]; the first positive is the smallest one
+ *     in the order.  Outputs per query:
+ *       rank[r]      = 1 + the number of non-excluded NEGATIVE columns that precede the first positive; 0 without a positive
+ *       pos_index[r] = gallery index of the first positive, or -1
+ *       pos_d2[r]    = its d2, or +inf
+ *   A minimum and an integer count: bitwise reproducible.  Two passes of the distance GEMM: one counts (2*nq*n*e FLOP), the
+ *   other finds the first positives and visits only the tile pairs whose label sets can meet (a per-tile label filter: a few
+ *   per cent of the tiles when labels come grouped by class, all of them when they come in random order).  O(nq + n) bytes
+ *   of workspace (>= embnet_retrieval_workspace_bytes(nq, n), 16-byte aligned, no initialisation needed; a short one is
+ *   refused with -3), no [nq,n] buffer, each embedding block below 2 GiB.  No allocation and no synchronisation inside.
+ * embnet_retrieval_reduce: over the queries with rank > 0, hits[j] = #{rank <= ks[j]} (ks[nk] device int32, every ks[j] >= 1,
+ *   no upper limit), *n_valid = #{rank > 0}, *sum_inv_rank = sum 1 / rank (f64, fixed order).  recall@K = hits / n_valid and
+ *   mrr = sum_inv_rank / n_valid are the caller's divisions. */
+size_t embnet_retrieval_workspace_bytes(int nq, int n);
+int embnet_retrieval_first_positive(const float* q, const int32_t* q_labels, int nq,
+                                    const float* x, const int32_t* x_labels, int n, int e, int self_exclude,
+                                    int32_t* rank, int32_t* pos_index, float* pos_d2,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int embnet_retrieval_reduce(const int32_t* rank, int nq, const int32_t* ks, int nk,
+                            int32_t* hits, int32_t* n_valid, double* sum_inv_rank, void* stream);
+
 /* ------------------------------------------------------------------ backbone layers
  * Stand-ins for the Keras layers that backbones.py:19-121 instantiates (TensorFlow kernels in the
  * reference).  All NHWC fp32. */

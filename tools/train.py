@@ -136,10 +136,40 @@ def device_augmentations(cfg, synthetic=0, rank=0):
     return aug
 
 
+def monitor_config(p_train, validate):
+    """TRAIN.retrieval_ks / TRAIN.monitor (both optional) -> (the K's of the per-epoch retrieval evaluation, the monitored name).
+    retrieval_ks: after each epoch's validation, Recall@K and MRR of the validation set (leave-one-out,
+    EmbeddingNet.calculate_retrieval_metrics) join the history as val_recall@K / val_mrr.  monitor: what plateau, early stop and
+    best checkpoint follow — 'val_loss' ('loss' without validation) by default, or 'loss', 'val_recall@K' with K in
+    retrieval_ks, 'val_mrr'.  Anything that cannot be honoured is a ValueError before training starts."""
+    ks = p_train.get('retrieval_ks') or []
+    if isinstance(ks, (int, float)):
+        ks = [ks]
+    if any(int(k) != k or int(k) < 1 for k in ks):
+        raise ValueError(f"TRAIN.retrieval_ks: every K must be an integer >= 1 (got {list(ks)})")
+    ks = [int(k) for k in ks]
+    if ks and not validate:
+        raise ValueError("TRAIN.retrieval_ks evaluates the validation set: it needs DATALOADER.validate (validation is off)")
+    default = 'val_loss' if validate else 'loss'
+    monitor = p_train.get('monitor') or default
+    if monitor.startswith('val_') and not validate:
+        raise ValueError(f"TRAIN.monitor: {monitor!r} needs DATALOADER.validate (validation is off)")
+    if monitor.startswith('val_recall@'):
+        if monitor not in [f'val_recall@{k}' for k in ks]:
+            raise ValueError(f"TRAIN.monitor: {monitor!r} names a K that TRAIN.retrieval_ks {ks} does not compute")
+    elif monitor == 'val_mrr':
+        if not ks:
+            raise ValueError("TRAIN.monitor: 'val_mrr' needs TRAIN.retrieval_ks")
+    elif monitor not in ('loss', 'val_loss'):
+        raise ValueError(f"TRAIN.monitor: unknown name {monitor!r} (loss, val_loss, val_recall@K, val_mrr)")
+    return ks, monitor
+
+
 def main():
     args = parse_args()
     cfg = parse_params(args.config)
     device_augmentations(cfg, args.synthetic)          # a bad GENERATOR.device_augmentations fails before the GPU is touched
+    monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
     paths = create_save_folders(cfg['general'])
@@ -160,7 +190,7 @@ def main():
                                           validate=p_loader.get('validate', True), seed=0)
     else:
         data_loader = ENDataLoader(**{k: v for k, v in p_loader.items() if k != 'csv_file'})
-    monitor = 'val_loss' if data_loader.validate else 'loss'
+    retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed')}
 
     siamese = p_model['mode'] == 'siamese'
@@ -216,6 +246,10 @@ def main():
             negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer)
     plateau = Plateau(persistent=bool(p_train.get('plateau_persistent', False)))
     history = {'loss': [], 'val_loss': []}
+    for k in retrieval_ks:
+        history[f'val_recall@{k}'] = []
+    if retrieval_ks:
+        history['val_mrr'] = []
     n_epochs = min(p_train['n_epochs'], args.max_epochs or p_train['n_epochs'])
 
     # triplet mode: batches are planned on this thread and decoded / uploaded ahead of the step (input_pipeline.Feeder: the
@@ -264,6 +298,18 @@ def main():
                 value = all_reduce_mean(float(torch.stack(vals).mean().item()))
                 history['val_loss'].append(value)
                 msg += f' - val_loss {value:.4f}'
+                if retrieval_ks:
+                    # every rank evaluates the whole validation set (BN buffers are rank-local, decisions must agree): the
+                    # values pass through all_reduce_mean like val_loss
+                    with torch.no_grad():
+                        found = model.calculate_retrieval_metrics(data_loader, ks=retrieval_ks)
+                    for name in [f'recall@{k}' for k in retrieval_ks] + ['mrr']:
+                        history['val_' + name].append(all_reduce_mean(float(found[name])))
+                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                if monitor == 'loss':
+                    value = epoch_loss
+                elif monitor != 'val_loss':
+                    value = 1.0 - history[monitor][-1]    # lower is better for plateau, early stop and best checkpoint
             if rank == 0:
                 print(msg, flush=True)
             improved, stop, lr_end = plateau.update(value, lr)   # `value` is the all-reduced mean: same decisions on every rank
@@ -280,7 +326,7 @@ def main():
                 save_optimizer_state(_optimizer_state_path(path), opt,
                                      {k: v for k, v in keras_weights(trainable).items() if isinstance(v, torch.nn.Parameter)},
                                      extra={'epoch': epoch + 1})
-                print(f'{monitor} improved to {value:.5f}, saving model to {path}')
+                print(f'{monitor} improved to {history[monitor][-1]:.5f}, saving model to {path}')
             if stop:
                 print('EarlyStopping')
                 break
