@@ -351,6 +351,10 @@ int embnet_conv1x1_thin_supported(int red, int ncols);
  * an abs-max pass); for activations the BatchNormalization's output bound (embnet_affine_act_planes_ex `y_bound`: RANGE SLOT above)
  * or, without one, a dry run of the pass.  (ABI 20 and earlier fixed s = 1 for activations: tensors of amplitude << 2^-3 sat on
  * the subnormal floor — 1.8e-4 relative error at amplitude 1e-4)
+ * What this costs ONE ELEMENT of a result, by how far its operands lie below their tensor's bound, is measured in DESIGN.md 3.14 (9)
+ * (the envelope table of tests/test_split_ref_cpu.py, and how deep the shipped ResNets' channels lie): fp32-class down to 2^16 below
+ * the bound, 2^(d - 39) of sum |a||b| at depth d beyond that; tests/test_three_product_elementwise_gpu.py holds every kernel to
+ * exactly this arithmetic, element by element.
  * The buffers keep the three-plane size below: planes 0 and 1 hold the pieces, the first two floats of the third plane's space
  * hold (s, 1 / s) (and a scratch word).  EMBNET_PLANES_F16=0: three bf16 pieces (exact split by truncation) and the six-term products documented above.
  *   planes of an activation / gradient x[pixels, c] (c % 16 == 0):  16-bit [3][c/16][pixels][16]  (piece, 16-channel chunk,

@@ -15,6 +15,8 @@ the tensor's range slot; a tensor nobody vouches for runs the six-term bf16 kern
   * ResNet18 with every BatchNormalization's gamma at 1e-3 against the float64 oracle.
 The gather kernels' own amplitude sweep is in tests/test_conv_ranges_gpu.py.  Reference layers: /root/reference/embedding_net/backbones.py:16,99-121.
 """
+import os
+import sys
 import threading
 
 import numpy as np
@@ -23,6 +25,9 @@ import torch
 
 from embeddingnet_amd import _lib
 from embeddingnet_amd import layers as L
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from split_ref import decode_planes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -66,12 +71,9 @@ def bn_forward(x2d, gamma, beta, act, partial=None, y=True, planes=False, use_bo
 
 
 def decode(planes, m, c):
-    """two-piece fp16 planes [2+][c/16][m][16] -> (float64 [m, c], s)."""
-    flat = planes.cpu().numpy().view(np.uint16).reshape(3, -1)
-    s, inv = flat[2][:4].view(np.float32)[:2]
-    assert s > 0 and s * inv == 1.0 and np.log2(s) == np.round(np.log2(s)), (s, inv)
-    v = (flat[0].view(np.float16).astype(np.float64) + flat[1].view(np.float16).astype(np.float64)) * float(inv)
-    return v.reshape(c // 16, m, 16).transpose(1, 0, 2).reshape(m, c), float(s)
+    """two-piece fp16 planes [2+][c/16][m][16] -> (float64 [m, c], s); the pieces themselves: tests/split_ref.py decode_planes."""
+    h1, h2, s = decode_planes(planes.cpu().numpy(), m, c)
+    return (h1.astype(np.float64) + h2.astype(np.float64)) * (1.0 / s), s
 
 
 # ---- the bound -------------------------------------------------------------------------------------------------------------------
