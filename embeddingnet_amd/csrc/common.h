@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <atomic>
 
 namespace embnet {
 
@@ -29,6 +30,24 @@ inline int check_launch(const char* what) {
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- dynamic LDS beyond the 64 KB a launch gets by default ----------------
+// A kernel that asks for more has to opt in, per device; BIG_LDS_BYTES (a gfx950 CU's 160 KB) is the bound of that opt-in and of
+// every plan that sizes dynamic LDS.  allow_big_lds<kernel>() in front of such a launch opts the kernel in on the CURRENT device
+// the first time it runs there: bit d of the kernel's own word says device d is done, so a launch costs hipGetDevice and one load.
+// Two threads may both find the bit clear and both set the attribute (the same value); the acquire / release pair orders the one
+// that finds it set behind the call that set it.  A device number past the word is never remembered, only slower.
+constexpr int BIG_LDS_BYTES = 160 * 1024;
+template <auto Kernel>
+inline void allow_big_lds() {
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = (unsigned)dev < 64 ? 1ull << dev : 0;
+  if (done.load(std::memory_order_acquire) & bit) return;
+  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES);
+  done.fetch_or(bit, std::memory_order_release);
+}
 
 // ---- optional per-kernel timing (embnet_trace_*, include/embnet.h) --------
 // A TraceScope around ONE kernel launch records a HIP event before and after it on the launch stream together with

@@ -842,7 +842,7 @@ __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const SlabBatch)
 
 using namespace embnet;
 
-// host helper for conv_patch.hip: the fix-up pass over `rem` left-over tiles cut into `parts` partial tiles (SplitTail)
+// the fix-up pass over `rem` left-over tiles cut into `parts` partial tiles (SplitTail); conv_patch.hip's launches end with it too
 namespace embnet {
 void launch_tail_fixup(const float* ws, int parts, int bm, int bn, int wtm, int n_full, int rem, int tiles_n, long m, int cols,
                        const float* bias, int relu, const float* residual, float* out, float* stats, int stats_rows,
@@ -851,7 +851,7 @@ void launch_tail_fixup(const float* ws, int parts, int bm, int bn, int wtm, int 
   tail_fixup_kernel<<<rem * (bm * bn / 1024), 256, 0, st>>>(ws, parts, bm, bn, wtm, n_full, tiles_n, m, cols, bias, relu,
                                                            residual, out, stats, stats_rows, bsum);
 }
-// host helper for conv_wgrad_planes.hip: the fixed-order sum of split-K slabs into the gradient
+// the fixed-order sum of split-K slabs into the gradient (conv_wgrad_planes.hip's too)
 void launch_slab_reduce(const float* slabs, int splits, long n, float* out, hipStream_t st) {
   EMBNET_TRACE("embnet::slab_reduce_kernel", TRACE_BYTES, 4.0 * n * (splits + 1), st);
   slab_reduce_kernel<<<(n & 3) ? cdiv(n, 256) : cdiv(n / 4, 32), 256, 0, st>>>(slabs, splits, n, out);
@@ -986,26 +986,19 @@ static const char* conv_kernel_name(const char* kernel, const char* params, int 
   return buf;
 }
 
-#define LAUNCH_TILED(KERNEL, VECARGS, tile, grid, st, p)                              \
-  switch (tile) {                                                                     \
-    case 0: KERNEL<G128x128, VECARGS><<<grid, 256, 0, st>>>(p); break;                \
-    case 1: KERNEL<G128x64, VECARGS><<<grid, 256, 0, st>>>(p); break;                 \
-    case 2: KERNEL<G128x32, VECARGS><<<grid, 256, 0, st>>>(p); break;                 \
-    default: KERNEL<G64x64, VECARGS><<<grid, 256, 0, st>>>(p); break;                 \
+// The tile dispatch of every launch below: launch(G{}) with the Geom type of `tile`, e.g.
+//   for_tile<false>(tile, [&](auto g) { conv_fwd_kernel<decltype(g), true><<<grid, 256, 0, st>>>(p); });
+// WGRAD: + the 192-row tile only the weight gradient plans (elsewhere no kernel is instantiated for it)
+template <bool WGRAD, class Launch>
+static void for_tile(int tile, Launch&& launch) {
+  switch (tile) {
+    case 0: return launch(G128x128{});
+    case 1: return launch(G128x64{});
+    case 2: return launch(G128x32{});
+    case 4: if constexpr (WGRAD) return launch(G192x64{});     // (elsewhere: the default)
+    default: return launch(G64x64{});
   }
-
-#define LAUNCH_TILED_H(KERNEL, tile, grid, st, p)                                     \
-  switch (tile) {                                                                     \
-    case 0: KERNEL<G128x128><<<grid, 256, 0, st>>>(p); break;                         \
-    case 1: KERNEL<G128x64><<<grid, 256, 0, st>>>(p); break;                          \
-    case 2: KERNEL<G128x32><<<grid, 256, 0, st>>>(p); break;                          \
-    default: KERNEL<G64x64><<<grid, 256, 0, st>>>(p); break;                          \
-  }
-#define LAUNCH_WGRAD_H(KERNEL, tile, grid, st, p)          /* + the 192-row tile only the weight gradient plans */ \
-  switch (tile) {                                                                     \
-    case 4: KERNEL<G192x64><<<grid, 256, 0, st>>>(p); break;                          \
-    default: LAUNCH_TILED_H(KERNEL, tile, grid, st, p)                                \
-  }
+}
 static const char* conv_h_kernel_name(const char* kernel, const char* params, int tile) {
   static thread_local char buf[160];
   snprintf(buf, sizeof buf, "void embnet::%s<embnet::Geom<%s> >(embnet::%s)", kernel, GEOM_NAME[tile], params);
@@ -1126,17 +1119,14 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
                       conv_kernel_name(in_scale ? "conv_fwd_tf_kernel" : "conv_fwd_kernel", "ConvFwdParams", tile,
                                        (vec || in_scale) ? "true" : "false"), flop,
                       4.0 * ((double)n * h * wd * c + (double)r * s * c * k + (double)M * k * (residual ? 2 : 1)), st);
-    if (hform) { LAUNCH_TILED_H(conv_fwd_h_kernel, tile, grid, st, p) }
-    else if (in_scale) { LAUNCH_TILED(conv_fwd_tf_kernel, true, tile, grid, st, p) }
-    else if (vec) { LAUNCH_TILED(conv_fwd_kernel, true, tile, grid, st, p) }
-    else { LAUNCH_TILED(conv_fwd_kernel, false, tile, grid, st, p) }
+    if (hform) for_tile<false>(tile, [&](auto g) { conv_fwd_h_kernel<decltype(g)><<<grid, 256, 0, st>>>(p); });
+    else if (in_scale) for_tile<false>(tile, [&](auto g) { conv_fwd_tf_kernel<decltype(g), true><<<grid, 256, 0, st>>>(p); });
+    else if (vec) for_tile<false>(tile, [&](auto g) { conv_fwd_kernel<decltype(g), true><<<grid, 256, 0, st>>>(p); });
+    else for_tile<false>(tile, [&](auto g) { conv_fwd_kernel<decltype(g), false><<<grid, 256, 0, st>>>(p); });
   }
-  if (p.tail.parts > 1) {
-    const int rem = (int)(tiles - p.tail.n_full), bm = TILE_BM[tile], bn = TILE_BN[tile];
-    EMBNET_TRACE("embnet::tail_fixup_kernel", TRACE_BYTES, 4.0 * rem * bm * bn * (p.tail.parts + 1 + (residual ? 1 : 0)), st);
-    tail_fixup_kernel<<<rem * (bm * bn / 1024), 256, 0, st>>>(p.tail.ws, p.tail.parts, bm, bn, TILE_WTM[tile], p.tail.n_full,
-                                                             cdiv(k, bn), M, k, bias, relu, residual, y, stats, p.stats_rows, BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0});
-  }
+  if (p.tail.parts > 1)
+    launch_tail_fixup(p.tail.ws, p.tail.parts, TILE_BM[tile], TILE_BN[tile], TILE_WTM[tile], p.tail.n_full, (int)(tiles - p.tail.n_full),
+                      cdiv(k, TILE_BN[tile]), M, k, bias, relu, residual, y, stats, p.stats_rows, NO_BN_SUMS, st);
   return check_launch("conv2d_fwd");
 }
 extern "C" int embnet_conv2d_fwd_f32(const float* x, const float* w, const float* bias, float* y, int n, int h,
@@ -1219,16 +1209,13 @@ static int conv2d_dgrad_impl(const float* dy, const float* w, float* dx, int n, 
                       conv_kernel_name("conv_dgrad_kernel", "ConvDgradParams", tile, vec ? "true" : "false"),
                       2.0 * n * oh * ow * (double)k * r * s * c,
                       4.0 * ((double)n * oh * ow * k + (double)r * s * c * k + (double)n * h * wd * c * (p.accumulate ? 2 : 1)), st);
-    if (hform) { LAUNCH_TILED_H(conv_dgrad_h_kernel, tile, grid, st, p) }
-    else if (vec) { LAUNCH_TILED(conv_dgrad_kernel, true, tile, grid, st, p) }
-    else { LAUNCH_TILED(conv_dgrad_kernel, false, tile, grid, st, p) }
+    if (hform) for_tile<false>(tile, [&](auto g) { conv_dgrad_h_kernel<decltype(g)><<<grid, 256, 0, st>>>(p); });
+    else if (vec) for_tile<false>(tile, [&](auto g) { conv_dgrad_kernel<decltype(g), true><<<grid, 256, 0, st>>>(p); });
+    else for_tile<false>(tile, [&](auto g) { conv_dgrad_kernel<decltype(g), false><<<grid, 256, 0, st>>>(p); });
   }
-  if (p.tail.parts > 1) {
-    const int rem = (int)(tiles - p.tail.n_full), bm = TILE_BM[tile], bn = TILE_BN[tile];
-    EMBNET_TRACE("embnet::tail_fixup_kernel", TRACE_BYTES, 4.0 * rem * bm * bn * (p.tail.parts + 1 + (p.accumulate ? 1 : 0)), st);
-    tail_fixup_kernel<<<rem * (bm * bn / 1024), 256, 0, st>>>(p.tail.ws, p.tail.parts, bm, bn, TILE_WTM[tile], p.tail.n_full,
-                                                             cdiv(c, bn), max_m, c, nullptr, 0, p.accumulate ? p.add_src : nullptr, dx, nullptr, 0, p.bn);
-  }
+  if (p.tail.parts > 1)
+    launch_tail_fixup(p.tail.ws, p.tail.parts, TILE_BM[tile], TILE_BN[tile], TILE_WTM[tile], p.tail.n_full, (int)(tiles - p.tail.n_full),
+                      cdiv(c, TILE_BN[tile]), max_m, c, nullptr, 0, p.accumulate ? p.add_src : nullptr, dx, nullptr, 0, p.bn, st);
   return check_launch("conv2d_dgrad");
 }
 
@@ -1237,7 +1224,7 @@ extern "C" int embnet_conv2d_dgrad_f32(const float* dy, const float* w, float* d
                                        int accumulate, const float* dx_add, void* workspace, size_t workspace_bytes,
                                        void* stream) {
   return conv2d_dgrad_impl(dy, w, dx, n, h, wd, c, r, s, k, stride, pad_t, pad_l, oh, ow, accumulate, dx_add, workspace,
-                           workspace_bytes, stream, BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0}, take_ranges());
+                           workspace_bytes, stream, NO_BN_SUMS, take_ranges());
 }
 extern "C" int embnet_conv2d_dgrad_f32_ex(const float* dy, const float* w, float* dx, int n, int h, int wd, int c,
                                           int r, int s, int k, int stride, int pad_t, int pad_l, int oh, int ow,
@@ -1245,7 +1232,7 @@ extern "C" int embnet_conv2d_dgrad_f32_ex(const float* dy, const float* w, float
                                           const uint32_t* dy_range, const uint32_t* w_range, void* stream) {
   (void)take_ranges();
   return conv2d_dgrad_impl(dy, w, dx, n, h, wd, c, r, s, k, stride, pad_t, pad_l, oh, ow, accumulate, dx_add, workspace,
-                           workspace_bytes, stream, BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0}, Ranges{dy_range, w_range});
+                           workspace_bytes, stream, NO_BN_SUMS, Ranges{dy_range, w_range});
 }
 
 // rows of the [2][C][rows] partial sums embnet_conv2d_dgrad_bnsums_f32 writes for this geometry; 0: not available
@@ -1335,15 +1322,6 @@ extern "C" size_t embnet_conv2d_wgrad_workspace_bytes(int n, int c, int r, int s
   return splits > 1 ? (size_t)splits * r * s * c * k * sizeof(float) : 0;
 }
 
-#define LAUNCH_WGRAD(KERNEL, VA, VB)                                                \
-  switch (tile) {                                                                       \
-    case 0: KERNEL<G128x128, VA, VB><<<grid, 256, 0, st>>>(p); break;                   \
-    case 1: KERNEL<G128x64, VA, VB><<<grid, 256, 0, st>>>(p); break;                    \
-    case 2: KERNEL<G128x32, VA, VB><<<grid, 256, 0, st>>>(p); break;                    \
-    case 4: KERNEL<G192x64, VA, VB><<<grid, 256, 0, st>>>(p); break;                    \
-    default: KERNEL<G64x64, VA, VB><<<grid, 256, 0, st>>>(p); break;                    \
-  }
-
 static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes, int n, int h,
                       int wd, int c, int r, int s, int k, int stride, int pad_t, int pad_l, int oh, int ow,
                       const float* in_scale, const float* in_shift, int in_act, void* stream, bool do_main,
@@ -1369,11 +1347,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspac
     if (do_main)
       if (int rc = launch_thin_wgrad(x, dy, p.splits > 1 ? (float*)workspace : dw, (long)n * oh * ow, c, k, stride, n, h, wd, oh, ow, st))
         return rc;
-    if (p.splits > 1 && do_reduce) {
-      const long cnt = (long)rows * k;
-      EMBNET_TRACE("embnet::slab_reduce_kernel", TRACE_BYTES, 4.0 * cnt * (p.splits + 1), st);
-      slab_reduce_kernel<<<(cnt & 3) ? cdiv(cnt, 256) : cdiv(cnt / 4, 32), 256, 0, st>>>((const float*)workspace, p.splits, cnt, dw);
-    }
+    if (p.splits > 1 && do_reduce) launch_slab_reduce((const float*)workspace, p.splits, (long)rows * k, dw, st);
     return check_launch("conv2d_wgrad");
   }
   const dim3 grid(cdiv(rows, TILE_BM[tile]) * cdiv(k, TILE_BN[tile]) * ((p.splits + 7) / 8 * 8));
@@ -1391,17 +1365,15 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, void* workspac
                                        (in_scale || (va && vb)) ? "true, true" : (vb ? "false, true" : "false, false")),
                       2.0 * n * oh * ow * (double)k * rows,
                       4.0 * ((double)n * h * wd * c + (double)n * oh * ow * k + (double)rows * k * p.splits), st);
-    if (hform) { LAUNCH_WGRAD_H(conv_wgrad_h_kernel, tile, grid, st, p) }
-    else if (in_scale) { LAUNCH_WGRAD(conv_wgrad_tf_kernel, true, true) }
-    else if (va && vb) { LAUNCH_WGRAD(conv_wgrad_kernel, true, true) }
-    else if (vb) { LAUNCH_WGRAD(conv_wgrad_kernel, false, true) }
-    else { LAUNCH_WGRAD(conv_wgrad_kernel, false, false) }
+    // (the h kernel's 192-row tile ahead of the dispatch: instantiated first, it keeps its place among this file's kernels in the code object)
+    if (hform && tile == 4) conv_wgrad_h_kernel<G192x64><<<grid, 256, 0, st>>>(p);
+    else if (hform) for_tile<false>(tile, [&](auto g) { conv_wgrad_h_kernel<decltype(g)><<<grid, 256, 0, st>>>(p); });
+    else if (in_scale) for_tile<true>(tile, [&](auto g) { conv_wgrad_tf_kernel<decltype(g), true, true><<<grid, 256, 0, st>>>(p); });
+    else if (va && vb) for_tile<true>(tile, [&](auto g) { conv_wgrad_kernel<decltype(g), true, true><<<grid, 256, 0, st>>>(p); });
+    else if (vb) for_tile<true>(tile, [&](auto g) { conv_wgrad_kernel<decltype(g), false, true><<<grid, 256, 0, st>>>(p); });
+    else for_tile<true>(tile, [&](auto g) { conv_wgrad_kernel<decltype(g), false, false><<<grid, 256, 0, st>>>(p); });
   }
-  if (p.splits > 1 && do_reduce) {
-    const long cnt = (long)rows * k;
-    EMBNET_TRACE("embnet::slab_reduce_kernel", TRACE_BYTES, 4.0 * cnt * (p.splits + 1), st);
-    slab_reduce_kernel<<<(cnt & 3) ? cdiv(cnt, 256) : cdiv(cnt / 4, 32), 256, 0, st>>>((const float*)workspace, p.splits, cnt, dw);
-  }
+  if (p.splits > 1 && do_reduce) launch_slab_reduce((const float*)workspace, p.splits, (long)rows * k, dw, st);
   return check_launch("conv2d_wgrad");
 }
 
@@ -1481,26 +1453,16 @@ extern "C" int embnet_conv2d_wgrad_reduce_f32(const float* x, const float* dy, f
 // so a caller can attribute its own HIP-event timings to the symbol the profiler reports.
 extern "C" const char* embnet_conv2d_kernel_name(int kind, int n, int h, int wd, int c, int r, int s, int k,
                                                  int oh, int ow) {
-  static thread_local char buf[160];
-  const char* const* geoms = GEOM_NAME;
-  const char* t = (c & 3) == 0 ? "true" : "false";
-  const char* tk = (k & 3) == 0 ? "true" : "false";
-  if (kind == 0) {
-    snprintf(buf, sizeof buf, "void embnet::conv_fwd_kernel<embnet::Geom<%s>, %s>(embnet::ConvFwdParams)",
-             geoms[pick_tile((long)n * oh * ow, k, false, (long)r * s * c)], ((c | k) & 3) == 0 ? "true" : "false");
-  } else if (kind == 1) {
-    long max_m = (long)n * ((h + 0) / 1) * wd;         // same tile choice as the launcher (all classes together)
-    snprintf(buf, sizeof buf, "void embnet::conv_dgrad_kernel<embnet::Geom<%s>, %s>(embnet::ConvDgradParams)",
-             geoms[pick_tile(max_m, c, oh < h, (long)r * s * k)], tk);
-  } else if (kind == 2) {
-    int tile, sp, kt;
-    wgrad_plan(r * s * c, k, (long)n * oh * ow, tile, sp, kt, r == 1 && s == 1);
-    if (tile < 0) snprintf(buf, sizeof buf, "embnet::thinw::thin_wgrad_kernel");
-    else
-      snprintf(buf, sizeof buf, "void embnet::conv_wgrad_kernel<embnet::Geom<%s>, %s, %s>(embnet::ConvWgradParams)",
-               geoms[tile], ((k & 3) == 0) ? t : "false", tk);
-  } else {
-    buf[0] = 0;
-  }
-  return buf;
+  if (kind == 0)
+    return conv_kernel_name("conv_fwd_kernel", "ConvFwdParams", pick_tile((long)n * oh * ow, k, false, (long)r * s * c),
+                            ((c | k) & 3) == 0 ? "true" : "false");
+  if (kind == 1)                                       // same tile choice as the launcher (all classes together)
+    return conv_kernel_name("conv_dgrad_kernel", "ConvDgradParams", pick_tile((long)n * h * wd, c, oh < h, (long)r * s * k),
+                            (k & 3) == 0 ? "true" : "false");
+  if (kind != 2) return "";
+  int tile, sp, kt;
+  wgrad_plan(r * s * c, k, (long)n * oh * ow, tile, sp, kt, r == 1 && s == 1);
+  if (tile < 0) return "embnet::thinw::thin_wgrad_kernel";
+  return conv_kernel_name("conv_wgrad_kernel", "ConvWgradParams", tile,
+                          (k & 3) ? "false, false" : ((c & 3) ? "false, true" : "true, true"));
 }

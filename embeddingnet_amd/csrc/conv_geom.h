@@ -38,11 +38,14 @@ __device__ __forceinline__ void split_k(int kk, const FastDiv& dinner, const Fas
 // kinds: 3 = partial has a THIRD plane [C][rows]: max |dz| per row band (the bound of the BatchNorm backward's dx, nn_kernels.hip
 // dx_channel_bound); 0 / 2 = the two sums only
 struct BnSums { const float* x; const float* scale; const float* shift; const float* mean; const float* rstd; int act; float* partial; int rows; int kinds; };
+constexpr BnSums NO_BN_SUMS = BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0};
 
 // conv.hip: fix-up pass over left-over tiles computed as K-split partial tiles (used by conv.hip and conv_patch.hip)
 void launch_tail_fixup(const float* ws, int parts, int bm, int bn, int wtm, int n_full, int rem, int tiles_n, long m, int cols,
                        const float* bias, int relu, const float* residual, float* out, float* stats, int stats_rows,
                        const BnSums& bsum, hipStream_t st);
+// conv.hip: the fixed-order sum of split-K slabs into a weight gradient (used by conv.hip and conv_wgrad_planes.hip)
+void launch_slab_reduce(const float* slabs, int splits, long n, float* out, hipStream_t st);
 
 // conv_thin.hip: 1x1 convolutions with a thin reduction as an HBM stream (EfficientNet's expand forward / project data gradient)
 bool thin_gemm_applies(int red, int ncols);

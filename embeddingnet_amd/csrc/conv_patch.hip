@@ -927,6 +927,22 @@ static int patch_rows(int n, int oh, int ow, int r, int s) {                 // 
 
 struct Plan { int bn, tps, nbs, LR, tiles, n_full, parts, cc_part, n_pieces, grid; size_t lds, ws_bytes; };
 
+// The tiles of a planes GEMM (256 pixels x pl.bn channels, reduction in `ncc` units) on a grid of 256 workgroups: whole rounds as
+// whole tiles, the left-over tiles cut along the reduction into partial tiles for the fix-up pass (conv.hip's tail_fixup_kernel)
+static void plan_tiles(Plan& pl, long M, int k, int ncc) {
+  pl.tiles = cdiv(M, 256) * cdiv(k, pl.bn);
+  pl.grid = 256;
+  pl.n_full = pl.tiles / pl.grid * pl.grid;
+  const int rem = pl.tiles - pl.n_full;
+  pl.parts = 1; pl.cc_part = ncc; pl.n_pieces = 0; pl.ws_bytes = 0;
+  if (rem > 0) {
+    int parts = pl.grid / rem; if (parts > ncc) parts = ncc; if (parts < 1) parts = 1;
+    pl.cc_part = cdiv(ncc, parts); pl.parts = cdiv(ncc, pl.cc_part);
+    if (pl.parts == 1) { pl.n_full = pl.tiles; }                            // whole tiles: nothing to fix up
+    else { pl.n_pieces = rem * pl.parts; pl.ws_bytes = (size_t)pl.n_pieces * 256 * pl.bn * 4; }
+  }
+}
+
 // the 1x1 planes GEMM (conv1x1_planes_kernel): G = 2 chunks per step, a ring of three stages; reduction units are 32-channel groups
 constexpr int ONE_G = 2, ONE_NS = 3;
 static bool make_plan1(int n, int c, int k, int stride, int oh, int ow, Plan& pl) {
@@ -937,19 +953,7 @@ static bool make_plan1(int n, int c, int k, int stride, int oh, int ow, Plan& pl
   pl.bn = k >= 128 ? 128 : 64;
   pl.tps = ONE_G; pl.nbs = ONE_NS; pl.LR = 256;
   pl.lds = (size_t)ONE_NS * ONE_G * 2 * 32 * (256 + pl.bn);
-  const long M = (long)n * oh * ow;
-  pl.tiles = cdiv(M, 256) * cdiv(k, pl.bn);
-  pl.grid = 256;
-  const int ncc = c / (16 * ONE_G);
-  pl.n_full = pl.tiles / pl.grid * pl.grid;
-  const int rem = pl.tiles - pl.n_full;
-  pl.parts = 1; pl.cc_part = ncc; pl.n_pieces = 0; pl.ws_bytes = 0;
-  if (rem > 0) {
-    int parts = pl.grid / rem; if (parts > ncc) parts = ncc; if (parts < 1) parts = 1;
-    pl.cc_part = cdiv(ncc, parts); pl.parts = cdiv(ncc, pl.cc_part);
-    if (pl.parts == 1) { pl.n_full = pl.tiles; }
-    else { pl.n_pieces = rem * pl.parts; pl.ws_bytes = (size_t)pl.n_pieces * 256 * pl.bn * 4; }
-  }
+  plan_tiles(pl, (long)n * oh * ow, k, c / (16 * ONE_G));
   return true;
 }
 
@@ -972,33 +976,18 @@ static bool make_plan(int n, int c, int r, int s, int k, int stride, int oh, int
   // three taps per barrier at BN = 128 too (two 36 KB slots): level with one tap per barrier while a step held six products per
   // fragment pair (10.39 vs 10.39 ms), + 1 % with three (C2 8.14 -> 8.06 ms, three alternating pairs): the default in that format
   static const int tps3 = (int)env_long("EMBNET_PATCH_TPS3", planes_f16() ? 1 : 0);
-  if (pl.bn == 128 && tps3 && 2 * np * pl.LR * 32 + (size_t)2 * 3 * np * 128 * 32 <= 160 * 1024) {
+  if (pl.bn == 128 && tps3 && 2 * np * pl.LR * 32 + (size_t)2 * 3 * np * 128 * 32 <= BIG_LDS_BYTES) {
     pl.tps = 3; pl.nbs = 2;
-    if (np == 2 && 2 * np * pl.LR * 32 + (size_t)3 * 3 * np * 128 * 32 <= 160 * 1024) pl.nbs = 3;      // two planes: room for a third slot
+    if (np == 2 && 2 * np * pl.LR * 32 + (size_t)3 * 3 * np * 128 * 32 <= BIG_LDS_BYTES) pl.nbs = 3;      // two planes: room for a third slot
   }
   pl.lds = 2 * np * pl.LR * 32 + (size_t)pl.nbs * pl.tps * np * pl.bn * 32;
-  if (pl.bn == 128 && pl.tps == 1 && pl.lds > 160 * 1024) {             // a long patch (small maps: many image seams per tile): shorter weight ring
+  if (pl.bn == 128 && pl.tps == 1 && pl.lds > BIG_LDS_BYTES) {             // a long patch (small maps: many image seams per tile): shorter weight ring
     pl.nbs = 4;
     pl.lds = 2 * np * pl.LR * 32 + (size_t)pl.nbs * pl.tps * np * pl.bn * 32;
   }
-  bool ok = pl.LR <= 512 && pl.lds <= 160 * 1024;
-  if (ok) {
-    const long M = (long)n * oh * ow;
-    pl.tiles = cdiv(M, 256) * cdiv(k, pl.bn);
-    pl.grid = 256;
-    const int ncc = c / 16;
-    pl.n_full = pl.tiles / pl.grid * pl.grid;
-    const int rem = pl.tiles - pl.n_full;
-    pl.parts = 1; pl.cc_part = ncc; pl.n_pieces = 0; pl.ws_bytes = 0;
-    if (rem > 0) {
-      int parts = pl.grid / rem; if (parts > ncc) parts = ncc; if (parts < 1) parts = 1;
-      pl.cc_part = cdiv(ncc, parts); pl.parts = cdiv(ncc, pl.cc_part);
-      if (pl.parts == 1) { pl.n_full = pl.tiles; }                            // whole tiles: nothing to fix up
-      else { pl.n_pieces = rem * pl.parts; pl.ws_bytes = (size_t)pl.n_pieces * 256 * pl.bn * 4; }
-    }
-  } else {
-    pl.bn = 0;
-  }
+  bool ok = pl.LR <= 512 && pl.lds <= BIG_LDS_BYTES;
+  if (ok) plan_tiles(pl, (long)n * oh * ow, k, c / 16);
+  else pl.bn = 0;
   keys[next] = Key{n, c, k, oh, ow}; plans[next] = pl; next = (next + 1) % 8; if (used < 8) ++used;
   return ok;
 }
@@ -1047,23 +1036,48 @@ extern "C" int embnet_conv_weight_planes(const void* table, int n_tensors, const
   return check_launch("conv_weight_planes");
 }
 
+// ---- one launch path for the three planes GEMMs (patch 3x3, planes 1x1, DMA 1x1) ----
+template <auto Kernel>
+static void launch_planes(const PatchParams& p, int threads, size_t lds, hipStream_t st) {
+  allow_big_lds<Kernel>();
+  Kernel<<<p.grid, threads, lds, st>>>(p);
+}
+typedef void (*PlanesLaunch)(const PatchParams& p, const Plan& pl, hipStream_t st);     // a family's choice of instantiation for a plan
+
+// An entry point fills what differs (operands, geometry, what its kernel family reads besides) and names its kernel; this finishes
+// the params from the plan — whole tiles where the workspace has no room for the partial ones —, traces and launches, runs the
+// fix-up pass over the left-over tiles and checks the launch.  operand_bytes: what the two inputs occupy, for the trace.
+static int launch_planes_gemm(PatchParams& p, Plan pl, const char* kname, double operand_bytes, PlanesLaunch launch,
+                              void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+  const ConvGeom& g = p.g;
+  const long M = (long)g.N * g.OH * g.OW;
+  p.stats_rows = cdiv(M, 256) * 4;
+  p.grid = pl.grid;
+  if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
+  p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    EMBNET_TRACE_FLOP(kname, 2.0 * M * g.K * g.R * g.S * g.C, operand_bytes + 4.0 * (double)M * g.K * (p.residual ? 2 : 1), st);
+    launch(p, pl, st);
+  }
+  if (p.n_pieces > 0)
+    launch_tail_fixup(p.ws, p.parts, 256, pl.bn, 64, p.n_full, pl.tiles - p.n_full, cdiv(g.K, pl.bn), M, g.K, p.bias, p.relu, p.residual,
+                      p.y, p.stats, p.stats_rows, p.bn, st);
+  return check_launch(who);
+}
+
 template <int BN, int TPS, int NBS>
-static void launch_patch(const PatchParams& p, size_t lds, hipStream_t st) {
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<BN, 3, 3, TPS, NBS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
-  if (planes_f16()) {
-    if (p.bn.x) conv_patch_kernel<BN, 3, 3, TPS, NBS, true, true><<<p.grid, 640, lds, st>>>(p);
-    else conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true><<<p.grid, 640, lds, st>>>(p);
-    return;
-  }
-  if (p.bn.x) conv_patch_kernel<BN, 3, 3, TPS, NBS, true, false><<<p.grid, 640, lds, st>>>(p);
-  else conv_patch_kernel<BN, 3, 3, TPS, NBS, false, false><<<p.grid, 640, lds, st>>>(p);
+static void launch_patch_as(const PatchParams& p, size_t lds, hipStream_t st) {
+  if (!p.bn.x) {
+    if (planes_f16()) launch_planes<conv_patch_kernel<BN, 3, 3, TPS, NBS, false, true, true>>(p, 640, lds, st);
+    else launch_planes<conv_patch_kernel<BN, 3, 3, TPS, NBS, false, false>>(p, 640, lds, st);
+  } else if (!planes_f16()) launch_planes<conv_patch_kernel<BN, 3, 3, TPS, NBS, true, false>>(p, 640, lds, st);
+  else launch_planes<conv_patch_kernel<BN, 3, 3, TPS, NBS, true, true>>(p, 640, lds, st);
+}
+static void launch_patch(const PatchParams& p, const Plan& pl, hipStream_t st) {
+  if (pl.bn == 128 && pl.tps == 3) { if (pl.nbs == 3) launch_patch_as<128, 3, 3>(p, pl.lds, st); else launch_patch_as<128, 3, 2>(p, pl.lds, st); }
+  else if (pl.bn == 128) { if (pl.nbs == 6) launch_patch_as<128, 1, 6>(p, pl.lds, st); else launch_patch_as<128, 1, 4>(p, pl.lds, st); }
+  else launch_patch_as<64, 3, 3>(p, pl.lds, st);
 }
 
 static int conv2d_patch_impl(const void* xp, const void* wp, const float* bias, float* y, int n, int h, int wd, int c,
@@ -1076,55 +1090,43 @@ static int conv2d_patch_impl(const void* xp, const void* wp, const float* bias, 
   EMBNET_CHECK_ARG(make_plan(n, c, r, s, k, 1, oh, ow, pl), "conv2d_patch: unsupported geometry (see embnet_conv2d_patch_supported)");
   PatchParams p{(const unsigned short*)xp, (const unsigned short*)wp, y, bias, residual, stats, 0, relu};
   if (int rc = make_geom(p.g, n, h, wd, c, r, s, k, 1, pad_t, pad_l, oh, ow, "conv2d_patch")) return rc;
-  const long M = (long)n * oh * ow;
   p.x_plane_bytes = (unsigned)((size_t)n * h * wd * c * 2);
   p.w_plane_bytes = (unsigned)((size_t)r * s * c * k * 2);
   p.PH = oh + r - 1; p.PW = ow + s - 1;
   p.dPHW = FastDiv::make(p.PH * p.PW); p.dPW = FastDiv::make(p.PW);
   p.LR = pl.LR;
-  p.stats_rows = cdiv(M, 256) * 4;
   p.bn = bsum;
-  p.grid = pl.grid;
-  if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
-  p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  {
-    // (the names rocprofv3 prints: bench.py looks the kernel's measured HBM traffic up by them)
-    static thread_local char kname[160];
-    snprintf(kname, sizeof kname, "void embnet::patch::conv_patch_kernel<%d, 3, 3, %d, %d, %s%s>(embnet::patch::PatchParams)", pl.bn, pl.tps, pl.nbs,
-             p.bn.x ? "true" : "false", planes_f16() ? (p.bn.x ? ", true" : ", true, true") : "");
-    EMBNET_TRACE_FLOP(kname,
-                      2.0 * M * k * r * s * c,
-                      (planes_f16() ? 4.0 : 6.0) * ((double)n * h * wd * c + (double)r * s * c * k) + 4.0 * (double)M * k * (residual ? 2 : 1), st);
-    if (pl.bn == 128 && pl.tps == 3) { if (pl.nbs == 3) launch_patch<128, 3, 3>(p, pl.lds, st); else launch_patch<128, 3, 2>(p, pl.lds, st); }
-    else if (pl.bn == 128) { if (pl.nbs == 6) launch_patch<128, 1, 6>(p, pl.lds, st); else launch_patch<128, 1, 4>(p, pl.lds, st); }
-    else launch_patch<64, 3, 3>(p, pl.lds, st);
-  }
-  if (p.n_pieces > 0)
-    launch_tail_fixup(p.ws, p.parts, 256, pl.bn, 64, p.n_full, pl.tiles - p.n_full, cdiv(k, pl.bn), M, k, bias, relu, residual, y,
-                      stats, p.stats_rows, bsum, st);
-  return check_launch("conv2d_patch");
+  // (the names rocprofv3 prints: bench.py looks the kernel's measured HBM traffic up by them)
+  static thread_local char kname[160];
+  snprintf(kname, sizeof kname, "void embnet::patch::conv_patch_kernel<%d, 3, 3, %d, %d, %s%s>(embnet::patch::PatchParams)", pl.bn, pl.tps, pl.nbs,
+           p.bn.x ? "true" : "false", planes_f16() ? (p.bn.x ? ", true" : ", true, true") : "");
+  return launch_planes_gemm(p, pl, kname, (planes_f16() ? 4.0 : 6.0) * ((double)n * h * wd * c + (double)r * s * c * k), launch_patch,
+                            workspace, workspace_bytes, stream, "conv2d_patch");
 }
 
 extern "C" int embnet_conv2d_patch_f32(const void* xp, const void* wp, const float* bias, float* y, int n, int h, int wd, int c,
                                        int r, int s, int k, int pad_t, int pad_l, int oh, int ow, int relu,
                                        const float* residual, float* stats, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-  return conv2d_patch_impl(xp, wp, bias, y, n, h, wd, c, r, s, k, pad_t, pad_l, oh, ow, relu, residual, stats,
-                           BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0}, workspace, workspace_bytes, stream);
+  return conv2d_patch_impl(xp, wp, bias, y, n, h, wd, c, r, s, k, pad_t, pad_l, oh, ow, relu, residual, stats, NO_BN_SUMS, workspace,
+                           workspace_bytes, stream);
+}
+
+// what the two 1x1 kernels share: one "patch" row per output pixel, no BatchNorm-backward sums
+static void fill_1x1(PatchParams& p) {
+  const ConvGeom& g = p.g;
+  p.w_plane_bytes = (unsigned)((size_t)g.C * g.K * 2);
+  p.PH = g.OH; p.PW = g.OW; p.dPHW = FastDiv::make(g.OH * g.OW); p.dPW = FastDiv::make(g.OW);
+  p.LR = 256;
+  p.bn = NO_BN_SUMS;
 }
 
 // 1x1 convolution on the planes (conv1x1_planes_kernel): y[n,oh,ow,k] = sum_c x[n, oh*stride, ow*stride, c] w[c,k]; x planes
 // [.][c/16][n*h*wd][16], kernel planes of a [1,1,c,k] kernel (flip 0) — or, with dy planes and flip-1 planes, c and k swapped, the
 // stride-1 data gradient.  Epilogue options as embnet_conv2d_patch_f32.
-template <int BN>
-static void launch_1x1(const PatchParams& p, size_t lds, hipStream_t st) {
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv1x1_planes_kernel<BN, ONE_G, ONE_NS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
-  conv1x1_planes_kernel<BN, ONE_G, ONE_NS, true><<<p.grid, 704, lds, st>>>(p);
+static void launch_1x1(const PatchParams& p, const Plan& pl, hipStream_t st) {
+  if (pl.bn == 128) launch_planes<conv1x1_planes_kernel<128, ONE_G, ONE_NS, true>>(p, 704, pl.lds, st);
+  else launch_planes<conv1x1_planes_kernel<64, ONE_G, ONE_NS, true>>(p, 704, pl.lds, st);
 }
 extern "C" int embnet_conv2d_planes1x1_f32(const void* xp, const void* wp, const float* bias, float* y, int n, int h, int wd, int c,
                                            int k, int stride, int oh, int ow, int relu, const float* residual, float* stats,
@@ -1134,27 +1136,11 @@ extern "C" int embnet_conv2d_planes1x1_f32(const void* xp, const void* wp, const
   EMBNET_CHECK_ARG(make_plan1(n, c, k, stride, oh, ow, pl), "conv2d_planes1x1: unsupported geometry (embnet_conv2d_patch_supported with r = s = 1)");
   PatchParams p{(const unsigned short*)xp, (const unsigned short*)wp, y, bias, residual, stats, 0, relu};
   if (int rc = make_geom(p.g, n, h, wd, c, 1, 1, k, stride, 0, 0, oh, ow, "conv2d_planes1x1")) return rc;
-  const long M = (long)n * oh * ow;
   p.x_plane_bytes = (unsigned)((size_t)n * h * wd * c * 2);
-  p.w_plane_bytes = (unsigned)((size_t)c * k * 2);
-  p.PH = oh; p.PW = ow; p.dPHW = FastDiv::make(oh * ow); p.dPW = FastDiv::make(ow);
-  p.LR = 256;
-  p.stats_rows = cdiv(M, 256) * 4;
-  p.bn = BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0};
-  p.grid = pl.grid;
-  if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
-  p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  {
-    static thread_local char kname[160];
-    snprintf(kname, sizeof kname, "void embnet::patch::conv1x1_planes_kernel<%d, %d, %d, true>(embnet::patch::PatchParams)", pl.bn, ONE_G, ONE_NS);
-    EMBNET_TRACE_FLOP(kname, 2.0 * M * k * c, 4.0 * ((double)M * c + (double)c * k) + 4.0 * (double)M * k * (residual ? 2 : 1), st);
-    if (pl.bn == 128) launch_1x1<128>(p, pl.lds, st); else launch_1x1<64>(p, pl.lds, st);
-  }
-  if (p.n_pieces > 0)
-    launch_tail_fixup(p.ws, p.parts, 256, pl.bn, 64, p.n_full, pl.tiles - p.n_full, cdiv(k, pl.bn), M, k, bias, relu, residual, y,
-                      stats, p.stats_rows, p.bn, st);
-  return check_launch("conv2d_planes1x1");
+  fill_1x1(p);
+  static thread_local char kname[160];
+  snprintf(kname, sizeof kname, "void embnet::patch::conv1x1_planes_kernel<%d, %d, %d, true>(embnet::patch::PatchParams)", pl.bn, ONE_G, ONE_NS);
+  return launch_planes_gemm(p, pl, kname, 4.0 * ((double)n * oh * ow * c + (double)c * k), launch_1x1, workspace, workspace_bytes, stream, "conv2d_planes1x1");
 }
 
 // 1x1 convolution with the ACTIVATION operand read as fp32 by LDS-DMA (conv1x1_a32_kernel): x fp32 [n,h,wd,c] with its RANGE SLOT
@@ -1164,14 +1150,9 @@ static bool dma1x1_ok(int n, int h, int wd, int c, int k, int stride, int oh, in
   if (!make_plan1(n, c, k, stride, oh, ow, pl)) return false;
   return (size_t)n * h * wd * c * 4 < 0xFFFFFFF0ull;            // (32-bit buffer offsets over the fp32 tensor)
 }
-template <int BN>
-static void launch_dma1x1(const PatchParams& p, size_t lds, hipStream_t st) {
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv1x1_a32_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
-  conv1x1_a32_kernel<BN><<<p.grid, 704, lds, st>>>(p);
+static void launch_dma1x1(const PatchParams& p, const Plan& pl, hipStream_t st) {
+  if (pl.bn == 128) launch_planes<conv1x1_a32_kernel<128>>(p, 704, pl.lds, st);
+  else launch_planes<conv1x1_a32_kernel<64>>(p, 704, pl.lds, st);
 }
 extern "C" int embnet_conv2d_dma1x1_supported(int n, int h, int wd, int c, int k, int stride, int oh, int ow) {
   Plan pl;
@@ -1186,27 +1167,12 @@ extern "C" int embnet_conv2d_dma1x1_f32(const float* x, const void* wp, const fl
   EMBNET_CHECK_ARG(dma1x1_ok(n, h, wd, c, k, stride, oh, ow, pl), "conv2d_dma1x1: unsupported geometry (embnet_conv2d_dma1x1_supported)");
   PatchParams p{(const unsigned short*)x, (const unsigned short*)wp, y, bias, residual, stats, 0, relu};
   if (int rc = make_geom(p.g, n, h, wd, c, 1, 1, k, stride, 0, 0, oh, ow, "conv2d_dma1x1")) return rc;
-  const long M = (long)n * oh * ow;
   p.x_plane_bytes = 0; p.x32_bytes = (unsigned)((size_t)n * h * wd * c * 4); p.a_range = x_range;
-  p.w_plane_bytes = (unsigned)((size_t)c * k * 2);
-  p.PH = oh; p.PW = ow; p.dPHW = FastDiv::make(oh * ow); p.dPW = FastDiv::make(ow);
-  p.LR = 256;
-  p.stats_rows = cdiv(M, 256) * 4;
-  p.bn = BnSums{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0};
-  p.grid = pl.grid;
-  if (pl.n_pieces > 0 && (pl.ws_bytes > workspace_bytes || !workspace)) { pl.n_full = pl.tiles; pl.n_pieces = 0; pl.parts = 1; }
-  p.n_full = pl.n_full; p.parts = pl.parts; p.cc_part = pl.cc_part; p.n_pieces = pl.n_pieces; p.ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  {
-    static thread_local char kname[160];
-    snprintf(kname, sizeof kname, "void embnet::patch::conv1x1_a32_kernel<%d>(embnet::patch::PatchParams)", pl.bn);
-    EMBNET_TRACE_FLOP(kname, 2.0 * M * k * c, 4.0 * ((double)M * c + (double)c * k) + 4.0 * (double)M * k * (residual ? 2 : 1), st);
-    if (pl.bn == 128) launch_dma1x1<128>(p, pl.lds, st); else launch_dma1x1<64>(p, pl.lds, st);
-  }
-  if (p.n_pieces > 0)
-    launch_tail_fixup(p.ws, p.parts, 256, pl.bn, 64, p.n_full, pl.tiles - p.n_full, cdiv(k, pl.bn), M, k, bias, relu, residual, y,
-                      stats, p.stats_rows, p.bn, st);
-  return check_launch("conv2d_dma1x1");
+  fill_1x1(p);
+  static thread_local char kname[160];
+  snprintf(kname, sizeof kname, "void embnet::patch::conv1x1_a32_kernel<%d>(embnet::patch::PatchParams)", pl.bn);
+  return launch_planes_gemm(p, pl, kname, 4.0 * ((double)n * oh * ow * c + (double)c * k), launch_dma1x1, workspace, workspace_bytes, stream,
+                            "conv2d_dma1x1");
 }
 
 // The patch kernel as a stride-1 DATA GRADIENT (xp: planes of dy [n,h,wd,c], wp: the flipped kernel planes, y: the gradient

@@ -250,11 +250,7 @@ extern "C" int embnet_conv2d_stem_f32(const float* x, const float* w, float* y, 
   p.stats_rows = p.tiles * 8;
   p.a_range = x_range; p.w_range = w_range;
   p.x_bytes = (unsigned)((size_t)n * h * wd * 16);
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)stem::conv_stem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
+  allow_big_lds<stem::conv_stem_kernel>();
   const long M = (long)n * oh * ow;
   const int grid = p.tiles < 256 ? p.tiles : 256;
   hipStream_t st = (hipStream_t)stream;

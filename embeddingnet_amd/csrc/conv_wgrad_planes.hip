@@ -34,7 +34,6 @@
 #include "../../include/embnet.h"
 
 namespace embnet {
-void launch_slab_reduce(const float* slabs, int splits, long n, float* out, hipStream_t st);   // conv.hip
 namespace wgp {
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -289,12 +288,8 @@ extern "C" int embnet_conv2d_wgrad_planes_f32(const void* x_planes, const void* 
   p.tiles_k = pl.tiles_k; p.tiles = pl.tiles; p.splits = pl.splits; p.stages_total = pl.stages_total;
   p.stages_per_split = pl.stages_per_split; p.HB = pl.HB; p.slab_elems = 9l * c * k;
   hipStream_t st = (hipStream_t)stream;
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_planes_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_planes_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
+  allow_big_lds<conv_wgrad_planes_kernel<false>>();
+  allow_big_lds<conv_wgrad_planes_kernel<false, true>>();
   const int grid = (pl.tiles * pl.splits + 7) / 8 * 8;
   {
     const double m = (double)n * h * wd;

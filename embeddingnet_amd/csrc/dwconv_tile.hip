@@ -456,9 +456,9 @@ static Plan make_plan(const DwGeom& g, int stats_kind) {
   const size_t tail = (size_t)(ks * ks + TW + ks - 1) * pl.CQ * 16;
   pl.lds = 2 * (size_t)pl.buf_bytes + tail;
   if (pl.lds < 2 * 256 * 16) pl.lds = 2 * 256 * 16;                            // the statistics reduction's scratch
-  if (pl.lds > 160 * 1024) return pl;
+  if (pl.lds > BIG_LDS_BYTES) return pl;
   // workgroups: every CU filled as far as LDS allows, two rounds of them, at least min_units units each
-  const long per_cu = (long)(160 * 1024 / pl.lds) < 8 ? (long)(160 * 1024 / pl.lds) : 8;
+  const long per_cu = (long)(BIG_LDS_BYTES / pl.lds) < 8 ? (long)(BIG_LDS_BYTES / pl.lds) : 8;
   const long target = blocks_target > 0 ? blocks_target : 2 * 256 * per_cu;
   long pgs = target / pl.chunks; if (pgs < 1) pgs = 1;
   long upw = (pl.units_total + pgs - 1) / pgs;
@@ -485,11 +485,7 @@ int tile_stats_rows(const DwGeom& g, int stats_kind) { const Plan pl = make_plan
 
 template <int KS, bool FLIP, int STATS, int CQ>
 static void launch_one(const Params& p, const Plan& pl, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dw_tile_kernel<KS, FLIP, STATS, CQ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+  allow_big_lds<dw_tile_kernel<KS, FLIP, STATS, CQ>>();
   dw_tile_kernel<KS, FLIP, STATS, CQ><<<(pl.chunks * pl.PG + 7) / 8 * 8, 256, pl.lds, st>>>(p);
 }
 template <int KS, bool FLIP, int STATS>
@@ -503,36 +499,35 @@ static void launch_ks(const Params& p, const Plan& pl, bool flip, int stats_kind
   else { if (stats_kind == 2) launch_cq<KS, true, 2>(p, pl, st); else launch_cq<KS, true, 0>(p, pl, st); }
 }
 
-void launch_tile(const float* x, const float* w, const DwGeom& g, bool flip, float* y, float* stats, const DwBn* bn, hipStream_t st) {
-  const int stats_kind = !stats ? 0 : (flip ? 2 : 1);
-  const Plan pl = make_plan(g, stats_kind);
+// the geometry and the plan as the kernels read them (the operands are the caller's)
+static Params plan_params(const DwGeom& g, const Plan& pl) {
   Params p{};
-  p.x = x; p.w = w; p.y = y; p.stats = stats;
-  if (bn) p.bn = *bn;
   p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.pad_t = g.pad_t; p.pad_l = g.pad_l;
   p.G = pl.G; p.BH = pl.BH; p.bands = pl.bands; p.IR = pl.IR; p.tile_f4 = pl.tile_f4; p.buf_bytes = pl.buf_bytes;
   p.CB = pl.CB; p.UT = pl.UT; p.npass = pl.npass; p.units_total = pl.units_total; p.upw = pl.upw; p.PG = pl.PG; p.chunks = pl.chunks;
+  return p;
+}
+
+void launch_tile(const float* x, const float* w, const DwGeom& g, bool flip, float* y, float* stats, const DwBn* bn, hipStream_t st) {
+  const int stats_kind = !stats ? 0 : (flip ? 2 : 1);
+  const Plan pl = make_plan(g, stats_kind);
+  Params p = plan_params(g, pl);
+  p.x = x; p.w = w; p.y = y; p.stats = stats;
+  if (bn) p.bn = *bn;
   if (g.R == 3) launch_ks<3>(p, pl, flip, stats_kind, st);
   else launch_ks<5>(p, pl, flip, stats_kind, st);
 }
 
 template <int KS, int CQ>
 static void launch_wgrad_one(const Params& p, const Plan& pl, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dw_tile_wgrad_kernel<KS, CQ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+  allow_big_lds<dw_tile_wgrad_kernel<KS, CQ>>();
   dw_tile_wgrad_kernel<KS, CQ><<<(pl.chunks * pl.PG + 7) / 8 * 8, 256, pl.lds, st>>>(p);
 }
 
 void launch_tile_wgrad(const float* x, const float* dy, const DwGeom& g, float* slabs, hipStream_t st) {
   const Plan pl = wgrad_plan(g);
-  Params p{};
+  Params p = plan_params(g, pl);
   p.x = x; p.dy = dy; p.y = slabs;
-  p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.pad_t = g.pad_t; p.pad_l = g.pad_l;
-  p.G = pl.G; p.BH = pl.BH; p.bands = pl.bands; p.IR = pl.IR; p.tile_f4 = pl.tile_f4; p.buf_bytes = pl.buf_bytes;
-  p.CB = pl.CB; p.UT = pl.UT; p.npass = pl.npass; p.units_total = pl.units_total; p.upw = pl.upw; p.PG = pl.PG; p.chunks = pl.chunks;
   if (g.R == 3) { if (pl.CQ == 8) launch_wgrad_one<3, 8>(p, pl, st); else launch_wgrad_one<3, 4>(p, pl, st); }
   else { if (pl.CQ == 8) launch_wgrad_one<5, 8>(p, pl, st); else launch_wgrad_one<5, 4>(p, pl, st); }
 }

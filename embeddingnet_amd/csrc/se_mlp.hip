@@ -355,8 +355,7 @@ extern "C" int embnet_se_mlp_fwd(const float* pooled, const float* w1, const flo
   EMBNET_CHECK_ARG(embnet_se_mlp_supported(n, c, s), "se_mlp_fwd: unsupported sizes (see embnet_se_mlp_supported)");
   const int JP = jp_of(s);
   const size_t lds = lds_rows(c, s);
-  static bool once = false;
-  if (!once) { (void)hipFuncSetAttribute((const void*)se_mlp_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); once = true; }
+  allow_big_lds<se_mlp_fwd_kernel>();
   EMBNET_TRACE_FLOP("embnet::semlp::se_mlp_fwd_kernel", 4.0 * n * c * s, 4.0 * (2.0 * n * c + 2.0 * c * s), stream);
   se_mlp_fwd_kernel<<<cdiv(n, SB), TH, lds, (hipStream_t)stream>>>(pooled, w1, b1, w2, b2, n, c, s, JP, z1, gate);
   return check_launch("se_mlp_fwd");
@@ -370,13 +369,9 @@ extern "C" int embnet_se_mlp_bwd(const float* dgate, const float* gate, const fl
   EMBNET_CHECK_ARG(embnet_se_mlp_supported(n, c, s), "se_mlp_bwd: unsupported sizes (see embnet_se_mlp_supported)");
   const int JP = jp_of(s);
   const size_t lds_a = lds_rows(c, s), lds_b = ((size_t)2 * CH + 2 * (size_t)s) * NTP * 4;
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void*)se_mlp_bwd_a_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)se_mlp_bwd_b_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)se_mlp_bwd_b_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
+  allow_big_lds<se_mlp_bwd_a_kernel>();
+  allow_big_lds<se_mlp_bwd_b_kernel<3>>();
+  allow_big_lds<se_mlp_bwd_b_kernel<10>>();
   hipStream_t st = (hipStream_t)stream;
   EMBNET_TRACE_FLOP("embnet::semlp::se_mlp_bwd_a_kernel", 4.0 * n * c * s, 4.0 * (3.0 * n * c + 2.0 * c * s), stream);
   se_mlp_bwd_a_kernel<<<cdiv(n, SB), TH, lds_a, st>>>(dgate, gate, z1, w1, w2, n, c, s, JP, dz1, dpooled);
