@@ -330,3 +330,476 @@ extern "C" int embnet_retrieval_reduce(const int32_t* rank, int nq, const int32_
   retrieval_reduce_kernel<<<1, 1024, 0, s>>>(rank, nq, ks, nk, hits, n_valid, sum_inv_rank);
   return check_launch("retrieval_reduce");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// MAP@R / R-precision: the position of EVERY positive of a query, not only the first (include/embnet.h, "positive ranks").
+// The same distance walk, order, exclusion and label filters as above; what changes is what the epilogue keeps:
+//   prep:   norms; class sizes by integer atomicAdd, x_slot[c] = the value that add returned (any bijection of a class onto
+//           0..count-1 will do: keys carry the gallery index, and the sort below removes the assignment from the result);
+//           R[r] = size of the query's class (- 1 with self-exclusion), offset = exclusive scan of R
+//   pass 1: every positive's key goes to keys[offset[r] + slot] — each address written once, plain 8-byte stores
+//   sort:   each query's segment ascending (a wave with shuffles up to 64 keys, the workgroup in LDS up to R_MAX)
+//   pass 2: a negative below the LARGEST positive key counts into between[offset[r] + j], j = the number of the row's positive
+//           keys below it (below the smallest one: j = 0, kept in registers as the counting pass above does; otherwise a
+//           binary search of the sorted segment and one integer atomicAdd)
+//   finish: pos_rank[offset[r] + j] = j + 1 + between[offset[r] + 0..j], pos_index from the key's low word
+// Integers only, so the atomics leave the result bitwise reproducible.  Counters, histogram and status are zeroed by a kernel.
+// Whatever depends on label contents (capacity, R_MAX, label range) raises `status`; the kernels behind it then exit, and
+// every offset-derived address is guarded (slot < R, offset + R <= capacity) whatever the status.
+// Roofline: MFMA f32, (1 + visited share) x 2*nq*n*e FLOP as above; on top of it pass 2 pays, per negative between a
+// query's first and last positive, ceil(log2 R) dependent 8-byte loads (L2) and one L2 atomic.
+namespace embnet {
+
+constexpr int R_MAX = EMBNET_RETRIEVAL_R_MAX;
+enum : int { MAP_OK = 0, MAP_CAPACITY = 1, MAP_RMAX = 2, MAP_LABEL = 3 };
+
+__global__ __launch_bounds__(256) void map_zero_kernel(int32_t* __restrict__ class_count, int num_classes,
+                                                       int32_t* __restrict__ between, long capacity, int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < num_classes) class_count[i] = 0;
+  if (i < capacity) between[i] = 0;
+  if (i == 0) *status = MAP_OK;
+}
+
+// one wave per row: norms as retrieval_prep_kernel; the gallery row also takes its slot in its class
+__global__ __launch_bounds__(256) void map_prep_kernel(const float* __restrict__ q, const int32_t* __restrict__ ql, int nq,
+                                                       const float* __restrict__ x, const int32_t* __restrict__ xl, int n, int e,
+                                                       int num_classes, float* __restrict__ qn, float* __restrict__ xn,
+                                                       int32_t* __restrict__ class_count, int32_t* __restrict__ x_slot,
+                                                       int32_t* __restrict__ status) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row < nq) {
+    const float* r = q + (long)row * e;
+    float s = 0.f;
+    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
+    s = wave_sum(s);
+    if (lane == 0) {
+      qn[row] = s;
+      if ((unsigned)ql[row] >= (unsigned)num_classes) atomicMax(status, (int)MAP_LABEL);
+    }
+  }
+  if (row < n) {
+    const float* r = x + (long)row * e;
+    float s = 0.f;
+    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
+    s = wave_sum(s);
+    if (lane == 0) {
+      xn[row] = s;
+      const int c = xl[row];
+      if ((unsigned)c < (unsigned)num_classes) x_slot[row] = atomicAdd(&class_count[c], 1);
+      else { x_slot[row] = 0; atomicMax(status, (int)MAP_LABEL); }
+    }
+  }
+}
+
+__device__ __forceinline__ int map_row_positives(const int32_t* ql, const int32_t* class_count, int num_classes, int self_exclude,
+                                                 int row) {
+  const int c = ql[row];
+  if ((unsigned)c >= (unsigned)num_classes) return 0;
+  const int r = class_count[c] - (self_exclude ? 1 : 0);
+  return r > 0 ? r : 0;
+}
+
+// offset = exclusive scan of R over the queries, one workgroup: thread t owns a contiguous run of queries
+__global__ __launch_bounds__(1024) void map_scan_kernel(const int32_t* __restrict__ ql, int nq,
+                                                        const int32_t* __restrict__ class_count, int num_classes, int self_exclude,
+                                                        long capacity, long long* __restrict__ offset, int32_t* __restrict__ status) {
+  __shared__ long long s_wave[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int run = (nq + 1023) / 1024;
+  const int i0 = min((long)tid * run, (long)nq), i1 = min((long)i0 + run, (long)nq);
+  long long sum = 0; int worst = 0;
+  for (int i = i0; i < i1; ++i) {
+    const int r = map_row_positives(ql, class_count, num_classes, self_exclude, i);
+    sum += r; worst = max(worst, r);
+  }
+  long long incl = sum;                                    // inclusive scan over the wave, then over the 16 waves
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  long long base = 0, total = 0;
+  for (int w = 0; w < 16; ++w) { if (w < wave) base += s_wave[w]; total += s_wave[w]; }
+  long long at = base + incl - sum;
+  for (int i = i0; i < i1; ++i) {
+    offset[i] = at;
+    at += map_row_positives(ql, class_count, num_classes, self_exclude, i);
+  }
+  if (tid == 0) {
+    offset[nq] = total;
+    if (total > capacity) atomicMax(status, (int)MAP_CAPACITY);
+  }
+  if (worst > R_MAX) atomicMax(status, (int)MAP_RMAX);
+}
+
+struct MapParams {
+  const float* q; const float* x; const float* qn; const float* xn;
+  const int32_t* ql; const int32_t* xl;
+  const long long* offset; const int32_t* x_slot; const int32_t* status;
+  unsigned long long* keys; int32_t* between;
+  const unsigned* qbloom; const unsigned* xbloom;
+  long capacity;
+  int nq, n, e, self_exclude, tiles_per_split;
+};
+
+// retrieval_walk_kernel's walk.  PASS 1 stores the positives' keys, PASS 2 counts the negatives by the number of positives in
+// front of them.  A row whose segment does not fit (or a row past nq) gets R = 0: nothing is stored or counted for it.
+template <class G, bool VEC, int PASS>
+__global__ __launch_bounds__(256, VEC ? 2 : 1) void map_walk_kernel(MapParams p) {
+  using TA = TileKC<G::BM>;
+  using TB = TileKC<G::BN>;
+  constexpr int SLOTS = G::TM * 16;
+  __shared__ __attribute__((aligned(16))) float smem[MAIN_FLOATS<TA, TB>];
+  __shared__ float s_qn[G::BM];
+  __shared__ int s_ql[G::BM];
+  __shared__ int s_R[G::BM];
+  __shared__ long long s_off[G::BM];
+  __shared__ int s_own[PASS == 1 ? G::BM : 1];
+  __shared__ unsigned long long s_first[PASS == 2 ? G::BM : 1];
+  __shared__ unsigned long long s_last[PASS == 2 ? G::BM : 1];
+  if (*p.status != MAP_OK) return;                         // the same answer in every thread
+  prio_hi();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
+  const int m0 = blockIdx.x * G::BM;
+  const int tiles_n = (p.n + G::BN - 1) / G::BN;
+  const int t0 = blockIdx.y * p.tiles_per_split, t1 = min(t0 + p.tiles_per_split, tiles_n);
+  const int kt_total = (p.e + BK - 1) / BK;
+
+  for (int i = tid; i < G::BM; i += NTHREADS) {
+    const int row = min(m0 + i, p.nq - 1);
+    const long long off = p.offset[row], R = p.offset[row + 1] - off;
+    const bool fits = m0 + i < p.nq && off >= 0 && R > 0 && R <= R_MAX && off + R <= p.capacity;
+    s_qn[i] = p.qn[row]; s_ql[i] = p.ql[row];
+    s_off[i] = off; s_R[i] = fits ? (int)R : 0;
+    if (PASS == 1) s_own[i] = p.self_exclude ? p.x_slot[row] : 0x7fffffff;
+    if (PASS == 2) { s_first[i] = fits ? p.keys[off] : 0ull; s_last[i] = fits ? p.keys[off + R - 1] : 0ull; }
+  }
+  __syncthreads();
+
+  LoadRowsKC<G::BM, VEC> la; la.init(p.q, p.e, p.nq, p.e, m0, tid);
+  unsigned qb = 0u;
+  if (PASS == 1) qb = p.qbloom[(long)blockIdx.x * BLOOM_WORDS + (lane & 31)];
+  int cnt[PASS == 2 ? SLOTS : 1];                          // negatives in front of the row's first positive
+#pragma unroll
+  for (int s = 0; s < (PASS == 2 ? SLOTS : 1); ++s) cnt[s] = 0;
+
+  for (int t = t0; t < t1; ++t) {
+    const int n0 = t * G::BN;
+    if (PASS == 1) {
+      const unsigned w = qb & p.xbloom[(long)t * BLOOM_WORDS + (lane & 31)];
+      if (__ballot(w != 0u) == 0ull) continue;
+    }
+    LoadRowsKC<G::BN, VEC> lb; lb.init(p.x, p.e, p.n, p.e, n0, tid);
+    float cn[G::TN]; int cl[G::TN]; int cc[G::TN]; int cs[G::TN];
+#pragma unroll
+    for (int in = 0; in < G::TN; ++in) {
+      const int col = n0 + wn + 32 * in + (lane & 31);
+      cc[in] = col < p.n ? col : -1;
+      cn[in] = p.xn[min(col, p.n - 1)]; cl[in] = p.xl[min(col, p.n - 1)];
+      cs[in] = PASS == 1 ? p.x_slot[min(col, p.n - 1)] : 0;
+    }
+    f32x16 acc[G::TM][G::TN];
+    gemm_mainloop<G, TA, TB>(la, lb, 0, kt_total, smem, acc);
+#pragma unroll
+    for (int im = 0; im < G::TM; ++im)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int rt = wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const float rn = s_qn[rt]; const int rl = s_ql[rt];
+        const int skip = p.self_exclude ? m0 + rt : -1;
+        const int R = s_R[rt];
+        unsigned long long first = 0, last = 0;
+        if (PASS == 2) { first = s_first[rt]; last = s_last[rt]; }
+#pragma unroll
+        for (int in = 0; in < G::TN; ++in) {
+          const float v = rn + cn[in] - 2.f * acc[im][in][r];
+          const float d2 = v != v ? INFINITY : fmaxf(v, 0.f);
+          const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)cc[in];
+          const bool live = cc[in] >= 0 && cc[in] != skip;
+          if (PASS == 1) {
+            if (live && cl[in] == rl) {
+              const int slot = cs[in] - (cs[in] > s_own[rt] ? 1 : 0);
+              if ((unsigned)slot < (unsigned)R) p.keys[s_off[rt] + slot] = k;
+            }
+          } else {
+            const bool neg = live && cl[in] != rl;
+            cnt[im * 16 + r] += (neg && k < first) ? 1 : 0;
+            if (neg && k > first && k < last) {            // between two positives: how many are in front of it
+              const unsigned long long* seg = p.keys + s_off[rt];
+              int lo = 1, hi = R - 1;                      // keys[0] < k < keys[R - 1]: the answer lies in 1 .. R - 1
+              while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (seg[mid] < k) lo = mid + 1; else hi = mid;
+              }
+              atomicAdd(&p.between[s_off[rt] + lo], 1);
+            }
+          }
+        }
+      }
+  }
+
+  if (PASS == 2) {
+#pragma unroll
+    for (int im = 0; im < G::TM; ++im)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int rt = wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        int c = cnt[im * 16 + r];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((lane & 31) == 0 && c != 0 && s_R[rt] > 0) atomicAdd(&p.between[s_off[rt]], c);
+      }
+  }
+}
+
+// a query's segment, or -1 when there is nothing to do for it (no positive, or a segment that does not fit)
+__device__ __forceinline__ int map_segment(const long long* offset, long capacity, int row, long long& off) {
+  off = offset[row];
+  const long long R = offset[row + 1] - off;
+  return (off >= 0 && R > 0 && R <= R_MAX && off + R <= capacity) ? (int)R : -1;
+}
+
+// four queries per workgroup.  R <= 64: the query's wave sorts in registers (bitonic over the lanes, NO_KEY padding);
+// above: the workgroup sorts the segment in LDS, one such query after the other.
+__global__ __launch_bounds__(256) void map_sort_kernel(const long long* __restrict__ offset, int nq, long capacity,
+                                                       const int32_t* __restrict__ status, unsigned long long* __restrict__ keys) {
+  __shared__ unsigned long long s[R_MAX];
+  if (*status != MAP_OK) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    const int row = blockIdx.x * 4 + wave;
+    long long off = 0;
+    const int R = row < nq ? map_segment(offset, capacity, row, off) : -1;
+    if (R > 1 && R <= 64) {
+      unsigned long long v = lane < R ? keys[off + lane] : NO_KEY;
+#pragma unroll
+      for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          const unsigned long long o = __shfl_xor(v, j, 64);
+          const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
+          v = (keep_min ? o < v : o > v) ? o : v;
+        }
+      if (lane < R) keys[off + lane] = v;
+    }
+  }
+  for (int w = 0; w < 4; ++w) {                            // the same rows in every thread: the barriers are uniform
+    const int row = blockIdx.x * 4 + w;
+    long long off = 0;
+    const int R = row < nq ? map_segment(offset, capacity, row, off) : -1;
+    if (R <= 64) continue;
+    int P = 128;
+    while (P < R) P <<= 1;
+    __syncthreads();                                       // the previous segment has left LDS
+    for (int i = tid; i < P; i += 256) s[i] = i < R ? keys[off + i] : NO_KEY;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < P; i += 256) {
+          const int o = i ^ j;
+          if (o > i) {
+            const unsigned long long a = s[i], b = s[o];
+            if (((i & k) == 0) == (a > b)) { s[i] = b; s[o] = a; }
+          }
+        }
+        __syncthreads();
+      }
+    for (int i = tid; i < R; i += 256) keys[off + i] = s[i];
+  }
+}
+
+// one wave per query: the running sum of `between` over the segment, 64 positives at a time
+__global__ __launch_bounds__(256) void map_finish_kernel(const long long* __restrict__ offset, int nq, long capacity,
+                                                         const int32_t* __restrict__ status,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const int32_t* __restrict__ between, int32_t* __restrict__ pos_index,
+                                                         int32_t* __restrict__ pos_rank) {
+  if (*status != MAP_OK) return;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nq) return;
+  long long off = 0;
+  const int R = map_segment(offset, capacity, row, off);
+  int carry = 0;
+  for (int j0 = 0; j0 < R; j0 += 64) {
+    const int j = j0 + lane;
+    int incl = j < R ? between[off + j] : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    if (j < R) {
+      pos_rank[off + j] = j + 1 + carry + incl;
+      pos_index[off + j] = (int32_t)(unsigned)(keys[off + j] & 0xffffffffull);
+    }
+    carry += __shfl(incl, 63, 64);
+  }
+}
+
+// one wave per query: ap@r, r_precision, ap in f64 (lane-strided partial sums, folded in the fixed order of wave_sum)
+__global__ __launch_bounds__(256) void map_query_kernel(const long long* __restrict__ offset, const int32_t* __restrict__ pos_rank,
+                                                        int nq, double* __restrict__ ap_at_r, double* __restrict__ r_precision,
+                                                        double* __restrict__ ap) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nq) return;
+  const long long off = offset[row], R = offset[row + 1] - off;
+  double s_in = 0.0, s_all = 0.0; int hits = 0;
+  for (long long j = lane; j < R; j += 64) {
+    const int pos = pos_rank[off + j];
+    const double term = (double)(j + 1) / (double)pos;
+    s_all += term;
+    if (pos <= R) { s_in += term; ++hits; }
+  }
+  s_in = wave_sum(s_in); s_all = wave_sum(s_all); hits = wave_sum(hits);
+  if (lane == 0) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    ap_at_r[row] = R > 0 ? s_in / (double)R : nan;
+    r_precision[row] = R > 0 ? (double)hits / (double)R : nan;
+    ap[row] = R > 0 ? s_all / (double)R : nan;
+  }
+}
+
+// sums[0..2] = the sums of ap_at_r, r_precision, ap over the queries with a positive, *n_valid their number: one workgroup,
+// strided partial sums folded in a fixed order as retrieval_reduce_kernel does
+__global__ __launch_bounds__(1024) void map_total_kernel(const long long* __restrict__ offset, int nq,
+                                                         const double* __restrict__ ap_at_r, const double* __restrict__ r_precision,
+                                                         const double* __restrict__ ap, double* __restrict__ sums,
+                                                         int32_t* __restrict__ n_valid) {
+  __shared__ double s_sum[3][16];
+  __shared__ int s_cnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double a = 0.0, b = 0.0, c = 0.0; int valid = 0;
+  for (int i = tid; i < nq; i += 1024)
+    if (offset[i + 1] > offset[i]) { a += ap_at_r[i]; b += r_precision[i]; c += ap[i]; ++valid; }
+  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); valid = wave_sum(valid);
+  if (lane == 0) { s_sum[0][wave] = a; s_sum[1][wave] = b; s_sum[2][wave] = c; s_cnt[wave] = valid; }
+  __syncthreads();
+  if (tid < 3) {
+    double t = 0.0;
+    for (int w = 0; w < 16; ++w) t += s_sum[tid][w];
+    sums[tid] = t;
+  }
+  if (tid == 0) {
+    int tv = 0;
+    for (int w = 0; w < 16; ++w) tv += s_cnt[w];
+    *n_valid = tv;
+  }
+}
+
+}  // namespace embnet
+
+// query norms f32[nq] | gallery norms f32[n] | label filters (query tiles, gallery tiles) | class sizes i32[num_classes] |
+// gallery slots i32[n] | keys u64[capacity] | between i32[capacity]
+extern "C" size_t embnet_retrieval_positive_ranks_workspace_bytes(int nq, int n, int num_classes, long capacity) {
+  if (nq <= 0 || n <= 0 || num_classes <= 0 || capacity <= 0) return 0;
+  return round16((size_t)nq * 4) + round16((size_t)n * 4) + bloom_bytes(nq) + bloom_bytes(n) + round16((size_t)num_classes * 4) +
+         round16((size_t)n * 4) + round16((size_t)capacity * 8) + round16((size_t)capacity * 4);
+}
+
+template <class G>
+static void map_launch(const MapParams& p, bool vec, int pass, dim3 grid, hipStream_t s) {
+  if (pass == 1) {
+    if (vec) map_walk_kernel<G, true, 1><<<grid, 256, 0, s>>>(p); else map_walk_kernel<G, false, 1><<<grid, 256, 0, s>>>(p);
+  } else {
+    if (vec) map_walk_kernel<G, true, 2><<<grid, 256, 0, s>>>(p); else map_walk_kernel<G, false, 2><<<grid, 256, 0, s>>>(p);
+  }
+}
+
+extern "C" int embnet_retrieval_positive_ranks(const float* q, const int32_t* q_labels, int nq,
+                                               const float* x, const int32_t* x_labels, int n, int e, int self_exclude,
+                                               int num_classes, long capacity, long long* offset, int32_t* pos_index,
+                                               int32_t* pos_rank, int32_t* status,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+  EMBNET_CHECK_ARG(q && q_labels && x && x_labels && offset && pos_index && pos_rank && status && workspace,
+                   "retrieval_positive_ranks: null pointer");
+  EMBNET_CHECK_ARG(nq > 0 && n > 0 && e > 0 && num_classes > 0 && capacity > 0,
+                   "retrieval_positive_ranks: nq=%d n=%d e=%d num_classes=%d capacity=%ld must be positive", nq, n, e, num_classes,
+                   capacity);
+  EMBNET_CHECK_ARG(!self_exclude || nq == n, "retrieval_positive_ranks: self_exclude needs nq == n (nq=%d n=%d)", nq, n);
+  EMBNET_CHECK_ARG((size_t)nq * e * 4 <= MAX_OPERAND_BYTES && (size_t)n * e * 4 <= MAX_OPERAND_BYTES,
+                   "retrieval_positive_ranks: an embedding block exceeds 2 GiB");
+  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "retrieval_positive_ranks: workspace must be 16-byte aligned");
+  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(offset) & 7) == 0, "retrieval_positive_ranks: offset must be 8-byte aligned");
+  const size_t need = embnet_retrieval_positive_ranks_workspace_bytes(nq, n, num_classes, capacity);
+  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "retrieval_positive_ranks: workspace %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)workspace;
+  float* qn = (float*)w;                             w += round16((size_t)nq * 4);
+  float* xn = (float*)w;                             w += round16((size_t)n * 4);
+  unsigned* qbloom = (unsigned*)w;                   w += bloom_bytes(nq);
+  unsigned* xbloom = (unsigned*)w;                   w += bloom_bytes(n);
+  int32_t* class_count = (int32_t*)w;                w += round16((size_t)num_classes * 4);
+  int32_t* x_slot = (int32_t*)w;                     w += round16((size_t)n * 4);
+  unsigned long long* keys = (unsigned long long*)w; w += round16((size_t)capacity * 8);
+  int32_t* between = (int32_t*)w;
+  {
+    EMBNET_TRACE("embnet::map_zero_kernel", TRACE_BYTES, 4.0 * ((double)num_classes + (double)capacity), s);
+    const long cells = capacity > num_classes ? capacity : num_classes;
+    map_zero_kernel<<<cdiv(cells, 256), 256, 0, s>>>(class_count, num_classes, between, capacity, status);
+  }
+  {
+    EMBNET_TRACE("embnet::map_prep_kernel", TRACE_BYTES, 4.0 * ((double)nq * e + (double)n * e), s);
+    map_prep_kernel<<<cdiv(nq > n ? nq : n, 4), 256, 0, s>>>(q, q_labels, nq, x, x_labels, n, e, num_classes, qn, xn, class_count,
+                                                             x_slot, status);
+  }
+  bool big; int splits, tps; retrieval_plan(nq, n, big, splits, tps);
+  const int tile_rows = big ? 128 : 64;
+  {
+    EMBNET_TRACE("embnet::retrieval_bloom_kernel", TRACE_BYTES, 4.0 * ((double)nq + n), s);
+    const int q_tiles = cdiv(nq, tile_rows);
+    retrieval_bloom_kernel<<<q_tiles + cdiv(n, tile_rows), 256, 0, s>>>(q_labels, nq, x_labels, n, tile_rows, q_tiles, qbloom, xbloom);
+  }
+  {
+    EMBNET_TRACE("embnet::map_scan_kernel", TRACE_BYTES, 16.0 * nq, s);
+    map_scan_kernel<<<1, 1024, 0, s>>>(q_labels, nq, class_count, num_classes, self_exclude ? 1 : 0, capacity, offset, status);
+  }
+  MapParams p{q, x, qn, xn, q_labels, x_labels, offset, x_slot, status, keys, between, qbloom, xbloom, capacity,
+              nq, n, e, self_exclude ? 1 : 0, tps};
+  const bool vec = (e & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  const dim3 grid(cdiv(nq, tile_rows), splits);
+  const double flop = 2.0 * nq * n * e, bytes = 4.0 * ((double)nq * e + (double)n * e) + 16.0 * nq + 12.0 * n + 12.0 * capacity;
+  using GS = Geom<64, 64, 2, 2>;
+  using GL = Geom<128, 128, 2, 2>;
+  {
+    EMBNET_TRACE_FLOP("embnet::map_walk_kernel<1>", flop, bytes, s);
+    if (big) map_launch<GL>(p, vec, 1, grid, s); else map_launch<GS>(p, vec, 1, grid, s);
+  }
+  {
+    EMBNET_TRACE("embnet::map_sort_kernel", TRACE_BYTES, 16.0 * capacity, s);
+    map_sort_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, keys);
+  }
+  {
+    EMBNET_TRACE_FLOP("embnet::map_walk_kernel<2>", flop, bytes, s);
+    if (big) map_launch<GL>(p, vec, 2, grid, s); else map_launch<GS>(p, vec, 2, grid, s);
+  }
+  {
+    EMBNET_TRACE("embnet::map_finish_kernel", TRACE_BYTES, 20.0 * capacity, s);
+    map_finish_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, keys, between, pos_index, pos_rank);
+  }
+  return check_launch("retrieval_positive_ranks");
+}
+
+extern "C" int embnet_retrieval_map_reduce(const long long* offset, const int32_t* pos_rank, int nq,
+                                           double* ap_at_r, double* r_precision, double* ap, double* sums, int32_t* n_valid,
+                                           void* stream) {
+  EMBNET_CHECK_ARG(offset && pos_rank && ap_at_r && r_precision && ap && sums && n_valid, "retrieval_map_reduce: null pointer");
+  EMBNET_CHECK_ARG(nq > 0, "retrieval_map_reduce: nq=%d must be positive", nq);
+  EMBNET_CHECK_ARG(((reinterpret_cast<uintptr_t>(offset) | reinterpret_cast<uintptr_t>(ap_at_r) | reinterpret_cast<uintptr_t>(r_precision) |
+                     reinterpret_cast<uintptr_t>(ap) | reinterpret_cast<uintptr_t>(sums)) & 7) == 0,
+                   "retrieval_map_reduce: 64-bit arrays must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    EMBNET_TRACE("embnet::map_query_kernel", TRACE_BYTES, 32.0 * nq, s);
+    map_query_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, pos_rank, nq, ap_at_r, r_precision, ap);
+  }
+  {
+    EMBNET_TRACE("embnet::map_total_kernel", TRACE_BYTES, 40.0 * nq, s);
+    map_total_kernel<<<1, 1024, 0, s>>>(offset, nq, ap_at_r, r_precision, ap, sums, n_valid);
+  }
+  return check_launch("retrieval_map_reduce");
+}

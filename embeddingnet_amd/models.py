@@ -159,18 +159,16 @@ class EmbeddingNet:
             total += len(imgs)
         return {'top1': top1 / max(total, 1), 'top5': top5 / max(total, 1)}
 
-    def calculate_retrieval_metrics(self, data_loader, ks=(1, 5, 10), gallery='val', batch_size=256):
-        """Recall@K / MRR of data_loader.val_data (retrieval.retrieval_metrics: the rank of the nearest same-class item).
-        gallery='val': leave-one-out within the validation set; gallery='train': the validation items are searched in
-        self.encoded_training_data (generate_encodings / load_encodings), nothing excluded.  The validation items are encoded
-        class by class in batches of at most batch_size; file lists and in-memory arrays are both handled."""
+    def _encode_validation(self, who, data_loader, gallery, batch_size):
+        """What the retrieval evaluations share: data_loader.val_data encoded class by class in batches of at most batch_size
+        (file lists and in-memory arrays are both handled) -> (encodings [rows, e], labels, the keyword arguments that name the
+        gallery: none for 'val', self.encoded_training_data for 'train', the model's device)."""
         from .datagenerators import get_image
-        from .retrieval import retrieval_metrics
         if gallery not in ('val', 'train'):
-            raise ValueError(f"calculate_retrieval_metrics: gallery must be 'val' or 'train' (got {gallery!r})")
+            raise ValueError(f"{who}: gallery must be 'val' or 'train' (got {gallery!r})")
         train = self.encoded_training_data
         if gallery == 'train' and not (train and 'encodings' in train and 'labels' in train):
-            raise ValueError("calculate_retrieval_metrics: gallery='train' needs encoded_training_data "
+            raise ValueError(f"{who}: gallery='train' needs encoded_training_data "
                              "(generate_encodings / load_encodings / fit_knn first)")
         encodings, labels = [], []
         for class_name, items in data_loader.val_data.items():
@@ -184,14 +182,29 @@ class EmbeddingNet:
                 encodings.append(enc.reshape(len(imgs), -1))
                 labels += [class_name] * len(imgs)
         if not encodings:
-            raise ValueError("calculate_retrieval_metrics: data_loader.val_data is empty")
+            raise ValueError(f"{who}: data_loader.val_data is empty")
         encodings = np.concatenate(encodings, axis=0)
-        dev = next(self.base_model.parameters()).device
+        kw = {'device': next(self.base_model.parameters()).device}
         if gallery == 'train':
             g = np.asarray(train['encodings'], np.float32)
-            return retrieval_metrics(encodings, labels, ks=ks, gallery=g.reshape(len(train['labels']), -1),
-                                     gallery_labels=train['labels'], device=dev)
-        return retrieval_metrics(encodings, labels, ks=ks, device=dev)
+            kw.update(gallery=g.reshape(len(train['labels']), -1), gallery_labels=train['labels'])
+        return encodings, labels, kw
+
+    def calculate_retrieval_metrics(self, data_loader, ks=(1, 5, 10), gallery='val', batch_size=256):
+        """Recall@K / MRR of data_loader.val_data (retrieval.retrieval_metrics: the rank of the nearest same-class item).
+        gallery='val': leave-one-out within the validation set; gallery='train': the validation items are searched in
+        self.encoded_training_data (generate_encodings / load_encodings), nothing excluded.  The validation items are encoded
+        class by class in batches of at most batch_size; file lists and in-memory arrays are both handled."""
+        from .retrieval import retrieval_metrics
+        encodings, labels, kw = self._encode_validation("calculate_retrieval_metrics", data_loader, gallery, batch_size)
+        return retrieval_metrics(encodings, labels, ks=ks, **kw)
+
+    def calculate_map_at_r(self, data_loader, gallery='val', batch_size=256):
+        """MAP@R / R-precision / MAP of data_loader.val_data (retrieval.retrieval_map_metrics: the position of every same-class
+        item).  gallery and batch_size as in calculate_retrieval_metrics; the validation items are encoded the same way."""
+        from .retrieval import retrieval_map_metrics
+        encodings, labels, kw = self._encode_validation("calculate_map_at_r", data_loader, gallery, batch_size)
+        return retrieval_map_metrics(encodings, labels, **kw)
 
 
 class _ClsHead(nn.Module):

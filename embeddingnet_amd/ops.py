@@ -487,3 +487,85 @@ def tsne_kl(p, y, return_grad=False, ws=None):
     check(_lib.lib().embnet_tsne_kl(ptr(p), n, ptr(y), out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws), ws.numel() * 8,
                                     stream()))
     return (out, grad) if return_grad else out
+
+
+# --------------------------------------------------------------------------- evaluation: retrieval (MAP@R, R-precision)
+R_MAX = 4096                                                # EMBNET_RETRIEVAL_R_MAX (include/embnet.h)
+_POSITIVE_RANKS_STATUS = {1: "the positives of all queries exceed `capacity`",
+                          2: f"a query has more than R_MAX = {R_MAX} positives (a class that large is refused)",
+                          3: "a label outside [0, num_classes)"}
+
+
+def retrieval_positive_ranks(q, q_labels, x=None, x_labels=None, num_classes=None, capacity=None):
+    """Position of EVERY same-class gallery item of each query, without the [nq,n] distance matrix (include/embnet.h).
+
+    q [nq,e], q_labels [nq]: dense class ids in [0, num_classes); x [n,e], x_labels [n] the gallery, or x None: leave-one-out
+    on q.  num_classes None: 1 + the largest label; capacity None: the number of positives of all queries — both then cost one
+    host read of the labels.  -> (offset int64 [nq+1], pos_index int32 [total], pos_rank int32 [total]) with total = offset[-1]
+    (with `capacity` given the two arrays keep that length): query r's positives are offset[r]:offset[r+1], in the order
+    (d2, gallery index); pos_rank = 1-based position among all non-excluded gallery items, so pos_rank[offset[r]] is
+    retrieval_first_positive's rank.  A condition the device finds in the labels raises EmbnetError naming it."""
+    q = _prep(q.detach())
+    ql = q_labels.to(torch.int32).contiguous()
+    self_exclude = x is None
+    if self_exclude:
+        if x_labels is not None:
+            raise _lib.EmbnetError("retrieval_positive_ranks: gallery labels without a gallery")
+        x, xl = q, ql
+    else:
+        if x_labels is None:
+            raise _lib.EmbnetError("retrieval_positive_ranks: a gallery needs its labels")
+        x = _prep(x.detach())
+        xl = x_labels.to(torch.int32).contiguous()
+    if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
+        raise _lib.EmbnetError(f"retrieval_positive_ranks: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
+    nq, e = q.shape
+    n = x.shape[0]
+    if x.shape[1] != e:
+        raise _lib.EmbnetError(f"retrieval_positive_ranks: widths differ ({e} vs {x.shape[1]})")
+    if tuple(ql.shape) != (nq,) or tuple(xl.shape) != (n,):
+        raise _lib.EmbnetError("retrieval_positive_ranks: one label per row is needed")
+    if num_classes is None:
+        num_classes = int(torch.maximum(ql.max(), xl.max()).item()) + 1
+    num_classes = int(num_classes)
+    if num_classes < 1:
+        raise _lib.EmbnetError(f"retrieval_positive_ranks: num_classes = {num_classes} (labels are dense ids >= 0)")
+    trim = capacity is None
+    if trim:      # labels out of range are clamped here and reported by the device below
+        sizes = torch.bincount(xl.long().clamp(0, num_classes - 1), minlength=num_classes)
+        capacity = int((sizes[ql.long().clamp(0, num_classes - 1)] - int(self_exclude)).clamp(min=0).sum().item())
+    capacity = max(int(capacity), 1)
+    lib = _lib.lib()
+    ws = _new((max(lib.embnet_retrieval_positive_ranks_workspace_bytes(nq, n, num_classes, capacity) // 8, 1),), q, torch.float64)
+    offset = _new((nq + 1,), q, torch.int64)
+    pos_index, pos_rank = _new((capacity,), q, torch.int32), _new((capacity,), q, torch.int32)
+    status = _new((1,), q, torch.int32)
+    check(lib.embnet_retrieval_positive_ranks(ptr(q), ptr(ql), nq, ptr(x), ptr(xl), n, e, int(self_exclude), num_classes, capacity,
+                                              ptr(offset), ptr(pos_index), ptr(pos_rank), ptr(status), ptr(ws), ws.numel() * 8,
+                                              stream()))
+    st = int(status.item())
+    if st != 0:
+        raise _lib.EmbnetError(f"retrieval_positive_ranks: status {st}: {_POSITIVE_RANKS_STATUS.get(st, 'unknown')}")
+    if trim:
+        total = int(offset[-1].item())
+        pos_index, pos_rank = pos_index[:total], pos_rank[:total]
+    return offset, pos_index, pos_rank
+
+
+def retrieval_map_reduce(offset, pos_rank):
+    """CSR (offset int64 [nq+1], pos_rank int32) of retrieval_positive_ranks -> (ap_at_r, r_precision, ap: float64 [nq], NaN for a
+    query without a positive; sums float64 [3] of the three over the valid queries; n_valid int32 []), on the device, fixed
+    summation order.  map@r = sums[0] / n_valid, r_precision = sums[1] / n_valid, map = sums[2] / n_valid."""
+    offset = offset.contiguous()
+    pos_rank = pos_rank.contiguous()
+    if offset.dtype != torch.int64 or pos_rank.dtype != torch.int32 or offset.dim() != 1 or offset.numel() < 2:
+        raise _lib.EmbnetError("retrieval_map_reduce: offset int64 [nq+1] and pos_rank int32 are needed")
+    nq = offset.numel() - 1
+    if pos_rank.numel() == 0:                               # no positive anywhere: nothing is read through this pointer
+        pos_rank = _new((1,), offset, torch.int32)
+    per = [_new((nq,), offset, torch.float64) for _ in range(3)]
+    sums = _new((3,), offset, torch.float64)
+    n_valid = _new((), offset, torch.int32)
+    check(_lib.lib().embnet_retrieval_map_reduce(ptr(offset), ptr(pos_rank), nq, ptr(per[0]), ptr(per[1]), ptr(per[2]), ptr(sums),
+                                                 ptr(n_valid), stream()))
+    return per[0], per[1], per[2], sums, n_valid

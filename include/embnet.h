@@ -165,6 +165,48 @@ int embnet_retrieval_first_positive(const float* q, const int32_t* q_labels, int
 int embnet_retrieval_reduce(const int32_t* rank, int nq, const int32_t* ks, int nk,
                             int32_t* hits, int32_t* n_valid, double* sum_inv_rank, void* stream);
 
+/* ---- retrieval evaluation (MAP@R, R-precision): the position of EVERY same-class gallery item of a query (csrc/retrieval.hip).
+ * Additions only: the ABI version stays 22.
+ *   Distance, order, exclusion, positives: exactly those of embnet_retrieval_first_positive above — d2 = rn + cn - 2 acc from the
+ *     same fp32 chain, NaN -> +inf, max(., 0); lexicographic order on (d2, gallery index); self_exclude skips the query's own
+ *     column; a positive is a non-excluded column with the query's label.
+ *   For query r let R be the number of its positives and p_1 .. p_R the positives in that order.  pos(p_j) = the 1-based position
+ *     of p_j among ALL non-excluded gallery items = j + the number of negatives in front of p_j.  Then
+ *       r_precision[r] = #{j : pos(p_j) <= R} / R
+ *       ap_at_r[r]     = (1 / R) * sum over {j : pos(p_j) <= R} of j / pos(p_j)
+ *       ap[r]          = (1 / R) * sum over all j of j / pos(p_j)
+ *     A query with R = 0 is invalid: its three values are NaN and it is left out of the sums.  map@r, r_precision and map are the
+ *     sums over the valid queries divided by n_valid (the caller's divisions).  pos(p_1) is embnet_retrieval_first_positive's rank.
+ * embnet_retrieval_positive_ranks.  Labels are DENSE ids in [0, num_classes).  Outputs (CSR):
+ *       offset[nq + 1] int64   offset[r + 1] - offset[r] = R of query r, offset[0] = 0
+ *       pos_index[capacity]    pos_index[offset[r] + j - 1] = gallery index of p_j
+ *       pos_rank[capacity]     pos_rank[offset[r] + j - 1]  = pos(p_j), strictly increasing within a query
+ *       status[1]              0 = ok; 1 = the sum of R exceeds `capacity`; 2 = some R exceeds EMBNET_RETRIEVAL_R_MAX; 3 = a label
+ *                              outside [0, num_classes) (the largest that applies).  Everything that depends on label CONTENTS is
+ *                              found on the device and reported here, not through the return value.  On a non-zero status offset is
+ *                              still written in full, pos_index / pos_rank are not written at all, and embnet_retrieval_map_reduce
+ *                              must not be called on them; every address derived from offset is guarded in the kernels (slot < R,
+ *                              offset + R <= capacity) whatever the status.
+ *   EMBNET_RETRIEVAL_R_MAX = 4096 positives per query: a segment of 4096 eight-byte keys is 32 KB, which a workgroup sorts in LDS
+ *     without the large-LDS opt-in.  Larger classes are refused (status 2).
+ *   Properties.  No [nq, n] buffer is formed: two walks of the distance GEMM consume d2 in registers.  The workspace is
+ *     O(nq + n + num_classes + capacity) bytes (>= embnet_retrieval_positive_ranks_workspace_bytes, 16-byte aligned, short -> -3).
+ *     Every result is an exact integer (stores of unique keys, a sort, integer counts).  The outputs are bitwise reproducible
+ *     across runs, streams and graph replay, although the slot a gallery item takes inside its class is not: the sort removes it.
+ *     The workspace needs no initialisation: counters, histogram and status are zeroed by the call's own kernels.  Both tile
+ *     geometries (64x64, 128x128, chosen as for embnet_retrieval_first_positive) and both loaders (16-byte; scalar for unaligned
+ *     pointers or e % 4 != 0) compute the same arithmetic.  No allocation and no synchronisation inside.
+ * embnet_retrieval_map_reduce: per query ap_at_r / r_precision / ap (f64[nq] each, NaN for R = 0) from offset and pos_rank;
+ *   sums[3] = their sums over the queries with R > 0 and *n_valid the number of those, folded in a fixed order (no float atomics). */
+#define EMBNET_RETRIEVAL_R_MAX 4096
+size_t embnet_retrieval_positive_ranks_workspace_bytes(int nq, int n, int num_classes, long capacity);
+int embnet_retrieval_positive_ranks(const float* q, const int32_t* q_labels, int nq,
+                                    const float* x, const int32_t* x_labels, int n, int e, int self_exclude,
+                                    int num_classes, long capacity, long long* offset, int32_t* pos_index, int32_t* pos_rank,
+                                    int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_retrieval_map_reduce(const long long* offset, const int32_t* pos_rank, int nq,
+                                double* ap_at_r, double* r_precision, double* ap, double* sums, int32_t* n_valid, void* stream);
+
 /* ------------------------------------------------------------------ backbone layers
  * Stand-ins for the Keras layers that backbones.py:19-121 instantiates (TensorFlow kernels in the
  * reference).  All NHWC fp32. */

@@ -17,7 +17,16 @@ generated from a seed on the device, leave-one-out:
   fused_kernel_us     per-kernel device time from the library's event trace, in a separate traced call
 Every size runs with the labels grouped by class (how encodings are produced: the nearest-positive pass is a sliver) and in
 shuffled order (nothing can be skipped: two full passes).
-Prints one JSON line per case; `--out` also writes the list to a file."""
+Prints one JSON line per case; `--out` also writes the list to a file.
+
+`--map`: the same table for ops.retrieval_positive_ranks + ops.retrieval_map_reduce (MAP@R / R-precision: the position of every
+positive), for classes of `--per-class` members (default 20 and 512), next to
+  (a) first_ms          ops.retrieval_first_positive + ops.retrieval_reduce at the same size — the same two GEMM walks without the
+                        key stores, the sort, the binary searches and the histogram atomics: the floor
+  (b) materialised_ms   ops.cross_distances(squared) + torch.sort(dim=1) + a gather of the labels, where the matrix fits
+the three alternating round by round in one process; `pass2_over_counting` = device time of map_walk_kernel<2> over that of
+retrieval_walk_kernel<2> from the library's event trace — what counting EVERY positive's negatives costs over counting the
+first's."""
 import argparse
 import json
 import os
@@ -65,6 +74,88 @@ def timed(fn):
     return a.elapsed_time(b), out
 
 
+def map_mode(args):
+    from embeddingnet_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    ks = torch.tensor([1, 10, 100, 1000], dtype=torch.int32, device=dev)
+
+    def positions(x, labels, classes, capacity):
+        offset, _, pos_rank = ops.retrieval_positive_ranks(x, labels, num_classes=classes, capacity=capacity)
+        return ops.retrieval_map_reduce(offset, pos_rank)
+
+    def first(x, labels):
+        rank, _, _ = ops.retrieval_first_positive(x, labels)
+        return ops.retrieval_reduce(rank, ks)
+
+    def materialised(x, labels):
+        d = ops.cross_distances(x, x, squared=True)
+        d.fill_diagonal_(float("inf"))
+        order = torch.sort(d, dim=1).indices
+        del d
+        return (labels[order] == labels[:, None]).nonzero()
+
+    def traced(fn, kernel):
+        _lib.trace_enable(True)
+        _lib.trace_reset()
+        fn()
+        torch.cuda.synchronize()
+        per = {}
+        for name, ms, _, _, _ in _lib.trace_records():
+            per[name.split("::")[-1]] = round(1e3 * ms, 1)
+        _lib.trace_enable(False)
+        _lib.trace_reset()
+        return per, per[kernel]
+
+    warm, wl = clustered(512, 64, dev)
+    positions(warm, wl, 32, 512 * 15), first(warm, wl), materialised(warm, wl)
+    results = []
+    for e in args.dims:
+        for n, per_class, order in [(n, c, o) for n in args.sizes for c in args.per_class for o in ("grouped", "shuffled")]:
+            x, labels = clustered(n, e, dev, order, per_class=per_class)
+            classes = max(n // per_class, 1)
+            capacity = int((torch.bincount(labels.long(), minlength=classes)[labels.long()] - 1).sum().item())
+            both = 4.0 * n * n <= args.max_matrix_gib * 2 ** 30           # (the sort adds a copy and 8-byte indices: 4x that)
+            run_p, run_f, run_m = (lambda: positions(x, labels, classes, capacity)), (lambda: first(x, labels)), (lambda: materialised(x, labels))
+            run_p(), run_f()
+            if both:
+                run_m()
+            t_p, t_f, t_m, out = [], [], [], None
+            for _ in range(args.rounds):
+                ms, out = timed(run_p)
+                t_p.append(ms)
+                t_f.append(timed(run_f)[0])
+                if both:
+                    t_m.append(timed(run_m)[0])
+                    torch.cuda.empty_cache()
+            per, walk2 = traced(run_p, "map_walk_kernel<2>")
+            _, count2 = traced(run_f, "retrieval_walk_kernel<2>")
+            sums, n_valid = out[3].cpu().numpy(), int(out[4].item())
+            p_ms, f_ms = float(np.median(t_p)), float(np.median(t_f))
+            res = {"mode": "map", "n": n, "e": e, "per_class": per_class, "label_order": order, "positives": capacity,
+                   "device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "leave_one_out": True,
+                   "map_ms": round(p_ms, 3), "map_ms_min_max": [round(min(t_p), 3), round(max(t_p), 3)],
+                   "first_ms": round(f_ms, 3), "first_ms_min_max": [round(min(t_f), 3), round(max(t_f), 3)],
+                   "map_over_first": round(p_ms / f_ms, 3), "pass2_over_counting": round(walk2 / count2, 3),
+                   "map_kernel_us": per, "map_at_r": round(float(sums[0]) / n_valid, 4), "r_precision": round(float(sums[1]) / n_valid, 4)}
+            if both:
+                m_ms = float(np.median(t_m))
+                res.update({"materialised_ms": round(m_ms, 3), "materialised_ms_min_max": [round(min(t_m), 3), round(max(t_m), 3)],
+                            "map_over_materialised": round(p_ms / m_ms, 3)})
+            print(json.dumps(res), flush=True)
+            results.append(res)
+            del x, labels
+            torch.cuda.empty_cache()
+    return results
+
+
+def write_out(args, results):
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[6100, 32768, 131072, 262144])
@@ -72,9 +163,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-matrix-gib", type=float, default=8.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--map", action="store_true", help="time the MAP@R primitive (see the module docstring)")
+    ap.add_argument("--per-class", type=int, nargs="+", default=[20, 512], help="--map: members per class")
     args = ap.parse_args()
     if args.rounds < 3:
         ap.error("--rounds must be at least 3")
+    if args.map:
+        if args.sizes == ap.get_default("sizes"):
+            args.sizes = [6100, 32768, 131072]
+        return write_out(args, map_mode(args))
     from embeddingnet_amd import _lib, ops
     dev = torch.device("cuda:0")
     ks = torch.tensor([1, 10, 100, 1000], dtype=torch.int32, device=dev)
@@ -130,11 +227,7 @@ def main():
             results.append(res)
             del x, labels
             torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+    write_out(args, results)
 
 
 if __name__ == "__main__":

@@ -136,12 +136,27 @@ def device_augmentations(cfg, synthetic=0, rank=0):
     return aug
 
 
+MAP_MONITORS = ('val_map@r', 'val_r_precision')
+
+
+def retrieval_map_config(p_train, validate):
+    """TRAIN.retrieval_map (optional, default off) -> bool: after each epoch's validation, MAP@R and R-precision of the validation
+    set (leave-one-out, EmbeddingNet.calculate_map_at_r) join the history as val_map@r / val_r_precision."""
+    on = p_train.get('retrieval_map') or False
+    if not isinstance(on, bool):
+        raise ValueError(f"TRAIN.retrieval_map: true or false (got {on!r})")
+    if on and not validate:
+        raise ValueError("TRAIN.retrieval_map evaluates the validation set: it needs DATALOADER.validate (validation is off)")
+    return on
+
+
 def monitor_config(p_train, validate):
     """TRAIN.retrieval_ks / TRAIN.monitor (both optional) -> (the K's of the per-epoch retrieval evaluation, the monitored name).
     retrieval_ks: after each epoch's validation, Recall@K and MRR of the validation set (leave-one-out,
     EmbeddingNet.calculate_retrieval_metrics) join the history as val_recall@K / val_mrr.  monitor: what plateau, early stop and
     best checkpoint follow — 'val_loss' ('loss' without validation) by default, or 'loss', 'val_recall@K' with K in
-    retrieval_ks, 'val_mrr'.  Anything that cannot be honoured is a ValueError before training starts."""
+    retrieval_ks, 'val_mrr', and with TRAIN.retrieval_map (retrieval_map_config) 'val_map@r' / 'val_r_precision' — larger is better
+    for all of those.  Anything that cannot be honoured is a ValueError before training starts."""
     ks = p_train.get('retrieval_ks') or []
     if isinstance(ks, (int, float)):
         ks = [ks]
@@ -160,8 +175,12 @@ def monitor_config(p_train, validate):
     elif monitor == 'val_mrr':
         if not ks:
             raise ValueError("TRAIN.monitor: 'val_mrr' needs TRAIN.retrieval_ks")
+    elif monitor in MAP_MONITORS:
+        if not retrieval_map_config(p_train, validate):
+            raise ValueError(f"TRAIN.monitor: {monitor!r} needs TRAIN.retrieval_map")
     elif monitor not in ('loss', 'val_loss'):
-        raise ValueError(f"TRAIN.monitor: unknown name {monitor!r} (loss, val_loss, val_recall@K, val_mrr)")
+        raise ValueError(f"TRAIN.monitor: unknown name {monitor!r} (loss, val_loss, val_recall@K, val_mrr, val_map@r, "
+                         "val_r_precision)")
     return ks, monitor
 
 
@@ -170,6 +189,7 @@ def main():
     cfg = parse_params(args.config)
     device_augmentations(cfg, args.synthetic)          # a bad GENERATOR.device_augmentations fails before the GPU is touched
     monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
+    retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
     paths = create_save_folders(cfg['general'])
@@ -191,6 +211,7 @@ def main():
     else:
         data_loader = ENDataLoader(**{k: v for k, v in p_loader.items() if k != 'csv_file'})
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
+    retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed')}
 
     siamese = p_model['mode'] == 'siamese'
@@ -250,6 +271,8 @@ def main():
         history[f'val_recall@{k}'] = []
     if retrieval_ks:
         history['val_mrr'] = []
+    if retrieval_map:
+        history['val_map@r'], history['val_r_precision'] = [], []
     n_epochs = min(p_train['n_epochs'], args.max_epochs or p_train['n_epochs'])
 
     # triplet mode: batches are planned on this thread and decoded / uploaded ahead of the step (input_pipeline.Feeder: the
@@ -304,6 +327,12 @@ def main():
                     with torch.no_grad():
                         found = model.calculate_retrieval_metrics(data_loader, ks=retrieval_ks)
                     for name in [f'recall@{k}' for k in retrieval_ks] + ['mrr']:
+                        history['val_' + name].append(all_reduce_mean(float(found[name])))
+                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                if retrieval_map:
+                    with torch.no_grad():
+                        found = model.calculate_map_at_r(data_loader)
+                    for name in ('map@r', 'r_precision'):
                         history['val_' + name].append(all_reduce_mean(float(found[name])))
                         msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
                 if monitor == 'loss':
