@@ -182,6 +182,7 @@ extern "C" int embnet_dense_dgrad_f32(const float* dy, const float* w, float* dx
                                       void* stream) {
   EMBNET_CHECK_ARG(dy && w && dx, "dense_dgrad: null pointer");
   EMBNET_CHECK_ARG(m > 0 && in > 0 && out > 0, "dense_dgrad: m=%d in=%d out=%d", m, in, out);
+  EMBNET_CHECK_ARG((size_t)m * out * 4 <= MAX_OPERAND_BYTES && (size_t)in * out * 4 <= MAX_OPERAND_BYTES, "dense: operand exceeds 2 GiB");
   DenseParams p{dy, w, nullptr, dx, m, in, out, 0, 0, 1, nullptr};
   const bool vec = (out & 3) == 0 && al16(dy) && al16(w);
   LAUNCH_DENSE(dense_dgrad_kernel, p, vec, (hipStream_t)stream);
@@ -192,6 +193,7 @@ extern "C" int embnet_dense_wgrad_f32(const float* x, const float* dy, float* dw
                                       void* stream) {
   EMBNET_CHECK_ARG(x && dy && dw, "dense_wgrad: null pointer");
   EMBNET_CHECK_ARG(m > 0 && in > 0 && out > 0, "dense_wgrad: m=%d in=%d out=%d", m, in, out);
+  EMBNET_CHECK_ARG((size_t)m * in * 4 <= MAX_OPERAND_BYTES && (size_t)m * out * 4 <= MAX_OPERAND_BYTES, "dense: operand exceeds 2 GiB");
   DenseParams p{x, dy, nullptr, dw, in, out, m, 0, 0, 1, nullptr};
   const bool vec = (in & 3) == 0 && (out & 3) == 0 && al16(x) && al16(dy);
   LAUNCH_DENSE(dense_wgrad_kernel, p, vec, (hipStream_t)stream);

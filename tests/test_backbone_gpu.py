@@ -432,6 +432,8 @@ def test_dense_gap_add_l2(dev):
     rs = np.random.RandomState(4)
     for m, i, o, relu in [(32, 9216, 256, True), (8, 512, 128, True), (5, 70, 33, False), (128, 12800, 512, True)]:
         d = L.Dense(i, o, activation="relu" if relu else None, gen=torch.Generator().manual_seed(i + o)).to(dev)
+        with torch.no_grad():
+            d.bias.copy_(g(0.5 * rs.randn(o), dev))           # (the layer starts at zero: a bias read from the wrong column would pass)
         x = rs.randn(m, i).astype(np.float32)
         tol = 2e-5 * max(1.0, (i / 2048) ** 0.5)            # k-ordered f32 chains of length `in` vs f64
         xt = g(x, dev).requires_grad_(True)

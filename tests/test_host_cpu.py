@@ -51,6 +51,25 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert rc == -1 and b"reaches outside" in lib.embnet_last_error()
 
 
+def test_dense_passes_refuse_operands_above_two_gib():
+    """Every operand of the Dense kernels is read through a buffer descriptor with a 32-bit size: all three passes refuse a matrix
+    above it before any launch (the pointers are dummies and never dereferenced)."""
+    from embeddingnet_amd import _lib
+    lib = _lib.lib()
+    p = 4096                                             # non-null, 16-byte aligned
+    big = [(32768, 16384, 8), (8, 32768, 16384), (32768, 8, 16384)]       # x, w, dy / y of 2 GiB each: over by 16 bytes
+    calls = {"fwd": lambda m, i, o: lib.embnet_dense_fwd_f32(p, p, None, p, m, i, o, 0, None, 0, None),
+             "dgrad": lambda m, i, o: lib.embnet_dense_dgrad_f32(p, p, p, m, i, o, None),
+             "wgrad": lambda m, i, o: lib.embnet_dense_wgrad_f32(p, p, p, m, i, o, None)}
+    reads = {"fwd": (0, 1), "dgrad": (1, 2), "wgrad": (0, 2)}              # which of (x, w, dy) a pass reads as an operand
+    for name, call in calls.items():
+        for which in reads[name]:
+            lib.embnet_dense_fwd_f32(None, None, None, None, 1, 1, 1, 0, None, 0, None)     # leaves another message behind
+            assert call(*big[which]) == -1 and b"dense: operand exceeds 2 GiB" in lib.embnet_last_error(), (name, which)
+    rc = lib.embnet_dense_dgrad_f32(None, p, p, 4, 4, 4, None)
+    assert rc == -1 and b"null pointer" in lib.embnet_last_error()
+
+
 def test_product_path_has_no_cpu_fallback():
     from embeddingnet_amd import _lib, ops
     from embeddingnet_amd.losses_and_accuracies import triplet_loss
