@@ -94,6 +94,13 @@ __device__ __forceinline__ int wave_sum(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// |row|^2 of e floats by the calling wave: lane-strided fma chain, then wave_sum — the same bits in every lane.  The distance
+// kernels (pairwise.hip, retrieval.hip) compare each other's results bit for bit, so their norms all come from here.
+__device__ __forceinline__ float row_sqnorm(const float* __restrict__ r, int e) {
+  float s = 0.f;
+  for (int k = threadIdx.x & 63; k < e; k += 64) s = fmaf(r[k], r[k], s);
+  return wave_sum(s);
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -13,13 +13,9 @@ namespace embnet {
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict__ x, int n, int e,
                                                          float* __restrict__ nn) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
   if (row >= n) return;
-  const float* r = x + (long)row * e;
-  float s = 0.f;
-  for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
-  s = wave_sum(s);
-  if (lane == 0) nn[row] = s;
+  const float s = row_sqnorm(x + (long)row * e, e);
+  if ((threadIdx.x & 63) == 0) nn[row] = s;
 }
 
 struct PairwiseParams {

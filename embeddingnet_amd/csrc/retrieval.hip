@@ -11,9 +11,12 @@
 // reproducible.  Pass 1 only needs the tiles that can hold a positive: every tile of 64 / 128 rows carries a 1 024-bit Bloom
 // filter of its labels (retrieval_bloom_kernel), and pass 1 skips a gallery tile whose filter shares no bit with the query
 // tile's.  With labels that come grouped by class (how encodings are produced) pass 1 is a sliver of pass 2; with labels
-// in random order nothing is skipped and the cost is two full passes — the result is the same either way.  A workgroup takes one tile of queries and WALKS a range of gallery tiles, keeping the minima / counts of
+// in random order nothing is skipped and the cost is two full passes — the result is the same either way.
+// A workgroup takes one tile of queries and WALKS a range of gallery tiles, keeping the minima / counts of
 // its rows in registers; it meets global memory with one atomic per row per wave at the end of the walk, so a row sees
 // (gallery splits) x (waves across the tile) atomics per pass, not one per gallery tile.
+// ONE walk (retrieval_walk) defines the metric for every kernel of this file: tile range, filter skip, d2, key, exclusion.  What
+// a pass keeps is its epilogue struct: NearestPositive and NegativesBelow here, StorePositives and CountByPosition for MAP@R.
 // Roofline: MFMA f32, 2 passes x 2*nq*n*e FLOP; HBM traffic O((nq + n) e), workspace O(nq + n).
 #include "gemm_engine.h"
 #include "../../include/embnet.h"
@@ -22,7 +25,7 @@ namespace embnet {
 
 constexpr unsigned long long NO_KEY = ~0ull;               // above every key: (+inf, any index) < NO_KEY
 
-// one wave per row: the squared norms of queries and gallery (row_sqnorm_kernel's chain), and the reset of the row's
+// one wave per row: the squared norms of queries and gallery (row_sqnorm, as row_sqnorm_kernel), and the reset of the row's
 // key and counter — by this kernel, not a memset node, so a replayed graph starts from a clean state
 __global__ __launch_bounds__(256) void retrieval_prep_kernel(const float* __restrict__ q, int nq, const float* __restrict__ x,
                                                              int n, int e, float* __restrict__ qn, float* __restrict__ xn,
@@ -30,17 +33,11 @@ __global__ __launch_bounds__(256) void retrieval_prep_kernel(const float* __rest
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row < nq) {
-    const float* r = q + (long)row * e;
-    float s = 0.f;
-    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
-    s = wave_sum(s);
+    const float s = row_sqnorm(q + (long)row * e, e);
     if (lane == 0) { qn[row] = s; key[row] = NO_KEY; count[row] = 0; }
   }
   if (row < n) {
-    const float* r = x + (long)row * e;
-    float s = 0.f;
-    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
-    s = wave_sum(s);
+    const float s = row_sqnorm(x + (long)row * e, e);
     if (lane == 0) xn[row] = s;
   }
 }
@@ -72,63 +69,88 @@ __global__ __launch_bounds__(256) void retrieval_bloom_kernel(const int32_t* __r
   if (threadIdx.x < BLOOM_WORDS) (is_q ? qbloom : xbloom)[(long)tile * BLOOM_WORDS + threadIdx.x] = s[threadIdx.x];
 }
 
-struct RetrievalParams {
+// What every walk reads; the kernels' parameter structs embed it.
+struct WalkParams {
   const float* q; const float* x; const float* qn; const float* xn;
   const int32_t* ql; const int32_t* xl;
-  unsigned long long* key; int32_t* count;
   const unsigned* qbloom; const unsigned* xbloom;
   int nq, n, e, self_exclude, tiles_per_split;
 };
 
-// PASS 1: nearest positive per row; PASS 2: negatives in front of it.  grid = (query tiles, gallery splits).
-// (two workgroups per CU asked for with the 16-byte loader, where the registers allow it without scratch; the scalar loader of
-// unaligned or ragged operands keeps 12 more address registers and runs one workgroup per SIMD at 128x128)
-template <class G, bool VEC, int PASS>
-__global__ __launch_bounds__(256, VEC ? 2 : 1) void retrieval_walk_kernel(RetrievalParams p) {
+// The row of the workgroup's tile of element r of this lane's accumulator block im (C/D map of the 32x32 MFMA: col = lane & 31,
+// row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).  The 32 lanes of a half wave hold the columns of the same rows.
+template <class G>
+__device__ __forceinline__ int walk_row(int im, int r) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  return (wave / G::WAVES_N) * G::WTM + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+}
+__device__ __forceinline__ unsigned long long half_wave_min(unsigned long long k) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) {
+    const unsigned long long ok = __shfl_xor(k, o, 64);
+    k = ok < k ? ok : k;
+  }
+  return k;
+}
+__device__ __forceinline__ int half_wave_sum(int c) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  return c;
+}
+
+// The walk: the workgroup's tile of queries (blockIdx.x) against its range of gallery tiles (blockIdx.y).  For every element
+// of every tile it hands the epilogue E the key (bits of d2) << 32 | column, `live` (a gallery column that is not the query's
+// own) and `same` (the labels agree), and keeps one Slot per row of the lane for it.  E has
+//   FILTER, Slot, INIT    FILTER: only positives matter: skip gallery tiles whose label filter shares no bit with the query tile's
+//   column(col)           what E needs per gallery column, fetched in front of the main loop that hides the load
+//   row(rt)               what E needs per row (rt = walk_row, the row in the tile), handed back to every visit of that row
+//   visit(slot value, rt, row value, column value, key, live, same) -> the new slot value
+//   half_wave(v), commit(rt, v)   the reduction over the row's lanes; what their first lane does with it for a row below nq
+// The barrier behind the row prologue also publishes the LDS rows the calling kernel filled for E before the call.
+template <class G, bool VEC, class E>
+__device__ __forceinline__ void retrieval_walk(const WalkParams& p, const E ep) {
   using TA = TileKC<G::BM>;
   using TB = TileKC<G::BN>;
-  constexpr int SLOTS = G::TM * 16;                        // rows of the tile this lane holds an element of
   __shared__ __attribute__((aligned(16))) float smem[MAIN_FLOATS<TA, TB>];
   __shared__ float s_qn[G::BM];
   __shared__ int s_ql[G::BM];
-  __shared__ unsigned long long s_thr[PASS == 2 ? G::BM : 1];
-  prio_hi();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
+  const int wn = (wave % G::WAVES_N) * G::WTN;
   const int m0 = blockIdx.x * G::BM;
   const int tiles_n = (p.n + G::BN - 1) / G::BN;
   const int t0 = blockIdx.y * p.tiles_per_split, t1 = min(t0 + p.tiles_per_split, tiles_n);
   const int kt_total = (p.e + BK - 1) / BK;
 
-  for (int i = tid; i < G::BM; i += NTHREADS) {            // the tile's rows: norm, label, pass-1 key
+  for (int i = tid; i < G::BM; i += NTHREADS) {            // the tile's rows: norm and label
     const int row = min(m0 + i, p.nq - 1);
     s_qn[i] = p.qn[row]; s_ql[i] = p.ql[row];
-    if (PASS == 2) s_thr[i] = p.key[row];
   }
   __syncthreads();
 
   LoadRowsKC<G::BM, VEC> la; la.init(p.q, p.e, p.nq, p.e, m0, tid);
   unsigned qb = 0u;                                        // this lane's word of the query tile's label filter
-  if (PASS == 1) qb = p.qbloom[(long)blockIdx.x * BLOOM_WORDS + (lane & 31)];
-  unsigned long long best[SLOTS];
-  int cnt[SLOTS];
+  if (E::FILTER) qb = p.qbloom[(long)blockIdx.x * BLOOM_WORDS + (lane & 31)];
+  // A plain local array that only this function touches, and visit() a pure function of its element: as a member of E, or
+  // handed to E by reference, the 128x128 kernels carry it twice through the tile loop and spill.
+  typename E::Slot out[G::TM * 16];
 #pragma unroll
-  for (int s = 0; s < SLOTS; ++s) { best[s] = NO_KEY; cnt[s] = 0; }
+  for (int s = 0; s < G::TM * 16; ++s) out[s] = E::INIT;
 
   for (int t = t0; t < t1; ++t) {
     const int n0 = t * G::BN;
-    if (PASS == 1) {                                       // no label in common: no positive here (the same answer in every wave)
+    if (E::FILTER) {                                       // no label in common: no positive here (the same answer in every wave)
       const unsigned w = qb & p.xbloom[(long)t * BLOOM_WORDS + (lane & 31)];
       if (__ballot(w != 0u) == 0ull) continue;
     }
     LoadRowsKC<G::BN, VEC> lb; lb.init(p.x, p.e, p.n, p.e, n0, tid);
     // the lane's columns: norm and label, requested in front of the main loop that hides them
-    float cn[G::TN]; int cl[G::TN]; int cc[G::TN];
+    float cn[G::TN]; int cl[G::TN]; int cc[G::TN]; int cx[G::TN];
 #pragma unroll
     for (int in = 0; in < G::TN; ++in) {
       const int col = n0 + wn + 32 * in + (lane & 31);
       cc[in] = col < p.n ? col : -1;                       // -1: past the gallery, never a positive and never counted
       cn[in] = p.xn[min(col, p.n - 1)]; cl[in] = p.xl[min(col, p.n - 1)];
+      cx[in] = ep.column(min(col, p.n - 1));
     }
     f32x16 acc[G::TM][G::TN];
     gemm_mainloop<G, TA, TB>(la, lb, 0, kt_total, smem, acc);
@@ -136,47 +158,89 @@ __global__ __launch_bounds__(256, VEC ? 2 : 1) void retrieval_walk_kernel(Retrie
     for (int im = 0; im < G::TM; ++im)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rt = wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int rt = walk_row<G>(im, r);
         const float rn = s_qn[rt]; const int rl = s_ql[rt];
         const int skip = p.self_exclude ? m0 + rt : -1;    // the query's own column
-        unsigned long long thr = 0;
-        if (PASS == 2) thr = s_thr[rt];
+        const auto rv = ep.row(rt);
 #pragma unroll
         for (int in = 0; in < G::TN; ++in) {
           const float v = rn + cn[in] - 2.f * acc[im][in][r];
           const float d2 = v != v ? INFINITY : fmaxf(v, 0.f);
           const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)cc[in];
           const bool live = cc[in] >= 0 && cc[in] != skip;
-          if (PASS == 1) {
-            if (live && cl[in] == rl && k < best[im * 16 + r]) best[im * 16 + r] = k;
-          } else {
-            cnt[im * 16 + r] += (live && cl[in] != rl && k < thr) ? 1 : 0;
-          }
+          out[im * 16 + r] = ep.visit(out[im * 16 + r], rt, rv, cx[in], k, live, cl[in] == rl);
         }
       }
   }
 
-  // the 32 lanes of a half wave hold the columns of the same rows
 #pragma unroll
   for (int im = 0; im < G::TM; ++im)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (PASS == 1) {
-        unsigned long long k = best[im * 16 + r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-          const unsigned long long ok = __shfl_xor(k, o, 64);
-          k = ok < k ? ok : k;
-        }
-        if ((lane & 31) == 0 && row < p.nq && k != NO_KEY) atomicMin(&p.key[row], k);
-      } else {
-        int c = cnt[im * 16 + r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if ((lane & 31) == 0 && row < p.nq && c != 0) atomicAdd(&p.count[row], c);
-      }
+      const auto v = E::half_wave(out[im * 16 + r]);
+      const int rt = walk_row<G>(im, r);
+      if ((lane & 31) == 0 && m0 + rt < p.nq) ep.commit(rt, v);
     }
+}
+
+// What an epilogue gets unless it says otherwise: an integer count per row, summed over the half wave; nothing to fetch per
+// column or per row, nothing to commit.
+struct WalkEpilogue {
+  static constexpr bool FILTER = false;
+  using Slot = int;
+  static constexpr Slot INIT = 0;
+  __device__ __forceinline__ int column(int) const { return 0; }
+  __device__ __forceinline__ int row(int) const { return 0; }
+  __device__ static __forceinline__ int half_wave(int c) { return half_wave_sum(c); }
+  __device__ __forceinline__ void commit(int, int) const {}
+};
+
+// pass 1 of Recall@K: the smallest key among each row's positives (key: of the tile's first row)
+struct NearestPositive : WalkEpilogue {
+  static constexpr bool FILTER = true;
+  using Slot = unsigned long long;
+  static constexpr Slot INIT = NO_KEY;
+  unsigned long long* key;
+  __device__ __forceinline__ Slot visit(Slot best, int, int, int, unsigned long long k, bool live, bool same) const {
+    // positives are rare.  Said so, the compiler keeps the update behind a branch, as it did when this was a conditional store
+    // into an array; as two selects per element a full pass 1 at 128x128 was 3.4 % slower in the one traced call of one
+    // session that compared them.
+    if (__builtin_expect(live && same, 0)) best = k < best ? k : best;
+    return best;
+  }
+  __device__ static __forceinline__ Slot half_wave(Slot k) { return half_wave_min(k); }
+  __device__ __forceinline__ void commit(int rt, Slot k) const { if (k != NO_KEY) atomicMin(&key[rt], k); }
+};
+
+// pass 2 of Recall@K: the negatives below the row's pass-1 key (s_thr: the tile's keys in LDS; count: of the tile's first row)
+struct NegativesBelow : WalkEpilogue {
+  const unsigned long long* s_thr; int32_t* count;
+  __device__ __forceinline__ unsigned long long row(int rt) const { return s_thr[rt]; }
+  __device__ __forceinline__ int visit(int cnt, int, unsigned long long thr, int, unsigned long long k, bool live, bool same) const {
+    return cnt + ((live && !same && k < thr) ? 1 : 0);
+  }
+  __device__ __forceinline__ void commit(int rt, int c) const { if (c != 0) atomicAdd(&count[rt], c); }
+};
+
+struct RetrievalParams {
+  WalkParams w;
+  unsigned long long* key; int32_t* count;
+};
+
+// PASS 1: nearest positive per row; PASS 2: negatives in front of it.  grid = (query tiles, gallery splits).
+// (two workgroups per CU asked for where the registers allow them without scratch at 128x128: every instantiation but pass 1
+// behind the scalar loader of unaligned or ragged operands, which keeps 12 more address registers next to the 64-bit minima)
+template <class G, bool VEC, int PASS>
+__global__ __launch_bounds__(256, (VEC || PASS == 2) ? 2 : 1) void retrieval_walk_kernel(RetrievalParams p) {
+  __shared__ unsigned long long s_thr[PASS == 2 ? G::BM : 1];
+  prio_hi();
+  const int m0 = blockIdx.x * G::BM;
+  if constexpr (PASS == 1) {
+    retrieval_walk<G, VEC>(p.w, NearestPositive{{}, p.key + m0});
+  } else {
+    for (int i = threadIdx.x; i < G::BM; i += NTHREADS) s_thr[i] = p.key[min(m0 + i, p.w.nq - 1)];
+    retrieval_walk<G, VEC>(p.w, NegativesBelow{{}, s_thr, p.count + m0});
+  }
 }
 
 __global__ __launch_bounds__(256) void retrieval_finish_kernel(const unsigned long long* __restrict__ key,
@@ -247,24 +311,61 @@ static void retrieval_plan(int nq, int n, bool& big, int& splits, int& tiles_per
   splits = cdiv(tiles_n, tiles_per_split);
 }
 
-static size_t round16(size_t v) { return (v + 15) / 16 * 16; }
+// A workspace handed out from the front in 16-byte steps.  Without a base it only adds up, so the constructor that carves a
+// workspace is also the one that sizes it.
+struct Bump {
+  char* base; size_t used = 0;
+  template <class T> T* take(size_t count) {
+    T* at = base ? (T*)(base + used) : nullptr;
+    used += (count * sizeof(T) + 15) / 16 * 16;
+    return at;
+  }
+  unsigned* take_bloom(int rows) { return take<unsigned>((size_t)cdiv(rows, 64) * BLOOM_WORDS); }   // sized for 64-row tiles
+};
 
-// keys u64[nq] | counters i32[nq] | query norms f32[nq] | gallery norms f32[n] | label filters of the query tiles | of the
-// gallery tiles (sized for 64-row tiles: 2 bytes per row)
-static size_t bloom_bytes(int rows) { return (size_t)cdiv(rows, 64) * BLOOM_WORDS * sizeof(unsigned); }
+struct RetrievalWorkspace {
+  unsigned long long* key; int32_t* count; float* qn; float* xn; unsigned* qbloom; unsigned* xbloom;
+  size_t bytes;
+  RetrievalWorkspace(void* base, int nq, int n) {
+    Bump b{(char*)base};
+    key = b.take<unsigned long long>(nq); count = b.take<int32_t>(nq);
+    qn = b.take<float>(nq); xn = b.take<float>(n);
+    qbloom = b.take_bloom(nq); xbloom = b.take_bloom(n);
+    bytes = b.used;
+  }
+};
 extern "C" size_t embnet_retrieval_workspace_bytes(int nq, int n) {
-  if (nq <= 0 || n <= 0) return 0;
-  return round16((size_t)nq * 8) + round16((size_t)nq * 4) + round16((size_t)nq * 4) + round16((size_t)n * 4) +
-         bloom_bytes(nq) + bloom_bytes(n);
+  return nq <= 0 || n <= 0 ? 0 : RetrievalWorkspace(nullptr, nq, n).bytes;
 }
 
-template <class G>
-static void retrieval_launch(const RetrievalParams& p, bool vec, int pass, dim3 grid, hipStream_t s) {
-  if (pass == 1) {
-    if (vec) retrieval_walk_kernel<G, true, 1><<<grid, 256, 0, s>>>(p); else retrieval_walk_kernel<G, false, 1><<<grid, 256, 0, s>>>(p);
-  } else {
-    if (vec) retrieval_walk_kernel<G, true, 2><<<grid, 256, 0, s>>>(p); else retrieval_walk_kernel<G, false, 2><<<grid, 256, 0, s>>>(p);
-  }
+// What the two entry points share in front of their walks: the plan, the loader, the grid, the label filters (launched here).
+// ws: the entry point's workspace, for its norms and filters.
+struct WalkSetup { WalkParams w; bool big, vec; dim3 grid; };
+template <class W>
+static WalkSetup walk_setup(const float* q, const int32_t* q_labels, int nq, const float* x, const int32_t* x_labels, int n, int e,
+                            int self_exclude, const W& ws, hipStream_t s) {
+  WalkSetup su{{q, x, ws.qn, ws.xn, q_labels, x_labels, ws.qbloom, ws.xbloom, nq, n, e, self_exclude ? 1 : 0, 0}};
+  int splits;
+  retrieval_plan(nq, n, su.big, splits, su.w.tiles_per_split);
+  const int tile_rows = su.big ? 128 : 64, q_tiles = cdiv(nq, tile_rows);
+  su.vec = (e & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  su.grid = dim3(q_tiles, splits);
+  EMBNET_TRACE("embnet::retrieval_bloom_kernel", TRACE_BYTES, 4.0 * ((double)nq + n), s);
+  retrieval_bloom_kernel<<<q_tiles + cdiv(n, tile_rows), 256, 0, s>>>(q_labels, nq, x_labels, n, tile_rows, q_tiles, ws.qbloom, ws.xbloom);
+  return su;
+}
+
+// One traced walk: launch(geometry, loader, pass), as types, for the instantiation that the setup and `pass` (1 or 2) select.
+// `extra_bytes`: what the family moves on top of the two embedding blocks.
+template <class F>
+static void walk_dispatch(const WalkSetup& su, int pass, const char* trace_name, double extra_bytes, hipStream_t s, F launch) {
+  const double rows = (double)su.w.nq + su.w.n;
+  EMBNET_TRACE_FLOP(trace_name, 2.0 * su.w.nq * su.w.n * su.w.e, 4.0 * rows * su.w.e + extra_bytes, s);
+  auto by_pass = [&](auto g, auto vec) {
+    if (pass == 1) launch(g, vec, std::integral_constant<int, 1>{}); else launch(g, vec, std::integral_constant<int, 2>{});
+  };
+  auto by_loader = [&](auto g) { if (su.vec) by_pass(g, std::true_type{}); else by_pass(g, std::false_type{}); };
+  if (su.big) by_loader(Geom<128, 128, 2, 2>{}); else by_loader(Geom<64, 64, 2, 2>{});
 }
 
 extern "C" int embnet_retrieval_first_positive(const float* q, const int32_t* q_labels, int nq,
@@ -277,44 +378,24 @@ extern "C" int embnet_retrieval_first_positive(const float* q, const int32_t* q_
   EMBNET_CHECK_ARG((size_t)nq * e * 4 <= MAX_OPERAND_BYTES && (size_t)n * e * 4 <= MAX_OPERAND_BYTES,
                    "retrieval: an embedding block exceeds 2 GiB");
   EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "retrieval: workspace must be 16-byte aligned");
-  if (workspace_bytes < embnet_retrieval_workspace_bytes(nq, n))
-    return fail(EMBNET_EWORKSPACE, "retrieval: workspace %zu < %zu bytes", workspace_bytes, embnet_retrieval_workspace_bytes(nq, n));
+  const RetrievalWorkspace w(workspace, nq, n);
+  if (workspace_bytes < w.bytes) return fail(EMBNET_EWORKSPACE, "retrieval: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)workspace;
-  unsigned long long* key = (unsigned long long*)w;  w += round16((size_t)nq * 8);
-  int32_t* count = (int32_t*)w;                      w += round16((size_t)nq * 4);
-  float* qn = (float*)w;                             w += round16((size_t)nq * 4);
-  float* xn = (float*)w;                             w += round16((size_t)n * 4);
-  unsigned* qbloom = (unsigned*)w;                   w += bloom_bytes(nq);
-  unsigned* xbloom = (unsigned*)w;
   {
     EMBNET_TRACE("embnet::retrieval_prep_kernel", TRACE_BYTES, 4.0 * ((double)nq * e + (double)n * e), s);
-    retrieval_prep_kernel<<<cdiv(nq > n ? nq : n, 4), 256, 0, s>>>(q, nq, x, n, e, qn, xn, key, count);
+    retrieval_prep_kernel<<<cdiv(nq > n ? nq : n, 4), 256, 0, s>>>(q, nq, x, n, e, w.qn, w.xn, w.key, w.count);
   }
-  bool big; int splits, tps; retrieval_plan(nq, n, big, splits, tps);
-  const int tile_rows = big ? 128 : 64;
-  {
-    EMBNET_TRACE("embnet::retrieval_bloom_kernel", TRACE_BYTES, 4.0 * ((double)nq + n), s);
-    const int q_tiles = cdiv(nq, tile_rows);
-    retrieval_bloom_kernel<<<q_tiles + cdiv(n, tile_rows), 256, 0, s>>>(q_labels, nq, x_labels, n, tile_rows, q_tiles, qbloom, xbloom);
-  }
-  RetrievalParams p{q, x, qn, xn, q_labels, x_labels, key, count, qbloom, xbloom, nq, n, e, self_exclude ? 1 : 0, tps};
-  const bool vec = (e & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-  const dim3 grid(cdiv(nq, tile_rows), splits);
-  const double flop = 2.0 * nq * n * e, bytes = 4.0 * ((double)nq * e + (double)n * e) + 16.0 * nq + 8.0 * n;
-  using GS = Geom<64, 64, 2, 2>;
-  using GL = Geom<128, 128, 2, 2>;
-  {
-    EMBNET_TRACE_FLOP("embnet::retrieval_walk_kernel<1>", flop, bytes, s);
-    if (big) retrieval_launch<GL>(p, vec, 1, grid, s); else retrieval_launch<GS>(p, vec, 1, grid, s);
-  }
-  {
-    EMBNET_TRACE_FLOP("embnet::retrieval_walk_kernel<2>", flop, bytes, s);
-    if (big) retrieval_launch<GL>(p, vec, 2, grid, s); else retrieval_launch<GS>(p, vec, 2, grid, s);
-  }
+  const WalkSetup su = walk_setup(q, q_labels, nq, x, x_labels, n, e, self_exclude, w, s);
+  const RetrievalParams p{su.w, w.key, w.count};
+  auto launch = [&](auto g, auto vec, auto pass) {
+    retrieval_walk_kernel<decltype(g), decltype(vec)::value, decltype(pass)::value><<<su.grid, 256, 0, s>>>(p);
+  };
+  const double extra = 16.0 * nq + 8.0 * n;
+  walk_dispatch(su, 1, "embnet::retrieval_walk_kernel<1>", extra, s, launch);
+  walk_dispatch(su, 2, "embnet::retrieval_walk_kernel<2>", extra, s, launch);
   {
     EMBNET_TRACE("embnet::retrieval_finish_kernel", TRACE_BYTES, 24.0 * nq, s);
-    retrieval_finish_kernel<<<cdiv(nq, 256), 256, 0, s>>>(key, count, nq, rank, pos_index, pos_d2);
+    retrieval_finish_kernel<<<cdiv(nq, 256), 256, 0, s>>>(w.key, w.count, nq, rank, pos_index, pos_d2);
   }
   return check_launch("retrieval_first_positive");
 }
@@ -333,7 +414,7 @@ extern "C" int embnet_retrieval_reduce(const int32_t* rank, int nq, const int32_
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // MAP@R / R-precision: the position of EVERY positive of a query, not only the first (include/embnet.h, "positive ranks").
-// The same distance walk, order, exclusion and label filters as above; what changes is what the epilogue keeps:
+// retrieval_walk again: the distance, order, exclusion and label filters are the ones above; what changes is the epilogue:
 //   prep:   norms; class sizes by integer atomicAdd, x_slot[c] = the value that add returned (any bijection of a class onto
 //           0..count-1 will do: keys carry the gallery index, and the sort below removes the assignment from the result);
 //           R[r] = size of the query's class (- 1 with self-exclusion), offset = exclusive scan of R
@@ -370,20 +451,14 @@ __global__ __launch_bounds__(256) void map_prep_kernel(const float* __restrict__
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row < nq) {
-    const float* r = q + (long)row * e;
-    float s = 0.f;
-    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
-    s = wave_sum(s);
+    const float s = row_sqnorm(q + (long)row * e, e);
     if (lane == 0) {
       qn[row] = s;
       if ((unsigned)ql[row] >= (unsigned)num_classes) atomicMax(status, (int)MAP_LABEL);
     }
   }
   if (row < n) {
-    const float* r = x + (long)row * e;
-    float s = 0.f;
-    for (int k = lane; k < e; k += 64) s = fmaf(r[k], r[k], s);
-    s = wave_sum(s);
+    const float s = row_sqnorm(x + (long)row * e, e);
     if (lane == 0) {
       xn[row] = s;
       const int c = xl[row];
@@ -437,25 +512,58 @@ __global__ __launch_bounds__(1024) void map_scan_kernel(const int32_t* __restric
 }
 
 struct MapParams {
-  const float* q; const float* x; const float* qn; const float* xn;
-  const int32_t* ql; const int32_t* xl;
+  WalkParams w;
   const long long* offset; const int32_t* x_slot; const int32_t* status;
   unsigned long long* keys; int32_t* between;
-  const unsigned* qbloom; const unsigned* xbloom;
   long capacity;
-  int nq, n, e, self_exclude, tiles_per_split;
 };
 
-// retrieval_walk_kernel's walk.  PASS 1 stores the positives' keys, PASS 2 counts the negatives by the number of positives in
-// front of them.  A row whose segment does not fit (or a row past nq) gets R = 0: nothing is stored or counted for it.
+// pass 1 of MAP@R: every positive's key goes to its slot of the row's segment.  s_R, s_off: the rows' segments; s_own: the
+// slot of the query's own column (the slots behind it move up by one), past every slot without self-exclusion.
+struct StorePositives : WalkEpilogue {
+  static constexpr bool FILTER = true;
+  const int32_t* x_slot; unsigned long long* keys;
+  const int* s_R; const long long* s_off; const int* s_own;
+  __device__ __forceinline__ int column(int col) const { return x_slot[col]; }
+  __device__ __forceinline__ int row(int rt) const { return s_R[rt]; }
+  __device__ __forceinline__ int visit(int, int rt, int R, int cs, unsigned long long k, bool live, bool same) const {
+    if (live && same) {
+      const int slot = cs - (cs > s_own[rt] ? 1 : 0);
+      if ((unsigned)slot < (unsigned)R) keys[s_off[rt] + slot] = k;
+    }
+    return 0;                                              // nothing to keep per row
+  }
+};
+
+// pass 2 of MAP@R: a negative counts by the number of the row's positives in front of it.  Below the first positive
+// (s_first): in the row's slot, as NegativesBelow; between the first and the last (s_last): a binary search of the sorted
+// segment and one atomic.
+struct CountByPosition : WalkEpilogue {
+  struct Row { unsigned long long first, last; int R; };
+  const unsigned long long* keys; int32_t* between;
+  const int* s_R; const long long* s_off; const unsigned long long* s_first; const unsigned long long* s_last;
+  __device__ __forceinline__ Row row(int rt) const { return {s_first[rt], s_last[rt], s_R[rt]}; }
+  __device__ __forceinline__ int visit(int cnt, int rt, Row w, int, unsigned long long k, bool live, bool same) const {
+    const bool neg = live && !same;
+    cnt += (neg && k < w.first) ? 1 : 0;
+    if (neg && k > w.first && k < w.last) {                // between two positives: how many are in front of it
+      const unsigned long long* seg = keys + s_off[rt];
+      int lo = 1, hi = w.R - 1;                            // keys[0] < k < keys[R - 1]: the answer lies in 1 .. R - 1
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (seg[mid] < k) lo = mid + 1; else hi = mid;
+      }
+      atomicAdd(&between[s_off[rt] + lo], 1);
+    }
+    return cnt;
+  }
+  __device__ __forceinline__ void commit(int rt, int c) const { if (c != 0 && s_R[rt] > 0) atomicAdd(&between[s_off[rt]], c); }
+};
+
+// PASS 1 stores the positives' keys, PASS 2 counts the negatives by the number of positives in front of them.  A row whose
+// segment does not fit (or a row past nq) gets R = 0: nothing is stored or counted for it.
 template <class G, bool VEC, int PASS>
 __global__ __launch_bounds__(256, VEC ? 2 : 1) void map_walk_kernel(MapParams p) {
-  using TA = TileKC<G::BM>;
-  using TB = TileKC<G::BN>;
-  constexpr int SLOTS = G::TM * 16;
-  __shared__ __attribute__((aligned(16))) float smem[MAIN_FLOATS<TA, TB>];
-  __shared__ float s_qn[G::BM];
-  __shared__ int s_ql[G::BM];
   __shared__ int s_R[G::BM];
   __shared__ long long s_off[G::BM];
   __shared__ int s_own[PASS == 1 ? G::BM : 1];
@@ -463,98 +571,17 @@ __global__ __launch_bounds__(256, VEC ? 2 : 1) void map_walk_kernel(MapParams p)
   __shared__ unsigned long long s_last[PASS == 2 ? G::BM : 1];
   if (*p.status != MAP_OK) return;                         // the same answer in every thread
   prio_hi();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave / G::WAVES_N) * G::WTM, wn = (wave % G::WAVES_N) * G::WTN;
   const int m0 = blockIdx.x * G::BM;
-  const int tiles_n = (p.n + G::BN - 1) / G::BN;
-  const int t0 = blockIdx.y * p.tiles_per_split, t1 = min(t0 + p.tiles_per_split, tiles_n);
-  const int kt_total = (p.e + BK - 1) / BK;
-
-  for (int i = tid; i < G::BM; i += NTHREADS) {
-    const int row = min(m0 + i, p.nq - 1);
+  for (int i = threadIdx.x; i < G::BM; i += NTHREADS) {
+    const int row = min(m0 + i, p.w.nq - 1);
     const long long off = p.offset[row], R = p.offset[row + 1] - off;
-    const bool fits = m0 + i < p.nq && off >= 0 && R > 0 && R <= R_MAX && off + R <= p.capacity;
-    s_qn[i] = p.qn[row]; s_ql[i] = p.ql[row];
+    const bool fits = m0 + i < p.w.nq && off >= 0 && R > 0 && R <= R_MAX && off + R <= p.capacity;
     s_off[i] = off; s_R[i] = fits ? (int)R : 0;
-    if (PASS == 1) s_own[i] = p.self_exclude ? p.x_slot[row] : 0x7fffffff;
+    if (PASS == 1) s_own[i] = p.w.self_exclude ? p.x_slot[row] : 0x7fffffff;
     if (PASS == 2) { s_first[i] = fits ? p.keys[off] : 0ull; s_last[i] = fits ? p.keys[off + R - 1] : 0ull; }
   }
-  __syncthreads();
-
-  LoadRowsKC<G::BM, VEC> la; la.init(p.q, p.e, p.nq, p.e, m0, tid);
-  unsigned qb = 0u;
-  if (PASS == 1) qb = p.qbloom[(long)blockIdx.x * BLOOM_WORDS + (lane & 31)];
-  int cnt[PASS == 2 ? SLOTS : 1];                          // negatives in front of the row's first positive
-#pragma unroll
-  for (int s = 0; s < (PASS == 2 ? SLOTS : 1); ++s) cnt[s] = 0;
-
-  for (int t = t0; t < t1; ++t) {
-    const int n0 = t * G::BN;
-    if (PASS == 1) {
-      const unsigned w = qb & p.xbloom[(long)t * BLOOM_WORDS + (lane & 31)];
-      if (__ballot(w != 0u) == 0ull) continue;
-    }
-    LoadRowsKC<G::BN, VEC> lb; lb.init(p.x, p.e, p.n, p.e, n0, tid);
-    float cn[G::TN]; int cl[G::TN]; int cc[G::TN]; int cs[G::TN];
-#pragma unroll
-    for (int in = 0; in < G::TN; ++in) {
-      const int col = n0 + wn + 32 * in + (lane & 31);
-      cc[in] = col < p.n ? col : -1;
-      cn[in] = p.xn[min(col, p.n - 1)]; cl[in] = p.xl[min(col, p.n - 1)];
-      cs[in] = PASS == 1 ? p.x_slot[min(col, p.n - 1)] : 0;
-    }
-    f32x16 acc[G::TM][G::TN];
-    gemm_mainloop<G, TA, TB>(la, lb, 0, kt_total, smem, acc);
-#pragma unroll
-    for (int im = 0; im < G::TM; ++im)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rt = wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float rn = s_qn[rt]; const int rl = s_ql[rt];
-        const int skip = p.self_exclude ? m0 + rt : -1;
-        const int R = s_R[rt];
-        unsigned long long first = 0, last = 0;
-        if (PASS == 2) { first = s_first[rt]; last = s_last[rt]; }
-#pragma unroll
-        for (int in = 0; in < G::TN; ++in) {
-          const float v = rn + cn[in] - 2.f * acc[im][in][r];
-          const float d2 = v != v ? INFINITY : fmaxf(v, 0.f);
-          const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)cc[in];
-          const bool live = cc[in] >= 0 && cc[in] != skip;
-          if (PASS == 1) {
-            if (live && cl[in] == rl) {
-              const int slot = cs[in] - (cs[in] > s_own[rt] ? 1 : 0);
-              if ((unsigned)slot < (unsigned)R) p.keys[s_off[rt] + slot] = k;
-            }
-          } else {
-            const bool neg = live && cl[in] != rl;
-            cnt[im * 16 + r] += (neg && k < first) ? 1 : 0;
-            if (neg && k > first && k < last) {            // between two positives: how many are in front of it
-              const unsigned long long* seg = p.keys + s_off[rt];
-              int lo = 1, hi = R - 1;                      // keys[0] < k < keys[R - 1]: the answer lies in 1 .. R - 1
-              while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (seg[mid] < k) lo = mid + 1; else hi = mid;
-              }
-              atomicAdd(&p.between[s_off[rt] + lo], 1);
-            }
-          }
-        }
-      }
-  }
-
-  if (PASS == 2) {
-#pragma unroll
-    for (int im = 0; im < G::TM; ++im)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rt = wm + 32 * im + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        int c = cnt[im * 16 + r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if ((lane & 31) == 0 && c != 0 && s_R[rt] > 0) atomicAdd(&p.between[s_off[rt]], c);
-      }
-  }
+  if constexpr (PASS == 1) retrieval_walk<G, VEC>(p.w, StorePositives{{}, p.x_slot, p.keys, s_R, s_off, s_own});
+  else retrieval_walk<G, VEC>(p.w, CountByPosition{{}, p.keys, p.between, s_R, s_off, s_first, s_last});
 }
 
 // a query's segment, or -1 when there is nothing to do for it (no positive, or a segment that does not fit)
@@ -693,21 +720,21 @@ __global__ __launch_bounds__(1024) void map_total_kernel(const long long* __rest
 
 }  // namespace embnet
 
-// query norms f32[nq] | gallery norms f32[n] | label filters (query tiles, gallery tiles) | class sizes i32[num_classes] |
-// gallery slots i32[n] | keys u64[capacity] | between i32[capacity]
-extern "C" size_t embnet_retrieval_positive_ranks_workspace_bytes(int nq, int n, int num_classes, long capacity) {
-  if (nq <= 0 || n <= 0 || num_classes <= 0 || capacity <= 0) return 0;
-  return round16((size_t)nq * 4) + round16((size_t)n * 4) + bloom_bytes(nq) + bloom_bytes(n) + round16((size_t)num_classes * 4) +
-         round16((size_t)n * 4) + round16((size_t)capacity * 8) + round16((size_t)capacity * 4);
-}
-
-template <class G>
-static void map_launch(const MapParams& p, bool vec, int pass, dim3 grid, hipStream_t s) {
-  if (pass == 1) {
-    if (vec) map_walk_kernel<G, true, 1><<<grid, 256, 0, s>>>(p); else map_walk_kernel<G, false, 1><<<grid, 256, 0, s>>>(p);
-  } else {
-    if (vec) map_walk_kernel<G, true, 2><<<grid, 256, 0, s>>>(p); else map_walk_kernel<G, false, 2><<<grid, 256, 0, s>>>(p);
+struct MapWorkspace {
+  float* qn; float* xn; unsigned* qbloom; unsigned* xbloom; int32_t* class_count; int32_t* x_slot;
+  unsigned long long* keys; int32_t* between;
+  size_t bytes;
+  MapWorkspace(void* base, int nq, int n, int num_classes, long capacity) {
+    Bump b{(char*)base};
+    qn = b.take<float>(nq); xn = b.take<float>(n);
+    qbloom = b.take_bloom(nq); xbloom = b.take_bloom(n);
+    class_count = b.take<int32_t>(num_classes); x_slot = b.take<int32_t>(n);
+    keys = b.take<unsigned long long>(capacity); between = b.take<int32_t>(capacity);
+    bytes = b.used;
   }
+};
+extern "C" size_t embnet_retrieval_positive_ranks_workspace_bytes(int nq, int n, int num_classes, long capacity) {
+  return nq <= 0 || n <= 0 || num_classes <= 0 || capacity <= 0 ? 0 : MapWorkspace(nullptr, nq, n, num_classes, capacity).bytes;
 }
 
 extern "C" int embnet_retrieval_positive_ranks(const float* q, const int32_t* q_labels, int nq,
@@ -725,61 +752,39 @@ extern "C" int embnet_retrieval_positive_ranks(const float* q, const int32_t* q_
                    "retrieval_positive_ranks: an embedding block exceeds 2 GiB");
   EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "retrieval_positive_ranks: workspace must be 16-byte aligned");
   EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(offset) & 7) == 0, "retrieval_positive_ranks: offset must be 8-byte aligned");
-  const size_t need = embnet_retrieval_positive_ranks_workspace_bytes(nq, n, num_classes, capacity);
-  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "retrieval_positive_ranks: workspace %zu < %zu bytes", workspace_bytes, need);
+  const MapWorkspace w(workspace, nq, n, num_classes, capacity);
+  if (workspace_bytes < w.bytes)
+    return fail(EMBNET_EWORKSPACE, "retrieval_positive_ranks: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)workspace;
-  float* qn = (float*)w;                             w += round16((size_t)nq * 4);
-  float* xn = (float*)w;                             w += round16((size_t)n * 4);
-  unsigned* qbloom = (unsigned*)w;                   w += bloom_bytes(nq);
-  unsigned* xbloom = (unsigned*)w;                   w += bloom_bytes(n);
-  int32_t* class_count = (int32_t*)w;                w += round16((size_t)num_classes * 4);
-  int32_t* x_slot = (int32_t*)w;                     w += round16((size_t)n * 4);
-  unsigned long long* keys = (unsigned long long*)w; w += round16((size_t)capacity * 8);
-  int32_t* between = (int32_t*)w;
   {
     EMBNET_TRACE("embnet::map_zero_kernel", TRACE_BYTES, 4.0 * ((double)num_classes + (double)capacity), s);
     const long cells = capacity > num_classes ? capacity : num_classes;
-    map_zero_kernel<<<cdiv(cells, 256), 256, 0, s>>>(class_count, num_classes, between, capacity, status);
+    map_zero_kernel<<<cdiv(cells, 256), 256, 0, s>>>(w.class_count, num_classes, w.between, capacity, status);
   }
   {
     EMBNET_TRACE("embnet::map_prep_kernel", TRACE_BYTES, 4.0 * ((double)nq * e + (double)n * e), s);
-    map_prep_kernel<<<cdiv(nq > n ? nq : n, 4), 256, 0, s>>>(q, q_labels, nq, x, x_labels, n, e, num_classes, qn, xn, class_count,
-                                                             x_slot, status);
+    map_prep_kernel<<<cdiv(nq > n ? nq : n, 4), 256, 0, s>>>(q, q_labels, nq, x, x_labels, n, e, num_classes, w.qn, w.xn,
+                                                             w.class_count, w.x_slot, status);
   }
-  bool big; int splits, tps; retrieval_plan(nq, n, big, splits, tps);
-  const int tile_rows = big ? 128 : 64;
-  {
-    EMBNET_TRACE("embnet::retrieval_bloom_kernel", TRACE_BYTES, 4.0 * ((double)nq + n), s);
-    const int q_tiles = cdiv(nq, tile_rows);
-    retrieval_bloom_kernel<<<q_tiles + cdiv(n, tile_rows), 256, 0, s>>>(q_labels, nq, x_labels, n, tile_rows, q_tiles, qbloom, xbloom);
-  }
+  const WalkSetup su = walk_setup(q, q_labels, nq, x, x_labels, n, e, self_exclude, w, s);
   {
     EMBNET_TRACE("embnet::map_scan_kernel", TRACE_BYTES, 16.0 * nq, s);
-    map_scan_kernel<<<1, 1024, 0, s>>>(q_labels, nq, class_count, num_classes, self_exclude ? 1 : 0, capacity, offset, status);
+    map_scan_kernel<<<1, 1024, 0, s>>>(q_labels, nq, w.class_count, num_classes, self_exclude ? 1 : 0, capacity, offset, status);
   }
-  MapParams p{q, x, qn, xn, q_labels, x_labels, offset, x_slot, status, keys, between, qbloom, xbloom, capacity,
-              nq, n, e, self_exclude ? 1 : 0, tps};
-  const bool vec = (e & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-  const dim3 grid(cdiv(nq, tile_rows), splits);
-  const double flop = 2.0 * nq * n * e, bytes = 4.0 * ((double)nq * e + (double)n * e) + 16.0 * nq + 12.0 * n + 12.0 * capacity;
-  using GS = Geom<64, 64, 2, 2>;
-  using GL = Geom<128, 128, 2, 2>;
-  {
-    EMBNET_TRACE_FLOP("embnet::map_walk_kernel<1>", flop, bytes, s);
-    if (big) map_launch<GL>(p, vec, 1, grid, s); else map_launch<GS>(p, vec, 1, grid, s);
-  }
+  const MapParams p{su.w, offset, w.x_slot, status, w.keys, w.between, capacity};
+  auto launch = [&](auto g, auto vec, auto pass) {
+    map_walk_kernel<decltype(g), decltype(vec)::value, decltype(pass)::value><<<su.grid, 256, 0, s>>>(p);
+  };
+  const double extra = 16.0 * nq + 12.0 * n + 12.0 * capacity;
+  walk_dispatch(su, 1, "embnet::map_walk_kernel<1>", extra, s, launch);
   {
     EMBNET_TRACE("embnet::map_sort_kernel", TRACE_BYTES, 16.0 * capacity, s);
-    map_sort_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, keys);
+    map_sort_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, w.keys);
   }
-  {
-    EMBNET_TRACE_FLOP("embnet::map_walk_kernel<2>", flop, bytes, s);
-    if (big) map_launch<GL>(p, vec, 2, grid, s); else map_launch<GS>(p, vec, 2, grid, s);
-  }
+  walk_dispatch(su, 2, "embnet::map_walk_kernel<2>", extra, s, launch);
   {
     EMBNET_TRACE("embnet::map_finish_kernel", TRACE_BYTES, 20.0 * capacity, s);
-    map_finish_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, keys, between, pos_index, pos_rank);
+    map_finish_kernel<<<cdiv(nq, 4), 256, 0, s>>>(offset, nq, capacity, status, w.keys, w.between, pos_index, pos_rank);
   }
   return check_launch("retrieval_positive_ranks");
 }

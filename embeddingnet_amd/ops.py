@@ -357,32 +357,39 @@ def knn_vote(idx, labels):
 
 
 # --------------------------------------------------------------------------- evaluation: retrieval (Recall@K, MRR)
+def _retrieval_blocks(who, q, q_labels, x, x_labels):
+    """The shared opening of the two retrieval primitives -> (q, ql, x, xl, self_exclude, nq, n, e): float32 blocks and int32
+    labels, contiguous; x None: leave-one-out, the gallery IS the query block.  Errors name the caller `who`."""
+    q = _prep(q.detach())
+    ql = q_labels.to(torch.int32).contiguous()
+    self_exclude = x is None
+    if self_exclude:
+        if x_labels is not None:
+            raise _lib.EmbnetError(f"{who}: gallery labels without a gallery")
+        x, xl = q, ql
+    else:
+        if x_labels is None:
+            raise _lib.EmbnetError(f"{who}: a gallery needs its labels")
+        x = _prep(x.detach())
+        xl = x_labels.to(torch.int32).contiguous()
+    if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
+        raise _lib.EmbnetError(f"{who}: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
+    nq, e = q.shape
+    n = x.shape[0]
+    if x.shape[1] != e:
+        raise _lib.EmbnetError(f"{who}: widths differ ({e} vs {x.shape[1]})")
+    if tuple(ql.shape) != (nq,) or tuple(xl.shape) != (n,):
+        raise _lib.EmbnetError(f"{who}: one label per row is needed")
+    return q, ql, x, xl, self_exclude, nq, n, e
+
+
 def retrieval_first_positive(q, q_labels, x=None, x_labels=None):
     """Rank of each query's nearest same-class gallery item, without the [nq,n] distance matrix (include/embnet.h).
 
     q [nq,e], q_labels [nq] (integers); x [n,e], x_labels [n] the gallery.  x is None: leave-one-out on q (column i is skipped
     for query i).  -> (rank int32 [nq]: 1 + negatives in front of the first positive in (d2, index) order, 0 without a positive;
     pos_index int32 [nq]: its gallery index or -1; pos_d2 float32 [nq]: its squared distance or +inf), on the device."""
-    q = _prep(q.detach())
-    ql = q_labels.to(torch.int32).contiguous()
-    self_exclude = x is None
-    if self_exclude:
-        if x_labels is not None:
-            raise _lib.EmbnetError("retrieval_first_positive: gallery labels without a gallery")
-        x, xl = q, ql
-    else:
-        if x_labels is None:
-            raise _lib.EmbnetError("retrieval_first_positive: a gallery needs its labels")
-        x = _prep(x.detach())
-        xl = x_labels.to(torch.int32).contiguous()
-    if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
-        raise _lib.EmbnetError(f"retrieval_first_positive: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
-    nq, e = q.shape
-    n = x.shape[0]
-    if x.shape[1] != e:
-        raise _lib.EmbnetError(f"retrieval_first_positive: widths differ ({e} vs {x.shape[1]})")
-    if tuple(ql.shape) != (nq,) or tuple(xl.shape) != (n,):
-        raise _lib.EmbnetError("retrieval_first_positive: one label per row is needed")
+    q, ql, x, xl, self_exclude, nq, n, e = _retrieval_blocks("retrieval_first_positive", q, q_labels, x, x_labels)
     lib = _lib.lib()
     ws = _new((max(lib.embnet_retrieval_workspace_bytes(nq, n) // 8, 1),), q, torch.float64)
     rank, pos = _new((nq,), q, torch.int32), _new((nq,), q, torch.int32)
@@ -505,26 +512,7 @@ def retrieval_positive_ranks(q, q_labels, x=None, x_labels=None, num_classes=Non
     (with `capacity` given the two arrays keep that length): query r's positives are offset[r]:offset[r+1], in the order
     (d2, gallery index); pos_rank = 1-based position among all non-excluded gallery items, so pos_rank[offset[r]] is
     retrieval_first_positive's rank.  A condition the device finds in the labels raises EmbnetError naming it."""
-    q = _prep(q.detach())
-    ql = q_labels.to(torch.int32).contiguous()
-    self_exclude = x is None
-    if self_exclude:
-        if x_labels is not None:
-            raise _lib.EmbnetError("retrieval_positive_ranks: gallery labels without a gallery")
-        x, xl = q, ql
-    else:
-        if x_labels is None:
-            raise _lib.EmbnetError("retrieval_positive_ranks: a gallery needs its labels")
-        x = _prep(x.detach())
-        xl = x_labels.to(torch.int32).contiguous()
-    if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
-        raise _lib.EmbnetError(f"retrieval_positive_ranks: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
-    nq, e = q.shape
-    n = x.shape[0]
-    if x.shape[1] != e:
-        raise _lib.EmbnetError(f"retrieval_positive_ranks: widths differ ({e} vs {x.shape[1]})")
-    if tuple(ql.shape) != (nq,) or tuple(xl.shape) != (n,):
-        raise _lib.EmbnetError("retrieval_positive_ranks: one label per row is needed")
+    q, ql, x, xl, self_exclude, nq, n, e = _retrieval_blocks("retrieval_positive_ranks", q, q_labels, x, x_labels)
     if num_classes is None:
         num_classes = int(torch.maximum(ql.max(), xl.max()).item()) + 1
     num_classes = int(num_classes)

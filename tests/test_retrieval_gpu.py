@@ -68,7 +68,12 @@ def _integer_case(rs, nq, n, e, self_exclude):
     return q, ql, x, xl
 
 
-EXACT_SHAPES = [(1, 5, 0), (3, 7, 0), (65, 130, 0), (130, 257, 0), (257, 1000, 0), (2, 2, 1), (64, 64, 1), (65, 65, 1), (1000, 1000, 1)]
+# The last three reach the walk shapes that the smaller ones do not (retrieval_plan in csrc/retrieval.hip): 1500 leave-one-out
+# is 24 x 24 tiles of 64 with two gallery tiles per workgroup and a ragged last tile; 4000 leave-one-out takes the 128-row
+# tiles, 32 x 32 of them in 16 splits of two, the own column excluded across tiles; 300 x 16400 is 3 x 129 tiles of 128, one
+# tile per split, ragged in both dimensions.
+EXACT_SHAPES = [(1, 5, 0), (3, 7, 0), (65, 130, 0), (130, 257, 0), (257, 1000, 0), (2, 2, 1), (64, 64, 1), (65, 65, 1), (1000, 1000, 1),
+                (1500, 1500, 1), (4000, 4000, 1), (300, 16400, 0)]
 
 
 @pytest.mark.parametrize("e", [5, 33, 64])

@@ -132,9 +132,10 @@ def _integer_case(rs, nq, n, e, self_exclude, forced):
     return q, ql, x, xl, num_classes
 
 
-# test_retrieval_gpu.py's EXACT_SHAPES, the last of each mode with n raised to hold the forced class sizes
+# test_retrieval_gpu.py's EXACT_SHAPES, the last small one of each mode with n raised to hold the forced class sizes; the last
+# two are its 128-row-tile shapes (two gallery tiles per workgroup; one tile per split, ragged in both dimensions)
 EXACT_SHAPES = [(1, 5, 0, 0), (3, 7, 0, 0), (65, 130, 0, 0), (130, 257, 0, 0), (257, 1500, 0, 1), (2, 2, 1, 0), (64, 64, 1, 0),
-                (65, 65, 1, 0), (1500, 1500, 1, 1)]
+                (65, 65, 1, 0), (1500, 1500, 1, 1), (4000, 4000, 1, 0), (300, 16400, 0, 0)]
 
 
 @pytest.mark.parametrize("e", [5, 33, 64])
