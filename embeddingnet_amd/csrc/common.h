@@ -106,6 +106,27 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// Maximum / sum over a 256-thread workgroup (every thread calls): the four waves' results through one LDS array, combined in a
+// fixed order (the sum left to right).  The result is thread 0's; block_max256<true> hands it to every thread.  The array
+// belongs to the function, not to the call: a kernel that calls one of them twice puts a __syncthreads() between the calls.
+template <bool ALL = false>
+__device__ __forceinline__ float block_max256(float v) {
+  __shared__ float wave_m[4];
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) wave_m[(threadIdx.x >> 6) & 3] = v;
+  __syncthreads();
+  if (ALL || threadIdx.x == 0) v = fmaxf(fmaxf(wave_m[0], wave_m[1]), fmaxf(wave_m[2], wave_m[3]));
+  return v;
+}
+template <class T>   // float or double
+__device__ __forceinline__ T block_sum256(T v) {
+  __shared__ T wave_s[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) wave_s[(threadIdx.x >> 6) & 3] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) v = wave_s[0] + wave_s[1] + wave_s[2] + wave_s[3];
+  return v;
+}
 
 // Range emission (conv.hip "Ranges"): the workgroup's max |value| joins a range word — the bit pattern of a non-negative float
 // under an unsigned maximum, independent of the order, so reproducible.  One atomic per workgroup (256 threads, every thread
@@ -115,12 +136,8 @@ __device__ __forceinline__ float wave_max(float v) {
 // in front) and a one-workgroup kernel folds them into word 0, which is what the consumers read.
 constexpr int RANGE_PARTIALS = 1024;
 __device__ __forceinline__ void range_emit_block(uint32_t* word, float amax) {
-  __shared__ float range_wm[4];
-  amax = wave_max(amax);
-  if ((threadIdx.x & 63) == 0) range_wm[(threadIdx.x >> 6) & 3] = amax;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    atomicMax(word, __float_as_uint(fmaxf(fmaxf(range_wm[0], range_wm[1]), fmaxf(range_wm[2], range_wm[3]))));
+  amax = block_max256(amax);
+  if (threadIdx.x == 0) atomicMax(word, __float_as_uint(amax));
 }
 __device__ __forceinline__ float amax4(float m, float4 v) {
   return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));

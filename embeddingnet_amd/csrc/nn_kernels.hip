@@ -11,6 +11,59 @@
 
 namespace embnet {
 
+// ---------------------------------------------------------------- channel quads
+// Four consecutive channels of an NHWC tensor per thread, 16 bytes per load: the arithmetic every four-channel kernel below
+// applies lane by lane is written once here.  (__forceinline__: each call compiles to the four scalar expressions it replaces.)
+__device__ __forceinline__ float4 ld4(const float* p, long i) { return reinterpret_cast<const float4*>(p)[i]; }
+__device__ __forceinline__ void st4(float* p, long i, float4 v) { reinterpret_cast<float4*>(p)[i] = v; }
+__device__ __forceinline__ void add4(float4& a, float4 v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+__device__ __forceinline__ float4 affine4(float4 v, float4 sc, float4 sh) {
+  return make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
+}
+__device__ __forceinline__ float4 act_apply4(int act, float4 v) {
+  return make_float4(act_apply(act, v.x), act_apply(act, v.y), act_apply(act, v.z), act_apply(act, v.w));
+}
+// dz = dy * act'(xv * sc + sh): the gradient of the activation behind a BatchNorm affine, z recomputed from the layer's input
+__device__ __forceinline__ float4 act_grad4(int act, float4 xv, float4 sc, float4 sh, float4 dz) {
+  return make_float4(act_grad(act, fmaf(xv.x, sc.x, sh.x), dz.x), act_grad(act, fmaf(xv.y, sc.y, sh.y), dz.y),
+                     act_grad(act, fmaf(xv.z, sc.z, sh.z), dz.z), act_grad(act, fmaf(xv.w, sc.w, sh.w), dz.w));
+}
+__device__ __forceinline__ float4 relu_mask4(float4 x, float4 v) {   // v where x > 0 (x: a ReLU's output)
+  return make_float4(x.x > 0.f ? v.x : 0.f, x.y > 0.f ? v.y : 0.f, x.z > 0.f ? v.z : 0.f, x.w > 0.f ? v.w : 0.f);
+}
+
+// The per-channel constants of a BatchNorm backward pass for channel quad q.  Frozen statistics (training == 0) use scale and
+// shift alone; a reduction, which has no dbeta / dgamma yet, asks for bn_consts<false> and passes NULL for them.
+struct BnConsts { float4 sc, sh, mu, rs, db, dg; };
+template <bool SUMS = true>
+__device__ __forceinline__ BnConsts bn_consts(int q, const float* scale, const float* shift, const float* mean, const float* rstd,
+                                              const float* dbeta, const float* dgamma, int training) {
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  BnConsts k{ld4(scale, q), ld4(shift, q), z4, z4, z4, z4};
+  if (training) {
+    k.mu = ld4(mean, q); k.rs = ld4(rstd, q);
+    if (SUMS) { k.db = ld4(dbeta, q); k.dg = ld4(dgamma, q); }
+  }
+  return k;
+}
+// dx = scale (dz - dbeta / m - xhat dgamma / m); frozen statistics: the plain affine's scale dz
+__device__ __forceinline__ float4 bn_dx4(float4 dz, float4 xv, const BnConsts& k, float inv_m, int training) {
+  const float4 sc = k.sc, mu = k.mu, rs = k.rs, db = k.db, dg = k.dg;
+  if (!training) return make_float4(sc.x * dz.x, sc.y * dz.y, sc.z * dz.z, sc.w * dz.w);
+  float4 o;
+  o.x = sc.x * (dz.x - db.x * inv_m - (xv.x - mu.x) * rs.x * dg.x * inv_m);
+  o.y = sc.y * (dz.y - db.y * inv_m - (xv.y - mu.y) * rs.y * dg.y * inv_m);
+  o.z = sc.z * (dz.z - db.z * inv_m - (xv.z - mu.z) * rs.z * dg.z * inv_m);
+  o.w = sc.w * (dz.w - db.w * inv_m - (xv.w - mu.w) * rs.w * dg.w * inv_m);
+  return o;
+}
+// the two sums of a BatchNorm backward: a += dz (dbeta), b += dz xhat (dgamma; one fma per lane)
+__device__ __forceinline__ void bn_sums4(float4& a, float4& b, float4 dz, float4 xv, float4 mu, float4 rs) {
+  add4(a, dz);
+  b.x = fmaf(dz.x, (xv.x - mu.x) * rs.x, b.x); b.y = fmaf(dz.y, (xv.y - mu.y) * rs.y, b.y);
+  b.z = fmaf(dz.z, (xv.z - mu.z) * rs.z, b.z); b.w = fmaf(dz.w, (xv.w - mu.w) * rs.w, b.w);
+}
+
 // Inverted dropout riding on another pass (the BatchNormalization in front of a Dropout layer, simple2's bn3 / bn6,
 // /root/reference/embedding_net/backbones.py:55,66): the mask of embnet_dropout — keep element i iff
 // rng_u32(seed, i, 1) >= thr — applied to the value in registers; thr == 0 switches it off.
@@ -20,6 +73,7 @@ static DropArg drop_arg(float rate, uint64_t seed, const uint64_t* seed_add) {
   if (rate > 0.f) { d.thr = (uint32_t)((double)rate * 4294967296.0); d.keep_scale = 1.f / (1.f - rate); }
   return d;
 }
+static DropArg no_drop() { return drop_arg(0.f, 0, nullptr); }
 __device__ __forceinline__ uint64_t drop_seed(const DropArg& d) { return d.seed + (d.seed_add ? *d.seed_add : 0ull); }
 __device__ __forceinline__ float4 drop4(const DropArg& d, uint64_t seed, long i4, float4 v) {   // elements 4*i4 .. 4*i4+3
   const uint64_t e = (uint64_t)i4 * 4;
@@ -89,12 +143,10 @@ __device__ __forceinline__ void block_partial_sums(const float* __restrict__ par
     const float* p2 = p1 + (long)c * blocks;
     if ((blocks & 3) == 0 && ((reinterpret_cast<uintptr_t>(partial) & 15) == 0)) {
       // thousands of row-band partials per channel on the early layers (56x56: 6272): 16-byte loads, four in flight
-      const float4* q1 = reinterpret_cast<const float4*>(p1);
-      const float4* q2 = reinterpret_cast<const float4*>(p2);
       const int nb4 = blocks >> 2;
 #pragma unroll 4
       for (int b = threadIdx.x; b < nb4; b += 256) {
-        const float4 u = q1[b], v = q2[b];
+        const float4 u = ld4(p1, b), v = ld4(p2, b);
         s += ((double)u.x + (double)u.y) + ((double)u.z + (double)u.w);
         ss += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
         qm = fmaxf(fmaxf(qm, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
@@ -134,13 +186,9 @@ __device__ __forceinline__ float channel_bound(float sc, float sh, float q_max) 
 }
 // max of bound[0 .. c) for every thread of a 256-thread workgroup (all threads call)
 __device__ __forceinline__ float tensor_bound(const float* __restrict__ bound, int c) {
-  __shared__ float tb_w[4];
   float m = 0.f;
   for (int i = threadIdx.x; i < c; i += 256) m = fmaxf(m, bound[i]);
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) tb_w[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return fmaxf(fmaxf(tb_w[0], tb_w[1]), fmaxf(tb_w[2], tb_w[3]));
+  return block_max256<true>(m);
 }
 
 // ---------------------------------------------------------------- BatchNorm
@@ -158,10 +206,10 @@ struct NoPrep { __device__ __forceinline__ int operator()(int) const { return 0;
 // F(row, quad, const K& k, float4& a, float4& b) with k = prep(quad): the per-channel constants of a column are fetched ONCE
 // per thread and column block, not once per row (bn_bwd_reduce4 issued four 16-byte constant loads beside the two data
 // loads of every element: 3.9 TB/s where the apply pass, two constant loads per element, reached 5.3)
-template <class P, class F, bool MAX3 = false>
+// MAX3: F takes a third accumulator `float4& mx`, a running per-element MAXIMUM (>= 0); the block's maxima go to pmax[block][c]
+template <bool MAX3 = false, class P, class F>
 __device__ __forceinline__ void col_reduce2_v4p(long m, int c4, ColGeom g, float* __restrict__ partial, P prep, F f,
                                                 float* __restrict__ pmax = nullptr) {
-  // MAX3: F takes a third accumulator, a running per-element MAXIMUM (>= 0); the block's maxima go to pmax[block][c]
   __shared__ float4 sh4[MAX3 ? 3 : 2][256];
   const int ci = threadIdx.x % g.cl, ri = threadIdx.x / g.cl;
   const long r0 = (long)blockIdx.x * g.rows_per_block;
@@ -208,16 +256,15 @@ __device__ __forceinline__ void col_reduce2_v4p(long m, int c4, ColGeom g, float
       if constexpr (MAX3) mx = sh4[2][ci];
       for (int k = 1; k < groups; ++k) {
         const float4 oa = sh4[0][k * g.cl + ci], ob = sh4[1][k * g.cl + ci];
-        a.x += oa.x; a.y += oa.y; a.z += oa.z; a.w += oa.w;
-        b.x += ob.x; b.y += ob.y; b.z += ob.z; b.w += ob.w;
+        add4(a, oa); add4(b, ob);
         if constexpr (MAX3) {
           const float4 om = sh4[2][k * g.cl + ci];
           mx.x = fmaxf(mx.x, om.x); mx.y = fmaxf(mx.y, om.y); mx.z = fmaxf(mx.z, om.z); mx.w = fmaxf(mx.w, om.w);
         }
       }
-      reinterpret_cast<float4*>(partial + ((long)blockIdx.x * 2 + 0) * c4 * 4)[q] = a;
-      reinterpret_cast<float4*>(partial + ((long)blockIdx.x * 2 + 1) * c4 * 4)[q] = b;
-      if constexpr (MAX3) reinterpret_cast<float4*>(pmax + (long)blockIdx.x * c4 * 4)[q] = mx;
+      st4(partial + ((long)blockIdx.x * 2 + 0) * c4 * 4, q, a);
+      st4(partial + ((long)blockIdx.x * 2 + 1) * c4 * 4, q, b);
+      if constexpr (MAX3) st4(pmax + (long)blockIdx.x * c4 * 4, q, mx);
     }
     __syncthreads();
   }
@@ -230,8 +277,8 @@ __device__ __forceinline__ void col_reduce2_v4(long m, int c4, ColGeom g, float*
 __global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict__ x, long m, int c4, ColGeom g,
                                                         float* __restrict__ partial) {
   col_reduce2_v4(m, c4, g, partial, [&](long r, int q, float4& a, float4& b) {
-    const float4 v = reinterpret_cast<const float4*>(x)[r * c4 + q];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    const float4 v = ld4(x, r * c4 + q);
+    add4(a, v);
     b.x = fmaf(v.x, v.x, b.x); b.y = fmaf(v.y, v.y, b.y); b.z = fmaf(v.z, v.z, b.z); b.w = fmaf(v.w, v.w, b.w);
   });
 }
@@ -242,31 +289,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
                                                              const float* __restrict__ rstd, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, int relu,
                                                              float* __restrict__ partial, const DropArg drop, float* __restrict__ pmax) {
-  struct K4 { float4 sc, sh, mu, rs; };
   const uint64_t dseed = drop.thr ? drop_seed(drop) : 0ull;
-  auto prep = [&](int q) {
-    return K4{reinterpret_cast<const float4*>(scale)[q], reinterpret_cast<const float4*>(shift)[q],
-              reinterpret_cast<const float4*>(mean)[q], reinterpret_cast<const float4*>(rstd)[q]};
-  };
-  auto body = [&](long r, int q, const K4& k, float4& a, float4& b, float4& mx) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[r * c4 + q];
-    float4 dz = reinterpret_cast<const float4*>(dy)[r * c4 + q];
+  auto prep = [&](int q) { return bn_consts<false>(q, scale, shift, mean, rstd, nullptr, nullptr, 1); };
+  auto body = [&](long r, int q, const BnConsts& k, float4& a, float4& b, float4& mx) {
+    const float4 xv = ld4(x, r * c4 + q);
+    float4 dz = ld4(dy, r * c4 + q);
     if (drop.thr) dz = drop4(drop, dseed, r * c4 + q, dz);   // dy of the Dropout behind this layer -> dy of the layer
-    const float4 sc = k.sc, sh = k.sh, mu = k.mu, rs = k.rs;
-    if (relu) {
-      dz.x = act_grad(relu, fmaf(xv.x, sc.x, sh.x), dz.x); dz.y = act_grad(relu, fmaf(xv.y, sc.y, sh.y), dz.y);
-      dz.z = act_grad(relu, fmaf(xv.z, sc.z, sh.z), dz.z); dz.w = act_grad(relu, fmaf(xv.w, sc.w, sh.w), dz.w);
-    }
-    a.x += dz.x; a.y += dz.y; a.z += dz.z; a.w += dz.w;
-    b.x = fmaf(dz.x, (xv.x - mu.x) * rs.x, b.x); b.y = fmaf(dz.y, (xv.y - mu.y) * rs.y, b.y);
-    b.z = fmaf(dz.z, (xv.z - mu.z) * rs.z, b.z); b.w = fmaf(dz.w, (xv.w - mu.w) * rs.w, b.w);
+    if (relu) dz = act_grad4(relu, xv, k.sc, k.sh, dz);
+    bn_sums4(a, b, dz, xv, k.mu, k.rs);
     mx.x = fmaxf(mx.x, fabsf(dz.x)); mx.y = fmaxf(mx.y, fabsf(dz.y)); mx.z = fmaxf(mx.z, fabsf(dz.z)); mx.w = fmaxf(mx.w, fabsf(dz.w));
   };
-  if (pmax) col_reduce2_v4p<decltype(prep), decltype(body), true>(m, c4, g, partial, prep, body, pmax);
-  else {
-    auto body2 = [&](long r, int q, const K4& k, float4& a, float4& b) { float4 mx = make_float4(0.f, 0.f, 0.f, 0.f); body(r, q, k, a, b, mx); };
-    col_reduce2_v4p(m, c4, g, partial, prep, body2);
-  }
+  if (pmax) col_reduce2_v4p<true>(m, c4, g, partial, prep, body, pmax);
+  else col_reduce2_v4p(m, c4, g, partial, prep, [&](long r, int q, const BnConsts& k, float4& a, float4& b) {
+    float4 mx = make_float4(0.f, 0.f, 0.f, 0.f); body(r, q, k, a, b, mx);      // (the maximum compiles away)
+  });
 }
 
 // MODE 0: as described.  MODE 1: dx_planes in the two-piece fp16 format, scaled by the s the slot holds.  MODE 2: the dry run in front
@@ -276,29 +312,23 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
 // MODE 4: MODE 1 without the dry run: the planes' scale from `dx_bound` [c] (bn_bwd_finalize_kernel's dx_channel_bound), + the range of
 // dx_add (`add_range`: the bound of the identity shortcut's gradient) where one is added; workgroup 0 leaves (s, 1 / s) in the planes'
 // slot and — range_slot != NULL — the bound in the range slot of the fp32 dx.
-template <int MODE = 0>
-__global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                            long total4, int c4, float inv_m, const float* __restrict__ mean,
-                                                            const float* __restrict__ rstd, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, const float* __restrict__ dbeta,
-                                                            const float* __restrict__ dgamma, int relu, int training,
-                                                            const float* __restrict__ dx_add, float* __restrict__ dx,
-                                                            unsigned short* __restrict__ dx_planes, uint32_t* __restrict__ range_slot = nullptr,
-                                                            const float* __restrict__ dx_bound = nullptr, const uint32_t* __restrict__ add_range = nullptr) {
+// dz_of(i) hands in the gradient of the layer's OUTPUT for channel quad i of the tensor: the loop below is the one apply body
+// under bn_bwd_apply4_kernel (dz = dy) and bn_bwd_apply4_gap_kernel (dz = dy * gate + dpool / hw).
+template <int MODE, class DZ>
+__device__ __forceinline__ void bn_bwd_apply4_body(DZ dz_of, const float* __restrict__ x, long total4, int c4, float inv_m,
+                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                   const float* __restrict__ scale, const float* __restrict__ shift,
+                                                   const float* __restrict__ dbeta, const float* __restrict__ dgamma, int relu,
+                                                   int training, const float* __restrict__ dx_add, float* __restrict__ dx,
+                                                   unsigned short* __restrict__ dx_planes, uint32_t* __restrict__ range_slot,
+                                                   const float* __restrict__ dx_bound, const uint32_t* __restrict__ add_range) {
   const long stride = (long)gridDim.x * 256;
   // (the launcher makes the stride a multiple of c4 whenever c4 divides a power of two, so a thread keeps its channel
   // quad and the six per-channel constants are loaded once; otherwise they are re-read per element)
   const bool fixed = stride % c4 == 0;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 sc = z4, sh = z4, mu = z4, rs = z4, db = z4, dg = z4;
-  auto consts = [&](int q) {
-    sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
-    if (training) {
-      mu = reinterpret_cast<const float4*>(mean)[q]; rs = reinterpret_cast<const float4*>(rstd)[q];
-      db = reinterpret_cast<const float4*>(dbeta)[q]; dg = reinterpret_cast<const float4*>(dgamma)[q];
-    }
-  };
-  if (fixed) consts((int)(((long)blockIdx.x * 256 + threadIdx.x) % c4));
+  BnConsts k{z4, z4, z4, z4, z4, z4};
+  if (fixed) k = bn_consts((int)(((long)blockIdx.x * 256 + threadIdx.x) % c4), scale, shift, mean, rstd, dbeta, dgamma, training);
   float amax = 0.f;
   float pscale = MODE == 1 ? planes_scale_slot(dx_planes, total4 * 4)[0] : 1.f;
   if (MODE == 4) {
@@ -312,29 +342,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
     }
   }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
-    if (!fixed) consts((int)(i % c4));
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    float4 dz = reinterpret_cast<const float4*>(dy)[i];
-    if (relu) {
-      dz.x = act_grad(relu, fmaf(xv.x, sc.x, sh.x), dz.x); dz.y = act_grad(relu, fmaf(xv.y, sc.y, sh.y), dz.y);
-      dz.z = act_grad(relu, fmaf(xv.z, sc.z, sh.z), dz.z); dz.w = act_grad(relu, fmaf(xv.w, sc.w, sh.w), dz.w);
-    }
-    float4 o;
-    if (training) {
-      o.x = sc.x * (dz.x - db.x * inv_m - (xv.x - mu.x) * rs.x * dg.x * inv_m);
-      o.y = sc.y * (dz.y - db.y * inv_m - (xv.y - mu.y) * rs.y * dg.y * inv_m);
-      o.z = sc.z * (dz.z - db.z * inv_m - (xv.z - mu.z) * rs.z * dg.z * inv_m);
-      o.w = sc.w * (dz.w - db.w * inv_m - (xv.w - mu.w) * rs.w * dg.w * inv_m);
-    } else {
-      o = make_float4(sc.x * dz.x, sc.y * dz.y, sc.z * dz.z, sc.w * dz.w);
-    }
-    if (dx_add) {                                        // gradient of the tensor's other consumer (identity shortcut)
-      const float4 a = reinterpret_cast<const float4*>(dx_add)[i];
-      o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-    }
+    if (!fixed) k = bn_consts((int)(i % c4), scale, shift, mean, rstd, dbeta, dgamma, training);
+    const float4 xv = ld4(x, i);
+    float4 dz = dz_of(i);
+    if (relu) dz = act_grad4(relu, xv, k.sc, k.sh, dz);
+    float4 o = bn_dx4(dz, xv, k, inv_m, training);
+    if (dx_add) add4(o, ld4(dx_add, i));                 // gradient of the tensor's other consumer (identity shortcut)
     if (MODE == 2) { amax = fmaxf(amax, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)))); continue; }
     if (MODE == 3) amax = amax4(amax, o);
-    if (dx) reinterpret_cast<float4*>(dx)[i] = o;        // (NULL: planes only — every consumer of dx reads the planes)
+    if (dx) st4(dx, i, o);                               // (NULL: planes only — every consumer of dx reads the planes)
     if (dx_planes) {                                     // the same values as bf16 pieces, chunk-major: dy operand of the
       const long pix = i / c4; const int q = (int)(i - pix * c4);      // patch data gradient of the convolution in front
       const long e = ((long)(q >> 2) * (total4 / c4) + pix) * 16 + 4 * (q & 3);
@@ -350,13 +366,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
     }
   }
   if (MODE == 2) {
-    amax = wave_max(amax);
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = amax;
-    __syncthreads();
-    if (threadIdx.x == 0) planes_scale_slot(dx_planes, total4 * 4)[2 + blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    amax = block_max256(amax);
+    if (threadIdx.x == 0) planes_scale_slot(dx_planes, total4 * 4)[2 + blockIdx.x] = amax;
   }
   if (MODE == 3) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, amax);
+}
+template <int MODE = 0>
+__global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                            long total4, int c4, float inv_m, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, const float* __restrict__ dbeta,
+                                                            const float* __restrict__ dgamma, int relu, int training,
+                                                            const float* __restrict__ dx_add, float* __restrict__ dx,
+                                                            unsigned short* __restrict__ dx_planes, uint32_t* __restrict__ range_slot = nullptr,
+                                                            const float* __restrict__ dx_bound = nullptr, const uint32_t* __restrict__ add_range = nullptr) {
+  bn_bwd_apply4_body<MODE>([&](long i) { return ld4(dy, i); }, x, total4, c4, inv_m, mean, rstd, scale, shift, dbeta, dgamma, relu,
+                           training, dx_add, dx, dx_planes, range_slot, dx_bound, add_range);
 }
 
 // (s, 1 / s) of a planes tensor from the workgroup maxima a dry run left behind its slot: the largest |value| lands in [2^14, 2^15)
@@ -364,12 +389,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
 __global__ __launch_bounds__(256) void planes_scale_kernel(float* __restrict__ slot, int blocks, uint32_t* __restrict__ range_out = nullptr) {
   float m = 0.f;
   for (int i = threadIdx.x; i < blocks; i += 256) m = fmaxf(m, slot[2 + i]);
-  m = wave_max(m);
-  __shared__ float wm[4];
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
+  m = block_max256(m);
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
     const float2 sp = scale_pair(scale_exponent_of(m));    // (zero, infinite or NaN: s = 1)
     slot[0] = sp.x; slot[1] = sp.y;
     if (range_out) *range_out = __float_as_uint(m);
@@ -379,8 +400,9 @@ __global__ __launch_bounds__(256) void planes_scale_kernel(float* __restrict__ s
 // BatchNorm backward of a layer whose output is also POOLED (squeeze-and-excite: layers._BNGapFn): the gradient is
 //   dy_total[n,p,c] = dy[n,p,c] + dpool[n,c] / hw
 // (embnet_gap_bwd's broadcast-add pass, 12 B per element on EfficientNet's 6C-wide tensors).  Here both BatchNorm passes form
-// it while they read dy — dpool[n, quad] is a 16-byte L1-resident load — with embnet_gap_bwd's two roundings (the two-launch chain's result to the
-// last bits), and the broadcast tensor is never written.
+// it while they read dy — dpool[n, quad] is a 16-byte L1-resident load — and the broadcast tensor is never written.  (__fmul_rn / __fadd_rn are
+// plain * and + to the compiler: add_pool4 contracts into one fma, so the result is the ONE-rounding sum; embnet_gap_bwd's two-launch
+// chain rounds twice and differs in the last bit — tests/test_bn_backward_forms_gpu.py.)
 struct DivU { uint32_t mul, shift; };                     // n / d for 0 <= n < 2^31 (conv_geom.h FastDiv)
 static DivU make_divu(uint32_t d) {
   uint32_t sft = 0; while ((1ull << sft) < d) ++sft;
@@ -395,7 +417,7 @@ __device__ __forceinline__ float4 add_pool4(float4 dy, float4 g, float inv) {
 // backward multiply (embnet_channel_scale_bwd's dx, one rounding) is applied here instead of being written and read back
 __device__ __forceinline__ float4 gate4(float4 dy, const float* __restrict__ gate, long idx) {
   if (!gate) return dy;
-  const float4 s = reinterpret_cast<const float4*>(gate)[idx];
+  const float4 s = ld4(gate, idx);
   return make_float4(__fmul_rn(dy.x, s.x), __fmul_rn(dy.y, s.y), __fmul_rn(dy.z, s.z), __fmul_rn(dy.w, s.w));
 }
 
@@ -405,23 +427,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_gap_kernel(const float* __
                                                                  const float* __restrict__ rstd, const float* __restrict__ scale,
                                                                  const float* __restrict__ shift, int relu,
                                                                  float* __restrict__ partial) {
-  struct K4 { float4 sc, sh, mu, rs; };
-  col_reduce2_v4p(m, c4, g, partial, [&](int q) {
-    return K4{reinterpret_cast<const float4*>(scale)[q], reinterpret_cast<const float4*>(shift)[q],
-              reinterpret_cast<const float4*>(mean)[q], reinterpret_cast<const float4*>(rstd)[q]};
-  }, [&](long r, int q, const K4& k, float4& a, float4& b) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[r * c4 + q];
+  col_reduce2_v4p(m, c4, g, partial, [&](int q) { return bn_consts<false>(q, scale, shift, mean, rstd, nullptr, nullptr, 1); },
+                  [&](long r, int q, const BnConsts& k, float4& a, float4& b) {
+    const float4 xv = ld4(x, r * c4 + q);
     const long nq = (long)divu((uint32_t)r, dhw) * c4 + q;
-    const float4 gp = reinterpret_cast<const float4*>(dpool)[nq];
-    float4 dz = add_pool4(gate4(reinterpret_cast<const float4*>(dy)[r * c4 + q], gate, nq), gp, inv_hw);
-    const float4 sc = k.sc, sh = k.sh, mu = k.mu, rs = k.rs;
-    if (relu) {
-      dz.x = act_grad(relu, fmaf(xv.x, sc.x, sh.x), dz.x); dz.y = act_grad(relu, fmaf(xv.y, sc.y, sh.y), dz.y);
-      dz.z = act_grad(relu, fmaf(xv.z, sc.z, sh.z), dz.z); dz.w = act_grad(relu, fmaf(xv.w, sc.w, sh.w), dz.w);
-    }
-    a.x += dz.x; a.y += dz.y; a.z += dz.z; a.w += dz.w;
-    b.x = fmaf(dz.x, (xv.x - mu.x) * rs.x, b.x); b.y = fmaf(dz.y, (xv.y - mu.y) * rs.y, b.y);
-    b.z = fmaf(dz.z, (xv.z - mu.z) * rs.z, b.z); b.w = fmaf(dz.w, (xv.w - mu.w) * rs.w, b.w);
+    const float4 gp = ld4(dpool, nq);
+    float4 dz = add_pool4(gate4(ld4(dy, r * c4 + q), gate, nq), gp, inv_hw);
+    if (relu) dz = act_grad4(relu, xv, k.sc, k.sh, dz);
+    bn_sums4(a, b, dz, xv, k.mu, k.rs);
   });
 }
 
@@ -431,34 +444,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_gap_kernel(const float* __r
                                                                 const float* __restrict__ rstd, const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, const float* __restrict__ dbeta,
                                                                 const float* __restrict__ dgamma, int relu, float* __restrict__ dx) {
-  const long stride = (long)gridDim.x * 256;
-  const bool fixed = stride % c4 == 0;                   // (as bn_bwd_apply4_kernel: the thread keeps its channel quad)
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 sc = z4, sh = z4, mu = z4, rs = z4, db = z4, dg = z4;
-  auto consts = [&](int q) {
-    sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
-    mu = reinterpret_cast<const float4*>(mean)[q]; rs = reinterpret_cast<const float4*>(rstd)[q];
-    db = reinterpret_cast<const float4*>(dbeta)[q]; dg = reinterpret_cast<const float4*>(dgamma)[q];
-  };
-  if (fixed) consts((int)(((long)blockIdx.x * 256 + threadIdx.x) % c4));
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
-    const int q = (int)(i % c4);
-    if (!fixed) consts(q);
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const long nq = (long)divu((uint32_t)i, dhwc4) * c4 + q;
-    const float4 gp = reinterpret_cast<const float4*>(dpool)[nq];
-    float4 dz = add_pool4(gate4(reinterpret_cast<const float4*>(dy)[i], gate, nq), gp, inv_hw);
-    if (relu) {
-      dz.x = act_grad(relu, fmaf(xv.x, sc.x, sh.x), dz.x); dz.y = act_grad(relu, fmaf(xv.y, sc.y, sh.y), dz.y);
-      dz.z = act_grad(relu, fmaf(xv.z, sc.z, sh.z), dz.z); dz.w = act_grad(relu, fmaf(xv.w, sc.w, sh.w), dz.w);
-    }
-    float4 o;
-    o.x = sc.x * (dz.x - db.x * inv_m - (xv.x - mu.x) * rs.x * dg.x * inv_m);
-    o.y = sc.y * (dz.y - db.y * inv_m - (xv.y - mu.y) * rs.y * dg.y * inv_m);
-    o.z = sc.z * (dz.z - db.z * inv_m - (xv.z - mu.z) * rs.z * dg.z * inv_m);
-    o.w = sc.w * (dz.w - db.w * inv_m - (xv.w - mu.w) * rs.w * dg.w * inv_m);
-    reinterpret_cast<float4*>(dx)[i] = o;
-  }
+  bn_bwd_apply4_body<0>([&](long i) {
+    const long nq = (long)divu((uint32_t)i, dhwc4) * c4 + (int)(i % c4);
+    const float4 gp = ld4(dpool, nq);
+    return add_pool4(gate4(ld4(dy, i), gate, nq), gp, inv_hw);
+  }, x, total4, c4, inv_m, mean, rstd, scale, shift, dbeta, dgamma, relu, 1, nullptr, dx, nullptr, nullptr, nullptr, nullptr);
 }
 
 // Per-(image, channel) sums over the pixels of an NHWC tensor (the squeeze-and-excite reductions): a workgroup = one image x
@@ -495,7 +485,7 @@ __device__ __forceinline__ void pixel_lane_sums(float4 (&v)[Q], int cls, F store
   if ((int)threadIdx.x < Q * cls) {
     const int q = threadIdx.x / cls;
     float4 a = sh[q][0][cl];
-    for (int w = 1; w < nw; ++w) { const float4 o = sh[q][w][cl]; a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w; }
+    for (int w = 1; w < nw; ++w) add4(a, sh[q][w][cl]);
     store(q, a);
   }
 }
@@ -518,10 +508,9 @@ __global__ __launch_bounds__(1024) void se_bn_sums4_kernel(const float* __restri
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 v[5] = {z4, z4, z4, z4, z4};                      // T0, S1 .. S4
   if (cq < c4) {
-    const float4 sc = reinterpret_cast<const float4*>(scale)[cq], sf = reinterpret_cast<const float4*>(shift)[cq];
-    const float4 mu = reinterpret_cast<const float4*>(mean)[cq], rs = reinterpret_cast<const float4*>(rstd)[cq];
-    const float4* dgi = reinterpret_cast<const float4*>(dg) + (long)n * hw * c4 + cq;
-    const float4* xi = reinterpret_cast<const float4*>(x) + (long)n * hw * c4 + cq;
+    const float4 sc = ld4(scale, cq), sf = ld4(shift, cq), mu = ld4(mean, cq), rs = ld4(rstd, cq);
+    const float* dgi = dg + 4 * ((long)n * hw * c4 + cq);  // this image and channel quad: pixel p is quad p * c4 behind
+    const float* xi = x + 4 * ((long)n * hw * c4 + cq);
     auto one = [&](float dgv, float xq, float scq, float sfq, float muq, float rsq, float& T0, float& S1, float& S2, float& S3, float& S4) {
       const float z = fmaf(xq, scq, sfq);
       float av, ad;                                        // act(z) and act'(z); swish from ONE sigmoid (exp + rcp are quarter rate)
@@ -540,10 +529,10 @@ __global__ __launch_bounds__(1024) void se_bn_sums4_kernel(const float* __restri
     };
     int p = pl;
     for (; p + npl < hw; p += 2 * npl) {                   // two pixels per trip: four 16-byte loads in flight per lane
-      const float4 d0 = dgi[(long)p * c4], x0 = xi[(long)p * c4], d1 = dgi[(long)(p + npl) * c4], x1 = xi[(long)(p + npl) * c4];
+      const float4 d0 = ld4(dgi, (long)p * c4), x0 = ld4(xi, (long)p * c4), d1 = ld4(dgi, (long)(p + npl) * c4), x1 = ld4(xi, (long)(p + npl) * c4);
       quad(d0, x0); quad(d1, x1);
     }
-    if (p < hw) quad(dgi[(long)p * c4], xi[(long)p * c4]);
+    if (p < hw) quad(ld4(dgi, (long)p * c4), ld4(xi, (long)p * c4));
   }
   pixel_lane_sums<5>(v, cls, [&](int q, const float4 a) {
     if (cq < c4) reinterpret_cast<float4*>(out)[((long)n * 5 + q) * c4 + cq] = a;
@@ -581,38 +570,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_inrelu4_kernel(const float* 
                                                                    int relu, int training, float* __restrict__ dz_out,
                                                                    float* __restrict__ partial, const DropArg drop,
                                                                    uint32_t* __restrict__ range_slot) {
-  struct K6 { float4 sc, sh, mu, rs, db, dg; };
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   const uint64_t dseed = drop.thr ? drop_seed(drop) : 0ull;
   float amax = 0.f;                                     // max |dz| of this thread's elements (range_slot: conv.hip Ranges)
-  col_reduce2_v4p(m, c4, g, partial, [&](int q) {
-    K6 k{reinterpret_cast<const float4*>(scale)[q], reinterpret_cast<const float4*>(shift)[q], z4, z4, z4, z4};
-    if (training) {
-      k.mu = reinterpret_cast<const float4*>(mean)[q]; k.rs = reinterpret_cast<const float4*>(rstd)[q];
-      k.db = reinterpret_cast<const float4*>(dbeta)[q]; k.dg = reinterpret_cast<const float4*>(dgamma)[q];
-    }
-    return k;
-  }, [&](long r, int q, const K6& k, float4& a, float4&) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[r * c4 + q];
-    float4 dz = reinterpret_cast<const float4*>(dy)[r * c4 + q];
+  col_reduce2_v4p(m, c4, g, partial, [&](int q) { return bn_consts(q, scale, shift, mean, rstd, dbeta, dgamma, training); },
+                  [&](long r, int q, const BnConsts& k, float4& a, float4&) {
+    const float4 xv = ld4(x, r * c4 + q);
+    float4 dz = ld4(dy, r * c4 + q);
     if (drop.thr) dz = drop4(drop, dseed, r * c4 + q, dz);
-    const float4 sc = k.sc, sh = k.sh, mu = k.mu, rs = k.rs, db = k.db, dg = k.dg;
-    if (relu) {
-      dz.x = act_grad(relu, fmaf(xv.x, sc.x, sh.x), dz.x); dz.y = act_grad(relu, fmaf(xv.y, sc.y, sh.y), dz.y);
-      dz.z = act_grad(relu, fmaf(xv.z, sc.z, sh.z), dz.z); dz.w = act_grad(relu, fmaf(xv.w, sc.w, sh.w), dz.w);
-    }
-    float4 o;
-    if (training) {                                      // (the arithmetic of bn_bwd_apply4_kernel, term for term)
-      o.x = sc.x * (dz.x - db.x * inv_m - (xv.x - mu.x) * rs.x * dg.x * inv_m);
-      o.y = sc.y * (dz.y - db.y * inv_m - (xv.y - mu.y) * rs.y * dg.y * inv_m);
-      o.z = sc.z * (dz.z - db.z * inv_m - (xv.z - mu.z) * rs.z * dg.z * inv_m);
-      o.w = sc.w * (dz.w - db.w * inv_m - (xv.w - mu.w) * rs.w * dg.w * inv_m);
-    } else {
-      o = make_float4(sc.x * dz.x, sc.y * dz.y, sc.z * dz.z, sc.w * dz.w);
-    }
-    o.x = xv.x > 0.f ? o.x : 0.f; o.y = xv.y > 0.f ? o.y : 0.f; o.z = xv.z > 0.f ? o.z : 0.f; o.w = xv.w > 0.f ? o.w : 0.f;
-    reinterpret_cast<float4*>(dz_out)[r * c4 + q] = o;
-    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+    if (relu) dz = act_grad4(relu, xv, k.sc, k.sh, dz);
+    const float4 o = relu_mask4(xv, bn_dx4(dz, xv, k, inv_m, training));
+    reinterpret_cast<float4*>(dz_out)[r * c4 + q] = o;    // (st4 here moves this kernel's register allocation: DESIGN 3.2)
+    add4(a, o);
     amax = amax4(amax, o);
   });
   if (range_slot) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, amax);
@@ -678,18 +646,17 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
     if (fixed) {
       const int q = (int)(((long)blockIdx.x * 256 + threadIdx.x) % c4);
-      sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
+      sc = ld4(scale, q); sh = ld4(shift, q);
     }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
       if (!fixed) {
         const int col = (int)((i * 4) % c);
-        sc = *reinterpret_cast<const float4*>(scale + col); sh = *reinterpret_cast<const float4*>(shift + col);
+        sc = ld4(scale + col, 0); sh = ld4(shift + col, 0);
       }
-      const float4 v = reinterpret_cast<const float4*>(x)[i];
-      float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
-      if (relu) { o.x = act_apply(relu, o.x); o.y = act_apply(relu, o.y); o.z = act_apply(relu, o.z); o.w = act_apply(relu, o.w); }
+      float4 o = affine4(ld4(x, i), sc, sh);
+      if (relu) o = act_apply4(relu, o);
       if (drop.thr) o = drop4(drop, dseed, i, o);
-      reinterpret_cast<float4*>(y)[i] = o;
+      st4(y, i, o);
     }
   } else {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
@@ -736,15 +703,12 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
   double s, ss;
   block_partial_sums(partial, blocks, c, col, s, ss, by_channel != 0);
   if (dx_bound) {
-    __shared__ float redm[4];
     float mz = 0.f;
     if (by_channel) for (int b = threadIdx.x; b < blocks; b += 256) mz = fmaxf(mz, pmax[(long)col * blocks + b]);
     else for (int b = threadIdx.x; b < blocks; b += 256) mz = fmaxf(mz, pmax[(long)b * c + col]);
-    mz = wave_max(mz);
-    if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = mz;
-    __syncthreads();
+    mz = block_max256(mz);
     if (threadIdx.x == 0)
-      dx_bound[col] = dx_channel_bound(scale[col], fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3])), (float)s, (float)ss,
+      dx_bound[col] = dx_channel_bound(scale[col], mz, (float)s, (float)ss,
                                        xhat_bound ? xhat_bound[col] : 0.f, inv_m, training && xhat_bound);
   }
   if (threadIdx.x == 0) { dbeta[col] = (float)s; dgamma[col] = (float)ss; }
@@ -852,7 +816,57 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
   dx[i] = g;
 }
 
-// Four channels per thread (C % 4 == 0): 16-byte loads/stores, 4-byte arg-max words.
+// Four channels per thread (C % 4 == 0): 16-byte loads/stores, 4-byte arg-max words (one tap byte per channel).
+// The forward window scan of output pixel (b, y_o, x_o), channel quad `col`: value_of_tap(x4) is what competes (the input itself,
+// or the BatchNorm + activation of it); returns the maxima, their taps and the winners' raw inputs.
+struct PoolWin { float best[4]; int tap[4]; float xin[4]; };
+template <class F>
+__device__ __forceinline__ PoolWin pool_scan4(const float* x, int b, int y_o, int x_o, int h, int w, int col, int c4, int k,
+                                              int stride, int pad, F value_of_tap) {
+  PoolWin win{{-INFINITY, -INFINITY, -INFINITY, -INFINITY}, {255, 255, 255, 255}, {0.f, 0.f, 0.f, 0.f}};
+  for (int dy = 0; dy < k; ++dy)
+    for (int dx = 0; dx < k; ++dx) {
+      const int ih = y_o * stride + dy - pad, iw = x_o * stride + dx - pad;
+      const bool in = (unsigned)ih < (unsigned)h && (unsigned)iw < (unsigned)w;
+      float vv[4] = {0.f, 0.f, 0.f, 0.f}, xx[4] = {0.f, 0.f, 0.f, 0.f};
+      if (in) {
+        const float4 v = ld4(x, (((long)b * h + ih) * w + iw) * c4 + col);
+        const float4 t = value_of_tap(v);
+        xx[0] = v.x; xx[1] = v.y; xx[2] = v.z; xx[3] = v.w;
+        vv[0] = t.x; vv[1] = t.y; vv[2] = t.z; vv[3] = t.w;
+      }
+      const int tap = in ? dy * k + dx : 255;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) if (vv[j] > win.best[j]) { win.best[j] = vv[j]; win.tap[j] = tap; win.xin[j] = xx[j]; }
+    }
+  return win;
+}
+__device__ __forceinline__ uint32_t pack_taps(const int (&bi)[4]) {
+  return (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
+}
+// d where the arg-max byte of the channel names `tap`, else 0
+__device__ __forceinline__ float4 tap_match4(uint32_t am, uint32_t tap, float4 d) {
+  return make_float4((am & 0xff) == tap ? d.x : 0.f, ((am >> 8) & 0xff) == tap ? d.y : 0.f,
+                     ((am >> 16) & 0xff) == tap ? d.z : 0.f, (am >> 24) == tap ? d.w : 0.f);
+}
+// The max-pool backward of input pixel (img, ih, iw), channel quad q: the pooled gradients of the windows that cover the pixel
+// and whose arg-max names it — windows (y_o, x_o) with y_o*stride - pad <= ih < y_o*stride - pad + k, likewise x_o.
+__device__ __forceinline__ float4 pool_taps_grad4(const float* dy, const uint8_t* argmax, int img, int ih, int iw, int q, int c4, int k,
+                                                  int stride, int pad, int oh, int ow) {
+  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int y_hi = min((ih + pad) / stride, oh - 1), x_hi = min((iw + pad) / stride, ow - 1);
+  for (int y_o = y_hi; y_o >= 0 && y_o * stride - pad + k > ih; --y_o)
+    for (int x_o = x_hi; x_o >= 0 && x_o * stride - pad + k > iw; --x_o) {
+      const uint32_t tap = (uint32_t)((ih - (y_o * stride - pad)) * k + (iw - (x_o * stride - pad)));
+      const long o = (((long)img * oh + y_o) * ow + x_o) * c4 + q;
+      // both loads unconditional: independent of each other and of the compare, so the (at most four)
+      // windows of a pixel are all in flight together; dy lines are shared by neighbouring pixels (L1/L2)
+      const uint32_t am = reinterpret_cast<const uint32_t*>(argmax)[o];
+      add4(g, tap_match4(am, tap, ld4(dy, o)));
+    }
+  return g;
+}
+
 __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restrict__ x, int n, int h, int w, int c4,
                                                            int k, int stride, int pad, int oh, int ow,
                                                            float* __restrict__ y, uint8_t* __restrict__ argmax,
@@ -866,23 +880,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restri
     const int x_o = (int)(t % ow); t /= ow;
     const int y_o = (int)(t % oh);
     const int b = (int)(t / oh);
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int bi[4] = {255, 255, 255, 255};
-    for (int dy = 0; dy < k; ++dy)
-      for (int dx = 0; dx < k; ++dx) {
-        const int ih = y_o * stride + dy - pad, iw = x_o * stride + dx - pad;
-        const bool in = (unsigned)ih < (unsigned)h && (unsigned)iw < (unsigned)w;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (in) v = reinterpret_cast<const float4*>(x)[(((long)b * h + ih) * w + iw) * c4 + col];
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-        const int tap = in ? dy * k + dx : 255;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (vv[j] > best[j]) { best[j] = vv[j]; bi[j] = tap; }
-      }
-    const float4 o = make_float4(best[0], best[1], best[2], best[3]);
-    reinterpret_cast<float4*>(y)[i] = o;
-    reinterpret_cast<uint32_t*>(argmax)[i] = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) |
-                                             ((uint32_t)bi[3] << 24);
+    const PoolWin win = pool_scan4(x, b, y_o, x_o, h, w, col, c4, k, stride, pad, [](float4 v) { return v; });
+    const float4 o = make_float4(win.best[0], win.best[1], win.best[2], win.best[3]);
+    st4(y, i, o);
+    reinterpret_cast<uint32_t*>(argmax)[i] = pack_taps(win.tap);
     amax = amax4(0.f, o);
   }
   // the exact max |y| of the pooled tensor for the three-product conv that reads it (conv.hip Ranges; `simple`: conv -> ReLU -> pool)
@@ -900,22 +901,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd4_kernel(const float* __restri
   const int iw = (int)(t % w); t /= w;
   const int ih = (int)(t % h);
   const int b = (int)(t / h);
-  float g[4] = {0.f, 0.f, 0.f, 0.f};
-  const int y_hi = min((ih + pad) / stride, oh - 1), x_hi = min((iw + pad) / stride, ow - 1);
-  for (int y_o = y_hi; y_o >= 0 && y_o * stride - pad + k > ih; --y_o)
-    for (int x_o = x_hi; x_o >= 0 && x_o * stride - pad + k > iw; --x_o) {
-      const uint32_t tap = (uint32_t)((ih - (y_o * stride - pad)) * k + (iw - (x_o * stride - pad)));
-      const long o = (((long)b * oh + y_o) * ow + x_o) * c4 + col;
-      // both loads unconditional: independent of each other and of the compare, so the (at most four)
-      // windows of a pixel are all in flight together; dy lines are shared by neighbouring pixels (L1/L2)
-      const uint32_t am = reinterpret_cast<const uint32_t*>(argmax)[o];
-      const float4 d = reinterpret_cast<const float4*>(dy)[o];
-      g[0] += (am & 0xff) == tap ? d.x : 0.f;
-      g[1] += ((am >> 8) & 0xff) == tap ? d.y : 0.f;
-      g[2] += ((am >> 16) & 0xff) == tap ? d.z : 0.f;
-      g[3] += (am >> 24) == tap ? d.w : 0.f;
-    }
-  reinterpret_cast<float4*>(dx)[i] = make_float4(g[0], g[1], g[2], g[3]);
+  st4(dx, i, pool_taps_grad4(dy, argmax, b, ih, iw, col, c4, k, stride, pad, oh, ow));
 }
 
 // conv -> ReLU -> MaxPool (the `simple` backbone, reference backbones.py:21-31): the pool's backward, the ReLU mask of the
@@ -933,24 +919,9 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_colsum4_kernel(
     const int iw = (int)((uint32_t)r - t * (uint32_t)w);
     const uint32_t img = divu(t, dh);
     const int ih = (int)(t - img * (uint32_t)h);
-    const float4 yv = reinterpret_cast<const float4*>(y)[r * c4 + q];
-    float gr[4] = {0.f, 0.f, 0.f, 0.f};
-    const int y_hi = min((ih + pad) / stride, oh - 1), x_hi = min((iw + pad) / stride, ow - 1);
-    for (int y_o = y_hi; y_o >= 0 && y_o * stride - pad + k > ih; --y_o)
-      for (int x_o = x_hi; x_o >= 0 && x_o * stride - pad + k > iw; --x_o) {
-        const uint32_t tap = (uint32_t)((ih - (y_o * stride - pad)) * k + (iw - (x_o * stride - pad)));
-        const long o = (((long)img * oh + y_o) * ow + x_o) * c4 + q;
-        const uint32_t am = reinterpret_cast<const uint32_t*>(argmax)[o];
-        const float4 d = reinterpret_cast<const float4*>(dy)[o];
-        gr[0] += (am & 0xff) == tap ? d.x : 0.f;
-        gr[1] += ((am >> 8) & 0xff) == tap ? d.y : 0.f;
-        gr[2] += ((am >> 16) & 0xff) == tap ? d.z : 0.f;
-        gr[3] += (am >> 24) == tap ? d.w : 0.f;
-      }
-    const float4 v = make_float4(yv.x > 0.f ? gr[0] : 0.f, yv.y > 0.f ? gr[1] : 0.f, yv.z > 0.f ? gr[2] : 0.f,
-                                 yv.w > 0.f ? gr[3] : 0.f);
-    reinterpret_cast<float4*>(dz)[r * c4 + q] = v;
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    const float4 v = relu_mask4(ld4(y, r * c4 + q), pool_taps_grad4(dy, argmax, (int)img, ih, iw, q, c4, k, stride, pad, oh, ow));
+    st4(dz, r * c4 + q, v);
+    add4(a, v);
     amax = amax4(amax, v);
   });
   if (range_slot) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, amax);
@@ -977,29 +948,13 @@ __global__ __launch_bounds__(256) void affine_act_maxpool_fwd4_kernel(
   const int x_o = (int)(t % ow); t /= ow;
   const int y_o = (int)(t % oh);
   const int b = (int)(t / oh);
-  const float4 sc = reinterpret_cast<const float4*>(scale)[col], sh = reinterpret_cast<const float4*>(shift)[col];
-  float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  float bx[4] = {0.f, 0.f, 0.f, 0.f};                    // the BN input at the winning tap (backward's reduction reads it)
-  int bi[4] = {255, 255, 255, 255};
-  for (int dy = 0; dy < k; ++dy)
-    for (int dx = 0; dx < k; ++dx) {
-      const int ih = y_o * stride + dy - pad, iw = x_o * stride + dx - pad;
-      const bool in = (unsigned)ih < (unsigned)h && (unsigned)iw < (unsigned)w;
-      float vv[4] = {0.f, 0.f, 0.f, 0.f}, xx[4] = {0.f, 0.f, 0.f, 0.f};
-      if (in) {
-        const float4 v = reinterpret_cast<const float4*>(x)[(((long)b * h + ih) * w + iw) * c4 + col];
-        xx[0] = v.x; xx[1] = v.y; xx[2] = v.z; xx[3] = v.w;
-        vv[0] = act_apply(act, fmaf(v.x, sc.x, sh.x)); vv[1] = act_apply(act, fmaf(v.y, sc.y, sh.y));
-        vv[2] = act_apply(act, fmaf(v.z, sc.z, sh.z)); vv[3] = act_apply(act, fmaf(v.w, sc.w, sh.w));
-      }
-      const int tap = in ? dy * k + dx : 255;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) if (vv[j] > best[j]) { best[j] = vv[j]; bi[j] = tap; bx[j] = xx[j]; }
-    }
-  if (xwin) reinterpret_cast<float4*>(xwin)[i] = make_float4(bx[0], bx[1], bx[2], bx[3]);
-  reinterpret_cast<float4*>(y)[i] = make_float4(best[0], best[1], best[2], best[3]);
-  reinterpret_cast<uint32_t*>(argmax)[i] = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) |
-                                           ((uint32_t)bi[3] << 24);
+  const float4 sc = ld4(scale, col), sh = ld4(shift, col);
+  const PoolWin win = pool_scan4(x, b, y_o, x_o, h, w, col, c4, k, stride, pad,
+                                 [&](float4 v) { return act_apply4(act, affine4(v, sc, sh)); });
+  // xwin: the BN input at the winning tap (backward's reduction reads it)
+  if (xwin) st4(xwin, i, make_float4(win.xin[0], win.xin[1], win.xin[2], win.xin[3]));
+  st4(y, i, make_float4(win.best[0], win.best[1], win.best[2], win.best[3]));
+  reinterpret_cast<uint32_t*>(argmax)[i] = pack_taps(win.tap);
 }
 
 // dbeta / dgamma partial sums over the pooled elements (rows = n*oh*ow pooled pixels)
@@ -1011,13 +966,12 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_reduce4_kernel(
   col_reduce2_v4(mp, c4, g, partial, [&](long r, int q, float4& a, float4& b) {
     const uint32_t am = reinterpret_cast<const uint32_t*>(argmax)[r * c4 + q];
     float4 xw4 = make_float4(0.f, 0.f, 0.f, 0.f);      // forward kept the winners' inputs: a streaming read, no gather
-    if (xwin) xw4 = reinterpret_cast<const float4*>(xwin)[r * c4 + q];
+    if (xwin) xw4 = ld4(xwin, r * c4 + q);
     const float xwv[4] = {xw4.x, xw4.y, xw4.z, xw4.w};
-    const float4 d = reinterpret_cast<const float4*>(dy)[r * c4 + q];
+    const float4 d = ld4(dy, r * c4 + q);
     const int x_o = (int)(r % ow); const long t = r / ow;
     const int y_o = (int)(t % oh), bb = (int)(t / oh);
-    const float4 sc = reinterpret_cast<const float4*>(scale)[q], sh = reinterpret_cast<const float4*>(shift)[q];
-    const float4 mu = reinterpret_cast<const float4*>(mean)[q], rs = reinterpret_cast<const float4*>(rstd)[q];
+    const float4 sc = ld4(scale, q), sh = ld4(shift, q), mu = ld4(mean, q), rs = ld4(rstd, q);
     const float dd[4] = {d.x, d.y, d.z, d.w}, scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
     const float muv[4] = {mu.x, mu.y, mu.z, mu.w}, rsv[4] = {rs.x, rs.y, rs.z, rs.w};
     float av[4], bv[4];
@@ -1030,10 +984,10 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_reduce4_kernel(
       const int iw = min(max(x_o * stride - pad + (int)(tp % (uint32_t)k), 0), w - 1);
       const float xv = xwin ? xwv[j] : x[((((long)bb * h + ih) * w + iw) * c4 + q) * 4 + j];
       const float dz = on ? act_grad(act, fmaf(xv, scv[j], shv[j]), dd[j]) : 0.f;
-      av[j] = dz; bv[j] = dz * ((xv - muv[j]) * rsv[j]);
+      av[j] = dz; bv[j] = dz * ((xv - muv[j]) * rsv[j]);   // (a product, then the add below: not bn_sums4's fma — kept, it is the result's rounding)
     }
-    a.x += av[0]; a.y += av[1]; a.z += av[2]; a.w += av[3];
-    b.x += bv[0]; b.y += bv[1]; b.z += bv[2]; b.w += bv[3];
+    add4(a, make_float4(av[0], av[1], av[2], av[3]));
+    add4(b, make_float4(bv[0], bv[1], bv[2], bv[3]));
   });
 }
 
@@ -1053,12 +1007,12 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply4_kernel(
   const int iw = (int)(t % w); t /= w;
   const int ih = (int)(t % h);
   const int b = (int)(t / h);
-  const float4 xv = reinterpret_cast<const float4*>(x)[i];
-  float g[4] = {0.f, 0.f, 0.f, 0.f};
-  const int y_hi = min((ih + pad) / stride, oh - 1), x_hi = min((iw + pad) / stride, ow - 1);
+  const float4 xv = ld4(x, i);
+  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
   if (k <= 2 * stride) {
     // at most two windows per dimension cover a pixel (3x3/2, 2x2/2): all four candidates are fetched unconditionally
-    // (clamped addresses, masked afterwards) so the loads are in flight together; same accumulation order as the loops
+    // (clamped addresses, masked afterwards) so the loads are in flight together; pool_taps_grad4's accumulation order
+    const int y_hi = min((ih + pad) / stride, oh - 1), x_hi = min((iw + pad) / stride, ow - 1);
     uint32_t am[4]; float4 d[4]; bool ok[4]; uint32_t tp[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1068,43 +1022,17 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply4_kernel(
       tp[j] = (uint32_t)((ih - (yc * stride - pad)) * k + (iw - (xc * stride - pad)));
       const long o = (((long)b * oh + yc) * ow + xc) * c4 + q;
       am[j] = reinterpret_cast<const uint32_t*>(argmax)[o];
-      d[j] = reinterpret_cast<const float4*>(dy)[o];
+      d[j] = ld4(dy, o);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!ok[j]) continue;
-      g[0] += (am[j] & 0xff) == tp[j] ? d[j].x : 0.f;
-      g[1] += ((am[j] >> 8) & 0xff) == tp[j] ? d[j].y : 0.f;
-      g[2] += ((am[j] >> 16) & 0xff) == tp[j] ? d[j].z : 0.f;
-      g[3] += (am[j] >> 24) == tp[j] ? d[j].w : 0.f;
-    }
-  } else
-  for (int y_o = y_hi; y_o >= 0 && y_o * stride - pad + k > ih; --y_o)
-    for (int x_o = x_hi; x_o >= 0 && x_o * stride - pad + k > iw; --x_o) {
-      const uint32_t tap = (uint32_t)((ih - (y_o * stride - pad)) * k + (iw - (x_o * stride - pad)));
-      const long o = (((long)b * oh + y_o) * ow + x_o) * c4 + q;
-      const uint32_t am = reinterpret_cast<const uint32_t*>(argmax)[o];
-      const float4 d = reinterpret_cast<const float4*>(dy)[o];
-      g[0] += (am & 0xff) == tap ? d.x : 0.f;
-      g[1] += ((am >> 8) & 0xff) == tap ? d.y : 0.f;
-      g[2] += ((am >> 16) & 0xff) == tap ? d.z : 0.f;
-      g[3] += (am >> 24) == tap ? d.w : 0.f;
-    }
-  const float4 sc = reinterpret_cast<const float4*>(scale)[q], sh = reinterpret_cast<const float4*>(shift)[q];
-  float4 dz = make_float4(act_grad(act, fmaf(xv.x, sc.x, sh.x), g[0]), act_grad(act, fmaf(xv.y, sc.y, sh.y), g[1]),
-                          act_grad(act, fmaf(xv.z, sc.z, sh.z), g[2]), act_grad(act, fmaf(xv.w, sc.w, sh.w), g[3]));
-  float4 o;
-  if (training) {
-    const float4 mu = reinterpret_cast<const float4*>(mean)[q], rs = reinterpret_cast<const float4*>(rstd)[q];
-    const float4 db = reinterpret_cast<const float4*>(dbeta)[q], dg = reinterpret_cast<const float4*>(dgamma)[q];
-    o.x = sc.x * (dz.x - db.x * inv_m - (xv.x - mu.x) * rs.x * dg.x * inv_m);
-    o.y = sc.y * (dz.y - db.y * inv_m - (xv.y - mu.y) * rs.y * dg.y * inv_m);
-    o.z = sc.z * (dz.z - db.z * inv_m - (xv.z - mu.z) * rs.z * dg.z * inv_m);
-    o.w = sc.w * (dz.w - db.w * inv_m - (xv.w - mu.w) * rs.w * dg.w * inv_m);
+    for (int j = 0; j < 4; ++j)
+      if (ok[j]) add4(g, tap_match4(am[j], tp[j], d[j]));
   } else {
-    o = make_float4(sc.x * dz.x, sc.y * dz.y, sc.z * dz.z, sc.w * dz.w);
+    g = pool_taps_grad4(dy, argmax, b, ih, iw, q, c4, k, stride, pad, oh, ow);
   }
-  if (valid) reinterpret_cast<float4*>(dx)[i] = o;
+  const BnConsts kc = bn_consts(q, scale, shift, mean, rstd, dbeta, dgamma, training);
+  const float4 o = bn_dx4(act_grad4(act, xv, kc.sc, kc.sh, g), xv, kc, inv_m, training);
+  if (valid) st4(dx, i, o);
   if (range_slot) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, valid ? amax4(0.f, o) : 0.f);
 }
 
@@ -1115,16 +1043,13 @@ __global__ __launch_bounds__(256) void gap_fwd4_kernel(const float* __restrict__
   const int cq = blockIdx.x * 16 + cl;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (cq < c4)
-    for (int p = pl; p < hw; p += 16) {
-      const float4 v = reinterpret_cast<const float4*>(x)[((long)n * hw + p) * c4 + cq];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
+    for (int p = pl; p < hw; p += 16) add4(acc, ld4(x, ((long)n * hw + p) * c4 + cq));
   sh[threadIdx.x] = acc;
   __syncthreads();
   if (pl == 0 && cq < c4) {
-    for (int k = 1; k < 16; ++k) { const float4 o = sh[k * 16 + cl]; acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
+    for (int k = 1; k < 16; ++k) add4(acc, sh[k * 16 + cl]);
     const float inv = 1.f / (float)hw;
-    reinterpret_cast<float4*>(y)[(long)n * c4 + cq] = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+    st4(y, (long)n * c4 + cq, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
   }
 }
 
@@ -1140,25 +1065,25 @@ __global__ __launch_bounds__(1024) void affine_act_gap4_kernel(const float* __re
   const int cq = blockIdx.x * cls + cl;
   float4 acc[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
   if (cq < c4) {
-    const float4 sc = reinterpret_cast<const float4*>(scale)[cq], sf = reinterpret_cast<const float4*>(shift)[cq];
-    const float4* xi = reinterpret_cast<const float4*>(x) + (long)n * hw * c4 + cq;
-    float4* yi = reinterpret_cast<float4*>(y) + (long)n * hw * c4 + cq;
+    const float4 sc = ld4(scale, cq), sf = ld4(shift, cq);
+    const float* xi = x + 4 * ((long)n * hw * c4 + cq);   // this image and channel quad: pixel p is quad p * c4 behind
+    float* yi = y + 4 * ((long)n * hw * c4 + cq);
     auto one = [&](const float4 v, int p) {
-      float4 o = make_float4(fmaf(v.x, sc.x, sf.x), fmaf(v.y, sc.y, sf.y), fmaf(v.z, sc.z, sf.z), fmaf(v.w, sc.w, sf.w));
-      if (act) { o.x = act_apply(act, o.x); o.y = act_apply(act, o.y); o.z = act_apply(act, o.z); o.w = act_apply(act, o.w); }
-      if (y) yi[(long)p * c4] = o;                        // y == NULL: pooled means only (the tensor is formed later, gated)
-      acc[0].x += o.x; acc[0].y += o.y; acc[0].z += o.z; acc[0].w += o.w;
+      float4 o = affine4(v, sc, sf);
+      if (act) o = act_apply4(act, o);
+      if (y) st4(yi, (long)p * c4, o);                    // y == NULL: pooled means only (the tensor is formed later, gated)
+      add4(acc[0], o);
     };
     int p = pl;
     for (; p + 3 * npl < hw; p += 4 * npl) {
-      const float4 v0 = xi[(long)p * c4], v1 = xi[(long)(p + npl) * c4], v2 = xi[(long)(p + 2 * npl) * c4], v3 = xi[(long)(p + 3 * npl) * c4];
+      const float4 v0 = ld4(xi, (long)p * c4), v1 = ld4(xi, (long)(p + npl) * c4), v2 = ld4(xi, (long)(p + 2 * npl) * c4), v3 = ld4(xi, (long)(p + 3 * npl) * c4);
       one(v0, p); one(v1, p + npl); one(v2, p + 2 * npl); one(v3, p + 3 * npl);
     }
-    for (; p < hw; p += npl) one(xi[(long)p * c4], p);
+    for (; p < hw; p += npl) one(ld4(xi, (long)p * c4), p);
   }
   const float inv = 1.f / (float)hw;
   pixel_lane_sums<1>(acc, cls, [&](int, const float4 a) {
-    if (cq < c4) reinterpret_cast<float4*>(gap)[(long)n * c4 + cq] = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+    if (cq < c4) st4(gap, (long)n * c4 + cq, make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv));
   });
 }
 
@@ -1191,13 +1116,10 @@ __global__ __launch_bounds__(256) void gap_bwd_add4_kernel(const float* __restri
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
     const int q = (int)(i % c4);
     const long b = i / ((long)hw * c4);
-    const float4 g = reinterpret_cast<const float4*>(dy)[b * c4 + q];
+    const float4 g = ld4(dy, b * c4 + q);
     float4 o = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
-    if (dx_add) {
-      const float4 a = reinterpret_cast<const float4*>(dx_add)[i];
-      o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-    }
-    reinterpret_cast<float4*>(dx)[i] = o;
+    if (dx_add) add4(o, ld4(dx_add, i));
+    st4(dx, i, o);
   }
 }
 
@@ -1236,24 +1158,18 @@ struct SumsqTensor { const float* x; long n; float alpha; int pad; };
 static_assert(sizeof(SumsqTensor) == 24, "descriptor layout is part of the ABI (include/embnet.h)");
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const SumsqTensor* __restrict__ table, const int* __restrict__ chunks,
                                                           float* __restrict__ partial) {
-  __shared__ float part[4];
   const SumsqTensor t = table[chunks[2 * blockIdx.x]];
   const long first = (long)chunks[2 * blockIdx.x + 1] * 4096, end = min(first + 4096, t.n);
   float s = 0.f;
   for (long i = first + threadIdx.x; i < end; i += 256) s = fmaf(t.x[i], t.x[i], s);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = t.alpha * (part[0] + part[1] + part[2] + part[3]);
+  s = block_sum256(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t.alpha * s;
 }
 __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ partial, int n, float* __restrict__ out) {
-  __shared__ double part[4];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (float)(part[0] + part[1] + part[2] + part[3]);
+  s = block_sum256(s);
+  if (threadIdx.x == 0) *out = (float)s;
 }
 
 __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, const float* __restrict__ b, long total,
@@ -1300,17 +1216,16 @@ __global__ __launch_bounds__(256) void affine_act_planes_kernel(const float* __r
   float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
   if (fixed) {
     const int q = (int)(((long)blockIdx.x * 256 + threadIdx.x) % c4);
-    sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
+    sc = ld4(scale, q); sh = ld4(shift, q);
   }
   float amax = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
     const long pix = i / c4; const int q = (int)(i - pix * c4);
-    if (!fixed) { sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q]; }
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
-    if (act) { o.x = act_apply(act, o.x); o.y = act_apply(act, o.y); o.z = act_apply(act, o.z); o.w = act_apply(act, o.w); }
+    if (!fixed) { sc = ld4(scale, q); sh = ld4(shift, q); }
+    float4 o = affine4(ld4(x, i), sc, sh);
+    if (act) o = act_apply4(act, o);
     if (SRC == 2) { amax = amax4(amax, o); continue; }
-    if (y) reinterpret_cast<float4*>(y)[i] = o;
+    if (y) st4(y, i, o);
     const long e = ((long)(q >> 2) * pixels + pix) * 16 + 4 * (q & 3);
     if (F16) {
       const Split4H s = split4h(o, ps);
@@ -1323,11 +1238,8 @@ __global__ __launch_bounds__(256) void affine_act_planes_kernel(const float* __r
     }
   }
   if (SRC == 2) {
-    amax = wave_max(amax);
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = amax;
-    __syncthreads();
-    if (threadIdx.x == 0) planes_scale_slot(planes, plane)[2 + blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    amax = block_max256(amax);
+    if (threadIdx.x == 0) planes_scale_slot(planes, plane)[2 + blockIdx.x] = amax;
   }
 }
 
@@ -1363,31 +1275,25 @@ __global__ __launch_bounds__(256) void pad_channels_kernel(const float* __restri
 // sum of squares -> partial per block (double finalize on one thread)
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, long total,
                                                             float* __restrict__ partial) {
-  __shared__ float part[4];
   float s = 0.f;
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) s = fmaf(x[i], x[i], s);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  s = block_sum256(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // out[c] = sum_{t,k} w[t][c][k] * s[t][k]   (t = filter tap): gradient of a per-channel input offset
 // through a convolution, from the per-tap sums s of the output gradient.  One workgroup per channel.
 __global__ __launch_bounds__(256) void tap_contract_kernel(const float* __restrict__ w, const float* __restrict__ s,
                                                            int taps, int c, int k, float* __restrict__ out) {
-  __shared__ float part[4];
   const int ch = blockIdx.x;
   float acc = 0.f;
   for (int i = threadIdx.x; i < taps * k; i += 256) {
     const int t = i / k, kk = i - t * k;
     acc = fmaf(w[((long)t * c + ch) * k + kk], s[i], acc);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[ch] = part[0] + part[1] + part[2] + part[3];
+  acc = block_sum256(acc);
+  if (threadIdx.x == 0) out[ch] = acc;
 }
 
 // Per-tap sums of a convolution's output gradient when that gradient sums to ZERO over all pixels of every channel
@@ -1513,6 +1419,18 @@ extern "C" size_t embnet_bn_workspace_bytes(long m, int c) {
   if ((c & 3) == 0) { const int b4 = col_geom(m, c / 4).blocks; if (b4 > blocks) blocks = b4; }
   return ((size_t)blocks * 3 * c + c) * sizeof(float);
 }
+// 0, or the error of a caller's workspace smaller than embnet_bn_workspace_bytes(m, c)
+static int bn_workspace_check(const char* who, size_t workspace_bytes, long m, int c) {
+  const size_t need = embnet_bn_workspace_bytes(m, c);
+  return workspace_bytes < need ? fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need) : 0;
+}
+// y = act(x * scale + shift) over [m, c], optionally with a fused Dropout and the range of y from the BatchNorm's bounds
+static void launch_affine_act(const float* x, long m, int c, const float* scale, const float* shift, int act, float* y,
+                              const DropArg drop, const float* bound, uint32_t* range, void* stream) {
+  EMBNET_TRACE("embnet::affine_act_kernel", TRACE_BYTES, 8.0 * m * c, stream);
+  const int blocks = (c & 3) ? ew_blocks(m * c / 4 + 1) : ew_blocks_c4(m * c / 4, c / 4);
+  affine_act_kernel<<<blocks, 256, 0, S(stream)>>>(x, m * c, c, scale, shift, act, y, drop, bound, range);
+}
 
 static int bn_train_fwd_impl(const float* x, long m, int c, const float* gamma, const float* beta, float eps,
                              float momentum, int relu, float* y, float* save_mean, float* save_rstd,
@@ -1523,8 +1441,7 @@ static int bn_train_fwd_impl(const float* x, long m, int c, const float* gamma, 
   EMBNET_CHECK_ARG(m > 0 && c > 0, "bn_train_fwd: m=%ld c=%d", m, c);
   EMBNET_CHECK_ARG(!y_range || (y_bound && y && !(reinterpret_cast<uintptr_t>(y_range) & 3)),
                    "bn_train_fwd: y_range (the range slot of the fp32 y) goes with y_bound and y");
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "bn_train_fwd: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("bn_train_fwd", workspace_bytes, m, c)) return e;
   const ColGeom g = col_geom(m, c);
   const float* partial = (const float*)workspace;
   int nblocks = g.blocks;
@@ -1541,7 +1458,7 @@ static int bn_train_fwd_impl(const float* x, long m, int c, const float* gamma, 
   { EMBNET_TRACE("embnet::bn_finalize_kernel", TRACE_BYTES, 8.0 * nblocks * c, stream); bn_finalize_kernel<<<c, 256, 0, S(stream)>>>(partial, nblocks, m, c, gamma, beta, eps, momentum, save_mean,
                                                           save_rstd, scale, shift, moving_mean, moving_var, partial_in != nullptr, y_bound, xhat_bound); }
   if (y)                                    // y == NULL: statistics + scale/shift only (a fused consumer applies them)
-    { EMBNET_TRACE("embnet::affine_act_kernel", TRACE_BYTES, 8.0 * m * c, stream); affine_act_kernel<<<((c & 3) ? ew_blocks(m * c / 4 + 1) : ew_blocks_c4(m * c / 4, c / 4)), 256, 0, S(stream)>>>(x, m * c, c, scale, shift, relu, y, DropArg{0, nullptr, 0u, 1.f}, y_bound, y_range); }
+    launch_affine_act(x, m, c, scale, shift, relu, y, no_drop(), y_bound, y_range, stream);
   return check_launch("bn_train_fwd");
 }
 extern "C" int embnet_bn_train_fwd(const float* x, long m, int c, const float* gamma, const float* beta, float eps,
@@ -1567,7 +1484,7 @@ extern "C" int embnet_bn_infer_fwd(const float* x, long m, int c, const float* g
   EMBNET_CHECK_ARG(x && moving_mean && moving_var && scale && shift, "bn_infer_fwd: null pointer");
   EMBNET_CHECK_ARG(m > 0 && c > 0, "bn_infer_fwd: m=%ld c=%d", m, c);
   bn_infer_prepare_kernel<<<cdiv(c, 256), 256, 0, S(stream)>>>(c, gamma, beta, moving_mean, moving_var, eps, scale, shift);
-  if (y) { EMBNET_TRACE("embnet::affine_act_kernel", TRACE_BYTES, 8.0 * m * c, stream); affine_act_kernel<<<((c & 3) ? ew_blocks(m * c / 4 + 1) : ew_blocks_c4(m * c / 4, c / 4)), 256, 0, S(stream)>>>(x, m * c, c, scale, shift, relu, y, DropArg{0, nullptr, 0u, 1.f}); }
+  if (y) launch_affine_act(x, m, c, scale, shift, relu, y, no_drop(), nullptr, nullptr, stream);
   return check_launch("bn_infer_fwd");
 }
 
@@ -1575,7 +1492,7 @@ extern "C" int embnet_affine_act(const float* x, long m, int c, const float* sca
                                  void* stream) {
   EMBNET_CHECK_ARG(x && scale && shift && y, "affine_act: null pointer");
   EMBNET_CHECK_ARG(m > 0 && c > 0, "affine_act: m=%ld c=%d", m, c);
-  { EMBNET_TRACE("embnet::affine_act_kernel", TRACE_BYTES, 8.0 * m * c, stream); affine_act_kernel<<<((c & 3) ? ew_blocks(m * c / 4 + 1) : ew_blocks_c4(m * c / 4, c / 4)), 256, 0, S(stream)>>>(x, m * c, c, scale, shift, act, y, DropArg{0, nullptr, 0u, 1.f}); }
+  launch_affine_act(x, m, c, scale, shift, act, y, no_drop(), nullptr, nullptr, stream);
   return check_launch("affine_act");
 }
 
@@ -1584,7 +1501,7 @@ extern "C" int embnet_affine_act_dropout(const float* x, long m, int c, const fl
   EMBNET_CHECK_ARG(x && scale && shift && y, "affine_act_dropout: null pointer");
   EMBNET_CHECK_ARG(m > 0 && c > 0, "affine_act_dropout: m=%ld c=%d", m, c);
   EMBNET_CHECK_ARG(rate >= 0.f && rate < 1.f, "affine_act_dropout: rate %f outside [0,1)", rate);
-  { EMBNET_TRACE("embnet::affine_act_kernel", TRACE_BYTES, 8.0 * m * c, stream); affine_act_kernel<<<((c & 3) ? ew_blocks(m * c / 4 + 1) : ew_blocks_c4(m * c / 4, c / 4)), 256, 0, S(stream)>>>(x, m * c, c, scale, shift, act, y, drop_arg(rate, seed, seed_add_dev)); }
+  launch_affine_act(x, m, c, scale, shift, act, y, drop_arg(rate, seed, seed_add_dev), nullptr, nullptr, stream);
   return check_launch("affine_act_dropout");
 }
 
@@ -1649,6 +1566,9 @@ static void launch_bn_bwd_apply4(const float* dy, const float* x, long m, int c,
                                  const float* scale, const float* shift, const float* dbeta, const float* dgamma, int relu,
                                  int training, const float* dx_add, float* dx, void* dx_planes, hipStream_t st,
                                  uint32_t* range_slot = nullptr, const float* dx_bound = nullptr, const uint32_t* add_range = nullptr) {
+  // (<1>: + the dry run <2>; the names rocprofv3 prints)
+  EMBNET_TRACE(dx_bound ? "void embnet::bn_bwd_apply4_kernel<4>" : range_slot && !dx_planes ? "void embnet::bn_bwd_apply4_kernel<3>" : dx_planes && planes_f16() ? "void embnet::bn_bwd_apply4_kernel<1>" : "void embnet::bn_bwd_apply4_kernel<0>",
+               TRACE_BYTES, ((dx_add ? 16.0 : 12.0) + (dx_planes && planes_f16() && !dx_bound ? 8.0 : 0.0)) * m * c, st);
   const long total4 = m * c / 4;
   const int blocks = ew_blocks_c4(total4, c / 4);
   const float inv_m = 1.f / (float)m;
@@ -1693,8 +1613,7 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
   EMBNET_CHECK_ARG(!dx_planes || ((c & 15) == 0 && (size_t)m * c * 2 < 0x7FFFFFF0ull / 3), "bn_bwd: dx_planes needs c %% 16 == 0");
   EMBNET_CHECK_ARG(!training || (save_mean && save_rstd), "bn_bwd: training needs saved statistics");
   EMBNET_CHECK_ARG(m > 0 && c > 0, "bn_bwd: m=%ld c=%d", m, c);
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "bn_bwd: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("bn_bwd", workspace_bytes, m, c)) return e;
   const ColGeom g = col_geom(m, c);
   float* partial = (float*)workspace;
   // inference-mode statistics: xhat uses the moving stats folded in scale/shift; dgamma then needs them too.
@@ -1710,7 +1629,7 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
       const ColGeom g4 = col_geom(m, c / 4);
       float* pmax = bound ? partial + (size_t)g4.blocks * 2 * c : nullptr;
       if (bound) dx_bound = pmax + (size_t)g4.blocks * c;
-      { EMBNET_TRACE("embnet::bn_bwd_reduce4_kernel", TRACE_BYTES, 8.0 * m * c, stream); bn_bwd_reduce4_kernel<<<g4.blocks, 256, 0, S(stream)>>>(dy, x, m, c / 4, g4, save_mean, save_rstd, scale, shift, relu, partial, DropArg{0, nullptr, 0u, 1.f}, pmax); }
+      { EMBNET_TRACE("embnet::bn_bwd_reduce4_kernel", TRACE_BYTES, 8.0 * m * c, stream); bn_bwd_reduce4_kernel<<<g4.blocks, 256, 0, S(stream)>>>(dy, x, m, c / 4, g4, save_mean, save_rstd, scale, shift, relu, partial, no_drop(), pmax); }
       bn_bwd_finalize_kernel<<<c, 256, 0, S(stream)>>>(partial, g4.blocks, c, dbeta, dgamma, 0, bound ? nullptr : emit, pmax, scale, xhat_bound,
                                                        1.f / (float)m, training, dx_bound);
     } else {
@@ -1721,8 +1640,7 @@ static int bn_bwd_impl(const float* dy, const float* x, long m, int c, const flo
     zero2_kernel<<<cdiv(c, 256), 256, 0, S(stream)>>>(dbeta, dgamma, c);
   }
   if ((c & 3) == 0)
-    { EMBNET_TRACE(dx_bound ? "void embnet::bn_bwd_apply4_kernel<4>" : emit && !dx_planes ? "void embnet::bn_bwd_apply4_kernel<3>" : dx_planes && planes_f16() ? "void embnet::bn_bwd_apply4_kernel<1>" : "void embnet::bn_bwd_apply4_kernel<0>", TRACE_BYTES, ((dx_add ? 16.0 : 12.0) + (dx_planes && planes_f16() && !dx_bound ? 8.0 : 0.0)) * m * c, stream);   // (<1>: + the dry run <2>; the names rocprofv3 prints)
-      launch_bn_bwd_apply4(dy, x, m, c, save_mean, save_rstd, scale, shift, dbeta, dgamma, relu, training, dx_add, dx, dx_planes, S(stream), emit, dx_bound, dx_add_range); }
+    launch_bn_bwd_apply4(dy, x, m, c, save_mean, save_rstd, scale, shift, dbeta, dgamma, relu, training, dx_add, dx, dx_planes, S(stream), emit, dx_bound, dx_add_range);
   else
     { EMBNET_TRACE("embnet::bn_bwd_apply_kernel", TRACE_BYTES, (dx_add ? 16.0 : 12.0) * m * c, stream); bn_bwd_apply_kernel<<<ew_blocks(m * c), 256, 0, S(stream)>>>(dy, x, m * c, c, 1.f / (float)m, save_mean, save_rstd,
                                                                  scale, shift, dbeta, dgamma, relu, training, dx_add, dx); }
@@ -1765,8 +1683,7 @@ static int bn_bwd_inrelu_impl(const float* dy, const float* x, long m, int c, co
   EMBNET_CHECK_ARG(dy && x && scale && shift && dz && dgamma && dbeta && dbias && workspace, "bn_bwd_inrelu: null pointer");
   EMBNET_CHECK_ARG(m > 0 && c > 0 && (c & 3) == 0, "bn_bwd_inrelu: m=%ld c=%d (c %% 4 == 0 required)", m, c);
   EMBNET_CHECK_ARG(!training || (save_mean && save_rstd), "bn_bwd_inrelu: training needs saved statistics");
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "bn_bwd_inrelu: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("bn_bwd_inrelu", workspace_bytes, m, c)) return e;
   float* partial = (float*)workspace;
   const ColGeom g4 = col_geom(m, c / 4);
   if (save_mean && save_rstd) {
@@ -1792,8 +1709,7 @@ extern "C" int embnet_bn_bwd_gap(const float* dy, const float* dpool, const floa
   EMBNET_CHECK_ARG(n > 0 && hw > 0 && c > 0 && (c & 3) == 0, "bn_bwd_gap: n=%d hw=%d c=%d (c %% 4 == 0)", n, hw, c);
   const long m = (long)n * hw;
   EMBNET_CHECK_ARG(m * (c / 4) < 0x7FFFFFFFl, "bn_bwd_gap: tensor too large");
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "bn_bwd_gap: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("bn_bwd_gap", workspace_bytes, m, c)) return e;
   float* partial = (float*)workspace;
   const ColGeom g4 = col_geom(m, c / 4);
   const float inv_hw = 1.f / (float)hw;
@@ -1855,8 +1771,7 @@ static int bn_bwd_partials_impl(const float* dy, const float* x, long m, int c, 
   float* dx_bound = bound ? planes_scale_slot(dx_planes, total4 * 4) + 2 : nullptr;
   bn_bwd_finalize_kernel<<<c, 256, 0, S(stream)>>>(partials, rows, c, dbeta, dgamma, 1, bound ? nullptr : emit,
                                                    bound ? partials + (size_t)2 * c * rows : nullptr, scale, xhat_bound, 1.f / (float)m, 1, dx_bound);
-  { EMBNET_TRACE(dx_bound ? "void embnet::bn_bwd_apply4_kernel<4>" : emit && !dx_planes ? "void embnet::bn_bwd_apply4_kernel<3>" : dx_planes && planes_f16() ? "void embnet::bn_bwd_apply4_kernel<1>" : "void embnet::bn_bwd_apply4_kernel<0>", TRACE_BYTES, ((dx_add ? 16.0 : 12.0) + (dx_planes && planes_f16() && !dx_bound ? 8.0 : 0.0)) * m * c, stream);   // (<1>: + the dry run <2>; the names rocprofv3 prints)
-    launch_bn_bwd_apply4(dy, x, m, c, save_mean, save_rstd, scale, shift, dbeta, dgamma, relu, 1, dx_add, dx, dx_planes, S(stream), emit, dx_bound, dx_add_range); }
+  launch_bn_bwd_apply4(dy, x, m, c, save_mean, save_rstd, scale, shift, dbeta, dgamma, relu, 1, dx_add, dx, dx_planes, S(stream), emit, dx_bound, dx_add_range);
   return check_launch("bn_bwd_partials");
 }
 extern "C" int embnet_bn_bwd_partials(const float* dy, const float* x, long m, int c, const float* save_mean,
@@ -1882,7 +1797,7 @@ extern "C" int embnet_bn_bwd_inrelu(const float* dy, const float* x, long m, int
                                     float* dz, float* dgamma, float* dbeta, float* dbias, void* workspace,
                                     size_t workspace_bytes, void* stream) {
   return bn_bwd_inrelu_impl(dy, x, m, c, save_mean, save_rstd, scale, shift, relu, training, dz, dgamma, dbeta, dbias, workspace,
-                            workspace_bytes, stream, DropArg{0, nullptr, 0u, 1.f});
+                            workspace_bytes, stream, no_drop());
 }
 
 extern "C" int embnet_bn_bwd_inrelu_dropout(const float* dy, const float* x, long m, int c, const float* save_mean,
@@ -1900,7 +1815,7 @@ extern "C" int embnet_bn_bwd_inrelu_ex(const float* dy, const float* x, long m, 
                                        float* dz, float* dgamma, float* dbeta, float* dbias, void* workspace,
                                        size_t workspace_bytes, uint32_t* dz_range, void* stream) {
   return bn_bwd_inrelu_impl(dy, x, m, c, save_mean, save_rstd, scale, shift, relu, training, dz, dgamma, dbeta, dbias, workspace,
-                            workspace_bytes, stream, DropArg{0, nullptr, 0u, 1.f}, dz_range);
+                            workspace_bytes, stream, no_drop(), dz_range);
 }
 extern "C" int embnet_bn_bwd_inrelu_dropout_ex(const float* dy, const float* x, long m, int c, const float* save_mean,
                                                const float* save_rstd, const float* scale, const float* shift, int relu,
@@ -1959,8 +1874,7 @@ extern "C" int embnet_maxpool_relu_bwd_colsum_ex(const float* dy, const uint8_t*
                    "maxpool_relu_bwd_colsum: window leaves the padded image");
   const long m = (long)n * h * w;
   EMBNET_CHECK_ARG(m < (1l << 31), "maxpool_relu_bwd_colsum: %ld pixels (limit 2^31 - 1)", m);
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "maxpool_relu_bwd_colsum: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("maxpool_relu_bwd_colsum", workspace_bytes, m, c)) return e;
   const ColGeom g4 = col_geom(m, c / 4);
   range_begin(dz_range, stream);
   { EMBNET_TRACE("embnet::maxpool_relu_bwd_colsum4_kernel", TRACE_BYTES, 8.0 * m * c + 5.0 * n * oh * ow * c, stream);
@@ -2007,8 +1921,7 @@ static int bn_act_maxpool_bwd_impl(const float* dy, const uint8_t* argmax, const
   EMBNET_CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0, "bn_act_maxpool_bwd: bad geometry");
   EMBNET_CHECK_ARG((c & 3) == 0, "bn_act_maxpool_bwd: channel count %d not a multiple of 4", c);
   const long mp = (long)n * oh * ow;
-  if (workspace_bytes < embnet_bn_workspace_bytes(mp, c))
-    return fail(EMBNET_EWORKSPACE, "bn_act_maxpool_bwd: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(mp, c));
+  if (const int e = bn_workspace_check("bn_act_maxpool_bwd", workspace_bytes, mp, c)) return e;
   if (save_mean && save_rstd) {
     const ColGeom g4 = col_geom(mp, c / 4);
     { EMBNET_TRACE("embnet::pool_bn_bwd_reduce4_kernel", TRACE_BYTES, 9.0 * mp * c, stream); pool_bn_bwd_reduce4_kernel<<<g4.blocks, 256, 0, S(stream)>>>(dy, argmax, x, mp, h, w, c / 4, k, stride, pad, oh, ow, g4,
@@ -2070,16 +1983,16 @@ __global__ __launch_bounds__(256) void affine_act_scale4_kernel(const float* __r
   float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
   if (fixed) {
     const int q = (int)(((long)blockIdx.x * 256 + threadIdx.x) % c4);
-    sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
+    sc = ld4(scale, q); sh = ld4(shift, q);
   }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
     const int q = (int)(i % c4);
-    if (!fixed) { sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q]; }
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    const float4 g = reinterpret_cast<const float4*>(gate)[(long)divu((uint32_t)i, dhwc4) * c4 + q];
-    float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
-    if (act) { o.x = act_apply(act, o.x); o.y = act_apply(act, o.y); o.z = act_apply(act, o.z); o.w = act_apply(act, o.w); }
-    reinterpret_cast<float4*>(y)[i] = make_float4(__fmul_rn(o.x, g.x), __fmul_rn(o.y, g.y), __fmul_rn(o.z, g.z), __fmul_rn(o.w, g.w));
+    if (!fixed) { sc = ld4(scale, q); sh = ld4(shift, q); }
+    const float4 v = ld4(x, i);
+    const float4 g = ld4(gate, (long)divu((uint32_t)i, dhwc4) * c4 + q);
+    float4 o = affine4(v, sc, sh);
+    if (act) o = act_apply4(act, o);
+    st4(y, i, make_float4(__fmul_rn(o.x, g.x), __fmul_rn(o.y, g.y), __fmul_rn(o.z, g.z), __fmul_rn(o.w, g.w)));
   }
 }
 
@@ -2110,20 +2023,20 @@ __global__ __launch_bounds__(256) void affine_drop_add4_kernel(const float* __re
   float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
   if (fixed) {
     const int q = (int)(((long)blockIdx.x * 256 + threadIdx.x) % c4);
-    sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q];
+    sc = ld4(scale, q); sh = ld4(shift, q);
   }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
     const int q = (int)(i % c4);
-    if (!fixed) { sc = reinterpret_cast<const float4*>(scale)[q]; sh = reinterpret_cast<const float4*>(shift)[q]; }
+    if (!fixed) { sc = ld4(scale, q); sh = ld4(shift, q); }
     const uint32_t nimg = divu((uint32_t)i, dhwc4);
     const bool keep = rate <= 0.f || rng_u32(seed, (uint64_t)nimg, 2) >= thr;
-    const float4 v = reinterpret_cast<const float4*>(x)[i], k = reinterpret_cast<const float4*>(skip)[i];
-    float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
+    const float4 v = ld4(x, i), k = ld4(skip, i);
+    float4 o = affine4(v, sc, sh);
     if (rate > 0.f) {
       o.x = keep ? __fmul_rn(o.x, keep_scale) : 0.f; o.y = keep ? __fmul_rn(o.y, keep_scale) : 0.f;
       o.z = keep ? __fmul_rn(o.z, keep_scale) : 0.f; o.w = keep ? __fmul_rn(o.w, keep_scale) : 0.f;
     }
-    reinterpret_cast<float4*>(y)[i] = make_float4(__fadd_rn(o.x, k.x), __fadd_rn(o.y, k.y), __fadd_rn(o.z, k.z), __fadd_rn(o.w, k.w));
+    st4(y, i, make_float4(__fadd_rn(o.x, k.x), __fadd_rn(o.y, k.y), __fadd_rn(o.z, k.z), __fadd_rn(o.w, k.w)));
   }
 }
 
@@ -2174,8 +2087,7 @@ extern "C" size_t embnet_colsum_workspace_bytes(long m, int c) { return embnet_b
 extern "C" int embnet_colsum(const float* x, long m, int c, float* out, void* workspace, size_t workspace_bytes,
                              void* stream) {
   EMBNET_CHECK_ARG(x && out && workspace && m > 0 && c > 0, "colsum: bad argument");
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "colsum: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("colsum", workspace_bytes, m, c)) return e;
   const ColGeom g = col_geom(m, c);
   { EMBNET_TRACE("embnet::colsum_kernel", TRACE_BYTES, 4.0 * m * c, stream); colsum_kernel<<<g.blocks, 256, 0, S(stream)>>>(x, m, c, g, (float*)workspace); }
   colsum_finalize_kernel<<<c, 256, 0, S(stream)>>>((const float*)workspace, g.blocks, c, out);
@@ -2186,8 +2098,7 @@ extern "C" int embnet_relu_bwd_colsum_ex(const float* dy, const float* y, long m
                                          size_t workspace_bytes, uint32_t* dz_range, void* stream) {
   EMBNET_CHECK_ARG(dy && y && dz && dbias && workspace && m > 0 && c > 0, "relu_bwd_colsum: bad argument");
   EMBNET_RANGE_ARG(dz_range, "relu_bwd_colsum");
-  if (workspace_bytes < embnet_bn_workspace_bytes(m, c))
-    return fail(EMBNET_EWORKSPACE, "relu_bwd_colsum: workspace %zu < %zu", workspace_bytes, embnet_bn_workspace_bytes(m, c));
+  if (const int e = bn_workspace_check("relu_bwd_colsum", workspace_bytes, m, c)) return e;
   const ColGeom g = col_geom(m, c);
   range_begin(dz_range, stream);
   { EMBNET_TRACE("embnet::relu_bwd_colsum_kernel", TRACE_BYTES, 12.0 * m * c, stream);
