@@ -5,6 +5,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   triplet_loss(margin)(y_true, y_pred)      reference :14-44  -> per-row [T] (caller means)
   accuracy(y_true, y_pred)                  reference :47-50
   batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
+  multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
 from . import ops
@@ -32,6 +33,18 @@ def batch_all_triplet_loss(k_classes, k_samples, margin=0.5):
 
     def loss_function(y_true, y_pred):
         return ops.batch_all_triplet_loss(y_pred, k_classes, k_samples, margin)[0]
+
+    return loss_function
+
+
+def multi_similarity_loss(k_classes, k_samples, alpha=2.0, beta=50.0, base=0.5, epsilon=0.1):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] embedding
+    block, y_true is ignored (Keras signature).  Multi-similarity loss (Wang et al. 2019; build-defined, not in the
+    reference): pairs mined with `epsilon` on the dot-product similarities, weighted through two log-sum-exps
+    (include/embnet.h, embnet_ms_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.multi_similarity_loss(y_pred, k_classes, k_samples, alpha, beta, base, epsilon)[0]
 
     return loss_function
 

@@ -236,6 +236,60 @@ def batch_all_triplet_loss(emb, k_classes, k_samples, margin, path="auto", retur
     return out if return_weights else out[:3]
 
 
+_MS_WS = {}
+MS_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
+
+
+class _MultiSimilarityLoss(torch.autograd.Function):
+    """Multi-similarity loss (include/embnet.h, embnet_ms_loss_fwd/bwd): one forward launch on the per-class path, similarity
+    matrix + sweep above it; one backward launch.  The pair weights G stay saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, emb, p, k, alpha, beta, base, epsilon, path):
+        emb = _prep(emb)
+        n, e = emb.shape
+        if n != p * k:
+            raise _lib.EmbnetError(f"multi_similarity_loss: {n} rows != k_classes*k_samples = {p}*{k}")
+        lib = _lib.lib()
+        g = _new((n, n), emb)
+        counts = _new((4,), emb, torch.int32)
+        mean = _new((), emb)
+        key = (emb.device.index, stream(), p, k, e)
+        ws = _MS_WS.get(key)
+        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
+            nbytes = lib.embnet_ms_loss_workspace_bytes(p, k, e)
+            ws = _MS_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
+        check(lib.embnet_ms_loss_fwd(ptr(emb), p, k, e, f32(alpha), f32(beta), f32(base), f32(epsilon), MS_PATHS[path],
+                                     ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
+        ctx.save_for_backward(emb, g)
+        ctx.mark_non_differentiable(counts, g)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return mean, counts, g
+
+    @staticmethod
+    def backward(ctx, dmean, _dcounts, _dg):
+        if dmean is None:
+            return (None,) * 8
+        emb, g = ctx.saved_tensors
+        n, e = emb.shape
+        demb = torch.empty_like(emb)
+        check(_lib.lib().embnet_ms_loss_bwd(ptr(emb), n, e, ptr(g), ptr(_prep(dmean)), ptr(demb), stream()))
+        return (demb,) + (None,) * 7
+
+
+def multi_similarity_loss(emb, k_classes, k_samples, alpha=2.0, beta=50.0, base=0.5, epsilon=0.1, path="auto",
+                          return_weights=False):
+    """Multi-similarity loss (Wang et al., CVPR 2019) over a class-contiguous [P*K, E] block, on the dot-product similarities
+    S = X X^T: negatives with S_in + epsilon > min_p S_ip and positives with max_n S_in + epsilon > S_ip are kept, and
+    l_i = log(1 + sum_p e^{-alpha (S_ip - base)}) / alpha + log(1 + sum_n e^{beta (S_in - base)}) / beta, mean over all N anchors
+    (include/embnet.h has the rounding forms).  -> (mean [autograd], counts int32 [4] = kept positives, kept negatives, active
+    anchors, kept pairs) on the device, no host synchronisation; return_weights adds the pair-weight matrix G [N,N] the
+    backward uses.  path: 'auto', 'per_class' or 'similarity_matrix'."""
+    out = _MultiSimilarityLoss.apply(emb, int(k_classes), int(k_samples), float(alpha), float(beta), float(base),
+                                     float(epsilon), path)
+    return out if return_weights else out[:2]
+
+
 # --------------------------------------------------------------------------- contrastive / accuracy
 class _Contrastive(torch.autograd.Function):
     @staticmethod

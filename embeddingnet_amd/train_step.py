@@ -31,17 +31,20 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path (or batch_all); anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
     all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
     negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
     (Hermans: one triplet per anchor) or 'batch_all' (every valid triplet, mean over those with a positive hinge; there are
-    no triplet rows, so last_triplets = (None, n_active)).  Under data parallelism every mode mines and normalises per rank."""
+    no triplet rows, so last_triplets = (None, n_active)) or 'multi_similarity' (Wang et al.: the pair-based loss of
+    ops.multi_similarity_loss with loss_params = dict(alpha, beta, base, epsilon), defaults 2, 50, 0.5, 0.1; `margin` is not
+    used; last_triplets = (None, kept pairs [1]) and last_pair_counts = int32 [4]: kept positives, kept negatives, active
+    anchors, kept pairs).  Under data parallelism every mode mines and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5,
-                 negatives_selection_mode="semihard", seed=0, reducer=None, graph=None):
+                 negatives_selection_mode="semihard", seed=0, reducer=None, graph=None, loss_params=None):
         env = os.environ.get("EMBNET_GRAPH", "0")
         self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
         self._graph, self._graph_failed = None, False
@@ -51,8 +54,14 @@ class TripletTrainer:
         self.ctx = L.StepContext(f"TripletTrainer@{id(self):x}")       # this trainer's fused hand-overs (layers.StepContext)
         # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
         self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
-        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all"):
+        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all", "multi_similarity"):
             raise KeyError(self.mode)
+        self.loss_params = dict(loss_params or {})
+        if self.loss_params and self.mode != "multi_similarity":
+            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity', not {self.mode!r}")
+        unknown = set(self.loss_params) - {"alpha", "beta", "base", "epsilon"}
+        if unknown:
+            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} (alpha, beta, base, epsilon)")
         from .optimizers import KerasOptimizer
         self._keras_opt = isinstance(optimizer, KerasOptimizer)
         if self._keras_opt:
@@ -82,6 +91,11 @@ class TripletTrainer:
             # EMBNET_FUSED_LOSS says); there are no triplet rows: last_triplets = (None, n_active)
             mean, count, _ = ops.batch_all_triplet_loss(emb, self.p, self.k, self.margin)
             self.last_triplets = (None, count)
+        elif self.mode == "multi_similarity":
+            # pair-based: no triplet rows either; the kept-pair count stands where the triplet count does
+            mean, counts = ops.multi_similarity_loss(emb, self.p, self.k, **self.loss_params)
+            count = counts[3:4]
+            self.last_triplets, self.last_pair_counts = (None, count), counts
         elif self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
             seed_dev = self._state.data_ptr() + 24 if self._graph_state_live() else None     # uint64 behind the 6 floats
             mean, _, trip, count = ops.fused_triplet_loss(emb, self.p, self.k, self.margin, self.mode,
@@ -98,7 +112,7 @@ class TripletTrainer:
         return getattr(self, "_state", None) is not None and torch.cuda.is_current_stream_capturing()
 
     def _graph_supported(self, images):
-        if not self._keras_opt or not (self.fused_loss or self.mode == "batch_all"):
+        if not self._keras_opt or not (self.fused_loss or self.mode in ("batch_all", "multi_similarity")):
             return False
         return self.opt.rule != "radam" or self.opt.iterations >= 6      # RAdam switches kernels while it warms up
 
@@ -160,6 +174,7 @@ class TripletTrainer:
                 if self.reducer is not None:
                     self.reducer.hold(False)
             self._g_last = (getattr(self, "last_triplets", None), self.last_total)     # the replayed step's (static) output tensors
+            self._g_pair_counts = getattr(self, "last_pair_counts", None)
             self._graph = g
         except Exception as exc:                                                  # stay correct: eager from here on
             self._graph, self._graph_failed, self._state = None, True, None
@@ -203,6 +218,8 @@ class TripletTrainer:
             self.reducer.reduce_all()                           # bucketed all-reduce, wait, average
             self._graph_opt.replay()
         self.last_triplets, self.last_total = self._g_last      # an eager step in between re-bound them
+        if self._g_pair_counts is not None:
+            self.last_pair_counts = self._g_pair_counts
         return self._gout.clone()                               # callers keep per-step losses; the graph's output is one buffer
 
     def _probe(self, images):

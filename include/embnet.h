@@ -887,6 +887,47 @@ int embnet_batch_all_loss_fwd(const float* emb, int p, int k, int e, float margi
 int embnet_batch_all_loss_bwd(const float* emb, int n, int e, const float* pair_w, const int32_t* n_active,
                               const float* upstream, float* demb, void* stream);
 
+/* Multi-similarity loss (Wang et al., CVPR 2019: the pair-based baseline of "A Metric Learning Reality Check", whose metrics
+ * embnet_retrieval_* report; the reference has no pair-based loss): build-defined, selected as
+ * TripletTrainer(negatives_selection_mode="multi_similarity").  Additions only: the ABI version stays 22.
+ *   Inputs.  emb[n,e] fp32, n = p*k; rows c*k .. c*k+k-1 are class c.
+ *   Similarity.  S_ij = sum_c x_ic x_jc: the cosine similarity of the L2-normalised rows the backbones produce; unit rows are
+ *     not required.
+ *   Parameters.  alpha > 0, beta > 0, base (the paper's lambda), epsilon >= 0; the Python layers default to 2, 50, 0.5, 0.1.
+ *   Pair sets of anchor i.  Positives P_i: the other rows of its class.  Negatives N_i: the rows of other classes.
+ *   Mining, one rounding form (the fp32 add of epsilon to the negative's similarity):
+ *     a negative n is kept iff fl(S_in + epsilon) > min_{p in P_i} S_ip;
+ *     a positive p is kept iff fl(max_{n in N_i} S_in + epsilon) > S_ip.
+ *     fl is monotone, so an anchor keeps both a positive and a negative (it is ACTIVE) or nothing.  The kept sets are constants
+ *     for the backward.
+ *   Per-anchor loss.  t+_p = -alpha (S_ip - base) over kept positives, t-_n = beta (S_in - base) over kept negatives,
+ *     l_i = (1/alpha) log(1 + sum_p e^{t+_p}) + (1/beta) log(1 + sum_n e^{t-_n}),
+ *     each logarithm in the stable form: with m = max(0, max t) the term is m + log(e^{-m} + sum e^{t-m}), so unnormalised
+ *     embeddings cannot overflow.  *mean_loss = (1/n) sum_i l_i; inactive anchors contribute 0.
+ *   Pair weights pair_g[n][n], the derivative of l_i by S_ij (without the 1/n); all n*n entries are written:
+ *     G[i,p] = -e^{t+_p - m+} / (e^{-m+} + sum e^{t+ - m+}) for kept positives,
+ *     G[i,n] = +e^{t-_n - m-} / (e^{-m-} + sum e^{t- - m-}) for kept negatives, 0 elsewhere, the diagonal included.  Every
+ *     row's positive part and negative part each have an absolute sum below 1.
+ *   Backward.  demb_i = (g / n) sum_j (G_ij + G_ji) x_j, g = *upstream (NULL = 1).
+ *   Counters.  counts[4], int32, exact: {kept positives, kept negatives, active anchors, kept positives + kept negatives}.
+ * Range: p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096; alpha, beta finite and positive, base finite, epsilon finite and
+ * non-negative; anything else is rejected before a launch.  path: 0 = auto (embnet_ms_loss_path), EMBNET_MS_PER_CLASS = one
+ * launch, a workgroup per class with its similarity rows in LDS (per-lane fma chain over the columns + wave sum; n <= 512,
+ * k <= 16, k*(e+n) floats in 64 KiB), EMBNET_MS_SIMILARITY_MATRIX = S = X X^T through embnet_dense_dgrad_f32 (a k-ordered fp32
+ * chain per element) into the workspace + a sweep launch over the anchor rows.  The backward is one launch on the f64 matrix
+ * instructions: one fp32 rounding of an f64 sum.  No floating-point atomics, every reduction in a fixed order: bitwise
+ * reproducible; no host synchronisation or allocation.
+ * workspace (embnet_ms_loss_workspace_bytes, either path, 16-byte aligned): zero-filled ONCE by the caller; every launch leaves
+ * its arrival counter zeroed. */
+enum { EMBNET_MS_PER_CLASS = 1, EMBNET_MS_SIMILARITY_MATRIX = 2 };
+int embnet_ms_loss_path(int p, int k, int e);             /* the path `auto` takes; 0 outside the range */
+size_t embnet_ms_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_ms_loss_fwd(const float* emb, int p, int k, int e, float alpha, float beta, float base, float epsilon, int path,
+                       float* pair_g, int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int embnet_ms_loss_bwd(const float* emb, int n, int e, const float* pair_g, const float* upstream, float* demb,
+                       void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

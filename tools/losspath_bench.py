@@ -5,7 +5,8 @@
 
 For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2 batch-hard and C5 (64x4 = 256, E = 512,
 semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
-run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead):
+run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
+ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -27,7 +28,9 @@ from embeddingnet_amd import _lib, ops  # noqa: E402
 CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batch_hard", 32, 4, 256, "batch_hard"),
          ("c5", 64, 4, 512, "semihard"),
          ("c1_batch_all", 8, 4, 256, "batch_all"), ("c2_batch_all", 32, 4, 256, "batch_all"),
-         ("c5_batch_all", 64, 4, 512, "batch_all")]
+         ("c5_batch_all", 64, 4, 512, "batch_all"),
+         ("c1_multi_similarity", 8, 4, 256, "multi_similarity"), ("c2_multi_similarity", 32, 4, 256, "multi_similarity"),
+         ("c5_multi_similarity", 64, 4, 512, "multi_similarity")]
 
 
 def measure(fn, iters):
@@ -52,10 +55,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--only", default=None, help="run only the cases whose name contains this")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     out = []
     for name, p, k, e, mode in CASES:
+        if a.only and a.only not in name:
+            continue
         n = p * k
         g = torch.Generator(device=dev).manual_seed(7)
         c = torch.rand((p, e), device=dev, generator=g)
@@ -84,6 +90,18 @@ def main():
             x.grad = None
             ops.fused_triplet_loss(x, p, k, 0.5, "hardest", seed=1)[0].backward()
 
+        def multi_similarity():
+            x.grad = None
+            ops.multi_similarity_loss(x, p, k)[0].backward()
+
+        if mode == "multi_similarity":                      # the three legs alternate in one process, at one shape
+            row = dict(config=name, N=n, E=e, mining=mode, multi_similarity=measure(multi_similarity, a.iters),
+                       hardest_fused=measure(hardest_fused, a.iters), batch_all=measure(batch_all, a.iters))
+            row["device_ratio_vs_hardest"] = round(row["multi_similarity"]["device_us"] / row["hardest_fused"]["device_us"], 3)
+            row["device_ratio_vs_batch_all"] = round(row["multi_similarity"]["device_us"] / row["batch_all"]["device_us"], 3)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if mode == "batch_all":                             # batch-all beside the fused `hardest` path, same shape and process
             row = dict(config=name, N=n, E=e, mining=mode, batch_all=measure(batch_all, a.iters),
                        hardest_fused=measure(hardest_fused, a.iters))

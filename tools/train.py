@@ -136,6 +136,28 @@ def device_augmentations(cfg, synthetic=0, rank=0):
     return aug
 
 
+MS_LOSS_KEYS = ('alpha', 'beta', 'base', 'epsilon')
+
+
+def ms_loss_config(cfg):
+    """GENERATOR.ms_loss (optional): {alpha, beta, base, epsilon}, any subset, of the multi-similarity loss -> the trainer's
+    loss_params (None without the key).  Only GENERATOR.negatives_selection_mode 'multi_similarity' of a triplet-mode model reads
+    it: given with anything else, or with other keys or non-numbers, it is a ValueError before training starts."""
+    value = cfg['generator'].get('ms_loss')
+    if value is None:
+        return None
+    mode = cfg['generator'].get('negatives_selection_mode')
+    if cfg['model']['mode'] == 'siamese' or mode != 'multi_similarity':
+        raise ValueError(f"GENERATOR.ms_loss sets the parameters of negatives_selection_mode 'multi_similarity'; this config "
+                         f"trains with {'the Siamese contrastive loss' if cfg['model']['mode'] == 'siamese' else repr(mode)}: "
+                         "drop the key or change the mode")
+    if not isinstance(value, dict) or set(value) - set(MS_LOSS_KEYS):
+        raise ValueError(f"GENERATOR.ms_loss: a mapping with keys out of {MS_LOSS_KEYS} (got {value!r})")
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value.values()):
+        raise ValueError(f"GENERATOR.ms_loss: every value must be a number (got {value!r})")
+    return {k: float(v) for k, v in value.items()}
+
+
 MAP_MONITORS = ('val_map@r', 'val_r_precision')
 
 
@@ -189,6 +211,7 @@ def main():
     cfg = parse_params(args.config)
     device_augmentations(cfg, args.synthetic)          # a bad GENERATOR.device_augmentations fails before the GPU is touched
     monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
+    ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
@@ -212,7 +235,7 @@ def main():
         data_loader = ENDataLoader(**{k: v for k, v in p_loader.items() if k != 'csv_file'})
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
-    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed')}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -264,7 +287,7 @@ def main():
     else:
         trainer = TripletTrainer(
             model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], margin=p_gen['margin'],
-            negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer)
+            negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer, loss_params=ms_loss)
     plateau = Plateau(persistent=bool(p_train.get('plateau_persistent', False)))
     history = {'loss': [], 'val_loss': []}
     for k in retrieval_ks:
