@@ -7,8 +7,8 @@ import importlib.abc
 import importlib.util
 import sys
 
-_MODULES = ("backbones", "datagenerators", "losses_and_accuracies", "models", "parallel", "retrieval", "train_step",
-            "utils")
+_MODULES = ("backbones", "clustering", "datagenerators", "kmeans", "losses_and_accuracies", "models", "parallel", "retrieval",
+            "train_step", "utils")
 
 
 class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):

@@ -206,6 +206,14 @@ class EmbeddingNet:
         encodings, labels, kw = self._encode_validation("calculate_map_at_r", data_loader, gallery, batch_size)
         return retrieval_map_metrics(encodings, labels, **kw)
 
+    def calculate_clustering_metrics(self, data_loader, n_clusters=None, seed=0, n_init=1, batch_size=256):
+        """NMI (and homogeneity, completeness, purity) of a k-means clustering of data_loader.val_data's encodings against
+        their class labels (clustering.clustering_metrics).  n_clusters None: the number of validation classes.  The
+        validation items are encoded as in calculate_retrieval_metrics."""
+        from .clustering import clustering_metrics
+        encodings, labels, kw = self._encode_validation("calculate_clustering_metrics", data_loader, 'val', batch_size)
+        return clustering_metrics(encodings, labels, n_clusters=n_clusters, seed=seed, n_init=n_init, device=kw['device'])
+
 
 class _ClsHead(nn.Module):
     def __init__(self, base_model, e):

@@ -611,3 +611,98 @@ def retrieval_map_reduce(offset, pos_rank):
     check(_lib.lib().embnet_retrieval_map_reduce(ptr(offset), ptr(pos_rank), nq, ptr(per[0]), ptr(per[1]), ptr(per[2]), ptr(sums),
                                                  ptr(n_valid), stream()))
     return per[0], per[1], per[2], sums, n_valid
+
+
+# --------------------------------------------------------------------------- k-means on encodings (csrc/kmeans.hip)
+def _kmeans_block(who, t, name):
+    """A block is taken as it is or refused: float32, contiguous, [rows, e] on the device.  (A silent copy would hide a cast
+    of a whole encodings block per Lloyd pass.)"""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _lib.EmbnetError(f"{who}: {name} must be a float32 tensor (got {getattr(t, 'dtype', type(t))})")
+    if t.dim() != 2:
+        raise _lib.EmbnetError(f"{who}: {name} must be [rows, e] (got {tuple(t.shape)})")
+    if not t.is_contiguous():
+        raise _lib.EmbnetError(f"{who}: {name} must be contiguous")
+    return t.detach()
+
+
+def _kmeans_labels(who, labels, n):
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise _lib.EmbnetError(f"{who}: labels must be a contiguous int32 tensor of {n} entries")
+    return labels
+
+
+def _kmeans_shapes(who, x, centres):
+    x, centres = _kmeans_block(who, x, "points"), _kmeans_block(who, centres, "centres")
+    if x.shape[1] != centres.shape[1]:
+        raise _lib.EmbnetError(f"{who}: widths differ (points e = {x.shape[1]}, centres e = {centres.shape[1]})")
+    return x, centres, x.shape[0], centres.shape[0], x.shape[1]
+
+
+def kmeans_workspace(n, k, e, like):
+    """The workspace every k-means call of one (n, k, e) problem shares; it also carries the point norms from the first assign
+    pass of a fit to the later ones.  A refused shape (k > n, a size <= 0) gets a token workspace: the call itself reports it."""
+    nbytes = _lib.lib().embnet_kmeans_workspace_bytes(int(n), int(k), int(e))
+    return _new((max(nbytes // 8, 2),), like, torch.float64)
+
+
+def kmeans_assign(x, centres, prev_labels=None, ws=None, reuse_point_norms=False):
+    """Nearest centre of every point, without the [n,k] distance matrix (include/embnet.h).
+
+    x [n,e], centres [k,e] float32.  -> (labels int32 [n]: ties to the smaller centre index; d2 float32 [n]: the squared distance
+    to that centre; changed int32 []: the labels that differ from prev_labels (n without them); inertia float64 []: sum d2),
+    on the device.  ws: kmeans_workspace(n, k, e, x); reuse_point_norms: ws already went through an assign call on this x."""
+    x, centres, n, k, e = _kmeans_shapes("kmeans_assign", x, centres)
+    if prev_labels is not None:
+        prev_labels = _kmeans_labels("kmeans_assign", prev_labels, n)
+    if ws is None:
+        ws, reuse_point_norms = kmeans_workspace(n, k, e, x), False
+    labels, d2 = _new((n,), x, torch.int32), _new((n,), x)
+    changed, inertia = _new((), x, torch.int32), _new((), x, torch.float64)
+    check(_lib.lib().embnet_kmeans_assign(ptr(x), n, ptr(centres), k, e, int(bool(reuse_point_norms)), ptr(prev_labels), ptr(labels),
+                                          ptr(d2), ptr(changed), ptr(inertia), ptr(ws), ws.numel() * 8, stream()))
+    return labels, d2, changed, inertia
+
+
+def kmeans_update(x, labels, centres, ws=None):
+    """The mean of every cluster's points (include/embnet.h).  x [n,e], labels int32 [n], centres [k,e] the previous centres.
+    -> (centres float32 [k,e]: an empty cluster keeps its previous centre; counts int32 [k]; shift float64 []: the sum of
+    |new - old|^2; n_empty int32 []), on the device; the same bits for the same labels."""
+    x, centres, n, k, e = _kmeans_shapes("kmeans_update", x, centres)
+    labels = _kmeans_labels("kmeans_update", labels, n)
+    if ws is None:
+        ws = kmeans_workspace(n, k, e, x)
+    out, counts = _new((k, e), x), _new((k,), x, torch.int32)
+    shift, n_empty = _new((), x, torch.float64), _new((), x, torch.int32)
+    check(_lib.lib().embnet_kmeans_update(ptr(x), ptr(labels), n, ptr(centres), k, e, ptr(out), ptr(counts), ptr(shift),
+                                          ptr(n_empty), ptr(ws), ws.numel() * 8, stream()))
+    return out, counts, shift, n_empty
+
+
+def kmeans_pp_update(x, index, mind2=None):
+    """k-means++ weights: mind2[i] = min(mind2[i], |x_i - x_c|^2) for the row c = index (int32 device tensor of one entry);
+    mind2 None: the first call, which creates it.  -> mind2 float32 [n] (updated in place when given)."""
+    x = _kmeans_block("kmeans_pp_update", x, "points")
+    n, e = x.shape
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or index.numel() != 1:
+        raise _lib.EmbnetError("kmeans_pp_update: index must be an int32 tensor of one entry")
+    first = mind2 is None
+    if first:
+        mind2 = _new((n,), x)
+    elif mind2.dtype != torch.float32 or tuple(mind2.shape) != (n,):
+        raise _lib.EmbnetError(f"kmeans_pp_update: mind2 must be float32 [{n}]")
+    check(_lib.lib().embnet_kmeans_pp_update(ptr(x), n, e, ptr(index), int(first), ptr(mind2), stream()))
+    return mind2
+
+
+def kmeans_pp_pick(mind2, seed, draw):
+    """Draw `draw` of a k-means++ seeding keyed by `seed`: draw 0 is uniform over the n rows (only mind2's length and device are
+    used); draw j >= 1 samples a row with probability mind2 / sum(mind2), never one of weight 0 while the sum is positive.
+    -> (index int32 [1], u float64 []: the draw's uniform number, 0 for draw 0) on the device."""
+    like = mind2
+    if not torch.is_tensor(mind2) or mind2.dtype != torch.float32 or mind2.dim() != 1 or mind2.numel() == 0:
+        raise _lib.EmbnetError("kmeans_pp_pick: mind2 must be a non-empty float32 [n] tensor")
+    index, u = _new((1,), like, torch.int32), _new((), like, torch.float64)
+    check(_lib.lib().embnet_kmeans_pp_pick(ptr(mind2), mind2.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), ptr(index), ptr(u),
+                                           stream()))
+    return index, u

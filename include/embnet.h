@@ -207,6 +207,44 @@ int embnet_retrieval_positive_ranks(const float* q, const int32_t* q_labels, int
 int embnet_retrieval_map_reduce(const long long* offset, const int32_t* pos_rank, int nq,
                                 double* ap_at_r, double* r_precision, double* ap, double* sums, int32_t* n_valid, void* stream);
 
+/* ---- k-means on encodings (the clustering behind the NMI evaluation; scikit-learn KMeans(algorithm='lloyd') is what it stands in
+ * for, the reference has none): csrc/kmeans.hip.  Additions only: the ABI version stays 22.
+ *   Shapes: points x[n,e], centres[k,e], 1 <= k <= n, each block below 2 GiB.  One workspace serves all of a fit's calls:
+ *     >= embnet_kmeans_workspace_bytes(n, k, e) bytes (0 for a refused shape), 16-byte aligned, no initialisation needed, short -> -3.
+ *     It grows as O(n + (n / 512 + k) * e) bytes.  Nothing allocates or synchronises.
+ * embnet_kmeans_assign: labels[i] = the centre nearest to point i.  Distance, NaN rule and order are those of
+ *     embnet_retrieval_first_positive (the same walk of the fp32 distance GEMM with the points as queries and the centres as
+ *     gallery): d2 = max(|x|^2 + |c|^2 - 2 x.c, 0), NaN -> +inf, order (d2, centre index) — ties go to the smaller index, exactly.
+ *     A point without a finite distance takes label 0 and d2 = +inf.  No [n,k] matrix is formed.
+ *       labels[n] int32, d2[n] float (to the chosen centre)
+ *       *changed int32 = #{i : labels[i] != labels_prev[i]} (labels_prev NULL: n); labels_prev must not be `labels`
+ *       *inertia f64 = sum of d2 in a fixed order (8-byte aligned)
+ *     reuse_point_norms != 0: the point norms an earlier call on the SAME x left in this workspace are used again (a fit computes
+ *     them once); the centre norms are computed by every call.  A minimum, an integer count and fixed-order sums: two calls
+ *     return the same bits.
+ * embnet_kmeans_update: centres_out[j] = the mean of the points with labels[i] == j (centres_out may be `centres`).
+ *       count[k] int32, exact.  A label outside [0,k) belongs to no cluster.
+ *       Each element is summed in f64 in an order that depends on (n, e, k, labels) alone — a cluster's points ascending by index
+ *       in chunks of 512, four interleaved row chains per chunk, the chunks in order — divided in f64 and rounded to f32 once.
+ *       A cluster without points keeps its centre bit for bit; *n_empty int32 counts them.
+ *       *shift f64 = sum over the non-empty clusters of |new - old|^2, fixed order (8-byte aligned).
+ * embnet_kmeans_pp_update / embnet_kmeans_pp_pick: k-means++ seeding by plain D^2 sampling, one draw per centre (not
+ *     scikit-learn's greedy variant).  pp_update: mind2[i] = min(mind2[i], |x_i - x_c|^2) for the row c = *index (device), by the
+ *     lane-strided fp32 chain on the difference; first != 0 stores instead of taking the minimum.  pp_pick, draw 0:
+ *     *index = rng(seed, 0, 0) mod n and *u = 0 (mind2 may be NULL).  Draw j >= 1: *u = (53 bits of rng(seed, j, 0) : rng(seed, j, 1))
+ *     * 2^-53 (f64, 8-byte aligned); *index = the first row of positive weight whose inclusive f64 prefix sum of mind2 (fixed
+ *     two-level order) exceeds *u * total, so a row of weight 0 is never drawn while total > 0; total == 0: floor(*u * n).
+ *     A non-finite or negative mind2 weighs 0.  rng is the library's counter-based generator (csrc/common.h rng_u32). */
+size_t embnet_kmeans_workspace_bytes(int n, int k, int e);
+int embnet_kmeans_assign(const float* x, int n, const float* centres, int k, int e, int reuse_point_norms,
+                         const int32_t* labels_prev, int32_t* labels, float* d2, int32_t* changed, double* inertia,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int embnet_kmeans_update(const float* x, const int32_t* labels, int n, const float* centres, int k, int e,
+                         float* centres_out, int32_t* count, double* shift, int32_t* n_empty,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int embnet_kmeans_pp_update(const float* x, int n, int e, const int32_t* index, int first, float* mind2, void* stream);
+int embnet_kmeans_pp_pick(const float* mind2, int n, uint64_t seed, int draw, int32_t* index, double* u, void* stream);
+
 /* ------------------------------------------------------------------ backbone layers
  * Stand-ins for the Keras layers that backbones.py:19-121 instantiates (TensorFlow kernels in the
  * reference).  All NHWC fp32. */

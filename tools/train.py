@@ -172,13 +172,25 @@ def retrieval_map_config(p_train, validate):
     return on
 
 
+def clustering_nmi_config(p_train, validate):
+    """TRAIN.clustering_nmi (optional, default off) -> bool: after each epoch's validation, the NMI of a k-means clustering of the
+    validation encodings against their classes (EmbeddingNet.calculate_clustering_metrics, as many clusters as classes, seed 0)
+    joins the history as val_nmi."""
+    on = p_train.get('clustering_nmi') or False
+    if not isinstance(on, bool):
+        raise ValueError(f"TRAIN.clustering_nmi: true or false (got {on!r})")
+    if on and not validate:
+        raise ValueError("TRAIN.clustering_nmi evaluates the validation set: it needs DATALOADER.validate (validation is off)")
+    return on
+
+
 def monitor_config(p_train, validate):
     """TRAIN.retrieval_ks / TRAIN.monitor (both optional) -> (the K's of the per-epoch retrieval evaluation, the monitored name).
     retrieval_ks: after each epoch's validation, Recall@K and MRR of the validation set (leave-one-out,
     EmbeddingNet.calculate_retrieval_metrics) join the history as val_recall@K / val_mrr.  monitor: what plateau, early stop and
     best checkpoint follow — 'val_loss' ('loss' without validation) by default, or 'loss', 'val_recall@K' with K in
-    retrieval_ks, 'val_mrr', and with TRAIN.retrieval_map (retrieval_map_config) 'val_map@r' / 'val_r_precision' — larger is better
-    for all of those.  Anything that cannot be honoured is a ValueError before training starts."""
+    retrieval_ks, 'val_mrr', with TRAIN.retrieval_map (retrieval_map_config) 'val_map@r' / 'val_r_precision', and with
+    TRAIN.clustering_nmi (clustering_nmi_config) 'val_nmi' — larger is better for all of those.  Anything that cannot be honoured is a ValueError before training starts."""
     ks = p_train.get('retrieval_ks') or []
     if isinstance(ks, (int, float)):
         ks = [ks]
@@ -200,9 +212,12 @@ def monitor_config(p_train, validate):
     elif monitor in MAP_MONITORS:
         if not retrieval_map_config(p_train, validate):
             raise ValueError(f"TRAIN.monitor: {monitor!r} needs TRAIN.retrieval_map")
+    elif monitor == 'val_nmi':
+        if not clustering_nmi_config(p_train, validate):
+            raise ValueError("TRAIN.monitor: 'val_nmi' needs TRAIN.clustering_nmi")
     elif monitor not in ('loss', 'val_loss'):
         raise ValueError(f"TRAIN.monitor: unknown name {monitor!r} (loss, val_loss, val_recall@K, val_mrr, val_map@r, "
-                         "val_r_precision)")
+                         "val_r_precision, val_nmi)")
     return ks, monitor
 
 
@@ -213,6 +228,7 @@ def main():
     monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
     ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
+    clustering_nmi_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
     paths = create_save_folders(cfg['general'])
@@ -235,6 +251,7 @@ def main():
         data_loader = ENDataLoader(**{k: v for k, v in p_loader.items() if k != 'csv_file'})
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
+    clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss')}
 
     siamese = p_model['mode'] == 'siamese'
@@ -296,6 +313,8 @@ def main():
         history['val_mrr'] = []
     if retrieval_map:
         history['val_map@r'], history['val_r_precision'] = [], []
+    if clustering_nmi:
+        history['val_nmi'] = []
     n_epochs = min(p_train['n_epochs'], args.max_epochs or p_train['n_epochs'])
 
     # triplet mode: batches are planned on this thread and decoded / uploaded ahead of the step (input_pipeline.Feeder: the
@@ -358,6 +377,11 @@ def main():
                     for name in ('map@r', 'r_precision'):
                         history['val_' + name].append(all_reduce_mean(float(found[name])))
                         msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                if clustering_nmi:
+                    with torch.no_grad():
+                        found = model.calculate_clustering_metrics(data_loader)
+                    history['val_nmi'].append(all_reduce_mean(float(found['nmi'])))
+                    msg += f" - val_nmi {history['val_nmi'][-1]:.4f}"
                 if monitor == 'loss':
                     value = epoch_loss
                 elif monitor != 'val_loss':
