@@ -6,6 +6,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   accuracy(y_true, y_pred)                  reference :47-50
   batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
   multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
+  supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
 from . import ops
@@ -45,6 +46,18 @@ def multi_similarity_loss(k_classes, k_samples, alpha=2.0, beta=50.0, base=0.5, 
 
     def loss_function(y_true, y_pred):
         return ops.multi_similarity_loss(y_pred, k_classes, k_samples, alpha, beta, base, epsilon)[0]
+
+    return loss_function
+
+
+def supcon_loss(k_classes, k_samples, temperature=0.1, denominator="all"):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] embedding
+    block, y_true is ignored (Keras signature).  The softmax / InfoNCE family (build-defined, not in the reference):
+    denominator 'all' is SupCon (Khosla et al. 2020, L_out), 'negatives' NT-Xent with the pair itself and the anchor's
+    negatives in the denominator (include/embnet.h, embnet_supcon_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.supcon_loss(y_pred, k_classes, k_samples, temperature, denominator)[0]
 
     return loss_function
 

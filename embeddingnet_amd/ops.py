@@ -290,6 +290,61 @@ def multi_similarity_loss(emb, k_classes, k_samples, alpha=2.0, beta=50.0, base=
     return out if return_weights else out[:2]
 
 
+_SUPCON_WS = {}
+SUPCON_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
+SUPCON_DENOMINATORS = {"all": 1, "negatives": 2}
+
+
+class _SupconLoss(torch.autograd.Function):
+    """SupCon / NT-Xent (include/embnet.h, embnet_supcon_loss_fwd): one forward launch on the per-class path, similarity matrix +
+    sweep above it; the backward is embnet_ms_loss_bwd's one launch on the saved pair weights G."""
+
+    @staticmethod
+    def forward(ctx, emb, p, k, temperature, denominator, path):
+        emb = _prep(emb)
+        n, e = emb.shape
+        if n != p * k:
+            raise _lib.EmbnetError(f"supcon_loss: {n} rows != k_classes*k_samples = {p}*{k}")
+        if denominator not in SUPCON_DENOMINATORS:
+            raise _lib.EmbnetError(f"supcon_loss: denominator {denominator!r} is not one of {sorted(SUPCON_DENOMINATORS)}")
+        lib = _lib.lib()
+        g = _new((n, n), emb)
+        counts = _new((2,), emb, torch.int32)
+        mean = _new((), emb)
+        key = (emb.device.index, stream(), p, k, e)
+        ws = _SUPCON_WS.get(key)
+        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
+            nbytes = lib.embnet_supcon_loss_workspace_bytes(p, k, e)
+            ws = _SUPCON_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
+        check(lib.embnet_supcon_loss_fwd(ptr(emb), p, k, e, f32(temperature), SUPCON_DENOMINATORS[denominator],
+                                         SUPCON_PATHS[path], ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
+        ctx.save_for_backward(emb, g)
+        ctx.mark_non_differentiable(counts, g)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return mean, counts, g
+
+    @staticmethod
+    def backward(ctx, dmean, _dcounts, _dg):
+        if dmean is None:
+            return (None,) * 6
+        emb, g = ctx.saved_tensors
+        n, e = emb.shape
+        demb = torch.empty_like(emb)
+        check(_lib.lib().embnet_ms_loss_bwd(ptr(emb), n, e, ptr(g), ptr(_prep(dmean)), ptr(demb), stream()))
+        return (demb,) + (None,) * 5
+
+
+def supcon_loss(emb, k_classes, k_samples, temperature=0.1, denominator="all", path="auto", return_weights=False):
+    """The softmax / InfoNCE family over a class-contiguous [P*K, E] block, on the logits t = S / temperature, S = X X^T.
+    denominator 'all': SupCon (Khosla et al. 2020, L_out), l_i = lse_{a != i} t_ia - mean_p t_ip; 'negatives': NT-Xent as
+    pytorch-metric-learning has it, l_i = mean_p (log(e^{t_ip} + sum_n e^{t_in}) - t_ip); mean over all N anchors (include/embnet.h
+    has the rounding and the stable forms).  -> (mean [autograd], counts int32 [2] = positive pairs, violating anchors: those
+    whose hardest negative is at least as similar as their hardest positive) on the device, no host synchronisation;
+    return_weights adds the pair-weight matrix G [N,N] the backward uses.  path: 'auto', 'per_class' or 'similarity_matrix'."""
+    out = _SupconLoss.apply(emb, int(k_classes), int(k_samples), float(temperature), denominator, path)
+    return out if return_weights else out[:2]
+
+
 # --------------------------------------------------------------------------- contrastive / accuracy
 class _Contrastive(torch.autograd.Function):
     @staticmethod

@@ -31,7 +31,7 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity); anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
     all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
     negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
@@ -39,8 +39,12 @@ class TripletTrainer:
     no triplet rows, so last_triplets = (None, n_active)) or 'multi_similarity' (Wang et al.: the pair-based loss of
     ops.multi_similarity_loss with loss_params = dict(alpha, beta, base, epsilon), defaults 2, 50, 0.5, 0.1; `margin` is not
     used; last_triplets = (None, kept pairs [1]) and last_pair_counts = int32 [4]: kept positives, kept negatives, active
-    anchors, kept pairs).  Under data parallelism every mode mines and normalises per rank."""
+    anchors, kept pairs) or 'supcon' (the softmax / InfoNCE family of ops.supcon_loss with loss_params = dict(temperature,
+    denominator), defaults 0.1 and 'all' = SupCon, 'negatives' = NT-Xent; `margin` is not used; last_triplets = (None, violating
+    anchors [1]) and last_pair_counts = int32 [2]: positive pairs, violating anchors).  Under data parallelism every mode mines
+    and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
+    LOSS_PARAMS = {"multi_similarity": ("alpha", "beta", "base", "epsilon"), "supcon": ("temperature", "denominator")}
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5,
@@ -54,14 +58,15 @@ class TripletTrainer:
         self.ctx = L.StepContext(f"TripletTrainer@{id(self):x}")       # this trainer's fused hand-overs (layers.StepContext)
         # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
         self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
-        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all", "multi_similarity"):
+        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all", "multi_similarity", "supcon"):
             raise KeyError(self.mode)
         self.loss_params = dict(loss_params or {})
-        if self.loss_params and self.mode != "multi_similarity":
-            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity', not {self.mode!r}")
-        unknown = set(self.loss_params) - {"alpha", "beta", "base", "epsilon"}
+        if self.loss_params and self.mode not in self.LOSS_PARAMS:
+            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity' or 'supcon', not {self.mode!r}")
+        unknown = set(self.loss_params) - set(self.LOSS_PARAMS.get(self.mode, ()))
         if unknown:
-            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} (alpha, beta, base, epsilon)")
+            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} for {self.mode!r} "
+                             f"({', '.join(self.LOSS_PARAMS[self.mode])})")
         from .optimizers import KerasOptimizer
         self._keras_opt = isinstance(optimizer, KerasOptimizer)
         if self._keras_opt:
@@ -96,6 +101,11 @@ class TripletTrainer:
             mean, counts = ops.multi_similarity_loss(emb, self.p, self.k, **self.loss_params)
             count = counts[3:4]
             self.last_triplets, self.last_pair_counts = (None, count), counts
+        elif self.mode == "supcon":
+            # softmax family: no triplet rows; the violating-anchor count stands where the triplet count does
+            mean, counts = ops.supcon_loss(emb, self.p, self.k, **self.loss_params)
+            count = counts[1:2]
+            self.last_triplets, self.last_pair_counts = (None, count), counts
         elif self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
             seed_dev = self._state.data_ptr() + 24 if self._graph_state_live() else None     # uint64 behind the 6 floats
             mean, _, trip, count = ops.fused_triplet_loss(emb, self.p, self.k, self.margin, self.mode,
@@ -112,7 +122,7 @@ class TripletTrainer:
         return getattr(self, "_state", None) is not None and torch.cuda.is_current_stream_capturing()
 
     def _graph_supported(self, images):
-        if not self._keras_opt or not (self.fused_loss or self.mode in ("batch_all", "multi_similarity")):
+        if not self._keras_opt or not (self.fused_loss or self.mode in ("batch_all", "multi_similarity", "supcon")):
             return False
         return self.opt.rule != "radam" or self.opt.iterations >= 6      # RAdam switches kernels while it warms up
 

@@ -966,6 +966,43 @@ int embnet_ms_loss_fwd(const float* emb, int p, int k, int e, float alpha, float
 int embnet_ms_loss_bwd(const float* emb, int n, int e, const float* pair_g, const float* upstream, float* demb,
                        void* stream);
 
+/* SupCon / NT-Xent (the softmax / InfoNCE family of the Reality Check's loss table; the reference has no such loss):
+ * build-defined, selected as TripletTrainer(negatives_selection_mode="supcon").  Additions only: the ABI version stays 22.
+ *   Inputs.  emb[n,e] fp32, n = p*k; rows c*k .. c*k+k-1 are class c.  S = X X^T; unit rows are not required.
+ *   Pair sets of anchor i.  Positives P_i: the other rows of its class, |P_i| = k-1.  Negatives N_i: the rows of other classes.
+ *   Parameters.  temperature tau, positive and finite, with fl(1/tau) a normal fp32 number; denominator EMBNET_SUPCON_ALL or
+ *     EMBNET_SUPCON_NEGATIVES.  The Python layers default to 0.1 and `all`.
+ *   Logit.  t_ij = S_ij / tau, in ONE rounding form: t_ij = fl(S_ij * r) with r = fl(1/tau), one correctly rounded division taken
+ *     once per call.  r > 0 and fl is monotone: the order of the logits is the order of S.
+ *   EMBNET_SUPCON_ALL (SupCon: Khosla et al., NeurIPS 2020, the L_out form).
+ *     l_i = lse_{a != i} t_ia - (1/(k-1)) sum_{p in P_i} t_ip,
+ *     G_ij = dl_i/dS_ij = (1/tau) (softmax_{a != i}(t_i.)_j - [j in P_i] / (k-1)),  G_ii = 0.
+ *   EMBNET_SUPCON_NEGATIVES (NT-Xent as "A Metric Learning Reality Check" and pytorch-metric-learning define it: the denominator
+ *     holds the pair itself and the anchor's negatives only).  d_ip = e^{t_ip} + sum_{n in N_i} e^{t_in},
+ *     l_ip = log d_ip - t_ip,  l_i = (1/(k-1)) sum_p l_ip,
+ *     G_ip = (1/tau) (1/(k-1)) (e^{t_ip} / d_ip - 1),  G_in = (1/tau) (1/(k-1)) e^{t_in} sum_p 1 / d_ip,  G_ii = 0.
+ *   Stable forms (part of the contract: every logarithm takes an argument >= 1, so no input of finite S overflows or takes
+ *     log 0).  `all`: with M = max_{a != i} t_ia,  l_i = log(sum_{a != i} e^{t_ia - M}) + (1/(k-1)) sum_p (M - t_ip).
+ *     `negatives`: the maximum is PER PAIR, m_ip = max(t_ip, max_n t_in):
+ *     l_ip = (m_ip - t_ip) + log(e^{t_ip - m_ip} + e^{max_n t_in - m_ip} sum_n e^{t_in - max_n t_in}).
+ *   Common.  *mean_loss = (1/n) sum_i l_i.  pair_g[n][n] = G (without the 1/n); all n*n entries are written; every row of G sums
+ *     to zero in exact arithmetic.  Backward: demb_i = (g / n) sum_j (G_ij + G_ji) x_j, g = *upstream (NULL = 1) — this is
+ *     embnet_ms_loss_bwd's contract, and embnet_ms_loss_bwd(emb, n, e, pair_g, upstream, demb, stream) is the backward.
+ *   Counters.  counts[2], int32, exact: counts[0] = positive pairs n (k-1); counts[1] = violating anchors, the anchors with
+ *     max_{n in N_i} S_in >= min_{p in P_i} S_ip on the device's fp32 S (it goes to zero as the classes separate).
+ * Range: p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096; anything else is rejected before a launch.  path: 0 = auto
+ * (embnet_supcon_loss_path), EMBNET_SUPCON_PER_CLASS, EMBNET_SUPCON_SIMILARITY_MATRIX: the two forward paths, the fit rule and the
+ * workspace of embnet_ms_loss_fwd (the kernels share one skeleton, csrc/pair_loss.h).  No floating-point atomics, every
+ * reduction in a fixed order: bitwise reproducible; no host synchronisation or allocation.
+ * workspace (embnet_supcon_loss_workspace_bytes, either path, 16-byte aligned): zero-filled ONCE by the caller; every launch
+ * leaves its arrival counter zeroed. */
+enum { EMBNET_SUPCON_ALL = 1, EMBNET_SUPCON_NEGATIVES = 2 };
+enum { EMBNET_SUPCON_PER_CLASS = 1, EMBNET_SUPCON_SIMILARITY_MATRIX = 2 };
+int embnet_supcon_loss_path(int p, int k, int e);         /* the path `auto` takes; 0 outside the range */
+size_t embnet_supcon_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_supcon_loss_fwd(const float* emb, int p, int k, int e, float temperature, int denominator, int path, float* pair_g,
+                           int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

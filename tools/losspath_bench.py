@@ -6,7 +6,8 @@
 For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2 batch-hard and C5 (64x4 = 256, E = 512,
 semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
-ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all):
+ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
+denominator beside ops.multi_similarity_loss):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -30,7 +31,8 @@ CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batc
          ("c1_batch_all", 8, 4, 256, "batch_all"), ("c2_batch_all", 32, 4, 256, "batch_all"),
          ("c5_batch_all", 64, 4, 512, "batch_all"),
          ("c1_multi_similarity", 8, 4, 256, "multi_similarity"), ("c2_multi_similarity", 32, 4, 256, "multi_similarity"),
-         ("c5_multi_similarity", 64, 4, 512, "multi_similarity")]
+         ("c5_multi_similarity", 64, 4, 512, "multi_similarity"),
+         ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")]
 
 
 def measure(fn, iters):
@@ -94,6 +96,21 @@ def main():
             x.grad = None
             ops.multi_similarity_loss(x, p, k)[0].backward()
 
+        def supcon(denominator):
+            def leg():
+                x.grad = None
+                ops.supcon_loss(x, p, k, 0.1, denominator)[0].backward()
+            return leg
+
+        if mode == "supcon":                                # the three legs alternate in one process, at one shape
+            row = dict(config=name, N=n, E=e, mining=mode, supcon_all=measure(supcon("all"), a.iters),
+                       supcon_negatives=measure(supcon("negatives"), a.iters),
+                       multi_similarity=measure(multi_similarity, a.iters))
+            for leg in ("supcon_all", "supcon_negatives"):
+                row[f"device_ratio_{leg}_vs_multi_similarity"] = round(row[leg]["device_us"] / row["multi_similarity"]["device_us"], 3)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if mode == "multi_similarity":                      # the three legs alternate in one process, at one shape
             row = dict(config=name, N=n, E=e, mining=mode, multi_similarity=measure(multi_similarity, a.iters),
                        hardest_fused=measure(hardest_fused, a.iters), batch_all=measure(batch_all, a.iters))

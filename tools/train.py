@@ -158,6 +158,37 @@ def ms_loss_config(cfg):
     return {k: float(v) for k, v in value.items()}
 
 
+SUPCON_LOSS_KEYS = ('temperature', 'denominator')
+
+
+def supcon_loss_config(cfg):
+    """GENERATOR.supcon_loss (optional): {temperature, denominator}, any subset, of the SupCon / NT-Xent loss -> the trainer's
+    loss_params (None without the key).  Only GENERATOR.negatives_selection_mode 'supcon' of a triplet-mode model reads it: given
+    with anything else, or with other keys, a temperature that is no number or a denominator other than 'all' / 'negatives', it
+    is a ValueError before training starts."""
+    value = cfg['generator'].get('supcon_loss')
+    if value is None:
+        return None
+    mode = cfg['generator'].get('negatives_selection_mode')
+    if cfg['model']['mode'] == 'siamese' or mode != 'supcon':
+        raise ValueError(f"GENERATOR.supcon_loss sets the parameters of negatives_selection_mode 'supcon'; this config "
+                         f"trains with {'the Siamese contrastive loss' if cfg['model']['mode'] == 'siamese' else repr(mode)}: "
+                         "drop the key or change the mode")
+    if not isinstance(value, dict) or set(value) - set(SUPCON_LOSS_KEYS):
+        raise ValueError(f"GENERATOR.supcon_loss: a mapping with keys out of {SUPCON_LOSS_KEYS} (got {value!r})")
+    out = {}
+    if 'temperature' in value:
+        t = value['temperature']
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not t > 0:
+            raise ValueError(f"GENERATOR.supcon_loss: temperature must be a positive number (got {t!r})")
+        out['temperature'] = float(t)
+    if 'denominator' in value:
+        if value['denominator'] not in ('all', 'negatives'):
+            raise ValueError(f"GENERATOR.supcon_loss: denominator must be 'all' or 'negatives' (got {value['denominator']!r})")
+        out['denominator'] = value['denominator']
+    return out
+
+
 MAP_MONITORS = ('val_map@r', 'val_r_precision')
 
 
@@ -227,6 +258,8 @@ def main():
     device_augmentations(cfg, args.synthetic)          # a bad GENERATOR.device_augmentations fails before the GPU is touched
     monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
     ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
+    supcon_loss = supcon_loss_config(cfg)              # and GENERATOR.supcon_loss
+    loss_params = ms_loss if ms_loss is not None else supcon_loss      # each is refused with the other's mode: at most one is set
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     clustering_nmi_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
@@ -252,7 +285,7 @@ def main():
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
-    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss')}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -304,7 +337,7 @@ def main():
     else:
         trainer = TripletTrainer(
             model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], margin=p_gen['margin'],
-            negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer, loss_params=ms_loss)
+            negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer, loss_params=loss_params)
     plateau = Plateau(persistent=bool(p_train.get('plateau_persistent', False)))
     history = {'loss': [], 'val_loss': []}
     for k in retrieval_ks:
