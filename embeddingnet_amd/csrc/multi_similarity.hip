@@ -11,9 +11,9 @@
 //   backward, kept sets held constant:  demb_i = (g / N) sum_j (G_ij + G_ji) x_j.
 //   counts = {kept positives, kept negatives, active anchors, kept positives + kept negatives}, exact.
 //
-// The forward's skeleton (similarity staging, row copy, ticket, reduction, workspace, fit rule) is pair_loss.h's, shared with
-// supcon.hip; this file holds the per-anchor body, the kernels' names and the backward.
-// Forward, per-class path (N <= 512, K <= 16, K (E + N) floats in 64 KiB of LDS: batch_all.hip's fit rule), ONE launch: a
+// The skeleton (similarity staging, row copy, ticket, reduction, workspace, fit rule, the backward's product) is pair_loss.h's,
+// shared with batch_all.hip and supcon.hip; this file holds the per-anchor body, the epilogue and the kernels' names.
+// Forward, per-class path (N <= 512, K <= 16, K (E + N) floats in 64 KiB of LDS), ONE launch: a
 // workgroup per class holds its K rows and their K x N similarity rows in LDS (per-lane fmaf chain over the columns + wave sum),
 // one wave per anchor mines, sums and writes the anchor's row of G (rows belong to their anchor: no atomics), the workgroup writes
 // a per-class partial and the last workgroup to arrive (agent-scope ticket, the hand-off of fused_loss.hip) reduces the partials
@@ -33,18 +33,18 @@
 
 namespace embnet {
 
-constexpr int MS_MAX_N = PAIR_MAX_N;
-constexpr int MS_MAX_E = PAIR_MAX_E;
+static_assert(EMBNET_MS_PER_CLASS == PAIR_PER_CLASS && EMBNET_MS_SIMILARITY_MATRIX == PAIR_MATRIX, "path constants");
 
 // one rounding order everywhere: t = fl(c * fl(s - base)), c = -alpha or +beta; monotone in s
 __device__ __forceinline__ float ms_t(float c, float s, float base) { return __fmul_rn(c, __fsub_rn(s, base)); }
 
-struct MsBody {
+struct MsBody : PairDotBody {
   struct Args { float alpha, beta, base, eps; };
+  using Sum = float;
 
   // One wave, one anchor (local index ai of class [lo, lo+k)), its similarity row srow[n] (LDS).  Writes all n entries of the
   // anchor's row of G and returns (the same in every lane) the anchor's loss and its kept counts (positives, negatives).
-  static __device__ PairAnchorOut anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane) {
+  static __device__ PairAnchorOut<float> anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane) {
     const float alpha = a.alpha, beta = a.beta, base = a.base, eps = a.eps;
     float mn = INFINITY, mx = -INFINITY;
     for (int j = lane; j < k; j += 64)
@@ -56,7 +56,7 @@ struct MsBody {
     const float mxe = __fadd_rn(mx, eps);
     if (!(mxe > mn)) {                                     // inactive (wave-uniform): nothing kept on either side
       for (int col = lane; col < n; col += 64) grow[col] = 0.f;
-      return PairAnchorOut{0.f, 0, 0};
+      return PairAnchorOut<float>{0.f, 0, 0};
     }
     // t is monotone in s, so the largest exponent of each side belongs to the hardest kept pair, which is kept whenever any is
     const float mp = fmaxf(0.f, ms_t(-alpha, mn, base));
@@ -86,14 +86,15 @@ struct MsBody {
     }
     const float lp = __fdiv_rn(__fadd_rn(mp, logf(dp)), alpha);
     const float ln = __fdiv_rn(__fadd_rn(mg, logf(dn)), beta);
-    return PairAnchorOut{__fadd_rn(lp, ln), wave_sum(cp), wave_sum(cn)};
+    return PairAnchorOut<float>{__fadd_rn(lp, ln), wave_sum(cp), wave_sum(cn)};
   }
-  static __device__ int third(const PairAnchorOut& o) { return o.c1 > 0; }          // active: it keeps a negative
-  static __device__ void write_counts(int32_t* counts, int, int, int c0, int c1, int c2) {
-    counts[0] = c0;                                        // <= N (K-1)
-    counts[1] = c1;                                        // <= N (N-K) < 2^24
-    counts[2] = c2;
-    counts[3] = c0 + c1;
+  static __device__ int third(const PairAnchorOut<float>& o) { return o.c1 > 0; }   // active: it keeps a negative
+  static __device__ void finish(const PairParams<MsBody>& q, double total, int c0, int c1, int c2) {
+    q.counts[0] = c0;                                      // <= N (K-1)
+    q.counts[1] = c1;                                      // <= N (N-K) < 2^24
+    q.counts[2] = c2;
+    q.counts[3] = c0 + c1;
+    *q.mean = (float)(total / (double)q.n);
   }
 };
 using MsParams = PairParams<MsBody>;
@@ -103,92 +104,49 @@ __global__ __launch_bounds__(PAIR_CLASS_THREADS) void ms_class_fwd_kernel(MsPara
 __global__ __launch_bounds__(PAIR_SWEEP_THREADS) void ms_sweep_kernel(MsParams q) { pair_sweep_fwd<MsBody>(q); }
 
 // ---- backward: demb = (g / N) (G + G^T) X ------------------------------------------------------------------------------
-// grid (ceil(N/32), ceil(E/32)), 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS.
-// v_mfma_f64_16x16x4_f64: A[i = l&15][k = l>>4], B[k = l>>4][col = l&15], D[row = (l>>4) + 4r][col = l&15] (the f64 map).
-using f64x4 = __attribute__((ext_vector_type(4))) double;
+struct MsEpilogue {
+  static constexpr bool ROW_SUM = false;
+  const float* upstream;
+  __device__ double scale(int n) const { return (upstream ? (double)*upstream : 1.0) / (double)n; }
+  __device__ double value(double scale, double y, double, const float*) const { return scale * y; }
+};
 
 __global__ __launch_bounds__(256) void ms_bwd_kernel(const float* __restrict__ emb, int n, int e, const float* __restrict__ gw,
                                                      const float* __restrict__ upstream, float* __restrict__ demb) {
-  __shared__ float wa[32][33];                           // G[i0 + ii][j0 + jj]
-  __shared__ float wb[32][33];                           // G[j0 + jj][i0 + ii], stored [jj][ii]
-  __shared__ float xs[32][33];                           // X[j0 + jj][e0 + ee]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
-  const int ro = 16 * (wave >> 1), co = 16 * (wave & 1);
-  const int lr = lane & 15, lk = lane >> 4;
-  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int j0 = 0; j0 < n; j0 += 32) {
-    for (int t = tid; t < 1024; t += 256) {
-      const int r = t >> 5, cc = t & 31;
-      const int i = i0 + r, j = j0 + cc, jr = j0 + r, ic = i0 + cc, ec = e0 + cc;
-      wa[r][cc] = (i < n && j < n) ? gw[(long)i * n + j] : 0.f;
-      wb[r][cc] = (jr < n && ic < n) ? gw[(long)jr * n + ic] : 0.f;
-      xs[r][cc] = (jr < n && ec < e) ? emb[(long)jr * e + ec] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const int kx = 4 * kk + lk;
-      const double av = (double)wa[ro + lr][kx] + (double)wb[kx][ro + lr];
-      const double bv = (double)xs[kx][co + lr];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  const double scale = (upstream ? (double)*upstream : 1.0) / (double)n;
-  const int col = e0 + co + lr;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = i0 + ro + lk + 4 * r;
-    if (row < n && col < e) demb[(long)row * e + col] = (float)(scale * acc[r]);
-  }
+  pair_bwd(emb, n, e, gw, MsEpilogue{upstream}, demb);
 }
 
 }  // namespace embnet
 
 using namespace embnet;
 
-extern "C" size_t embnet_ms_loss_workspace_bytes(int p, int k, int e) { return pair_workspace_bytes(p, k, e); }
+extern "C" size_t embnet_ms_loss_workspace_bytes(int p, int k, int e) { return pair_workspace_bytes<MsBody>(p, k, e); }
 
-extern "C" int embnet_ms_loss_path(int p, int k, int e) {
-  if (!pair_range_ok(p, k, e)) return 0;
-  return pair_class_path_fits(p, k, e) ? EMBNET_MS_PER_CLASS : EMBNET_MS_SIMILARITY_MATRIX;
-}
+extern "C" int embnet_ms_loss_path(int p, int k, int e) { return pair_path(p, k, e); }
 
 extern "C" int embnet_ms_loss_fwd(const float* emb, int p, int k, int e, float alpha, float beta, float base, float epsilon,
                                   int path, float* pair_g, int32_t* counts, float* mean_loss, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  int rc = pair_check_common("ms_loss_fwd", emb, pair_g, counts, mean_loss, workspace, p, k, e);
+  int rc = pair_check_common("ms_loss_fwd", emb && pair_g && counts && mean_loss && workspace, p, k, e);
   if (rc != EMBNET_OK) return rc;
   EMBNET_CHECK_ARG(isfinite(alpha) && alpha > 0.f, "ms_loss_fwd: alpha=%g must be finite and positive", (double)alpha);
   EMBNET_CHECK_ARG(isfinite(beta) && beta > 0.f, "ms_loss_fwd: beta=%g must be finite and positive", (double)beta);
   EMBNET_CHECK_ARG(isfinite(base), "ms_loss_fwd: base=%g must be finite", (double)base);
   EMBNET_CHECK_ARG(isfinite(epsilon) && epsilon >= 0.f, "ms_loss_fwd: epsilon=%g must be finite and non-negative",
                    (double)epsilon);
-  rc = pair_check_path_and_workspace("ms_loss_fwd", p, k, e, path, workspace, workspace_bytes);
+  rc = pair_check_path_and_workspace("ms_loss_fwd", p, k, e, path, workspace, workspace_bytes,
+                                     embnet_ms_loss_workspace_bytes(p, k, e));
   if (rc != EMBNET_OK) return rc;
-  const int n = p * k;
-  if (path == 0) path = embnet_ms_loss_path(p, k, e);
-  const PairWorkspace w = pair_workspace(workspace, n);
-  MsParams q{emb, n, p, k, e, {alpha, beta, base, epsilon}, pair_g, counts, mean_loss, w.ticket, w.part_loss, w.part_cnt, w.sim};
-  hipStream_t s = (hipStream_t)stream;
-  if (path == EMBNET_MS_PER_CLASS) {
-    EMBNET_TRACE_FLOP("embnet::ms_class_fwd_kernel", 2.0 * n * n * e, 4.0 * n * e * (p + 1.0) + 4.0 * n * n, stream);
-    ms_class_fwd_kernel<<<p, PAIR_CLASS_THREADS, 0, s>>>(q);
-    return check_launch("ms_loss_fwd");
-  }
-  rc = embnet_dense_dgrad_f32(emb, emb, w.sim, n, n, e, stream);              // S = X X^T
-  if (rc != EMBNET_OK) return rc;
-  EMBNET_TRACE("embnet::ms_sweep_kernel", TRACE_BYTES, 8.0 * n * n, stream);
-  ms_sweep_kernel<<<cdiv(n, PAIR_SWEEP_THREADS / 64), PAIR_SWEEP_THREADS, 0, s>>>(q);
-  return check_launch("ms_loss_fwd");
+  static const PairKernels<MsBody> kernels{ms_class_fwd_kernel, "embnet::ms_class_fwd_kernel", ms_sweep_kernel,
+                                           "embnet::ms_sweep_kernel"};
+  return pair_launch<MsBody>("ms_loss_fwd", kernels, emb, p, k, e, {alpha, beta, base, epsilon}, path, pair_g, counts, mean_loss,
+                             workspace, stream);
 }
 
 extern "C" int embnet_ms_loss_bwd(const float* emb, int n, int e, const float* pair_g, const float* upstream, float* demb,
                                   void* stream) {
-  EMBNET_CHECK_ARG(emb && pair_g && demb, "ms_loss_bwd: null pointer");
-  EMBNET_CHECK_ARG(n >= 4 && n <= MS_MAX_N, "ms_loss_bwd: n=%d outside [4, %d]", n, MS_MAX_N);
-  EMBNET_CHECK_ARG(e >= 1 && e <= MS_MAX_E, "ms_loss_bwd: e=%d outside [1, %d]", e, MS_MAX_E);
+  const int rc = pair_check_bwd("ms_loss_bwd", emb && pair_g && demb, n, e);
+  if (rc != EMBNET_OK) return rc;
   EMBNET_TRACE_FLOP("embnet::ms_bwd_kernel", 2.0 * n * n * e, 4.0 * (2.0 * n * n + 2.0 * n * e), stream);
   ms_bwd_kernel<<<dim3(cdiv(n, 32), cdiv(e, 32)), 256, 0, (hipStream_t)stream>>>(emb, n, e, pair_g, upstream, demb);
   return check_launch("ms_loss_bwd");

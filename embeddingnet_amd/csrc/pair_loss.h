@@ -1,26 +1,36 @@
-// The forward skeleton the pair-based losses over a class-contiguous P x K batch share (multi_similarity.hip, supcon.hip): what
-// differs between them is what ONE WAVE does with ONE ANCHOR's row of similarities, the Body.
+// The skeleton the losses over a class-contiguous P x K batch share (batch_all.hip, multi_similarity.hip, supcon.hip): what
+// differs between them is what ONE WAVE does with ONE ANCHOR's row of the pair matrix, the Body.
 //
-//   X [N, E] fp32, N = P*K, rows c*K .. c*K+K-1 are class c;  S = X X^T.
-//   per-class path (N <= 512, K <= 16, K (E + N) floats in 64 KiB of LDS: batch_all.hip's fit rule), ONE launch: a workgroup per
-//   class holds its K rows and their K x N similarity rows in LDS (per-lane fmaf chain over the columns + wave sum), one wave per
-//   anchor runs the Body, the workgroup writes a per-class partial and the last workgroup to arrive (agent-scope ticket, the
-//   hand-off of fused_loss.hip) reduces the partials in class order.
-//   similarity-matrix path (everything else up to N = E = 4096): S through embnet_dense_dgrad_f32 (the exact-fp32 matrix-instruction
-//   GEMM, a k-ordered chain per element) into the workspace, then a sweep takes one anchor row per wave from an LDS copy of its row
-//   of S; per-anchor partials, the same ticket and fixed-order reduction.
+//   X [N, E] fp32, N = P*K, rows c*K .. c*K+K-1 are class c;  the pair matrix S is X X^T (similarities) or the squared distances.
+//   per-class path (N <= 512, K <= 16, K (E + N) floats in 64 KiB of LDS), ONE launch: a workgroup per class holds its K rows and
+//   their K x N rows of S in LDS (per-lane chain of Body::term over the columns + wave sum), one wave per anchor runs the Body,
+//   the workgroup writes a per-class partial and the last workgroup to arrive (agent-scope ticket, the hand-off of
+//   fused_loss.hip) reduces the partials in class order.
+//   matrix path (everything else up to N = E = 4096): S through Body::matrix (a library GEMM) into the workspace, then a sweep
+//   takes one anchor row per wave from an LDS copy of its row of S; per-anchor partials, the same ticket and fixed-order reduction.
+//   backward, one launch: Y = (M + M^T) X on the f64 matrix instructions, M the pair weights the forward wrote; an Epilogue turns
+//   Y into demb.
 //
 // A Body is a struct with
 //   struct Args { ... };                                       the loss's parameters, passed by value with the launch
-//   static __device__ PairAnchorOut anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane);
-//       one wave, anchor ai of class [lo, lo + k), its similarity row srow[n] (LDS): writes all n entries of the anchor's row of
-//       the pair weights and returns, the same in every lane, the anchor's loss and two counters;
-//   static __device__ int third(const PairAnchorOut& o);       a third per-anchor counter derived from the two
-//   static __device__ void write_counts(int32_t* counts, int n, int k, int c0, int c1, int c2);     the block's totals -> counts[]
+//   using Sum = float or double;                               the type of an anchor's loss (widened to f64 exactly from there on)
+//   static constexpr int CLASS_TRACE_UNIT;                     how the per-class kernel's trace entry counts its work
+//   static __device__ float term(float a, float y, float acc); per-class path: one column's step of S's chain
+//   static int matrix(const float* emb, int n, int e, float* s, void* extra, void* stream);    matrix path, host: S [n][n]
+//   static size_t matrix_extra_bytes(int n, int e);            workspace bytes `matrix` needs behind S
+//   static __device__ PairAnchorOut<Sum> anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane);
+//       one wave, anchor ai of class [lo, lo + k), its row srow[n] of S (LDS): writes all n entries of the anchor's row of the
+//       pair weights and returns, the same in every lane, the anchor's loss and two counters;
+//   static __device__ int third(const PairAnchorOut<Sum>& o);  a third per-anchor counter derived from the two
+//   static __device__ void finish(const PairParams<Body>& q, double total, int c0, int c1, int c2);     the batch's f64 loss
+//       total and counter totals -> every output (counts, mean, whatever else Args points to); one thread
+// The counters are int: a Body states why its totals fit.  PairDotBody has term / matrix for S = X X^T.
 // The kernels themselves stay in the loss's own file (their names are what a profile shows); they call pair_class_fwd /
-// pair_sweep_fwd.  Nothing is atomic in floating point, every reduction has a fixed order; no host synchronisation, no allocation.
+// pair_sweep_fwd / pair_bwd, and pair_launch launches them.  Nothing is atomic in floating point, every reduction has a fixed
+// order; no host synchronisation, no allocation.
 #pragma once
 #include "common.h"
+#include "../../include/embnet.h"
 
 namespace embnet {
 
@@ -29,8 +39,9 @@ constexpr int PAIR_MAX_E = 4096;
 constexpr int PAIR_CLASS_MAX_N = 512;
 constexpr int PAIR_CLASS_MAX_K = 16;
 constexpr int PAIR_LDS_FLOATS = 16 * 1024;               // 64 KiB: K*(E + N) floats
-constexpr int PAIR_CLASS_THREADS = 1024;                 // 16 waves: one per anchor, and the similarity phase's L2 round trips
-constexpr int PAIR_SWEEP_THREADS = 256;                  // 4 anchors per workgroup, a 16 KiB similarity row each
+constexpr int PAIR_CLASS_THREADS = 1024;                 // 16 waves: one per anchor, and the pair-matrix phase's L2 round trips
+constexpr int PAIR_SWEEP_THREADS = 256;                  // 4 anchors per workgroup, a 16 KiB row of S each
+enum { PAIR_PER_CLASS = 1, PAIR_MATRIX = 2 };            // the value of every loss's two path constants (include/embnet.h)
 
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
@@ -38,14 +49,26 @@ __device__ __forceinline__ float wave_min(float v) {
   return v;
 }
 
-struct PairAnchorOut { float loss; int c0, c1; };
+template <class Sum>
+struct PairAnchorOut { Sum loss; int c0, c1; };
 
 template <class Body>
 struct PairParams {
   const float* emb; int n, p, k, e; typename Body::Args a;
   float* g; int32_t* counts; float* mean;
   int* ticket; double* part_loss; int4* part_cnt;        // workspace: arrival counter (zero between launches), partials
-  const float* sim;                                      // similarity-matrix path: S [n][n]
+  const float* sim;                                      // matrix path: S [n][n]
+};
+
+// S = X X^T: the per-class chain is a dot product, the matrix comes from the exact-fp32 matrix-instruction GEMM (a k-ordered
+// chain per element).
+struct PairDotBody {
+  static constexpr int CLASS_TRACE_UNIT = TRACE_FLOP;
+  static __device__ float term(float a, float y, float acc) { return fmaf(a, y, acc); }
+  static int matrix(const float* emb, int n, int e, float* s, void*, void* stream) {
+    return embnet_dense_dgrad_f32(emb, emb, s, n, n, e, stream);
+  }
+  static size_t matrix_extra_bytes(int, int) { return 0; }
 };
 
 // Arrival ticket (fused_loss.hip's hand-off): every storing wave drains, barrier, one lane releases at agent scope and takes
@@ -88,25 +111,25 @@ __device__ __forceinline__ void pair_finish(const PairParams<Body>& q, int slots
     double ts = 0.0;
     int t0 = 0, t1 = 0, t2 = 0;
     for (int w = 0; w < THREADS / 64; ++w) { ts += ws_loss[w]; t0 += ws_cnt[w][0]; t1 += ws_cnt[w][1]; t2 += ws_cnt[w][2]; }
-    Body::write_counts(q.counts, q.n, q.k, t0, t1, t2);
-    *q.mean = (float)(ts / (double)q.n);
+    Body::finish(q, ts, t0, t1, t2);
   }
 }
 
 // ---- forward, per-class path: grid = P workgroups of PAIR_CLASS_THREADS ------------------------------------------------
 template <class Body>
 __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
+  using Sum = typename Body::Sum;
   __shared__ __attribute__((aligned(16))) float lds[PAIR_LDS_FLOATS];
-  __shared__ float wloss[PAIR_CLASS_MAX_K];
+  __shared__ Sum wloss[PAIR_CLASS_MAX_K];
   __shared__ int wcnt[PAIR_CLASS_MAX_K][2];
   const int n = q.n, k = q.k, e = q.e, c = blockIdx.x, lo = c * k;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = PAIR_CLASS_THREADS / 64;
   float* A = lds;                                        // [k][e] the class's rows
-  float* S = lds + k * e;                                // [k][n] similarities anchor -> row
+  float* S = lds + k * e;                                // [k][n] pair matrix, anchor -> row
   for (int i = tid; i < k * e; i += PAIR_CLASS_THREADS) A[i] = q.emb[(long)lo * e + i];
   __syncthreads();
-  // row r of the block against the K anchors: the row is read once, eight loads in flight per lane (batch_all.hip's loop)
+  // row r of the block against the K anchors: the row is read once, eight loads in flight per lane (fused_loss.hip's loop)
   for (int r = wave; r < n; r += NW) {
     const float* y = q.emb + (long)r * e;
     float acc[PAIR_CLASS_MAX_K];
@@ -122,7 +145,7 @@ __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
         if (cc < e) {
 #pragma unroll
           for (int a = 0; a < PAIR_CLASS_MAX_K; ++a)
-            if (a < k) acc[a] = fmaf(A[a * e + cc], yv[j], acc[a]);
+            if (a < k) acc[a] = Body::term(A[a * e + cc], yv[j], acc[a]);
         }
       }
     }
@@ -136,7 +159,7 @@ __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
   }
   __syncthreads();
   if (wave < k) {
-    const PairAnchorOut o = Body::anchor(S + wave * n, n, k, lo, wave, q.a, q.g + (long)(lo + wave) * n, lane);
+    const PairAnchorOut<Sum> o = Body::anchor(S + wave * n, n, k, lo, wave, q.a, q.g + (long)(lo + wave) * n, lane);
     if (lane == 0) { wloss[wave] = o.loss; wcnt[wave][0] = o.c0; wcnt[wave][1] = o.c1; }
   }
   __syncthreads();
@@ -145,7 +168,7 @@ __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
     int c0 = 0, c1 = 0, c2 = 0;
     for (int a = 0; a < k; ++a) {
       s += (double)wloss[a]; c0 += wcnt[a][0]; c1 += wcnt[a][1];
-      c2 += Body::third(PairAnchorOut{wloss[a], wcnt[a][0], wcnt[a][1]});
+      c2 += Body::third(PairAnchorOut<Sum>{wloss[a], wcnt[a][0], wcnt[a][1]});
     }
     q.part_loss[c] = s;
     q.part_cnt[c] = make_int4(c0, c1, c2, 0);
@@ -153,7 +176,7 @@ __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
   pair_finish<Body, PAIR_CLASS_THREADS>(q, q.p);
 }
 
-// ---- forward, similarity-matrix path: grid = ceil(N / 4) workgroups of PAIR_SWEEP_THREADS, one anchor per wave -----------
+// ---- forward, matrix path: grid = ceil(N / 4) workgroups of PAIR_SWEEP_THREADS, one anchor per wave -----------------------
 template <class Body>
 __device__ __forceinline__ void pair_sweep_fwd(const PairParams<Body>& q) {
   __shared__ __attribute__((aligned(16))) float rows[PAIR_SWEEP_THREADS / 64][PAIR_MAX_N];
@@ -167,13 +190,71 @@ __device__ __forceinline__ void pair_sweep_fwd(const PairParams<Body>& q) {
   __syncthreads();
   if (a < n) {
     const int lo = (a / k) * k;
-    const PairAnchorOut o = Body::anchor(srow, n, k, lo, a - lo, q.a, q.g + (long)a * n, lane);
+    const PairAnchorOut<typename Body::Sum> o = Body::anchor(srow, n, k, lo, a - lo, q.a, q.g + (long)a * n, lane);
     if (lane == 0) { q.part_loss[a] = (double)o.loss; q.part_cnt[a] = make_int4(o.c0, o.c1, Body::third(o), 0); }
   }
   pair_finish<Body, PAIR_SWEEP_THREADS>(q, n);
 }
 
-// ---- host side: range, fit rule, workspace layout ------------------------------------------------------------------------
+// ---- backward: Y = (M + M^T) X, demb = Epilogue(Y) ------------------------------------------------------------------------
+// grid (ceil(N/32), ceil(E/32)), 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS.
+// v_mfma_f64_16x16x4_f64: A[i = l&15][k = l>>4], B[k = l>>4][col = l&15], D[row = (l>>4) + 4r][col = l&15] (the f64 map).
+// Not the f32 instructions: an f32 chain over j rounds relative to sum_j |M_ij| |x_j|, and what the caller keeps of the result
+// can be far below that.  M + M^T is formed in f64 while staging; the result carries one fp32 rounding of an f64 sum.
+// An Epilogue is built by the kernel from its arguments and has
+//   static constexpr bool ROW_SUM;                             whether value() wants s_i = sum_j (M + M^T)_ij
+//   __device__ double scale(int n) const;                      read once per thread, after the products
+//   __device__ double value(double scale, double y, double s, const float* x) const;     demb[i][c] from Y_ic, s_i, &X[i][c]
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+template <class Epilogue>
+__device__ __forceinline__ void pair_bwd(const float* __restrict__ emb, int n, int e, const float* __restrict__ w,
+                                         const Epilogue& ep, float* __restrict__ demb) {
+  __shared__ float wa[32][33];                           // M[i0 + ii][j0 + jj]
+  __shared__ float wb[32][33];                           // M[j0 + jj][i0 + ii], stored [jj][ii]
+  __shared__ float xs[32][33];                           // X[j0 + jj][e0 + ee]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
+  const int ro = 16 * (wave >> 1), co = 16 * (wave & 1);
+  const int lr = lane & 15, lk = lane >> 4;
+  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  double srow = 0.0;                                     // sum of this lane's (M + M^T)[ro + lr][k] operands
+  for (int j0 = 0; j0 < n; j0 += 32) {
+    for (int t = tid; t < 1024; t += 256) {
+      const int r = t >> 5, cc = t & 31;
+      const int i = i0 + r, j = j0 + cc, jr = j0 + r, ic = i0 + cc, ec = e0 + cc;
+      wa[r][cc] = (i < n && j < n) ? w[(long)i * n + j] : 0.f;
+      wb[r][cc] = (jr < n && ic < n) ? w[(long)jr * n + ic] : 0.f;
+      xs[r][cc] = (jr < n && ec < e) ? emb[(long)jr * e + ec] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      const int kx = 4 * kk + lk;
+      const double av = (double)wa[ro + lr][kx] + (double)wb[kx][ro + lr];
+      const double bv = (double)xs[kx][co + lr];
+      if constexpr (Epilogue::ROW_SUM) srow += av;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  if constexpr (Epilogue::ROW_SUM) {
+    srow += __shfl_xor(srow, 16, 64);                    // the four k-lanes of row lr: s_i
+    srow += __shfl_xor(srow, 32, 64);
+  }
+  const double scale = ep.scale(n);
+  const int col = e0 + co + lr;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int rl = lk + 4 * r;
+    double s = 0.0;
+    if constexpr (Epilogue::ROW_SUM) s = __shfl(srow, rl, 64);       // lane rl holds s of row rl
+    const int row = i0 + ro + rl;
+    if (row < n && col < e) demb[(long)row * e + col] = (float)ep.value(scale, acc[r], s, emb + (long)row * e + col);
+  }
+}
+
+// ---- host side: range, fit rule, workspace layout, argument checks, launches ----------------------------------------------
 inline bool pair_class_path_fits(int p, int k, int e) {
   const long n = (long)p * k;
   return k <= PAIR_CLASS_MAX_K && n <= PAIR_CLASS_MAX_N && (long)k * (e + n) <= PAIR_LDS_FLOATS;
@@ -185,26 +266,24 @@ inline bool pair_range_ok(int p, int k, int e) {
   return p >= 2 && k >= 2 && e >= 1 && e <= PAIR_MAX_E && (long long)p * k <= PAIR_MAX_N;
 }
 
-// workspace: [16 B ticket][n f64 partial losses][n int4 partial counts][n*n f32 similarities]
+inline int pair_path(int p, int k, int e) {              // the path `auto` takes; 0 outside the range
+  if (!pair_range_ok(p, k, e)) return 0;
+  return pair_class_path_fits(p, k, e) ? PAIR_PER_CLASS : PAIR_MATRIX;
+}
+
+// workspace: [16 B ticket][n f64 partial losses][n int4 partial counts][n*n f32 pair matrix][Body::matrix's own workspace]
 // (sized for both forward paths, so a caller may force either); 0 outside the range
+template <class Body>
 inline size_t pair_workspace_bytes(int p, int k, int e) {
   if (!pair_range_ok(p, k, e)) return 0;
   const size_t n = (size_t)p * k;
-  return 16 + pair_align16(n * 8) + n * 16 + pair_align16(n * n * 4);
+  return 16 + pair_align16(n * 8) + n * 16 + pair_align16(n * n * 4) + pair_align16(Body::matrix_extra_bytes((int)n, e));
 }
 
-struct PairWorkspace { int* ticket; double* part_loss; int4* part_cnt; float* sim; };
-
-inline PairWorkspace pair_workspace(void* workspace, int n) {
-  char* ws = (char*)workspace;
-  int4* part_cnt = (int4*)(ws + 16 + pair_align16((size_t)n * 8));
-  return PairWorkspace{(int*)ws, (double*)(ws + 16), part_cnt, (float*)((char*)part_cnt + (size_t)n * 16)};
-}
-
-// The argument checks the two losses share, in multi_similarity's words.  `what` is the entry point's name without `embnet_`.
-inline int pair_check_common(const char* what, const void* emb, const void* pair_g, const void* counts, const void* mean_loss,
-                             const void* workspace, int p, int k, int e) {
-  EMBNET_CHECK_ARG(emb && pair_g && counts && mean_loss && workspace, "%s: null pointer", what);
+// The argument checks the losses share.  `what` is the entry point's name without `embnet_`, `pointers` whether all are set,
+// `need` the loss's own workspace size.
+inline int pair_check_common(const char* what, bool pointers, int p, int k, int e) {
+  EMBNET_CHECK_ARG(pointers, "%s: null pointer", what);
   EMBNET_CHECK_ARG(p >= 2 && k >= 2, "%s: need p >= 2 classes and k >= 2 samples (p=%d k=%d)", what, p, k);
   EMBNET_CHECK_ARG((long long)p * k <= PAIR_MAX_N, "%s: n = p*k = %lld > %d", what, (long long)p * k, PAIR_MAX_N);
   EMBNET_CHECK_ARG(e >= 1 && e <= PAIR_MAX_E, "%s: e=%d outside [1, %d]", what, e, PAIR_MAX_E);
@@ -212,14 +291,53 @@ inline int pair_check_common(const char* what, const void* emb, const void* pair
 }
 
 inline int pair_check_path_and_workspace(const char* what, int p, int k, int e, int path, const void* workspace,
-                                         size_t workspace_bytes) {
-  EMBNET_CHECK_ARG(path >= 0 && path <= 2, "%s: unknown path %d", what, path);
-  EMBNET_CHECK_ARG(path != 1 || pair_class_path_fits(p, k, e), "%s: p=%d k=%d e=%d does not fit the per-class path", what, p, k,
-                   e);
+                                         size_t workspace_bytes, size_t need) {
+  EMBNET_CHECK_ARG(path >= 0 && path <= PAIR_MATRIX, "%s: unknown path %d", what, path);
+  EMBNET_CHECK_ARG(path != PAIR_PER_CLASS || pair_class_path_fits(p, k, e), "%s: p=%d k=%d e=%d does not fit the per-class path",
+                   what, p, k, e);
   EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-  if (workspace_bytes < pair_workspace_bytes(p, k, e))
-    return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, pair_workspace_bytes(p, k, e));
+  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
   return EMBNET_OK;
+}
+
+inline int pair_check_bwd(const char* what, bool pointers, int n, int e) {
+  EMBNET_CHECK_ARG(pointers, "%s: null pointer", what);
+  EMBNET_CHECK_ARG(n >= 4 && n <= PAIR_MAX_N, "%s: n=%d outside [4, %d]", what, n, PAIR_MAX_N);
+  EMBNET_CHECK_ARG(e >= 1 && e <= PAIR_MAX_E, "%s: e=%d outside [1, %d]", what, e, PAIR_MAX_E);
+  return EMBNET_OK;
+}
+
+// A loss's two forward kernels (its own __global__ wrappers) under the names its trace entries carry.
+template <class Body>
+struct PairKernels {
+  void (*class_fwd)(PairParams<Body>); const char* class_name;
+  void (*sweep)(PairParams<Body>); const char* sweep_name;
+};
+
+// The forward on checked arguments: the per-class kernel, or Body::matrix and then the sweep.
+template <class Body>
+inline int pair_launch(const char* what, const PairKernels<Body>& kn, const float* emb, int p, int k, int e,
+                       const typename Body::Args& a, int path, float* pair_g, int32_t* counts, float* mean_loss, void* workspace,
+                       void* stream) {
+  const int n = p * k;
+  char* ws = (char*)workspace;
+  int4* part_cnt = (int4*)(ws + 16 + pair_align16((size_t)n * 8));
+  float* sim = (float*)((char*)part_cnt + (size_t)n * 16);
+  PairParams<Body> q{emb, n, p, k, e, a, pair_g, counts, mean_loss, (int*)ws, (double*)(ws + 16), part_cnt, sim};
+  hipStream_t s = (hipStream_t)stream;
+  if (path == 0) path = pair_path(p, k, e);
+  if (path == PAIR_PER_CLASS) {
+    const double bytes = 4.0 * n * e * (p + 1.0) + 4.0 * n * n;
+    TraceScope trace(kn.class_name, Body::CLASS_TRACE_UNIT, Body::CLASS_TRACE_UNIT == TRACE_FLOP ? 2.0 * n * n * e : bytes, stream,
+                     bytes);
+    kn.class_fwd<<<p, PAIR_CLASS_THREADS, 0, s>>>(q);
+    return check_launch(what);
+  }
+  const int rc = Body::matrix(emb, n, e, sim, (char*)sim + pair_align16((size_t)n * n * 4), stream);
+  if (rc != EMBNET_OK) return rc;
+  EMBNET_TRACE(kn.sweep_name, TRACE_BYTES, 8.0 * n * n, stream);
+  kn.sweep<<<cdiv(n, PAIR_SWEEP_THREADS / 64), PAIR_SWEEP_THREADS, 0, s>>>(q);
+  return check_launch(what);
 }
 
 }  // namespace embnet

@@ -16,7 +16,7 @@
 //   loss = (1/N) sum_i l_i;  backward demb_i = (g / N) sum_j (G_ij + G_ji) x_j: embnet_ms_loss_bwd's contract, and its kernel.
 //   counts = {positive pairs N (K-1), violating anchors: max_n S_in >= min_p S_ip on the fp32 S}, exact.
 //
-// The forward is pair_loss.h's skeleton (per-class path, similarity-matrix path, ticket, fixed-order reduction) around the
+// The forward is pair_loss.h's skeleton (per-class path, similarity-matrix path, ticket, fixed-order reduction, launch) around the
 // per-anchor body below: a wave minimum over the positives and maxima over both sides, lane-strided expf sums, for `negatives` a
 // lane-strided loop over the <= K-1 positives (K reaches 2048 on the matrix path), and the anchor's row of G.
 // Nothing is atomic in floating point, every reduction has a fixed order: bitwise reproducible.  No host synchronisation, no
@@ -28,11 +28,14 @@
 
 namespace embnet {
 
-template <int DENOM>
-struct SupconBody {
-  struct Args { float r; };                              // fl(1 / tau)
+static_assert(EMBNET_SUPCON_PER_CLASS == PAIR_PER_CLASS && EMBNET_SUPCON_SIMILARITY_MATRIX == PAIR_MATRIX, "path constants");
 
-  static __device__ PairAnchorOut anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane) {
+template <int DENOM>
+struct SupconBody : PairDotBody {
+  struct Args { float r; };                              // fl(1 / tau)
+  using Sum = float;
+
+  static __device__ PairAnchorOut<float> anchor(const float* srow, int n, int k, int lo, int ai, const Args& a, float* grow, int lane) {
     const float r = a.r;
     const float kf = (float)(k - 1);
     const float ck = __fdiv_rn(1.f, kf);
@@ -61,7 +64,7 @@ struct SupconBody {
         }
         grow[col] = g;
       }
-      return PairAnchorOut{__fadd_rn(logf(d), __fdiv_rn(wave_sum(sh), kf)), viol, 0};
+      return PairAnchorOut<float>{__fadd_rn(logf(d), __fdiv_rn(wave_sum(sh), kf)), viol, 0};
     } else {
       const float Mn = __fmul_rn(mx, r);
       float se = 0.f;
@@ -92,13 +95,14 @@ struct SupconBody {
         }
         grow[col] = g;
       }
-      return PairAnchorOut{__fdiv_rn(wave_sum(sl), kf), viol, 0};
+      return PairAnchorOut<float>{__fdiv_rn(wave_sum(sl), kf), viol, 0};
     }
   }
-  static __device__ int third(const PairAnchorOut&) { return 0; }
-  static __device__ void write_counts(int32_t* counts, int n, int k, int c0, int, int) {
-    counts[0] = n * (k - 1);                             // <= 4096 * 2047 < 2^23
-    counts[1] = c0;
+  static __device__ int third(const PairAnchorOut<float>&) { return 0; }
+  static __device__ void finish(const PairParams<SupconBody>& q, double total, int c0, int, int) {
+    q.counts[0] = q.n * (q.k - 1);                       // <= 4096 * 2047 < 2^23
+    q.counts[1] = c0;
+    *q.mean = (float)(total / (double)q.n);
   }
 };
 using SupconAll = SupconBody<EMBNET_SUPCON_ALL>;
@@ -110,39 +114,21 @@ template <class Body>
 __global__ __launch_bounds__(PAIR_SWEEP_THREADS) void supcon_sweep_kernel(PairParams<Body> q) { pair_sweep_fwd<Body>(q); }
 
 template <class Body>
-static int supcon_launch(const float* emb, int p, int k, int e, float r, int path, float* pair_g, int32_t* counts, float* mean_loss,
-                         void* workspace, void* stream) {
-  const int n = p * k;
-  const PairWorkspace w = pair_workspace(workspace, n);
-  PairParams<Body> q{emb, n, p, k, e, {r}, pair_g, counts, mean_loss, w.ticket, w.part_loss, w.part_cnt, w.sim};
-  hipStream_t s = (hipStream_t)stream;
-  if (path == EMBNET_SUPCON_PER_CLASS) {
-    EMBNET_TRACE_FLOP("embnet::supcon_class_fwd_kernel", 2.0 * n * n * e, 4.0 * n * e * (p + 1.0) + 4.0 * n * n, stream);
-    supcon_class_fwd_kernel<Body><<<p, PAIR_CLASS_THREADS, 0, s>>>(q);
-    return check_launch("supcon_loss_fwd");
-  }
-  const int rc = embnet_dense_dgrad_f32(emb, emb, w.sim, n, n, e, stream);    // S = X X^T
-  if (rc != EMBNET_OK) return rc;
-  EMBNET_TRACE("embnet::supcon_sweep_kernel", TRACE_BYTES, 8.0 * n * n, stream);
-  supcon_sweep_kernel<Body><<<cdiv(n, PAIR_SWEEP_THREADS / 64), PAIR_SWEEP_THREADS, 0, s>>>(q);
-  return check_launch("supcon_loss_fwd");
-}
+static const PairKernels<Body> supcon_kernels{supcon_class_fwd_kernel<Body>, "embnet::supcon_class_fwd_kernel",
+                                              supcon_sweep_kernel<Body>, "embnet::supcon_sweep_kernel"};
 
 }  // namespace embnet
 
 using namespace embnet;
 
-extern "C" size_t embnet_supcon_loss_workspace_bytes(int p, int k, int e) { return pair_workspace_bytes(p, k, e); }
+extern "C" size_t embnet_supcon_loss_workspace_bytes(int p, int k, int e) { return pair_workspace_bytes<SupconAll>(p, k, e); }
 
-extern "C" int embnet_supcon_loss_path(int p, int k, int e) {
-  if (!pair_range_ok(p, k, e)) return 0;
-  return pair_class_path_fits(p, k, e) ? EMBNET_SUPCON_PER_CLASS : EMBNET_SUPCON_SIMILARITY_MATRIX;
-}
+extern "C" int embnet_supcon_loss_path(int p, int k, int e) { return pair_path(p, k, e); }
 
 extern "C" int embnet_supcon_loss_fwd(const float* emb, int p, int k, int e, float temperature, int denominator, int path,
                                       float* pair_g, int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  int rc = pair_check_common("supcon_loss_fwd", emb, pair_g, counts, mean_loss, workspace, p, k, e);
+  int rc = pair_check_common("supcon_loss_fwd", emb && pair_g && counts && mean_loss && workspace, p, k, e);
   if (rc != EMBNET_OK) return rc;
   EMBNET_CHECK_ARG(isfinite(temperature) && temperature > 0.f, "supcon_loss_fwd: temperature=%g must be finite and positive",
                    (double)temperature);
@@ -150,10 +136,12 @@ extern "C" int embnet_supcon_loss_fwd(const float* emb, int p, int k, int e, flo
   EMBNET_CHECK_ARG(isnormal(r), "supcon_loss_fwd: temperature=%g: 1/temperature is not a normal fp32 number", (double)temperature);
   EMBNET_CHECK_ARG(denominator == EMBNET_SUPCON_ALL || denominator == EMBNET_SUPCON_NEGATIVES,
                    "supcon_loss_fwd: unknown denominator %d", denominator);
-  rc = pair_check_path_and_workspace("supcon_loss_fwd", p, k, e, path, workspace, workspace_bytes);
+  rc = pair_check_path_and_workspace("supcon_loss_fwd", p, k, e, path, workspace, workspace_bytes,
+                                     embnet_supcon_loss_workspace_bytes(p, k, e));
   if (rc != EMBNET_OK) return rc;
-  if (path == 0) path = embnet_supcon_loss_path(p, k, e);
   if (denominator == EMBNET_SUPCON_ALL)
-    return supcon_launch<SupconAll>(emb, p, k, e, r, path, pair_g, counts, mean_loss, workspace, stream);
-  return supcon_launch<SupconNeg>(emb, p, k, e, r, path, pair_g, counts, mean_loss, workspace, stream);
+    return pair_launch<SupconAll>("supcon_loss_fwd", supcon_kernels<SupconAll>, emb, p, k, e, {r}, path, pair_g, counts, mean_loss,
+                                  workspace, stream);
+  return pair_launch<SupconNeg>("supcon_loss_fwd", supcon_kernels<SupconNeg>, emb, p, k, e, {r}, path, pair_g, counts, mean_loss,
+                                workspace, stream);
 }

@@ -185,46 +185,72 @@ def fused_triplet_loss(emb, k_classes, k_samples, margin, mode, seed=0, seed_dev
     return _FusedTripletLoss.apply(emb, int(k_classes), int(k_samples), float(margin), mode, int(seed), seed_dev)
 
 
-_BATCH_ALL_WS = {}
 BATCH_ALL_PATHS = {"auto": 0, "per_class": 1, "distance_matrix": 2}
+MS_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
+SUPCON_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
+SUPCON_DENOMINATORS = {"all": 1, "negatives": 2}
 
 
-class _BatchAllLoss(torch.autograd.Function):
-    """Batch-all triplet loss (include/embnet.h, embnet_batch_all_loss_fwd/bwd): one forward launch on the per-class path,
-    distance matrix + sweep above it; one backward launch.  The pair weights W stay saved for the backward."""
+def _supcon_scalars(temperature, denominator):
+    if denominator not in SUPCON_DENOMINATORS:
+        raise _lib.EmbnetError(f"supcon_loss: denominator {denominator!r} is not one of {sorted(SUPCON_DENOMINATORS)}")
+    return f32(temperature), SUPCON_DENOMINATORS[denominator]
+
+
+# The losses over a class-contiguous block (csrc/pair_loss.h), by the name of their public function.  Every forward entry point
+# takes (emb, p, k, e, *scalars, path, pair weights [N,N], *outputs, mean, workspace, bytes, stream); every backward
+# (emb, n, e, pair weights, [outputs[0]], upstream, demb, stream).
+#   name: (forward, workspace size, path table, Python scalars -> C arguments, outputs beside the mean as (shape, dtype),
+#          backward, whether it takes outputs[0])
+_PAIR_LOSSES = {
+    "batch_all_triplet_loss": ("embnet_batch_all_loss_fwd", "embnet_batch_all_workspace_bytes", BATCH_ALL_PATHS,
+                               lambda margin: (f32(margin),), (((1,), torch.int32), ((), torch.float32)),
+                               "embnet_batch_all_loss_bwd", True),
+    "multi_similarity_loss": ("embnet_ms_loss_fwd", "embnet_ms_loss_workspace_bytes", MS_PATHS,
+                              lambda *abbe: tuple(map(f32, abbe)), (((4,), torch.int32),), "embnet_ms_loss_bwd", False),
+    "supcon_loss": ("embnet_supcon_loss_fwd", "embnet_supcon_loss_workspace_bytes", SUPCON_PATHS, _supcon_scalars,
+                    (((2,), torch.int32),), "embnet_ms_loss_bwd", False),     # demb = (g / N)(G + G^T) X is MS's backward
+}
+_PAIR_WS = {}
+
+
+class _PairLoss(torch.autograd.Function):
+    """A loss of _PAIR_LOSSES (include/embnet.h): one forward launch on the per-class path, pair matrix + sweep above it; one
+    backward launch.  The pair weights stay saved for the backward."""
 
     @staticmethod
-    def forward(ctx, emb, p, k, margin, path):
+    def forward(ctx, emb, loss, p, k, scalars, path):
+        fwd, ws_bytes, paths, marshal, outputs, bwd, bwd_takes_output = _PAIR_LOSSES[loss]
         emb = _prep(emb)
         n, e = emb.shape
         if n != p * k:
-            raise _lib.EmbnetError(f"batch_all_triplet_loss: {n} rows != k_classes*k_samples = {p}*{k}")
+            raise _lib.EmbnetError(f"{loss}: {n} rows != k_classes*k_samples = {p}*{k}")
+        scalars = marshal(*scalars)
         lib = _lib.lib()
-        w = _new((n, n), emb)
-        n_active = _new((1,), emb, torch.int32)
-        frac, mean = _new((), emb), _new((), emb)
-        key = (emb.device.index, stream(), p, k, e)
-        ws = _BATCH_ALL_WS.get(key)
+        g = _new((n, n), emb)
+        outs = [_new(shape, emb, dtype) for shape, dtype in outputs]
+        mean = _new((), emb)
+        key = (loss, emb.device.index, stream(), p, k, e)
+        ws = _PAIR_WS.get(key)
         if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
-            nbytes = lib.embnet_batch_all_workspace_bytes(p, k, e)
-            ws = _BATCH_ALL_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
-        check(lib.embnet_batch_all_loss_fwd(ptr(emb), p, k, e, f32(margin), BATCH_ALL_PATHS[path], ptr(w), ptr(n_active),
-                                            ptr(frac), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
-        ctx.save_for_backward(emb, w, n_active)
-        ctx.mark_non_differentiable(n_active, frac, w)
+            ws = _PAIR_WS[key] = torch.zeros(max(getattr(lib, ws_bytes)(p, k, e) // 4, 4), device=emb.device)
+        check(getattr(lib, fwd)(ptr(emb), p, k, e, *scalars, paths[path], ptr(g), *map(ptr, outs), ptr(mean), ptr(ws),
+                                ws.numel() * 4, stream()))
+        ctx.bwd = bwd
+        ctx.save_for_backward(emb, g, *(outs[:1] if bwd_takes_output else ()))
+        ctx.mark_non_differentiable(*outs, g)
         ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
-        return mean, n_active, frac, w
+        return (mean, *outs, g)
 
     @staticmethod
-    def backward(ctx, dmean, _dn, _dfrac, _dw):
+    def backward(ctx, dmean, *_):
         if dmean is None:
-            return None, None, None, None, None
-        emb, w, n_active = ctx.saved_tensors
+            return (None,) * 6
+        emb, g, *output = ctx.saved_tensors
         n, e = emb.shape
         demb = torch.empty_like(emb)
-        check(_lib.lib().embnet_batch_all_loss_bwd(ptr(emb), n, e, ptr(w), ptr(n_active), ptr(_prep(dmean)), ptr(demb),
-                                                   stream()))
-        return demb, None, None, None, None
+        check(getattr(_lib.lib(), ctx.bwd)(ptr(emb), n, e, ptr(g), *map(ptr, output), ptr(_prep(dmean)), ptr(demb), stream()))
+        return (demb,) + (None,) * 5
 
 
 def batch_all_triplet_loss(emb, k_classes, k_samples, margin, path="auto", return_weights=False):
@@ -232,49 +258,8 @@ def batch_all_triplet_loss(emb, k_classes, k_samples, margin, path="auto", retur
     valid triplet with b > 0 (d squared L2).  -> (mean [autograd], n_active int32 [1], frac_active []) on the device, no host
     synchronisation; return_weights adds the pair-weight matrix W [N,N] the backward uses.  path: 'auto', 'per_class' or
     'distance_matrix' (include/embnet.h)."""
-    out = _BatchAllLoss.apply(emb, int(k_classes), int(k_samples), float(margin), path)
+    out = _PairLoss.apply(emb, "batch_all_triplet_loss", int(k_classes), int(k_samples), (float(margin),), path)
     return out if return_weights else out[:3]
-
-
-_MS_WS = {}
-MS_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
-
-
-class _MultiSimilarityLoss(torch.autograd.Function):
-    """Multi-similarity loss (include/embnet.h, embnet_ms_loss_fwd/bwd): one forward launch on the per-class path, similarity
-    matrix + sweep above it; one backward launch.  The pair weights G stay saved for the backward."""
-
-    @staticmethod
-    def forward(ctx, emb, p, k, alpha, beta, base, epsilon, path):
-        emb = _prep(emb)
-        n, e = emb.shape
-        if n != p * k:
-            raise _lib.EmbnetError(f"multi_similarity_loss: {n} rows != k_classes*k_samples = {p}*{k}")
-        lib = _lib.lib()
-        g = _new((n, n), emb)
-        counts = _new((4,), emb, torch.int32)
-        mean = _new((), emb)
-        key = (emb.device.index, stream(), p, k, e)
-        ws = _MS_WS.get(key)
-        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
-            nbytes = lib.embnet_ms_loss_workspace_bytes(p, k, e)
-            ws = _MS_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
-        check(lib.embnet_ms_loss_fwd(ptr(emb), p, k, e, f32(alpha), f32(beta), f32(base), f32(epsilon), MS_PATHS[path],
-                                     ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
-        ctx.save_for_backward(emb, g)
-        ctx.mark_non_differentiable(counts, g)
-        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
-        return mean, counts, g
-
-    @staticmethod
-    def backward(ctx, dmean, _dcounts, _dg):
-        if dmean is None:
-            return (None,) * 8
-        emb, g = ctx.saved_tensors
-        n, e = emb.shape
-        demb = torch.empty_like(emb)
-        check(_lib.lib().embnet_ms_loss_bwd(ptr(emb), n, e, ptr(g), ptr(_prep(dmean)), ptr(demb), stream()))
-        return (demb,) + (None,) * 7
 
 
 def multi_similarity_loss(emb, k_classes, k_samples, alpha=2.0, beta=50.0, base=0.5, epsilon=0.1, path="auto",
@@ -285,53 +270,9 @@ def multi_similarity_loss(emb, k_classes, k_samples, alpha=2.0, beta=50.0, base=
     (include/embnet.h has the rounding forms).  -> (mean [autograd], counts int32 [4] = kept positives, kept negatives, active
     anchors, kept pairs) on the device, no host synchronisation; return_weights adds the pair-weight matrix G [N,N] the
     backward uses.  path: 'auto', 'per_class' or 'similarity_matrix'."""
-    out = _MultiSimilarityLoss.apply(emb, int(k_classes), int(k_samples), float(alpha), float(beta), float(base),
-                                     float(epsilon), path)
+    out = _PairLoss.apply(emb, "multi_similarity_loss", int(k_classes), int(k_samples),
+                          (float(alpha), float(beta), float(base), float(epsilon)), path)
     return out if return_weights else out[:2]
-
-
-_SUPCON_WS = {}
-SUPCON_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
-SUPCON_DENOMINATORS = {"all": 1, "negatives": 2}
-
-
-class _SupconLoss(torch.autograd.Function):
-    """SupCon / NT-Xent (include/embnet.h, embnet_supcon_loss_fwd): one forward launch on the per-class path, similarity matrix +
-    sweep above it; the backward is embnet_ms_loss_bwd's one launch on the saved pair weights G."""
-
-    @staticmethod
-    def forward(ctx, emb, p, k, temperature, denominator, path):
-        emb = _prep(emb)
-        n, e = emb.shape
-        if n != p * k:
-            raise _lib.EmbnetError(f"supcon_loss: {n} rows != k_classes*k_samples = {p}*{k}")
-        if denominator not in SUPCON_DENOMINATORS:
-            raise _lib.EmbnetError(f"supcon_loss: denominator {denominator!r} is not one of {sorted(SUPCON_DENOMINATORS)}")
-        lib = _lib.lib()
-        g = _new((n, n), emb)
-        counts = _new((2,), emb, torch.int32)
-        mean = _new((), emb)
-        key = (emb.device.index, stream(), p, k, e)
-        ws = _SUPCON_WS.get(key)
-        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
-            nbytes = lib.embnet_supcon_loss_workspace_bytes(p, k, e)
-            ws = _SUPCON_WS[key] = torch.zeros(max(nbytes // 4, 4), device=emb.device)
-        check(lib.embnet_supcon_loss_fwd(ptr(emb), p, k, e, f32(temperature), SUPCON_DENOMINATORS[denominator],
-                                         SUPCON_PATHS[path], ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
-        ctx.save_for_backward(emb, g)
-        ctx.mark_non_differentiable(counts, g)
-        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
-        return mean, counts, g
-
-    @staticmethod
-    def backward(ctx, dmean, _dcounts, _dg):
-        if dmean is None:
-            return (None,) * 6
-        emb, g = ctx.saved_tensors
-        n, e = emb.shape
-        demb = torch.empty_like(emb)
-        check(_lib.lib().embnet_ms_loss_bwd(ptr(emb), n, e, ptr(g), ptr(_prep(dmean)), ptr(demb), stream()))
-        return (demb,) + (None,) * 5
 
 
 def supcon_loss(emb, k_classes, k_samples, temperature=0.1, denominator="all", path="auto", return_weights=False):
@@ -341,8 +282,19 @@ def supcon_loss(emb, k_classes, k_samples, temperature=0.1, denominator="all", p
     has the rounding and the stable forms).  -> (mean [autograd], counts int32 [2] = positive pairs, violating anchors: those
     whose hardest negative is at least as similar as their hardest positive) on the device, no host synchronisation;
     return_weights adds the pair-weight matrix G [N,N] the backward uses.  path: 'auto', 'per_class' or 'similarity_matrix'."""
-    out = _SupconLoss.apply(emb, int(k_classes), int(k_samples), float(temperature), denominator, path)
+    out = _PairLoss.apply(emb, "supcon_loss", int(k_classes), int(k_samples), (float(temperature), denominator), path)
     return out if return_weights else out[:2]
+
+
+# The training modes (TripletTrainer's negatives_selection_mode) whose loss is one of the above over the whole batch; they have no
+# triplet rows, a device count stands where the triplet count does.
+#   mode: (function, the loss_params it takes or None = it takes `margin`, the element of its counts that is that count or
+#          None = the counts are the count; with an element the trainer keeps all of them as last_pair_counts)
+PAIR_LOSS_MODES = {
+    "batch_all": (batch_all_triplet_loss, None, None),                                          # n_active
+    "multi_similarity": (multi_similarity_loss, ("alpha", "beta", "base", "epsilon"), 3),       # kept pairs
+    "supcon": (supcon_loss, ("temperature", "denominator"), 1),                                 # violating anchors
+}
 
 
 # --------------------------------------------------------------------------- contrastive / accuracy

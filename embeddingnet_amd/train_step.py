@@ -44,7 +44,7 @@ class TripletTrainer:
     anchors [1]) and last_pair_counts = int32 [2]: positive pairs, violating anchors).  Under data parallelism every mode mines
     and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
-    LOSS_PARAMS = {"multi_similarity": ("alpha", "beta", "base", "epsilon"), "supcon": ("temperature", "denominator")}
+    LOSS_PARAMS = {mode: keys for mode, (_, keys, _) in ops.PAIR_LOSS_MODES.items() if keys is not None}
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5,
@@ -58,7 +58,7 @@ class TripletTrainer:
         self.ctx = L.StepContext(f"TripletTrainer@{id(self):x}")       # this trainer's fused hand-overs (layers.StepContext)
         # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
         self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
-        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard", "batch_all", "multi_similarity", "supcon"):
+        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES):
             raise KeyError(self.mode)
         self.loss_params = dict(loss_params or {})
         if self.loss_params and self.mode not in self.LOSS_PARAMS:
@@ -91,21 +91,13 @@ class TripletTrainer:
         if images.shape[0] != self.p * self.k:
             raise ValueError(f"batch of {images.shape[0]} images != k_classes*k_samples = {self.p * self.k}")
         emb = self.model(images)
-        if self.mode == "batch_all":
-            # every valid triplet, mean over the active ones (ops.batch_all_triplet_loss, at every batch size and whatever
-            # EMBNET_FUSED_LOSS says); there are no triplet rows: last_triplets = (None, n_active)
-            mean, count, _ = ops.batch_all_triplet_loss(emb, self.p, self.k, self.margin)
+        if self.mode in ops.PAIR_LOSS_MODES:                # at every batch size and whatever EMBNET_FUSED_LOSS says
+            fn, keys, at = ops.PAIR_LOSS_MODES[self.mode]
+            mean, counts = fn(emb, self.p, self.k, **({"margin": self.margin} if keys is None else self.loss_params))[:2]
+            count = counts if at is None else counts[at:at + 1]             # a slice view of the counts
+            if at is not None:
+                self.last_pair_counts = counts
             self.last_triplets = (None, count)
-        elif self.mode == "multi_similarity":
-            # pair-based: no triplet rows either; the kept-pair count stands where the triplet count does
-            mean, counts = ops.multi_similarity_loss(emb, self.p, self.k, **self.loss_params)
-            count = counts[3:4]
-            self.last_triplets, self.last_pair_counts = (None, count), counts
-        elif self.mode == "supcon":
-            # softmax family: no triplet rows; the violating-anchor count stands where the triplet count does
-            mean, counts = ops.supcon_loss(emb, self.p, self.k, **self.loss_params)
-            count = counts[1:2]
-            self.last_triplets, self.last_pair_counts = (None, count), counts
         elif self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
             seed_dev = self._state.data_ptr() + 24 if self._graph_state_live() else None     # uint64 behind the 6 floats
             mean, _, trip, count = ops.fused_triplet_loss(emb, self.p, self.k, self.margin, self.mode,
@@ -122,7 +114,7 @@ class TripletTrainer:
         return getattr(self, "_state", None) is not None and torch.cuda.is_current_stream_capturing()
 
     def _graph_supported(self, images):
-        if not self._keras_opt or not (self.fused_loss or self.mode in ("batch_all", "multi_similarity", "supcon")):
+        if not self._keras_opt or not (self.fused_loss or self.mode in ops.PAIR_LOSS_MODES):
             return False
         return self.opt.rule != "radam" or self.opt.iterations >= 6      # RAdam switches kernels while it warms up
 

@@ -184,6 +184,31 @@ def test_huge_margin_makes_every_triplet_active(dev, path):
     _check_against_ref(got, ref, x)
 
 
+def test_every_triplet_active_at_the_int32_limit(dev):
+    """32 x 128 rows: T = 4096 * 127 * 3968 = 2 064 121 856, the largest count the range rule admits at n = 4096, on the
+    distance-matrix path (k > 16).  Every triplet is active, so the expected values have a closed form: W[a,p] = n - k,
+    W[a,n] = -(k - 1), loss = margin + sum_a ((n - k) sum_p d(a,p) - (k - 1) sum_n d(a,n)) / T.  Coordinates are multiples of
+    1/8, so every d and every b is a multiple of 1/64 below 2^14: exact in fp32 in either rounding form."""
+    from embeddingnet_amd import _lib
+    p, k, e, margin = 32, 128, 4, 1e4
+    n = p * k
+    T = n * (k - 1) * (n - k)
+    assert T == 2064121856 < 2 ** 31 and _lib.lib().embnet_batch_all_path(p, k, e) == 2
+    x = grid_embeddings(9, p, k, e)
+    xd = x.astype(np.float64)
+    sq = (xd * xd).sum(1)
+    d = sq[:, None] + sq[None, :] - 2.0 * xd @ xd.T                  # exact: multiples of 1/64
+    assert d.max() < margin and d.max() + margin < 2.0 ** 14
+    same = np.kron(np.eye(p, dtype=bool), np.ones((k, k), dtype=bool))
+    W = np.where(same, float(n - k), -float(k - 1))
+    np.fill_diagonal(W, 0.0)
+    loss = margin + ((n - k) * d[same].sum() - (k - 1) * d[~same].sum()) / T
+    ref = dict(loss=loss, A=T, T=T, W=W)
+    got = _run(x, p, k, margin, dev)
+    assert got["A"] == T and got["frac"] == 1.0
+    _check_against_ref(got, ref, x, rows=np.r_[0:96, n // 2:n // 2 + 32, n - 96:n])
+
+
 def test_duplicate_rows(dev):
     p, k, e = 5, 4, 32
     x = grid_embeddings(8, p, k, e)
