@@ -7,7 +7,7 @@ import importlib.abc
 import importlib.util
 import sys
 
-_MODULES = ("backbones", "clustering", "datagenerators", "kmeans", "losses_and_accuracies", "models", "parallel", "retrieval",
+_MODULES = ("backbones", "clustering", "datagenerators", "kmeans", "losses_and_accuracies", "models", "parallel", "proxies", "retrieval",
             "train_step", "utils")
 
 

@@ -1,0 +1,528 @@
+// Proxy-Anchor (Kim et al., CVPR 2020) and CosFace / NormSoftmax (Wang et al., CVPR 2018; Zhai & Wu 2019): the losses that score a
+// batch against one learnable vector per class.  Build-defined: the reference has no such loss.  Semantics: include/embnet.h.
+//
+//   X [n, e] fp32 embeddings, W [c, e] fp32 proxies, y [n] int32 labels (any order; outside [0, c) = unlabelled).
+//   q_c = (float)(1 / sqrt(sum_k w_ck^2)) (f64, k order; 0 for a zero proxy),  D = fp32 dot products,  S = fl(D q_c).
+//   Both losses are ONE rectangle seen from its two sides: anchors A [na, e] meet others B [nb, e], one wave owns one anchor's row.
+//     Proxy-Anchor: the anchors are the proxies (na = c, nb = n), G is [c][n];  a row's positives are the samples of its class.
+//     CosFace:      the anchors are the samples (na = n, nb = c), G is [n][c];  a row's positive is the sample's own class.
+//   prep launch (a wave per class): q, the class sizes cnt[c] (every workgroup of the forward adds them up to |C+| and n_l:
+//     integers, any order).
+//   small path (e + max(n, c) <= 4096 and n c e <= 2^25), ONE more launch: a workgroup holds four anchors and their four rows of D
+//     in LDS (per-lane fma chain over the columns + wave sum, pair_loss.h's staging), one wave per anchor runs the body.
+//   matrix path, TWO more launches: D through embnet_dense_dgrad_f32 (the exact-fp32 matrix-instruction GEMM, a k-ordered chain
+//     per element) into the workspace, then a sweep: one wave per anchor walks its row of D from L2 in three passes (extrema, sums,
+//     weights).  A CosFace row reaches 16384 floats = 64 KiB, four times pair_sweep_fwd's per-wave LDS row: it is not staged at all.
+//   per-anchor partials, pair_loss.h's arrival ticket, a fixed-order f64 reduction by the last workgroup.
+//   backward, three launches (four with demb's class sum split, see proxy_bwd_split) on the f64 matrix instructions
+//     (v_mfma_f64_16x16x4_f64, pair_bwd's tiling): demb = g Q^(T) W,
+//     Y = G^(T) X in f64 into the workspace, then a wave per class: dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c), every output
+//     one fp32 rounding of an f64 expression.
+// A label is compared, and used as an index (CosFace: the sample's own column) only behind the range check that makes it a class
+// index; an unlabelled value addresses nothing.  Nothing is atomic in floating point, every reduction has a fixed order: bitwise
+// reproducible.  No host synchronisation, no allocation: capturable in a graph.
+#include <math.h>
+#include "common.h"
+#include "pair_loss.h"
+#include "../../include/embnet.h"
+
+namespace embnet {
+
+constexpr int PROXY_MAX_N = 4096;
+constexpr int PROXY_MAX_C = 16384;
+constexpr int PROXY_MAX_E = 4096;
+constexpr int PROXY_THREADS = 256;                       // 4 waves: one anchor each
+constexpr int PROXY_WG_ANCHORS = PROXY_THREADS / 64;
+constexpr int PROXY_LDS_FLOATS = 16 * 1024;              // small path: 4 (e + nb) floats
+constexpr long PROXY_SMALL_MACS = 1L << 25;              // small path: n c e, every workgroup re-reads all of B from L2
+static_assert(EMBNET_PROXY_SMALL == 1 && EMBNET_PROXY_MATRIX == 2, "path constants");
+
+struct ProxyParams {
+  const float* anchors;                                  // [na][e]
+  const float* others;                                   // [nb][e]
+  const int32_t* labels;                                 // [n]
+  const float* q;                                        // [c]
+  const int32_t* cnt;                                    // [c] class sizes (prep)
+  int na, nb, e, n, c, kind;
+  float a, b;                                            // alpha, delta | scale, margin
+  float* g; int32_t* counts; float* mean;
+  int* ticket; double2* part_loss; int4* part_cnt;       // workspace: arrival counter (zero between launches), partials
+  const float* d;                                        // matrix path: D [na][nb]
+};
+
+struct ProxyAnchorOut { float lp, ln; int has, viol; };
+
+// ---- prep: q and the class sizes; one wave per class ------------------------------------------------------------------------------
+// The wave reads 64 consecutive elements of the row at a time (coalesced) and squares them in f64, which is exact; the chain over
+// k is contractual, so every lane then adds the 64 squares in lane order, taken from the other lanes one by one: the same f64
+// additions in the same order as a serial loop, and past the row's end exact zeros.  The labels are counted lane-strided (integers).
+__global__ __launch_bounds__(PROXY_THREADS) void proxy_prep_kernel(const float* __restrict__ w, const int32_t* __restrict__ labels,
+                                                                   int n, int c, int e, float* __restrict__ q,
+                                                                   int32_t* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  const int cl = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
+  if (cl >= c) return;                                   // wave-uniform
+  const float* r = w + (long)cl * e;
+  double ss = 0.0;
+  for (int k0 = 0; k0 < e; k0 += 64) {
+    const double v = k0 + lane < e ? (double)r[k0 + lane] : 0.0;
+    const double v2 = v * v;
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) ss += __shfl(v2, j, 64);
+  }
+  int m = 0;
+  for (int i = lane; i < n; i += 64) m += labels[i] == cl;
+  m = wave_sum(m);
+  if (lane == 0) {
+    q[cl] = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
+    cnt[cl] = m;
+  }
+}
+
+// (classes with a sample, labelled samples), the same in every thread of the workgroup
+__device__ __forceinline__ int2 proxy_totals(const int32_t* __restrict__ cnt, int c) {
+  __shared__ int sp[PROXY_WG_ANCHORS], sl[PROXY_WG_ANCHORS];
+  int p = 0, l = 0;
+  for (int i = threadIdx.x; i < c; i += PROXY_THREADS) { const int v = cnt[i]; p += v > 0; l += v; }
+  p = wave_sum(p); l = wave_sum(l);
+  if ((threadIdx.x & 63) == 0) { sp[threadIdx.x >> 6] = p; sl[threadIdx.x >> 6] = l; }
+  __syncthreads();
+  int tp = 0, tl = 0;
+#pragma unroll
+  for (int w = 0; w < PROXY_WG_ANCHORS; ++w) { tp += sp[w]; tl += sl[w]; }
+  return make_int2(tp, tl);
+}
+
+// one rounding order: t = fl(c fl(s + o)); monotone in s for either sign of c
+__device__ __forceinline__ float proxy_t(float c, float s, float o) { return __fmul_rn(c, __fadd_rn(s, o)); }
+
+// Proxy-Anchor, one wave, anchor = class ai: its row drow[n] of D over the samples.  Writes all n entries of the row of G.
+__device__ __forceinline__ ProxyAnchorOut proxy_anchor_row(const float* drow, const ProxyParams& P, int ai, int2 tot, float* grow,
+                                                           int lane) {
+  const int n = P.nb, c = P.c;
+  const float alpha = P.a, delta = P.b, qa = P.q[ai];
+  float mn = INFINITY, mx = -INFINITY;
+  for (int col = lane; col < n; col += 64) {
+    const int y = P.labels[col];
+    if ((unsigned)y >= (unsigned)c) continue;
+    const float s = __fmul_rn(drow[col], qa);
+    if (y == ai) mn = fminf(mn, s); else mx = fmaxf(mx, s);
+  }
+  mn = wave_min(mn);                                     // min over the positives (+inf: none)
+  mx = wave_max(mx);                                     // max over the negatives (-inf: none)
+  // t is monotone in s: the largest exponent of a side belongs to its hardest pair; an empty side has t = -inf and m = 0
+  const float mp = fmaxf(0.f, proxy_t(-alpha, mn, -delta));
+  const float mg = fmaxf(0.f, proxy_t(alpha, mx, delta));
+  float sp = 0.f, sn = 0.f;
+  for (int col = lane; col < n; col += 64) {             // lane-strided, column order
+    const int y = P.labels[col];
+    if ((unsigned)y >= (unsigned)c) continue;
+    const float s = __fmul_rn(drow[col], qa);
+    if (y == ai) sp += expf(__fsub_rn(proxy_t(-alpha, s, -delta), mp));
+    else sn += expf(__fsub_rn(proxy_t(alpha, s, delta), mg));
+  }
+  const float dp = __fadd_rn(expf(-mp), wave_sum(sp));   // e^{-m} + sum e^{t - m} >= 1
+  const float dn = __fadd_rn(expf(-mg), wave_sum(sn));
+  const float cp = __fdiv_rn(alpha, (float)max(tot.x, 1));           // the normalisers 1/|C+| and 1/c join alpha
+  const float cn = __fdiv_rn(alpha, (float)c);
+  for (int col = lane; col < n; col += 64) {
+    const int y = P.labels[col];
+    float g = 0.f;
+    if ((unsigned)y < (unsigned)c) {
+      const float s = __fmul_rn(drow[col], qa);
+      if (y == ai) g = -__fmul_rn(cp, __fdiv_rn(expf(__fsub_rn(proxy_t(-alpha, s, -delta), mp)), dp));
+      else g = __fmul_rn(cn, __fdiv_rn(expf(__fsub_rn(proxy_t(alpha, s, delta), mg)), dn));
+    }
+    grow[col] = g;
+  }
+  const int npos = P.cnt[ai];
+  const int has = npos > 0;
+  return ProxyAnchorOut{__fadd_rn(mp, logf(dp)), __fadd_rn(mg, logf(dn)), has, has && tot.y - npos > 0 && mx >= mn};
+}
+
+// CosFace, one wave, anchor = sample ai: its row drow[c] of D over the classes.  Writes all c entries of the row of G.
+__device__ __forceinline__ ProxyAnchorOut proxy_softmax_row(const float* drow, const ProxyParams& P, int ai, int2 tot, float* grow,
+                                                            int lane) {
+  const int c = P.nb;
+  const int y = P.labels[ai];
+  if ((unsigned)y >= (unsigned)c) {                      // unlabelled (wave-uniform): a zero row, no loss
+    for (int col = lane; col < c; col += 64) grow[col] = 0.f;
+    return ProxyAnchorOut{0.f, 0.f, 0, 0};
+  }
+  const float sigma = P.a, mu = P.b;
+  float M = -INFINITY, mxo = -INFINITY;
+  for (int col = lane; col < c; col += 64) {
+    const float s = __fmul_rn(drow[col], P.q[col]);
+    if (col != y) mxo = fmaxf(mxo, s);
+    M = fmaxf(M, __fmul_rn(sigma, col == y ? __fsub_rn(s, mu) : s));
+  }
+  M = wave_max(M);
+  mxo = wave_max(mxo);
+  const float sy = __fmul_rn(drow[y], P.q[y]);
+  const float ty = __fmul_rn(sigma, __fsub_rn(sy, mu));
+  float se = 0.f;
+  for (int col = lane; col < c; col += 64) {             // lane-strided, column order
+    const float s = __fmul_rn(drow[col], P.q[col]);
+    se += expf(__fsub_rn(__fmul_rn(sigma, col == y ? __fsub_rn(s, mu) : s), M));
+  }
+  const float d = wave_sum(se);                          // >= 1: the largest logit gives e^0
+  const float cs = __fdiv_rn(sigma, (float)max(tot.y, 1));           // the normaliser 1/n_l joins sigma
+  for (int col = lane; col < c; col += 64) {
+    const float s = __fmul_rn(drow[col], P.q[col]);
+    const float w = __fdiv_rn(expf(__fsub_rn(__fmul_rn(sigma, col == y ? __fsub_rn(s, mu) : s), M)), d);
+    grow[col] = __fmul_rn(cs, col == y ? __fsub_rn(w, 1.f) : w);
+  }
+  return ProxyAnchorOut{__fadd_rn(logf(d), __fsub_rn(M, ty)), 0.f, 1, mxo >= sy};
+}
+
+__device__ __forceinline__ void proxy_row(const float* drow, const ProxyParams& P, int a, int2 tot, int lane) {
+  float* grow = P.g + (long)a * P.nb;
+  const ProxyAnchorOut o = P.kind == EMBNET_PROXY_ANCHOR ? proxy_anchor_row(drow, P, a, tot, grow, lane)
+                                                         : proxy_softmax_row(drow, P, a, tot, grow, lane);
+  if (lane == 0) {
+    P.part_loss[a] = make_double2((double)o.lp, (double)o.ln);
+    P.part_cnt[a] = make_int4(o.has, o.viol, 0, 0);
+  }
+}
+
+// pair_finish's ticket around two loss sums: the last workgroup to arrive re-arms the counter and reduces the na partials in index
+// order.  loss = sum lp / (anchors with a positive term) + sum ln / c  (the second sum is zero for CosFace).
+__device__ __forceinline__ void proxy_finish(const ProxyParams& P, int2 tot) {
+  __shared__ int s_last;
+  __shared__ double ws_loss[PROXY_WG_ANCHORS][2];
+  __shared__ int ws_cnt[PROXY_WG_ANCHORS][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int t = atomicAdd(P.ticket, 1);
+    s_last = t == (int)gridDim.x - 1;
+    if (s_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *P.ticket = 0;                                     // re-arm the counter for the next launch
+    }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  double sp = 0.0, sn = 0.0;
+  int c0 = 0, c1 = 0;
+  const double* pl = (const double*)P.part_loss;
+  const int* pc = (const int*)P.part_cnt;
+  for (int i = tid; i < P.na; i += PROXY_THREADS) {
+    sp += __hip_atomic_load(&pl[2 * i + 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sn += __hip_atomic_load(&pl[2 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c0 += __hip_atomic_load(&pc[4 * i + 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c1 += __hip_atomic_load(&pc[4 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  sp = wave_sum(sp); sn = wave_sum(sn);
+  c0 = wave_sum(c0); c1 = wave_sum(c1);
+  if (lane == 0) { ws_loss[wave][0] = sp; ws_loss[wave][1] = sn; ws_cnt[wave][0] = c0; ws_cnt[wave][1] = c1; }
+  __syncthreads();
+  if (tid == 0) {
+    double tp = 0.0, tn = 0.0;
+    int t0 = 0, t1 = 0;
+    for (int w = 0; w < PROXY_WG_ANCHORS; ++w) { tp += ws_loss[w][0]; tn += ws_loss[w][1]; t0 += ws_cnt[w][0]; t1 += ws_cnt[w][1]; }
+    P.counts[0] = t0;                                    // |C+| or n_l: at most 16384
+    P.counts[1] = tot.y;                                 // labelled samples: at most 4096
+    P.counts[2] = t1;
+    *P.mean = (float)((t0 > 0 ? tp / (double)t0 : 0.0) + tn / (double)P.c);
+  }
+}
+
+// ---- forward, small path: grid = ceil(na / 4) workgroups -------------------------------------------------------------------------
+__global__ __launch_bounds__(PROXY_THREADS) void proxy_small_fwd_kernel(ProxyParams P) {
+  __shared__ __attribute__((aligned(16))) float lds[PROXY_LDS_FLOATS];
+  const int na = P.na, nb = P.nb, e = P.e;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int a0 = blockIdx.x * PROXY_WG_ANCHORS;
+  const int2 tot = proxy_totals(P.cnt, P.c);
+  float* A = lds;                                        // [4][e] the workgroup's anchors (zero rows past na)
+  float* D = lds + PROXY_WG_ANCHORS * e;                 // [4][nb] their rows of D
+  for (int i = tid; i < PROXY_WG_ANCHORS * e; i += PROXY_THREADS) A[i] = a0 + i / e < na ? P.anchors[(long)a0 * e + i] : 0.f;
+  __syncthreads();
+  // row r of B against the four anchors: the row is read once, eight loads in flight per lane (pair_class_fwd's loop)
+  for (int r = wave; r < nb; r += PROXY_WG_ANCHORS) {
+    const float* y = P.others + (long)r * e;
+    float acc[PROXY_WG_ANCHORS];
+#pragma unroll
+    for (int a = 0; a < PROXY_WG_ANCHORS; ++a) acc[a] = 0.f;
+    for (int c0 = 0; c0 < e; c0 += 512) {
+      float yv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const int cc = c0 + lane + 64 * j; yv[j] = cc < e ? y[cc] : 0.f; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int cc = c0 + lane + 64 * j;
+        if (cc < e) {
+#pragma unroll
+          for (int a = 0; a < PROXY_WG_ANCHORS; ++a) acc[a] = fmaf(A[a * e + cc], yv[j], acc[a]);
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < PROXY_WG_ANCHORS; ++a) {
+      const float v = wave_sum(acc[a]);
+      if (lane == 0) D[a * nb + r] = v;
+    }
+  }
+  __syncthreads();
+  if (a0 + wave < na) proxy_row(D + wave * nb, P, a0 + wave, tot, lane);
+  proxy_finish(P, tot);
+}
+
+// ---- forward, matrix path: grid = ceil(na / 4) workgroups, one wave walks one row of D from L2 -----------------------------------
+__global__ __launch_bounds__(PROXY_THREADS) void proxy_sweep_kernel(ProxyParams P) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int a = blockIdx.x * PROXY_WG_ANCHORS + wave;
+  const int2 tot = proxy_totals(P.cnt, P.c);
+  if (a < P.na) proxy_row(P.d + (long)a * P.nb, P, a, tot, lane);
+  proxy_finish(P, tot);
+}
+
+// ---- backward: Out[r][col] = sum_j M(r, j) B[j][col] on the f64 matrix instructions -----------------------------------------------
+// grid (ceil(R/32), ceil(e/32)), 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS (pair_bwd's tiling
+// and lane map).  M(r, j) = G[r][j] (G is [R][J]) or, TRANS, G[j][r] (G is [J][R]); SCALE: times qv[j], an exact f64 product.
+// OutT float: one fp32 rounding of g * sum (g = *upstream, NULL = 1); double: the sum itself.  The sum runs over j in [jb, je).
+template <bool TRANS, bool SCALE, class OutT>
+__device__ __forceinline__ void proxy_mm(const float* __restrict__ G, const float* __restrict__ qv, const float* __restrict__ B, int R,
+                                         int J, int e, int jb, int je, const float* __restrict__ upstream, OutT* __restrict__ out) {
+  __shared__ float wa[32][33];                           // M[i0 + ii][j0 + jj]
+  __shared__ float xs[32][33];                           // B[j0 + jj][e0 + ee]
+  __shared__ float qs[32];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
+  const int ro = 16 * (wave >> 1), co = 16 * (wave & 1);
+  const int lr = lane & 15, lk = lane >> 4;
+  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int j0 = jb; j0 < je; j0 += 32) {                 // (jb is a multiple of 32 and je of 32 or J: j < J guards the tail)
+    for (int t = tid; t < 1024; t += 256) {
+      const int r = t >> 5, cc = t & 31;
+      if constexpr (TRANS) {
+        const int j = j0 + r, i = i0 + cc;
+        wa[cc][r] = (i < R && j < J) ? G[(long)j * R + i] : 0.f;
+      } else {
+        const int i = i0 + r, j = j0 + cc;
+        wa[r][cc] = (i < R && j < J) ? G[(long)i * J + j] : 0.f;
+      }
+      const int jr = j0 + r, ec = e0 + cc;
+      xs[r][cc] = (jr < J && ec < e) ? B[(long)jr * e + ec] : 0.f;
+    }
+    if constexpr (SCALE) {
+      if (tid < 32) qs[tid] = j0 + tid < J ? qv[j0 + tid] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      const int kx = 4 * kk + lk;
+      double av = (double)wa[ro + lr][kx];
+      if constexpr (SCALE) av *= (double)qs[kx];
+      const double bv = (double)xs[kx][co + lr];
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const int col = e0 + co + lr;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = i0 + ro + lk + 4 * r;
+    if (row < R && col < e) {
+      if constexpr (sizeof(OutT) == 4) out[(long)row * e + col] = (float)((upstream ? (double)*upstream : 1.0) * acc[r]);
+      else out[(long)row * e + col] = acc[r];
+    }
+  }
+}
+
+template <bool TRANS>
+__global__ __launch_bounds__(256) void proxy_bwd_emb_kernel(const float* __restrict__ G, const float* __restrict__ q,
+                                                            const float* __restrict__ proxies, int n, int c, int e,
+                                                            const float* __restrict__ upstream, float* __restrict__ demb) {
+  proxy_mm<TRANS, true, float>(G, q, proxies, n, c, e, 0, c, upstream, demb);
+}
+
+// Few samples against many classes leave the grid above ceil(n/32) ceil(e/32) workgroups with c / 32 serial rounds each: the
+// classes are then split over blockIdx.z in chunks of `jchunk` (a multiple of 32), every slice writes its f64 sums, and
+// proxy_bwd_emb_sum_kernel adds the slices in slice order, scales by g and rounds once.
+template <bool TRANS>
+__global__ __launch_bounds__(256) void proxy_bwd_emb_part_kernel(const float* __restrict__ G, const float* __restrict__ q,
+                                                                 const float* __restrict__ proxies, int n, int c, int e, int jchunk,
+                                                                 double* __restrict__ part) {
+  const int jb = blockIdx.z * jchunk;
+  proxy_mm<TRANS, true, double>(G, q, proxies, n, c, e, jb, min(c, jb + jchunk), nullptr, part + (long)blockIdx.z * n * e);
+}
+
+__global__ __launch_bounds__(256) void proxy_bwd_emb_sum_kernel(const double* __restrict__ part, int splits, long ne,
+                                                                const float* __restrict__ upstream, float* __restrict__ demb) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ne) return;
+  double s = 0.0;
+  for (int z = 0; z < splits; ++z) s += part[z * ne + i];
+  demb[i] = (float)((upstream ? (double)*upstream : 1.0) * s);
+}
+
+template <bool TRANS>
+__global__ __launch_bounds__(256) void proxy_bwd_y_kernel(const float* __restrict__ G, const float* __restrict__ emb, int n, int c,
+                                                          int e, double* __restrict__ y) {
+  proxy_mm<TRANS, false, double>(G, nullptr, emb, c, n, e, 0, n, nullptr, y);
+}
+
+// a wave per class: t = Y_c . w_c (lane-strided f64 chains + butterfly), dproxies_c = g q (Y_c - q^2 t w_c)
+__global__ __launch_bounds__(PROXY_THREADS) void proxy_bwd_proxies_kernel(const double* __restrict__ y, const float* __restrict__ proxies,
+                                                                          const float* __restrict__ q, int c, int e,
+                                                                          const float* __restrict__ upstream,
+                                                                          float* __restrict__ dproxies) {
+  const int lane = threadIdx.x & 63;
+  const int cl = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
+  if (cl >= c) return;                                   // wave-uniform
+  const double* yr = y + (long)cl * e;
+  const float* wr = proxies + (long)cl * e;
+  double t = 0.0;
+  for (int k = lane; k < e; k += 64) t = fma(yr[k], (double)wr[k], t);
+  t = wave_sum(t);
+  const double qc = (double)q[cl];
+  const double gq = (upstream ? (double)*upstream : 1.0) * qc;
+  const double f = qc * qc * t;
+  for (int k = lane; k < e; k += 64) dproxies[(long)cl * e + k] = (float)(gq * (yr[k] - f * (double)wr[k]));
+}
+
+// ---- host side: range, path rule, workspace layout ---------------------------------------------------------------------------------
+inline bool proxy_range_ok(int n, int c, int e) {
+  return n >= 2 && n <= PROXY_MAX_N && c >= 2 && c <= PROXY_MAX_C && e >= 1 && e <= PROXY_MAX_E;
+}
+
+inline bool proxy_small_fits(int n, int c, int e) {
+  return PROXY_WG_ANCHORS * (e + (n > c ? n : c)) <= PROXY_LDS_FLOATS && (long)n * c * e <= PROXY_SMALL_MACS;
+}
+
+// [16 B ticket][c int32 class sizes][m double2 partial losses][m int4 partial counts][c*n f32 D][c*e f64 Y], m = max(n, c)
+struct ProxyWorkspace {
+  size_t cnt, part_loss, part_cnt, d, y, bytes;
+  ProxyWorkspace(int n, int c, int e) {
+    const size_t m = (size_t)(n > c ? n : c);
+    cnt = 16;
+    part_loss = cnt + pair_align16((size_t)c * 4);
+    part_cnt = part_loss + m * 16;
+    d = part_cnt + m * 16;
+    y = d + pair_align16((size_t)c * n * 4);
+    bytes = y + pair_align16((size_t)c * e * 8);
+  }
+};
+
+// demb's class split: none while the unsplit grid has 1024 workgroups or a slice would hold fewer than 256 classes; the slices'
+// f64 sums (splits n e doubles) live where Y will be written afterwards (c e doubles), so splits n <= c.  -> (splits, jchunk)
+inline void proxy_bwd_split(int n, int c, int e, int& splits, int& jchunk) {
+  const int base = cdiv(n, 32) * cdiv(e, 32);
+  int s = cdiv(1024, base);
+  if (s > c / 256) s = c / 256;
+  if (s > c / n) s = c / n;
+  if (s < 1) s = 1;
+  jchunk = cdiv(cdiv(c, s), 32) * 32;
+  splits = cdiv(c, jchunk);
+}
+
+inline int proxy_check_common(const char* what, bool pointers, int n, int c, int e, int kind, const void* workspace,
+                              size_t workspace_bytes) {
+  EMBNET_CHECK_ARG(pointers, "%s: null pointer", what);
+  EMBNET_CHECK_ARG(n >= 2 && n <= PROXY_MAX_N, "%s: n=%d outside [2, %d]", what, n, PROXY_MAX_N);
+  EMBNET_CHECK_ARG(c >= 2 && c <= PROXY_MAX_C, "%s: c=%d outside [2, %d]", what, c, PROXY_MAX_C);
+  EMBNET_CHECK_ARG(e >= 1 && e <= PROXY_MAX_E, "%s: e=%d outside [1, %d]", what, e, PROXY_MAX_E);
+  EMBNET_CHECK_ARG(kind == EMBNET_PROXY_ANCHOR || kind == EMBNET_PROXY_SOFTMAX, "%s: unknown kind %d", what, kind);
+  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+  const size_t need = ProxyWorkspace(n, c, e).bytes;
+  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+  return EMBNET_OK;
+}
+
+}  // namespace embnet
+
+using namespace embnet;
+
+extern "C" size_t embnet_proxy_loss_workspace_bytes(int n, int c, int e) {
+  return proxy_range_ok(n, c, e) ? ProxyWorkspace(n, c, e).bytes : 0;
+}
+
+extern "C" int embnet_proxy_loss_path(int n, int c, int e) {
+  if (!proxy_range_ok(n, c, e)) return 0;
+  return proxy_small_fits(n, c, e) ? EMBNET_PROXY_SMALL : EMBNET_PROXY_MATRIX;
+}
+
+extern "C" int embnet_proxy_loss_fwd(const float* emb, const float* proxies, const int32_t* labels, int n, int c, int e, int kind,
+                                     float a, float b, int path, float* pair_g, float* q, int32_t* counts, float* mean_loss,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  const char* what = "proxy_loss_fwd";
+  EMBNET_CHECK_ARG(path >= 0 && path <= EMBNET_PROXY_MATRIX, "%s: unknown path %d", what, path);
+  EMBNET_CHECK_ARG(isfinite(a) && a > 0.f, "%s: %s=%g must be finite and positive", what, kind == EMBNET_PROXY_SOFTMAX ? "scale" : "alpha",
+                   (double)a);
+  EMBNET_CHECK_ARG(isfinite(b), "%s: %s=%g must be finite", what, kind == EMBNET_PROXY_SOFTMAX ? "margin" : "delta", (double)b);
+  const int rc = proxy_check_common(what, emb && proxies && labels && pair_g && q && counts && mean_loss && workspace, n, c, e, kind,
+                                    workspace, workspace_bytes);
+  if (rc != EMBNET_OK) return rc;
+  EMBNET_CHECK_ARG(path != EMBNET_PROXY_SMALL || proxy_small_fits(n, c, e), "%s: n=%d c=%d e=%d does not fit the small path", what, n,
+                   c, e);
+  if (path == 0) path = embnet_proxy_loss_path(n, c, e);
+  const ProxyWorkspace L(n, c, e);
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* cnt = (int32_t*)(ws + L.cnt);
+  float* d = (float*)(ws + L.d);
+  const bool pa = kind == EMBNET_PROXY_ANCHOR;
+  const int na = pa ? c : n, nb = pa ? n : c;
+  ProxyParams P{pa ? proxies : emb, pa ? emb : proxies, labels, q, cnt, na, nb, e, n, c, kind, a, b, pair_g, counts, mean_loss,
+                (int*)ws, (double2*)(ws + L.part_loss), (int4*)(ws + L.part_cnt), d};
+  {
+    EMBNET_TRACE("embnet::proxy_prep_kernel", TRACE_BYTES, 4.0 * c * e + 4.0 * n + 8.0 * c, stream);
+    proxy_prep_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, s>>>(proxies, labels, n, c, e, q, cnt);
+  }
+  const int grid = cdiv(na, PROXY_WG_ANCHORS);
+  if (path == EMBNET_PROXY_SMALL) {
+    EMBNET_TRACE_FLOP("embnet::proxy_small_fwd_kernel", 2.0 * n * c * e, 4.0 * e * (na + (double)grid * nb) + 4.0 * n * c, stream);
+    proxy_small_fwd_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
+    return check_launch(what);
+  }
+  const int rg = embnet_dense_dgrad_f32(P.anchors, P.others, d, na, nb, e, stream);
+  if (rg != EMBNET_OK) return rg;
+  EMBNET_TRACE("embnet::proxy_sweep_kernel", TRACE_BYTES, 16.0 * n * c, stream);
+  proxy_sweep_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
+  return check_launch(what);
+}
+
+extern "C" int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int n, int c, int e, int kind, const float* pair_g,
+                                     const float* q, const float* upstream, float* demb, float* dproxies, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  const char* what = "proxy_loss_bwd";
+  const int rc = proxy_check_common(what, emb && proxies && pair_g && q && demb && dproxies && workspace, n, c, e, kind, workspace,
+                                    workspace_bytes);
+  if (rc != EMBNET_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* y = (double*)((char*)workspace + ProxyWorkspace(n, c, e).y);
+  const bool pa = kind == EMBNET_PROXY_ANCHOR;               // G is [c][n]: transposed for demb's rows, direct for Y's
+  const double flop = 2.0 * n * c * e, gbytes = 4.0 * n * c;
+  const dim3 ge(cdiv(n, 32), cdiv(e, 32)), gy(cdiv(c, 32), cdiv(e, 32));
+  int splits, jchunk;
+  proxy_bwd_split(n, c, e, splits, jchunk);
+  {
+    EMBNET_TRACE_FLOP(splits == 1 ? "embnet::proxy_bwd_emb_kernel" : "embnet::proxy_bwd_emb_part_kernel", flop, gbytes + 4.0 * e * (c + n), stream);
+    if (splits == 1) {
+      if (pa) proxy_bwd_emb_kernel<true><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+      else proxy_bwd_emb_kernel<false><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+    } else {                                             // the slices' sums sit in Y's place until the next launch but one writes Y
+      const dim3 gz(ge.x, ge.y, splits);
+      if (pa) proxy_bwd_emb_part_kernel<true><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+      else proxy_bwd_emb_part_kernel<false><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+    }
+  }
+  if (splits > 1) {
+    EMBNET_TRACE("embnet::proxy_bwd_emb_sum_kernel", TRACE_BYTES, 8.0 * splits * n * e + 4.0 * n * e, stream);
+    proxy_bwd_emb_sum_kernel<<<cdiv((long)n * e, 256), 256, 0, s>>>(y, splits, (long)n * e, upstream, demb);
+  }
+  {
+    EMBNET_TRACE_FLOP("embnet::proxy_bwd_y_kernel", flop, gbytes + 4.0 * e * n + 8.0 * e * c, stream);
+    if (pa) proxy_bwd_y_kernel<false><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
+    else proxy_bwd_y_kernel<true><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
+  }
+  EMBNET_TRACE("embnet::proxy_bwd_proxies_kernel", TRACE_BYTES, 16.0 * c * e, stream);
+  proxy_bwd_proxies_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, s>>>(y, proxies, q, c, e, upstream, dproxies);
+  return check_launch(what);
+}

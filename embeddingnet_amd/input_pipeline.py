@@ -18,6 +18,7 @@ single-threaded decode on the training thread would bound the whole job, so:
 Both hand `TripletTrainer.step` the class-contiguous float32 [P*K, H, W, 3] tensor `sample_batch()` would have produced, value
 for value (float32 `x / 255.`).
 """
+import collections
 import os
 import queue
 import threading
@@ -300,10 +301,13 @@ class Feeder:
     """What tools/train.py steps on: `.next()` -> the next class-contiguous float32 device batch of a TripletsDataGenerator.
     In-memory float datasets (synthetic): the generator's own batch, copied; files without host augmentations that fit
     `store_budget` bytes: DeviceImageStore; otherwise: BatchPrefetcher.  The generator's `device_augmentations` (a DeviceAugment)
-    augment every batch on the GPU, on either file path."""
+    augment every batch on the GPU, on either file path.  `.next_labelled()` -> (that batch, its rows' global class indices: the
+    positions in gen.class_names, int32 [P*K] on the device) for the losses on class proxies (train_step.ProxyTrainer)."""
 
     def __init__(self, gen, device, depth=10, workers=None, store_budget=32 << 30, log=None):
         self.gen, self.device = gen, torch.device(device)
+        self._class_index = {name: i for i, name in enumerate(gen.class_names)}
+        self._plan_labels = collections.deque()            # the class indices of the plans drawn and not yet delivered, oldest first
         any_src = next(iter(gen.class_files_paths.values()))
         self.kind, self.store, self.prefetch = "memory", None, None
         self.augment = getattr(gen, "device_augmentations", None)
@@ -319,18 +323,37 @@ class Feeder:
                 b = gen.k_classes * gen.k_samples
                 procs = gen.augmentations is None and os.environ.get("EMBNET_DECODE_PROCESSES", "1") != "0"
                 self.kind = "prefetch (worker processes)" if procs else "prefetch (worker threads)"
-                self.prefetch = BatchPrefetcher(gen.sample_plan, gen.load_plan_u8, (b, gen.input_shape[1], gen.input_shape[0], 3),
+                self.prefetch = BatchPrefetcher(self._plan, gen.load_plan_u8, (b, gen.input_shape[1], gen.input_shape[0], 3),
                                                 device, depth, workers, paths_fn=gen.plan_paths if procs else None,
                                                 input_shape=gen.input_shape, augment=self.augment)
         if log:
             log(f"input pipeline: {self.kind}")
 
+    def _plan(self):
+        """gen.sample_plan(), with the plan's class indices (one per row) queued behind those of the plans drawn before it."""
+        plan = self.gen.sample_plan()
+        self._plan_labels.append(np.repeat(np.asarray([self._class_index[cl] for cl in plan[0]], np.int32),
+                                           [len(ix) for ix in plan[1]]))
+        return plan
+
     def next(self):
         if self.store is not None:
             return self.store.batch(self.gen.sample_plan(), augment=self.augment)
         if self.prefetch is not None:
+            self._plan_labels.popleft()                     # the delivered batch's: the prefetcher draws its plans through _plan
             return self.prefetch.next()
         return torch.from_numpy(self.gen.sample_batch()).to(self.device)
+
+    def next_labelled(self):
+        """-> (the batch next() would deliver, labels int32 [P*K] on the device).  The plans are drawn in next()'s order from
+        the same np.random stream, up to `depth` batches ahead on the prefetch path: the labels wait in a FIFO for their batch."""
+        if self.store is not None:
+            images = self.store.batch(self._plan(), augment=self.augment)
+        elif self.prefetch is not None:
+            images = self.prefetch.next()
+        else:
+            images = torch.from_numpy(self.gen.load_plan(self._plan())).to(self.device)
+        return images, torch.from_numpy(self._plan_labels.popleft()).to(self.device)
 
     def close(self):
         if self.prefetch is not None:

@@ -7,6 +7,8 @@ meaning), computing on the GPU through libembnet_hip.so.
   batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
   multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
+  proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
+  proxy_softmax_loss(head, scale, margin)(y_true, y_pred)   build-defined (CosFace / NormSoftmax against a ProxyHead's proxies) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
 from . import ops
@@ -58,6 +60,27 @@ def supcon_loss(k_classes, k_samples, temperature=0.1, denominator="all"):
 
     def loss_function(y_true, y_pred):
         return ops.supcon_loss(y_pred, k_classes, k_samples, temperature, denominator)[0]
+
+    return loss_function
+
+
+def proxy_anchor_loss(head, alpha=32.0, delta=0.1):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_true is the int32 [N] tensor of global class indices (outside
+    [0, C): unlabelled), y_pred the [N, E] embeddings, head a proxies.ProxyHead whose parameter receives a gradient.  Proxy-Anchor
+    (Kim et al. 2020; build-defined, not in the reference; include/embnet.h, embnet_proxy_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.proxy_anchor_loss(y_pred, head.proxies, y_true, alpha, delta)[0]
+
+    return loss_function
+
+
+def proxy_softmax_loss(head, scale=64.0, margin=0.35):
+    """Returns loss_function(y_true, y_pred) -> scalar; arguments as proxy_anchor_loss.  CosFace (Wang et al. 2018), with
+    margin = 0 NormSoftmax (build-defined, not in the reference; include/embnet.h, embnet_proxy_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.proxy_softmax_loss(y_pred, head.proxies, y_true, scale, margin)[0]
 
     return loss_function
 

@@ -297,6 +297,88 @@ PAIR_LOSS_MODES = {
 }
 
 
+# --------------------------------------------------------------------------- losses on learnable class proxies (csrc/proxy_loss.hip)
+PROXY_PATHS = {"auto": 0, "small": 1, "matrix": 2}
+PROXY_KINDS = {"proxy_anchor_loss": 1, "proxy_softmax_loss": 2}      # EMBNET_PROXY_ANCHOR, EMBNET_PROXY_SOFTMAX
+_PROXY_WS = {}
+
+
+class _ProxyLoss(torch.autograd.Function):
+    """embnet_proxy_loss_fwd / _bwd (include/embnet.h): a prep launch and one forward launch on the small path, prep + D + sweep
+    above it; three backward launches.  G [c,n] (Proxy-Anchor) or [n,c] (CosFace) and q stay saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, emb, proxies, labels, loss, a, b, path):
+        emb, proxies = _prep(emb), _prep(proxies)
+        n, e = emb.shape
+        c = proxies.shape[0]
+        if proxies.dim() != 2 or proxies.shape[1] != e:
+            raise _lib.EmbnetError(f"{loss}: proxies {tuple(proxies.shape)} do not match embeddings of width {e}")
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+            raise _lib.EmbnetError(f"{loss}: labels must be an int32 tensor of {n} entries")
+        if path not in PROXY_PATHS:
+            raise _lib.EmbnetError(f"{loss}: path {path!r} is not one of {sorted(PROXY_PATHS)}")
+        labels = labels.contiguous()
+        kind = PROXY_KINDS[loss]
+        lib = _lib.lib()
+        g = _new((c, n) if kind == 1 else (n, c), emb)
+        q, counts, mean = _new((c,), emb), _new((3,), emb, torch.int32), _new((), emb)
+        key = (emb.device.index, stream(), n, c, e)
+        ws = _PROXY_WS.get(key)
+        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
+            ws = _PROXY_WS[key] = torch.zeros(max(lib.embnet_proxy_loss_workspace_bytes(n, c, e) // 8, 2), device=emb.device,
+                                              dtype=torch.float64)
+        check(lib.embnet_proxy_loss_fwd(ptr(emb), ptr(proxies), ptr(labels), n, c, e, kind, f32(a), f32(b), PROXY_PATHS[path],
+                                        ptr(g), ptr(q), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8, stream()))
+        ctx.kind, ctx.ws = kind, ws
+        ctx.save_for_backward(emb, proxies, g, q)
+        ctx.mark_non_differentiable(counts, g)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return mean, counts, g
+
+    @staticmethod
+    def backward(ctx, dmean, *_):
+        if dmean is None:
+            return (None,) * 7
+        emb, proxies, g, q = ctx.saved_tensors
+        n, e = emb.shape
+        c = proxies.shape[0]
+        demb, dproxies = torch.empty_like(emb), torch.empty_like(proxies)
+        check(_lib.lib().embnet_proxy_loss_bwd(ptr(emb), ptr(proxies), n, c, e, ctx.kind, ptr(g), ptr(q), ptr(_prep(dmean)),
+                                               ptr(demb), ptr(dproxies), ptr(ctx.ws), ctx.ws.numel() * 8, stream()))
+        return (demb, dproxies) + (None,) * 5
+
+
+def proxy_anchor_loss(emb, proxies, labels, alpha=32.0, delta=0.1, path="auto", return_weights=False):
+    """Proxy-Anchor loss (Kim et al., CVPR 2020) of embeddings [N,E] against learnable proxies [C,E], labels int32 [N] of global
+    class indices in any order (outside [0, C): unlabelled, ignored).  S_ci = x_i . w_c / |w_c| (the embeddings as they are),
+    loss = mean over the classes present of log(1 + sum_{i in c} e^{-alpha (S_ci - delta)}) + mean over all C classes of
+    log(1 + sum_{i labelled, not in c} e^{alpha (S_ci + delta)}) (include/embnet.h has the rounding and the stable forms).
+    -> (mean [autograd w.r.t. emb and proxies], counts int32 [3] = classes present, labelled samples, violating anchors: the
+    present classes whose hardest negative is at least as similar as their hardest positive) on the device, no host
+    synchronisation; return_weights adds G [C,N] = dloss/dS.  path: 'auto', 'small' or 'matrix'."""
+    out = _ProxyLoss.apply(emb, proxies, labels, "proxy_anchor_loss", float(alpha), float(delta), path)
+    return out if return_weights else out[:2]
+
+
+def proxy_softmax_loss(emb, proxies, labels, scale=64.0, margin=0.35, path="auto", return_weights=False):
+    """CosFace (Wang et al., CVPR 2018: the large-margin cosine loss) of embeddings [N,E] against learnable proxies [C,E], labels
+    int32 [N] as in proxy_anchor_loss; margin = 0 is NormSoftmax (Zhai & Wu 2019).  t_ic = scale (S_ic - margin [c = y_i]),
+    loss = mean over the labelled samples of lse_c t_ic - t_iy (include/embnet.h has the rounding and the stable forms).
+    -> (mean [autograd w.r.t. emb and proxies], counts int32 [3] = labelled samples, labelled samples, violating anchors: the
+    samples with another class's proxy at least as similar as their own) on the device, no host synchronisation; return_weights
+    adds G [N,C] = dloss/dS.  path: 'auto', 'small' or 'matrix'."""
+    out = _ProxyLoss.apply(emb, proxies, labels, "proxy_softmax_loss", float(scale), float(margin), path)
+    return out if return_weights else out[:2]
+
+
+# The training modes of train_step.ProxyTrainer:  mode: (function, the loss_params it takes)
+PROXY_LOSS_MODES = {
+    "proxy_anchor": (proxy_anchor_loss, ("alpha", "delta")),
+    "proxy_softmax": (proxy_softmax_loss, ("scale", "margin")),
+}
+
+
 # --------------------------------------------------------------------------- contrastive / accuracy
 class _Contrastive(torch.autograd.Function):
     @staticmethod

@@ -408,3 +408,70 @@ class SiameseTrainer(TripletTrainer):
 
     def step(self, x1, x2, y):
         return super().step((x1, x2, y))
+
+
+class ProxyTrainer(TripletTrainer):
+    """The training step of the proxy / classification losses (ops.PROXY_LOSS_MODES: 'proxy_anchor' = Proxy-Anchor, Kim et al.
+    2020; 'proxy_softmax' = CosFace, Wang et al. 2018, with margin 0 NormSoftmax) with TripletTrainer's machinery: its own step
+    context, the weight-gradient slab sums deferred to one launch per flush, the KerasOptimizer's one-launch update — the proxies
+    are one more tensor of its single group — and, graph=True / 'auto', the whole step captured once into a HIP graph and replayed,
+    the labels copied into a static buffer beside the images.
+
+    base_model: images -> embeddings [N, E];  head: a proxies.ProxyHead(C, E) whose parameter the optimizer (and the reducer)
+    must hold;  loss_params: dict(alpha, delta), defaults 32 and 0.1, or dict(scale, margin), defaults 64 and 0.35; unknown keys
+    are refused.  step(images, labels) -> the loss of the step (detached); labels: int32 device tensor [N] of global class
+    indices in any order (outside [0, C): unlabelled).  last_pair_counts = int32 [3]: anchors with a positive term, labelled
+    samples, violating anchors (include/embnet.h); last_triplets = (None, violating anchors [1]).
+    Under data parallelism each rank's loss covers its own batch against ALL proxies; the proxies are replicated, so the mean of the
+    ranks' gradients — what the reducer forms — is the gradient of the mean of the ranks' losses, for the proxies as for the
+    backbone.  (Proxy-Anchor's 1/|C+| is each rank's own: the mean is over the ranks' losses, not the loss of the pooled batch.)"""
+    LOSS_PARAMS = {mode: keys for mode, (_, keys) in ops.PROXY_LOSS_MODES.items()}
+
+    def __init__(self, base_model, head, optimizer, loss="proxy_anchor", loss_params=None, seed=0, reducer=None, graph=None):
+        from .optimizers import KerasOptimizer
+        env = os.environ.get("EMBNET_GRAPH", "0")
+        self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
+        self._graph, self._graph_failed = None, False
+        if loss not in ops.PROXY_LOSS_MODES:
+            raise KeyError(loss)
+        self.loss_params = dict(loss_params or {})
+        unknown = set(self.loss_params) - set(self.LOSS_PARAMS[loss])
+        if unknown:
+            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} for {loss!r} ({', '.join(self.LOSS_PARAMS[loss])})")
+        if not any(q is head.proxies for g in optimizer.param_groups for q in g["params"]):
+            raise ValueError("ProxyTrainer: the optimizer does not hold head.proxies (build it over the backbone's parameters "
+                             "and the head's)")
+        self.model, self.head, self.opt, self.mode = base_model, head, optimizer, loss
+        self.seed, self.step_no, self.reducer = int(seed), 0, reducer
+        self.ctx = L.StepContext(f"ProxyTrainer@{id(self):x}")
+        self.fused_loss = False
+        self.last_triplets = None
+        self._keras_opt = isinstance(optimizer, KerasOptimizer)
+        if self._keras_opt:
+            optimizer.set_l2(L.regularized_kernels(base_model))
+            if reducer is not None:
+                reducer.direct(True)          # one gradient per parameter and step, the proxies' included
+
+    def loss(self, inputs):
+        images, labels = inputs
+        emb = self.model(images)
+        mean, counts = ops.PROXY_LOSS_MODES[self.mode][0](emb, self.head.proxies, labels, **self.loss_params)
+        count = counts[2:3]                                 # a slice view of the counts
+        self.last_pair_counts = counts
+        self.last_triplets = (None, count)
+        reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
+        return (mean if reg is None else mean + reg), mean, count
+
+    def _graph_supported(self, inputs):
+        if not self._keras_opt:
+            return False
+        return self.opt.rule != "radam" or self.opt.iterations >= 6
+
+    _inputs_like = staticmethod(SiameseTrainer._inputs_like)
+    _inputs_copy = SiameseTrainer._inputs_copy
+    _inputs_match = SiameseTrainer._inputs_match
+
+    def step(self, images, labels):
+        if labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+            raise ValueError(f"ProxyTrainer.step: labels must be int32 [{images.shape[0]}] (got {labels.dtype} {tuple(labels.shape)})")
+        return super().step((images, labels))

@@ -1003,6 +1003,60 @@ size_t embnet_supcon_loss_workspace_bytes(int p, int k, int e);   /* sized for e
 int embnet_supcon_loss_fwd(const float* emb, int p, int k, int e, float temperature, int denominator, int path, float* pair_g,
                            int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Proxy-Anchor (Kim et al., CVPR 2020) and CosFace / NormSoftmax (Wang et al., CVPR 2018; Zhai & Wu, BMVC 2019): the proxy /
+ * classification family of the Reality Check's loss table, a batch scored against one learnable vector per class (the reference
+ * has no such loss): build-defined, selected as ProxyTrainer(loss="proxy_anchor" | "proxy_softmax").  Additions only: the ABI
+ * version stays 22.
+ *   Inputs.  emb[n,e] fp32, proxies[c,e] fp32, labels[n] int32: general labels, the batch need not be class-contiguous.  A label
+ *     outside [0, c) marks an UNLABELLED sample: it belongs to no set, its column (Proxy-Anchor) or row (CosFace) of G is zero
+ *     and it receives no gradient.  A label value is compared, and used as an index only after the check 0 <= y < c has
+ *     passed (the guard in the kernels is what keeps every label value from reading or writing out of bounds: it stays); there
+ *     is no host check of the labels.
+ *   Similarity, ONE rounding form.  ss_c = sum_k w_ck^2 in f64, in k order;  q_c = (float)(1.0 / sqrt(ss_c)), q_c = 0 when
+ *     ss_c = 0 (a zero proxy has S = 0 and gets no gradient);  D_ic = the fp32 dot product of x_i and w_c;  S_ic = fl(D_ic q_c).
+ *     Embedding rows are used as they are (unit rows are not required); proxies are normalised by q only.  q[c] is an output of
+ *     the forward and an input of the backward.
+ *   EMBNET_PROXY_ANCHOR (a = alpha > 0, b = delta; the Python layers default to 32 and 0.1; G stored [c][n]).
+ *     P_c = {i : y_i = c},  N_c = the labelled samples with y_i != c,  C+ = {c : P_c not empty}.
+ *     t+_ci = -alpha (S_ci - delta) = fl(-alpha fl(S_ci - delta)),  t-_ci = alpha (S_ci + delta) = fl(alpha fl(S_ci + delta)),
+ *     loss = (1/|C+|) sum_{c in C+} log(1 + sum_{P_c} e^{t+}) + (1/c) sum_c log(1 + sum_{N_c} e^{t-});
+ *     an empty sum gives log 1 = 0, the first term is 0 when C+ is empty.  Stable form (multi-similarity's): every logarithm is
+ *     m + log(e^{-m} + sum e^{t - m}) with m = max(0, max t), its argument >= 1: unnormalised embeddings cannot overflow.
+ *     G_ci = -(alpha/|C+|) e^{t+ - m+} / (e^{-m+} + sum) on P_c,  +(alpha/c) e^{t- - m-} / (e^{-m-} + sum) on N_c,  0 elsewhere.
+ *   EMBNET_PROXY_SOFTMAX (a = scale sigma > 0, b = margin mu; the Python layers default to 64 and 0.35; mu = 0 is NormSoftmax;
+ *     G stored [n][c]).  For a labelled sample i of class y:  t_ic = sigma (S_ic - mu [c = y]) = fl(sigma fl(S_iy - mu)) for c = y
+ *     and fl(sigma S_ic) otherwise;  l_i = lse_c t_ic - t_iy in the stable form log(sum_c e^{t_ic - M}) + (M - t_iy), M = max_c t_ic
+ *     (the logarithm's argument is >= 1);  loss = (1/n_l) sum l_i over the n_l labelled samples, 0 when n_l = 0.
+ *     G_ic = (sigma/n_l)(e^{t_ic - M} / sum - [c = y]);  an unlabelled row is zero.
+ *   Common.  *mean_loss = loss.  pair_g = dloss/dS, normalisers included, every entry written.  Backward, g = *upstream (NULL = 1),
+ *     Q_ci = q_c G_ci:  demb = g Q^T W (Proxy-Anchor) or g Q W (CosFace);  Y_c = sum_i G_ci x_i,
+ *     dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c).  The sums run on the f64 matrix instructions; every output element is one
+ *     fp32 rounding of an f64 expression.
+ *   Counters.  counts[3], int32, exact on the device's fp32 S:  counts[0] = anchors that carry a positive term (|C+| for
+ *     Proxy-Anchor, n_l for CosFace);  counts[1] = labelled samples;  counts[2] = violating anchors, which go to zero as the classes
+ *     separate: the c in C+ with N_c not empty and max_{N_c} S >= min_{P_c} S (Proxy-Anchor), the labelled i with
+ *     max_{c != y} S_ic >= S_iy (CosFace).
+ * Range: 2 <= n <= 4096, 2 <= c <= 16384, 1 <= e <= 4096; a and b finite, a > 0; kind one of the two; anything else is rejected
+ * before a launch.  path: 0 = auto (embnet_proxy_loss_path), EMBNET_PROXY_SMALL = a prep launch (q, class sizes) and one launch
+ * in which a workgroup holds four anchors and their rows of D in LDS (per-lane fma chain over the columns + wave sum; it needs
+ * e + max(n, c) <= 4096 and n c e <= 2^25), EMBNET_PROXY_MATRIX = prep, D through embnet_dense_dgrad_f32 (a k-ordered fp32
+ * chain per element) into the workspace and a sweep launch in which one wave walks one anchor's row of D.  The backward is three
+ * launches, four where few samples meet many classes (demb's class sum is then split into slices added in slice order).  No floating-point atomics, every reduction in a fixed order: bitwise reproducible; no host synchronisation or
+ * allocation.
+ * workspace (embnet_proxy_loss_workspace_bytes, either path and the backward, 16-byte aligned; 4 c n + 8 c e bytes and a few per
+ * anchor): zero-filled ONCE by the caller; every launch leaves its arrival counter zeroed.  The backward uses it as scratch
+ * only: it need not be the forward's. */
+enum { EMBNET_PROXY_ANCHOR = 1, EMBNET_PROXY_SOFTMAX = 2 };
+enum { EMBNET_PROXY_SMALL = 1, EMBNET_PROXY_MATRIX = 2 };
+int embnet_proxy_loss_path(int n, int c, int e);          /* the path `auto` takes; 0 outside the range */
+size_t embnet_proxy_loss_workspace_bytes(int n, int c, int e);    /* sized for either path and the backward; 0 outside the range */
+int embnet_proxy_loss_fwd(const float* emb, const float* proxies, const int32_t* labels, int n, int c, int e, int kind, float a,
+                          float b, int path, float* pair_g, float* q, int32_t* counts, float* mean_loss, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int n, int c, int e, int kind, const float* pair_g,
+                          const float* q, const float* upstream, float* demb, float* dproxies, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

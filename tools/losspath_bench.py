@@ -7,7 +7,7 @@ For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2
 semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
-denominator beside ops.multi_similarity_loss):
+denominator beside ops.multi_similarity_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -35,6 +35,12 @@ CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batc
          ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")]
 
 
+# the losses on class proxies: (name, p, k, e, classes, mode)
+PROXY_CASES = [(f"{cfg}_{mode}", p, k, e, 100, mode) for mode in ("proxy_anchor", "proxy_softmax")
+               for cfg, p, k, e in (("c1", 8, 4, 256), ("c2", 32, 4, 256), ("c5", 64, 4, 512))] + \
+              [("c2_proxy_anchor_c4096", 32, 4, 256, 4096, "proxy_anchor"), ("c2_proxy_softmax_c4096", 32, 4, 256, 4096, "proxy_softmax")]
+
+
 def measure(fn, iters):
     for _ in range(5):
         fn()
@@ -51,6 +57,140 @@ def measure(fn, iters):
     wall = (time.perf_counter() - t0) / iters
     return dict(launches=len(rec), device_us=round(1e3 * sum(r[1] for r in rec), 1), wall_us_per_pass=round(1e6 * wall, 1),
                 kernels={r[0].replace("embnet::", ""): round(1e3 * r[1], 1) for r in rec})
+
+
+def torch_proxy_loss(mode, x, w, labels, a, b):
+    """The same loss composed from torch ops (matmul, logsumexp, autograd): the yardstick of the proxy cases."""
+    c = w.shape[0]
+    s = (x @ w.T) * torch.rsqrt((w * w).sum(1))
+    pos = labels[:, None] == torch.arange(c, device=x.device)[None, :]
+    if mode == "proxy_softmax":
+        t = a * (s - b * pos)
+        return (torch.logsumexp(t, 1) - (t * pos).sum(1)).mean()       # (no boolean gather: the leg is captured in a graph)
+    ninf = torch.full((), -float("inf"), device=x.device)
+    z = torch.zeros((c, 1), device=x.device)
+    lp = torch.logsumexp(torch.cat([z, torch.where(pos, -a * (s - b), ninf).T], 1), 1)
+    ln = torch.logsumexp(torch.cat([z, torch.where(pos, ninf, a * (s + b)).T], 1), 1)
+    present = pos.any(0)
+    return (lp * present).sum() / present.sum() + ln.sum() / c
+
+
+def graph_rounds(legs, rounds, reps):
+    """Each leg (a forward + backward) captured once into a graph; `rounds` alternating rounds of `reps` replays timed with events.
+    -> {leg: median device microseconds per pass}.  Replays leave the host out: this is device time for library and torch legs alike."""
+    graphs = {}
+    side = torch.cuda.Stream()
+    for name, fn in legs.items():
+        with torch.cuda.stream(side):                        # warm-up off the default stream, as capture wants it
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        graphs[name] = g
+    times = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            g.replay()
+            t0.record()
+            for _ in range(reps):
+                g.replay()
+            t1.record()
+            t1.synchronize()
+            times[name].append(1e3 * t0.elapsed_time(t1) / reps)
+    return {name: round(sorted(v)[len(v) // 2], 2) for name, v in times.items()}
+
+
+def proxy_cases(a, dev, out):
+    """ops.proxy_anchor_loss / ops.proxy_softmax_loss (forward + backward w.r.t. embeddings and proxies) beside two other legs in the
+    same process, alternating: the same loss composed from torch ops, and ops.multi_similarity_loss at the same N and E.  Device
+    microseconds are medians of alternating rounds of graph replays; launches and per-kernel times of the library leg come from the
+    library's trace."""
+    for name, p, k, e, c, mode in PROXY_CASES:
+        if a.only and a.only not in name:
+            continue
+        n = p * k
+        g = torch.Generator(device=dev).manual_seed(7)
+        cen = torch.rand((p, e), device=dev, generator=g)
+        x = (cen.repeat_interleave(k, 0) + 0.25 * torch.randn((n, e), device=dev, generator=g)).abs()
+        x = (x / x.norm(dim=1, keepdim=True)).requires_grad_(True)
+        w = (torch.randn((c, e), device=dev, generator=g) * (2.0 / c) ** 0.5).requires_grad_(True)
+        labels = torch.randperm(c, device=dev, generator=g)[:p].repeat_interleave(k).to(torch.int32)
+        fn = ops.PROXY_LOSS_MODES[mode][0]
+        sa, sb = (32.0, 0.1) if mode == "proxy_anchor" else (64.0, 0.35)
+        lab64 = labels.long()
+
+        def hip():
+            x.grad = w.grad = None
+            fn(x, w, labels, sa, sb)[0].backward()
+
+        def composed():
+            x.grad = w.grad = None
+            torch_proxy_loss(mode, x, w, lab64, sa, sb).backward()
+
+        def multi_similarity():
+            x.grad = None
+            ops.multi_similarity_loss(x, p, k)[0].backward()
+
+        def hip_fwd():
+            fn(x, w, labels, sa, sb)
+
+        def composed_fwd():
+            torch_proxy_loss(mode, x, w, lab64, sa, sb)
+
+        trace = measure(hip, a.iters)
+        med = graph_rounds(dict(hip=hip, torch_composed=composed, multi_similarity=multi_similarity, hip_forward=hip_fwd,
+                                torch_composed_forward=composed_fwd), rounds=15, reps=20)
+        row = dict(config=name, N=n, E=e, C=c, mining=mode, path={1: "small", 2: "matrix"}[_lib.lib().embnet_proxy_loss_path(n, c, e)],
+                   hip=trace, device_us_median=med,
+                   device_ratio_vs_torch_composed=round(med["hip"] / med["torch_composed"], 3),
+                   device_ratio_vs_multi_similarity=round(med["hip"] / med["multi_similarity"], 3))
+        out.append(row)
+        print(json.dumps(row), flush=True)
+
+
+def step_times(out, rounds=9, steps=10):
+    """The simple2 64 x 64 training step, 8 x 4 batches, in proxy_anchor mode (ProxyTrainer, 100 classes) beside supcon mode
+    (TripletTrainer), eager steps, alternating rounds of `steps` steps timed with events: median milliseconds per step."""
+    from embeddingnet_amd import backbones as B
+    from embeddingnet_amd.optimizers import KerasOptimizer
+    from embeddingnet_amd.proxies import ProxyHead
+    from embeddingnet_amd.train_step import ProxyTrainer, TripletTrainer
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(3)
+    x = torch.rand((32, 64, 64, 3), device=dev, generator=g)
+    y = torch.arange(8, dtype=torch.int32, device=dev).repeat_interleave(4)
+    legs = {}
+    for mode in ("proxy_anchor", "supcon"):
+        base, _ = B.get_backbone((64, 64, 3), encodings_len=256, backbone_name="simple2", backbone_weights=None, seed=1, device=dev)
+        params = [q for q in base.parameters() if q.requires_grad]
+        if mode == "supcon":
+            tr = TripletTrainer(base, KerasOptimizer(params, "adam", 1e-3), 8, 4, negatives_selection_mode="supcon", graph=False)
+            legs[mode] = lambda tr=tr: tr.step(x)
+        else:
+            head = ProxyHead(100, 256).to(dev)
+            tr = ProxyTrainer(base, head, KerasOptimizer(params + [head.proxies], "adam", 1e-3), loss=mode, graph=False)
+            legs[mode] = lambda tr=tr: tr.step(x, y)
+    for fn in legs.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(steps):
+                fn()
+            t1.record()
+            t1.synchronize()
+            times[name].append(t0.elapsed_time(t1) / steps)
+    row = dict(config="simple2_step_8x4_64px", step_ms_median={k: round(sorted(v)[len(v) // 2], 3) for k, v in times.items()},
+               step_ms_min_max={k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()})
+    out.append(row)
+    print(json.dumps(row), flush=True)
 
 
 def main():
@@ -131,6 +271,9 @@ def main():
             row["fused"] = measure(fused, a.iters)
         out.append(row)
         print(json.dumps(row), flush=True)
+    proxy_cases(a, dev, out)
+    if a.only and a.only in "proxy_step_time":
+        step_times(out)
     if a.json:
         json.dump(out, open(a.json, "w"), indent=1)
 

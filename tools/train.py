@@ -9,6 +9,8 @@ optimizer); siamese mode trains SiameseNet with contrastive_loss.  Per-epoch sch
 lr0 * decay^floor(epoch/step) (train.py:80-81), ReduceLROnPlateau(0.1, patience 4) (:82-83),
 EarlyStopping(patience 10) (:84-86), best-only checkpoints weights/epoch_XXX.npz (:87-90).
 Multi-GPU: launch with torchrun; classes are sharded per rank and gradients all-reduced over RCCL.
+GENERATOR.negatives_selection_mode 'proxy_anchor' / 'proxy_softmax' train the backbone together with one learnable proxy per
+class (train_step.ProxyTrainer on the feeder's labelled batches); the proxies are checkpointed as proxies/epoch_XXX.npz.
 `--synthetic` swaps the file loader for an in-memory synthetic dataset (no dataset ships with the repo).
 """
 import argparse
@@ -189,6 +191,55 @@ def supcon_loss_config(cfg):
     return out
 
 
+PROXY_LOSS_KEYS = {'proxy_anchor': ('alpha', 'delta'), 'proxy_softmax': ('scale', 'margin')}
+
+
+def proxy_loss_config(cfg):
+    """GENERATOR.proxy_loss (optional): {alpha, delta} of negatives_selection_mode 'proxy_anchor' or {scale, margin} of
+    'proxy_softmax', any subset -> the trainer's loss_params (None without the key).  Only those two modes of a triplet-mode model
+    read it: given with anything else, or with other keys, non-numbers or a non-positive alpha / scale, it is a ValueError before
+    training starts.  The two modes themselves need a triplet-mode model."""
+    mode = cfg['generator'].get('negatives_selection_mode')
+    siamese = cfg['model']['mode'] == 'siamese'
+    value = cfg['generator'].get('proxy_loss')
+    if value is None:
+        return None
+    if siamese or mode not in PROXY_LOSS_KEYS:
+        raise ValueError(f"GENERATOR.proxy_loss sets the parameters of negatives_selection_mode 'proxy_anchor' or 'proxy_softmax'; "
+                         f"this config trains with {'the Siamese contrastive loss' if siamese else repr(mode)}: "
+                         "drop the key or change the mode")
+    keys = PROXY_LOSS_KEYS[mode]
+    if not isinstance(value, dict) or set(value) - set(keys):
+        raise ValueError(f"GENERATOR.proxy_loss: a mapping with keys out of {keys} for {mode!r} (got {value!r})")
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value.values()):
+        raise ValueError(f"GENERATOR.proxy_loss: every value must be a number (got {value!r})")
+    if keys[0] in value and not value[keys[0]] > 0:
+        raise ValueError(f"GENERATOR.proxy_loss: {keys[0]} must be positive (got {value[keys[0]]!r})")
+    return {k: float(v) for k, v in value.items()}
+
+
+def _proxies_path(weights_path):
+    """<project>/weights/epoch_007.npz -> <project>/proxies/epoch_007.npz (the class proxies of the proxy losses)."""
+    d, f = os.path.split(os.path.abspath(weights_path))
+    return os.path.join(os.path.dirname(d), 'proxies', f)
+
+
+def save_proxies(path, head, class_names):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, proxies=head.proxies.detach().cpu().numpy(), class_names=np.asarray(list(class_names), dtype=str))
+
+
+def load_proxies(path, head, class_names):
+    """The proxies of a checkpoint into `head`; a file for other classes (or another order of them) is refused."""
+    d = np.load(path, allow_pickle=False)
+    if [str(v) for v in d['class_names']] != [str(v) for v in class_names]:
+        raise ValueError(f"{path}: its class_names differ from the dataset's: the proxies belong to other classes")
+    if tuple(d['proxies'].shape) != tuple(head.proxies.shape):
+        raise ValueError(f"{path}: proxies {tuple(d['proxies'].shape)} do not match {tuple(head.proxies.shape)}")
+    with torch.no_grad():
+        head.proxies.copy_(torch.from_numpy(d['proxies']).to(head.proxies.device))
+
+
 MAP_MONITORS = ('val_map@r', 'val_r_precision')
 
 
@@ -259,7 +310,12 @@ def main():
     monitor_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))      # likewise a bad TRAIN.monitor / retrieval_ks
     ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
     supcon_loss = supcon_loss_config(cfg)              # and GENERATOR.supcon_loss
-    loss_params = ms_loss if ms_loss is not None else supcon_loss      # each is refused with the other's mode: at most one is set
+    proxy_loss = proxy_loss_config(cfg)                # and GENERATOR.proxy_loss
+    # each is refused with another's mode: at most one is set
+    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss) if v is not None), None)
+    proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS
+    if proxy_mode and cfg['model']['mode'] == 'siamese':
+        raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     clustering_nmi_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
@@ -285,7 +341,7 @@ def main():
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
-    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss')}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -308,6 +364,15 @@ def main():
     if args.resume_from is not None:
         model.load_model(args.resume_from)            # the mining model IS base_model, so it resumes too
     broadcast_model(trainable)                        # identical start on every rank: parameters and BN buffers
+    head = None
+    if proxy_mode:
+        # one learnable proxy per class of the WHOLE dataset, replicated on every rank (seeded on the CPU: identical everywhere)
+        from embeddingnet_amd.proxies import ProxyHead
+        head = ProxyHead(len(data_loader.class_names), p_model['encodings_len'], seed=0).to(dev)
+        if args.resume_from is not None and os.path.exists(_proxies_path(args.resume_from)):
+            load_proxies(_proxies_path(args.resume_from), head, data_loader.class_names)
+            print(f'resumed proxies from {_proxies_path(args.resume_from)}')
+        broadcast_model(head)
     if 'softmax' in cfg:                              # reference train.py:164-170
         # every rank pre-trains on its own batches with the gradients all-reduced (no rank waits in a collective for the
         # length of a pre-training: the RCCL watchdog would abort it); rank 0 writes the pre-training checkpoints
@@ -316,17 +381,24 @@ def main():
                                   max_epochs=args.max_epochs, distributed=world > 1)
         broadcast_model(trainable)                    # belt and braces: BN moving statistics are rank-local
 
-    params = [p for p in trainable.parameters() if p.requires_grad]
+    params = [p for p in trainable.parameters() if p.requires_grad] + ([head.proxies] if head is not None else [])
+
+    def named_slots():
+        """The parameters whose optimizer slots a checkpoint holds, by name: the Keras weight names, and the proxies."""
+        from embeddingnet_amd.backbones import keras_weights
+        named = {k: v for k, v in keras_weights(trainable).items() if isinstance(v, torch.nn.Parameter)}
+        if head is not None:
+            named['proxy_head/proxies'] = head.proxies
+        return named
+
     opt = p_train['optimizer'].build(params)
     lr0 = p_train['learning_rate']
     if args.resume_from is not None:                  # optimizer slots and step count, when the checkpoint has them (Keras'
         # load_model restores the optimizer with the weights; the epoch count and LR schedule restart, as in the reference)
-        from embeddingnet_amd.backbones import keras_weights
         from embeddingnet_amd.optimizers import load_optimizer_state
         opt_path = _optimizer_state_path(args.resume_from)
         if os.path.exists(opt_path):
-            extra = load_optimizer_state(opt_path, opt, {k: v for k, v in keras_weights(trainable).items()
-                                                         if isinstance(v, torch.nn.Parameter)})
+            extra = load_optimizer_state(opt_path, opt, named_slots())
             print(f'resumed optimizer state from {opt_path} (iterations {opt.iterations}, saved after epoch {int(extra.get("epoch", 0))})')
     reducer = GradReducer(params) if world > 1 else None
     if siamese:
@@ -334,6 +406,12 @@ def main():
         # context, one-launch optimizer, and a captured step where the host cannot keep up (EMBNET_GRAPH=auto)
         from embeddingnet_amd.train_step import SiameseTrainer
         trainer = SiameseTrainer(model.model, opt, contrastive_loss, seed=rank, reducer=reducer)
+    elif proxy_mode:
+        # each rank's loss covers its own batch against ALL proxies; the reducer's mean over the ranks' gradients is the gradient
+        # of the mean of the ranks' losses, for the (replicated) proxies as for the backbone (train_step.ProxyTrainer)
+        from embeddingnet_amd.train_step import ProxyTrainer
+        trainer = ProxyTrainer(model.base_model, head, opt, loss=p_gen['negatives_selection_mode'], loss_params=loss_params,
+                               seed=rank, reducer=reducer)
     else:
         trainer = TripletTrainer(
             model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], margin=p_gen['margin'],
@@ -372,9 +450,13 @@ def main():
                     losses.append(trainer.step(torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev),
                                                torch.from_numpy(np.asarray(y, dtype=np.float32)).to(dev).reshape(-1, 1)))
                 else:
-                    xb = feeder.next()
+                    if proxy_mode:
+                        xb, yb = feeder.next_labelled()
+                        losses.append(trainer.step(xb, yb))
+                    else:
+                        xb = feeder.next()
+                        losses.append(trainer.step(xb))
                     n_images += xb.shape[0]
-                    losses.append(trainer.step(xb))
             epoch_loss = all_reduce_mean(float(torch.stack(losses).mean().item()))     # mean over ranks (logging + monitor)
             history['loss'].append(epoch_loss)
             msg = f'Epoch {epoch + 1}/{n_epochs} - lr {lr:.3g} - loss {epoch_loss:.4f}'
@@ -429,12 +511,11 @@ def main():
             if improved and rank == 0:
                 path = os.path.join(paths['weights'], f'epoch_{epoch + 1:03d}.npz')
                 model.save_weights(path)
-                from embeddingnet_amd.backbones import keras_weights
                 from embeddingnet_amd.optimizers import save_optimizer_state
                 os.makedirs(os.path.dirname(_optimizer_state_path(path)), exist_ok=True)
-                save_optimizer_state(_optimizer_state_path(path), opt,
-                                     {k: v for k, v in keras_weights(trainable).items() if isinstance(v, torch.nn.Parameter)},
-                                     extra={'epoch': epoch + 1})
+                save_optimizer_state(_optimizer_state_path(path), opt, named_slots(), extra={'epoch': epoch + 1})
+                if head is not None:
+                    save_proxies(_proxies_path(path), head, data_loader.class_names)
                 print(f'{monitor} improved to {history[monitor][-1]:.5f}, saving model to {path}')
             if stop:
                 print('EarlyStopping')
@@ -447,6 +528,8 @@ def main():
     dump = os.environ.get('EMBNET_DUMP_FINAL_WEIGHTS')     # diagnostics: EVERY rank's final weights -> <prefix><rank>.npz
     if dump:                                               # (data-parallel ranks must end with identical trainable weights)
         model.save_weights(f'{dump}{rank}.npz')
+        if head is not None:
+            save_proxies(f'{dump}{rank}_proxies.npz', head, data_loader.class_names)
     return history
 
 
