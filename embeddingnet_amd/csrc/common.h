@@ -128,6 +128,30 @@ __device__ __forceinline__ T block_sum256(T v) {
   return v;
 }
 
+// Arrival ticket: whether the calling workgroup is the last of its grid to get here (every thread calls; the answer is
+// workgroup-uniform).  `ticket` is zero before the launch and zero again after it: the last arriver re-arms it.  The hand-off
+// is the order MI355X_MICROARCH.md prescribes: every storing wave drains its stores, barrier, one lane releases at agent scope,
+// drains, then takes the ticket; the last arriver acquires, drains, and a barrier lets its waves read what the other workgroups
+// wrote (with relaxed agent-scope loads).
+__device__ __forceinline__ bool last_workgroup_to_arrive(int* ticket) {
+  __shared__ int s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int t = atomicAdd(ticket, 1);
+    s_last = t == (int)gridDim.x - 1;
+    if (s_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *ticket = 0;                                       // re-arm the counter for the next launch
+    }
+  }
+  __syncthreads();
+  return s_last != 0;
+}
+
 // Range emission (conv.hip "Ranges"): the workgroup's max |value| joins a range word — the bit pattern of a non-negative float
 // under an unsigned maximum, independent of the order, so reproducible.  One atomic per workgroup (256 threads, every thread
 // calls; amax >= 0, threads without an element pass 0).  A kernel of thousands of workgroups must NOT aim them all at one word

@@ -54,7 +54,6 @@ constexpr int FUSED_THREADS = 1024;                      // 16 waves: the distan
 __global__ __launch_bounds__(FUSED_THREADS) void fused_triplet_loss_fwd_kernel(FusedLossParams q) {
   __shared__ __attribute__((aligned(16))) float lds[FUSED_LDS_FLOATS];
   __shared__ float norm_a[16];
-  __shared__ int s_last;
   const int n = q.n, k = q.k, e = q.e, c = blockIdx.x, lo = c * k;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = FUSED_THREADS / 64;
@@ -73,6 +72,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_triplet_loss_fwd_kernel(F
   // A: distances.  Row r of the block against the K anchors; the row is read once, 16 anchors per sweep at most.
   // (the first version walked a row 64 columns at a time, one dependent L2 round trip each: 128 of them per wave at
   // N = 128, E = 256 = 124 us for the launch; eight loads in flight per lane and 16 waves leave 8 round trips)
+  // Not pair_loss.h's anchor_dots: the row norm ny rides in the same pass and joins the store; a hook for that would outweigh the copy.
   for (int r = wave; r < n; r += NW) {
     const float* y = q.emb + (long)r * e;
     float dot[16], ny = 0.f;
@@ -195,23 +195,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_triplet_loss_fwd_kernel(F
   }
 
   // ---- last workgroup: compaction, fallback, mean -------------------------------------------------------------
-  // hand-off as MI355X_MICROARCH.md prescribes: every storing wave drains its stores, barrier, one lane releases at
-  // agent scope, drains, then takes the ticket; the last arriver acquires, drains, and a barrier lets its waves read.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = atomicAdd(q.ticket, 1);
-    s_last = t == (int)gridDim.x - 1;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *q.ticket = 0;                                     // re-arm the counter for the next launch
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!last_workgroup_to_arrive(q.ticket)) return;
   // the reductions keep the 256-thread order of the kernels they stand in for (mine_compact_kernel, mean_first_kernel):
   // waves 4..15 only take part in the barriers
   __shared__ float part[NW];

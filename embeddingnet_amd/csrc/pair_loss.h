@@ -28,6 +28,11 @@
 // The kernels themselves stay in the loss's own file (their names are what a profile shows); they call pair_class_fwd /
 // pair_sweep_fwd / pair_bwd, and pair_launch launches them.  Nothing is atomic in floating point, every reduction has a fixed
 // order; no host synchronisation, no allocation.
+//
+// Four pieces here know nothing of P x K and serve proxy_loss.hip's rectangle as well: the arrival ticket (common.h's
+// last_workgroup_to_arrive), reduce_partials (the last workgroup's fixed-order totals), anchor_dots (rows of B against a few
+// anchors in LDS) and mm_f64_tile (the 32 x 32 f64 matrix-instruction product).  The P x K skeleton proper is the Body, PairParams,
+// pair_class_fwd / pair_sweep_fwd / pair_finish / pair_bwd, the fit rule, the workspace layout, the checks and pair_launch.
 #pragma once
 #include "common.h"
 #include "../../include/embnet.h"
@@ -71,47 +76,92 @@ struct PairDotBody {
   static size_t matrix_extra_bytes(int, int) { return 0; }
 };
 
-// Arrival ticket (fused_loss.hip's hand-off): every storing wave drains, barrier, one lane releases at agent scope and takes
-// the ticket; the last arriver acquires, re-arms the counter and reduces the `slots` partials in index order.
+// Totals of `slots` per-anchor partials (NS f64 sums, a stride of NS doubles; NC counters out of an int4) for the last
+// workgroup, all THREADS threads calling: thread-strided relaxed agent-scope loads, wave butterflies, then thread 0 adds the
+// waves in order.  The totals are thread 0's: true there, false elsewhere.
+template <int THREADS, int NS, int NC>
+__device__ __forceinline__ bool reduce_partials(const double* part_loss, const int4* part_cnt, int slots, double (&ts)[NS],
+                                                int (&tc)[NC]) {
+  __shared__ double ws_loss[THREADS / 64][NS];
+  __shared__ int ws_cnt[THREADS / 64][NC];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* pc = (const int*)part_cnt;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) ts[j] = 0.0;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) tc[j] = 0;
+  for (int i = tid; i < slots; i += THREADS) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) ts[j] += __hip_atomic_load(&part_loss[NS * i + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int j = 0; j < NC; ++j) tc[j] += __hip_atomic_load(&pc[4 * i + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int j = 0; j < NS; ++j) ts[j] = wave_sum(ts[j]);   // the butterflies first, one store block behind them: they interleave
+#pragma unroll
+  for (int j = 0; j < NC; ++j) tc[j] = wave_sum(tc[j]);
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) ws_loss[wave][j] = ts[j];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) ws_cnt[wave][j] = tc[j];
+  }
+  __syncthreads();
+  if (tid != 0) return false;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) ts[j] = 0.0;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) tc[j] = 0;
+  for (int w = 0; w < THREADS / 64; ++w) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) ts[j] += ws_loss[w][j];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) tc[j] += ws_cnt[w][j];
+  }
+  return true;
+}
+
+// The last workgroup to arrive reduces the `slots` partials in index order and hands the totals to the Body.
 template <class Body, int THREADS>
 __device__ __forceinline__ void pair_finish(const PairParams<Body>& q, int slots) {
-  __shared__ int s_last;
-  __shared__ double ws_loss[THREADS / 64];
-  __shared__ int ws_cnt[THREADS / 64][3];
+  if (!last_workgroup_to_arrive(q.ticket)) return;
+  double ts[1];
+  int tc[3];
+  if (reduce_partials<THREADS>(q.part_loss, q.part_cnt, slots, ts, tc)) Body::finish(q, ts[0], tc[0], tc[1], tc[2]);
+}
+
+// Rows r = wave, wave + NW, ... of B [nb][e] against the first na <= MAX_A of the anchors A [MAX_A][e] held in LDS, all NW waves
+// calling: S[a * nb + r] = the lane-strided chain of Term::term over the columns + wave sum.  A row is read once, eight loads in
+// flight per lane (fused_loss.hip's loop).
+template <int MAX_A, int NW, class Term>
+__device__ __forceinline__ void anchor_dots(const float* A, int na, const float* B, int nb, int e, float* S) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = atomicAdd(q.ticket, 1);
-    s_last = t == (int)gridDim.x - 1;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *q.ticket = 0;                                     // re-arm the counter for the next launch
+  for (int r = wave; r < nb; r += NW) {
+    const float* y = B + (long)r * e;
+    float acc[MAX_A];
+#pragma unroll
+    for (int a = 0; a < MAX_A; ++a) acc[a] = 0.f;
+    for (int c0 = 0; c0 < e; c0 += 512) {
+      float yv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const int cc = c0 + lane + 64 * j; yv[j] = cc < e ? y[cc] : 0.f; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int cc = c0 + lane + 64 * j;
+        if (cc < e) {
+#pragma unroll
+          for (int a = 0; a < MAX_A; ++a)
+            if (a < na) acc[a] = Term::term(A[a * e + cc], yv[j], acc[a]);
+        }
+      }
     }
-  }
-  __syncthreads();
-  if (!s_last) return;
-  double s = 0.0;
-  int c0 = 0, c1 = 0, c2 = 0;
-  const int* pc = (const int*)q.part_cnt;
-  for (int i = tid; i < slots; i += THREADS) {
-    s += __hip_atomic_load(&q.part_loss[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c0 += __hip_atomic_load(&pc[4 * i + 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c1 += __hip_atomic_load(&pc[4 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c2 += __hip_atomic_load(&pc[4 * i + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  s = wave_sum(s);
-  c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
-  if (lane == 0) { ws_loss[wave] = s; ws_cnt[wave][0] = c0; ws_cnt[wave][1] = c1; ws_cnt[wave][2] = c2; }
-  __syncthreads();
-  if (tid == 0) {
-    double ts = 0.0;
-    int t0 = 0, t1 = 0, t2 = 0;
-    for (int w = 0; w < THREADS / 64; ++w) { ts += ws_loss[w]; t0 += ws_cnt[w][0]; t1 += ws_cnt[w][1]; t2 += ws_cnt[w][2]; }
-    Body::finish(q, ts, t0, t1, t2);
+#pragma unroll
+    for (int a = 0; a < MAX_A; ++a) {
+      if (a < na) {
+        const float g = wave_sum(acc[a]);
+        if (lane == 0) (S + r)[a * nb] = g;              // S + r first: keeps MAX_A row pointers out of the scalar registers
+      }
+    }
   }
 }
 
@@ -129,34 +179,7 @@ __device__ __forceinline__ void pair_class_fwd(const PairParams<Body>& q) {
   float* S = lds + k * e;                                // [k][n] pair matrix, anchor -> row
   for (int i = tid; i < k * e; i += PAIR_CLASS_THREADS) A[i] = q.emb[(long)lo * e + i];
   __syncthreads();
-  // row r of the block against the K anchors: the row is read once, eight loads in flight per lane (fused_loss.hip's loop)
-  for (int r = wave; r < n; r += NW) {
-    const float* y = q.emb + (long)r * e;
-    float acc[PAIR_CLASS_MAX_K];
-#pragma unroll
-    for (int a = 0; a < PAIR_CLASS_MAX_K; ++a) acc[a] = 0.f;
-    for (int c0 = 0; c0 < e; c0 += 512) {
-      float yv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const int cc = c0 + lane + 64 * j; yv[j] = cc < e ? y[cc] : 0.f; }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int cc = c0 + lane + 64 * j;
-        if (cc < e) {
-#pragma unroll
-          for (int a = 0; a < PAIR_CLASS_MAX_K; ++a)
-            if (a < k) acc[a] = Body::term(A[a * e + cc], yv[j], acc[a]);
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < PAIR_CLASS_MAX_K; ++a) {
-      if (a < k) {
-        const float g = wave_sum(acc[a]);
-        if (lane == 0) S[a * n + r] = g;
-      }
-    }
-  }
+  anchor_dots<PAIR_CLASS_MAX_K, NW, Body>(A, k, q.emb, n, e, S);
   __syncthreads();
   if (wave < k) {
     const PairAnchorOut<Sum> o = Body::anchor(S + wave * n, n, k, lo, wave, q.a, q.g + (long)(lo + wave) * n, lane);
@@ -196,62 +219,93 @@ __device__ __forceinline__ void pair_sweep_fwd(const PairParams<Body>& q) {
   pair_finish<Body, PAIR_SWEEP_THREADS>(q, n);
 }
 
-// ---- backward: Y = (M + M^T) X, demb = Epilogue(Y) ------------------------------------------------------------------------
-// grid (ceil(N/32), ceil(E/32)), 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS.
+// ---- the f64 tile product: Out[i][col] = sum_{j in [jb, je)} M(i, j) B[j][col], i < R, col < e ------------------------------
+// grid (ceil(R/32), ceil(e/32)), 256 threads: 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS
+// (jb is a multiple of 32 and je of 32 or J: j < J guards the tail).
 // v_mfma_f64_16x16x4_f64: A[i = l&15][k = l>>4], B[k = l>>4][col = l&15], D[row = (l>>4) + 4r][col = l&15] (the f64 map).
-// Not the f32 instructions: an f32 chain over j rounds relative to sum_j |M_ij| |x_j|, and what the caller keeps of the result
-// can be far below that.  M + M^T is formed in f64 while staging; the result carries one fp32 rounding of an f64 sum.
-// An Epilogue is built by the kernel from its arguments and has
-//   static constexpr bool ROW_SUM;                             whether value() wants s_i = sum_j (M + M^T)_ij
-//   __device__ double scale(int n) const;                      read once per thread, after the products
-//   __device__ double value(double scale, double y, double s, const float* x) const;     demb[i][c] from Y_ic, s_i, &X[i][c]
+// Not the f32 instructions: an f32 chain over j rounds relative to sum_j |M_ij| |b_j|, and what the caller keeps of the result
+// can be far below that.
+// The left operand M comes from a matrix G of floats: MM_DIRECT G[i][j] (G is [R][J]); MM_TRANS G[j][i] (G is [J][R]); MM_SYM
+// G[i][j] + G[j][i] (R = J), formed in f64 while the operand is read; SCALE: times qv[j], an exact f64 product.
+// An Out says how a result leaves:
+//   static constexpr bool ROW_SUM;                             whether put() wants s_i = sum_j M(i, j)
+//   __device__ double begin() const;                           read once per thread, after the products
+//   __device__ void put(double begun, long at, double y, double s) const;     element at = i * e + col from the f64 sum y and s_i
 using f64x4 = __attribute__((ext_vector_type(4))) double;
+enum { MM_DIRECT, MM_TRANS, MM_SYM };
 
-template <class Epilogue>
-__device__ __forceinline__ void pair_bwd(const float* __restrict__ emb, int n, int e, const float* __restrict__ w,
-                                         const Epilogue& ep, float* __restrict__ demb) {
-  __shared__ float wa[32][33];                           // M[i0 + ii][j0 + jj]
-  __shared__ float wb[32][33];                           // M[j0 + jj][i0 + ii], stored [jj][ii]
-  __shared__ float xs[32][33];                           // X[j0 + jj][e0 + ee]
+template <int LEFT, bool SCALE, class Out>
+__device__ __forceinline__ void mm_f64_tile(const float* __restrict__ G, const float* __restrict__ qv, const float* __restrict__ B,
+                                            int R, int J, int e, int jb, int je, const Out& out) {
+  // (an array no instantiated branch below touches gets no LDS: 12 672 B with wb, 8 576 B with qs, 8 448 B with neither)
+  __shared__ float wa[32][33];                           // M's first term, [ii][jj]
+  __shared__ float wb[32][33];                           // MM_SYM: G[j0 + jj][i0 + ii], stored [jj][ii]
+  __shared__ float xs[32][33];                           // B[j0 + jj][e0 + ee]
+  __shared__ float qs[32];                               // SCALE: qv[j0 + jj]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
   const int ro = 16 * (wave >> 1), co = 16 * (wave & 1);
   const int lr = lane & 15, lk = lane >> 4;
   f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  double srow = 0.0;                                     // sum of this lane's (M + M^T)[ro + lr][k] operands
-  for (int j0 = 0; j0 < n; j0 += 32) {
+  double srow = 0.0;                                     // ROW_SUM: sum of this lane's M(ro + lr, k) operands
+  for (int j0 = jb; j0 < je; j0 += 32) {
     for (int t = tid; t < 1024; t += 256) {
       const int r = t >> 5, cc = t & 31;
       const int i = i0 + r, j = j0 + cc, jr = j0 + r, ic = i0 + cc, ec = e0 + cc;
-      wa[r][cc] = (i < n && j < n) ? w[(long)i * n + j] : 0.f;
-      wb[r][cc] = (jr < n && ic < n) ? w[(long)jr * n + ic] : 0.f;
-      xs[r][cc] = (jr < n && ec < e) ? emb[(long)jr * e + ec] : 0.f;
+      if constexpr (LEFT == MM_TRANS) wa[cc][r] = (ic < R && jr < J) ? G[(long)jr * R + ic] : 0.f;
+      else wa[r][cc] = (i < R && j < J) ? G[(long)i * J + j] : 0.f;
+      if constexpr (LEFT == MM_SYM) wb[r][cc] = (jr < J && ic < R) ? G[(long)jr * R + ic] : 0.f;
+      xs[r][cc] = (jr < J && ec < e) ? B[(long)jr * e + ec] : 0.f;
+    }
+    if constexpr (SCALE) {
+      if (tid < 32) qs[tid] = j0 + tid < J ? qv[j0 + tid] : 0.f;
     }
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
       const int kx = 4 * kk + lk;
-      const double av = (double)wa[ro + lr][kx] + (double)wb[kx][ro + lr];
+      double av = (double)wa[ro + lr][kx];
+      if constexpr (LEFT == MM_SYM) av += (double)wb[kx][ro + lr];
+      if constexpr (SCALE) av *= (double)qs[kx];
       const double bv = (double)xs[kx][co + lr];
-      if constexpr (Epilogue::ROW_SUM) srow += av;
+      if constexpr (Out::ROW_SUM) srow += av;
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
     }
     __syncthreads();
   }
-  if constexpr (Epilogue::ROW_SUM) {
+  if constexpr (Out::ROW_SUM) {
     srow += __shfl_xor(srow, 16, 64);                    // the four k-lanes of row lr: s_i
     srow += __shfl_xor(srow, 32, 64);
   }
-  const double scale = ep.scale(n);
+  const double begun = out.begin();
   const int col = e0 + co + lr;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int rl = lk + 4 * r;
     double s = 0.0;
-    if constexpr (Epilogue::ROW_SUM) s = __shfl(srow, rl, 64);       // lane rl holds s of row rl
+    if constexpr (Out::ROW_SUM) s = __shfl(srow, rl, 64);                // lane rl holds s of row rl
     const int row = i0 + ro + rl;
-    if (row < n && col < e) demb[(long)row * e + col] = (float)ep.value(scale, acc[r], s, emb + (long)row * e + col);
+    if (row < R && col < e) out.put(begun, (long)row * e + col, acc[r], s);
   }
+}
+
+// ---- backward: Y = (M + M^T) X, demb = Epilogue(Y), M the pair weights [n][n] ----------------------------------------------
+// The result carries one fp32 rounding of an f64 sum.  An Epilogue is built by the kernel from its arguments and has
+//   static constexpr bool ROW_SUM;                             whether value() wants s_i = sum_j (M + M^T)_ij
+//   __device__ double scale(int n) const;                      read once per thread, after the products
+//   __device__ double value(double scale, double y, double s, const float* x) const;     demb[i][c] from Y_ic, s_i, &X[i][c]
+template <class Epilogue>
+struct PairBwdOut {
+  static constexpr bool ROW_SUM = Epilogue::ROW_SUM;
+  const Epilogue& ep; const float* emb; int n; float* demb;
+  __device__ double begin() const { return ep.scale(n); }
+  __device__ void put(double scale, long at, double y, double s) const { demb[at] = (float)ep.value(scale, y, s, emb + at); }
+};
+
+template <class Epilogue>
+__device__ __forceinline__ void pair_bwd(const float* __restrict__ emb, int n, int e, const float* __restrict__ w,
+                                         const Epilogue& ep, float* __restrict__ demb) {
+  mm_f64_tile<MM_SYM, false>(w, nullptr, emb, n, n, e, 0, n, PairBwdOut<Epilogue>{ep, emb, n, demb});
 }
 
 // ---- host side: range, fit rule, workspace layout, argument checks, launches ----------------------------------------------

@@ -9,13 +9,13 @@
 //   prep launch (a wave per class): q, the class sizes cnt[c] (every workgroup of the forward adds them up to |C+| and n_l:
 //     integers, any order).
 //   small path (e + max(n, c) <= 4096 and n c e <= 2^25), ONE more launch: a workgroup holds four anchors and their four rows of D
-//     in LDS (per-lane fma chain over the columns + wave sum, pair_loss.h's staging), one wave per anchor runs the body.
+//     in LDS (pair_loss.h's anchor_dots), one wave per anchor runs the body.
 //   matrix path, TWO more launches: D through embnet_dense_dgrad_f32 (the exact-fp32 matrix-instruction GEMM, a k-ordered chain
 //     per element) into the workspace, then a sweep: one wave per anchor walks its row of D from L2 in three passes (extrema, sums,
 //     weights).  A CosFace row reaches 16384 floats = 64 KiB, four times pair_sweep_fwd's per-wave LDS row: it is not staged at all.
-//   per-anchor partials, pair_loss.h's arrival ticket, a fixed-order f64 reduction by the last workgroup.
+//   per-anchor partials, the arrival ticket, pair_loss.h's fixed-order f64 reduction by the last workgroup.
 //   backward, three launches (four with demb's class sum split, see proxy_bwd_split) on the f64 matrix instructions
-//     (v_mfma_f64_16x16x4_f64, pair_bwd's tiling): demb = g Q^(T) W,
+//     (pair_loss.h's mm_f64_tile): demb = g Q^(T) W,
 //     Y = G^(T) X in f64 into the workspace, then a wave per class: dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c), every output
 //     one fp32 rounding of an f64 expression.
 // A label is compared, and used as an index (CosFace: the sample's own column) only behind the range check that makes it a class
@@ -185,50 +185,17 @@ __device__ __forceinline__ void proxy_row(const float* drow, const ProxyParams& 
   }
 }
 
-// pair_finish's ticket around two loss sums: the last workgroup to arrive re-arms the counter and reduces the na partials in index
-// order.  loss = sum lp / (anchors with a positive term) + sum ln / c  (the second sum is zero for CosFace).
+// The last workgroup to arrive reduces the na partials (two loss sums, two counters) in index order.
+// loss = sum lp / (anchors with a positive term) + sum ln / c  (the second sum is zero for CosFace).
 __device__ __forceinline__ void proxy_finish(const ProxyParams& P, int2 tot) {
-  __shared__ int s_last;
-  __shared__ double ws_loss[PROXY_WG_ANCHORS][2];
-  __shared__ int ws_cnt[PROXY_WG_ANCHORS][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = atomicAdd(P.ticket, 1);
-    s_last = t == (int)gridDim.x - 1;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *P.ticket = 0;                                     // re-arm the counter for the next launch
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
-  double sp = 0.0, sn = 0.0;
-  int c0 = 0, c1 = 0;
-  const double* pl = (const double*)P.part_loss;
-  const int* pc = (const int*)P.part_cnt;
-  for (int i = tid; i < P.na; i += PROXY_THREADS) {
-    sp += __hip_atomic_load(&pl[2 * i + 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sn += __hip_atomic_load(&pl[2 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c0 += __hip_atomic_load(&pc[4 * i + 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c1 += __hip_atomic_load(&pc[4 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  sp = wave_sum(sp); sn = wave_sum(sn);
-  c0 = wave_sum(c0); c1 = wave_sum(c1);
-  if (lane == 0) { ws_loss[wave][0] = sp; ws_loss[wave][1] = sn; ws_cnt[wave][0] = c0; ws_cnt[wave][1] = c1; }
-  __syncthreads();
-  if (tid == 0) {
-    double tp = 0.0, tn = 0.0;
-    int t0 = 0, t1 = 0;
-    for (int w = 0; w < PROXY_WG_ANCHORS; ++w) { tp += ws_loss[w][0]; tn += ws_loss[w][1]; t0 += ws_cnt[w][0]; t1 += ws_cnt[w][1]; }
-    P.counts[0] = t0;                                    // |C+| or n_l: at most 16384
+  if (!last_workgroup_to_arrive(P.ticket)) return;
+  double ts[2];
+  int tc[2];
+  if (reduce_partials<PROXY_THREADS>((const double*)P.part_loss, P.part_cnt, P.na, ts, tc)) {
+    P.counts[0] = tc[0];                                 // |C+| or n_l: at most 16384
     P.counts[1] = tot.y;                                 // labelled samples: at most 4096
-    P.counts[2] = t1;
-    *P.mean = (float)((t0 > 0 ? tp / (double)t0 : 0.0) + tn / (double)P.c);
+    P.counts[2] = tc[1];
+    *P.mean = (float)((tc[0] > 0 ? ts[0] / (double)tc[0] : 0.0) + ts[1] / (double)P.c);
   }
 }
 
@@ -243,31 +210,7 @@ __global__ __launch_bounds__(PROXY_THREADS) void proxy_small_fwd_kernel(ProxyPar
   float* D = lds + PROXY_WG_ANCHORS * e;                 // [4][nb] their rows of D
   for (int i = tid; i < PROXY_WG_ANCHORS * e; i += PROXY_THREADS) A[i] = a0 + i / e < na ? P.anchors[(long)a0 * e + i] : 0.f;
   __syncthreads();
-  // row r of B against the four anchors: the row is read once, eight loads in flight per lane (pair_class_fwd's loop)
-  for (int r = wave; r < nb; r += PROXY_WG_ANCHORS) {
-    const float* y = P.others + (long)r * e;
-    float acc[PROXY_WG_ANCHORS];
-#pragma unroll
-    for (int a = 0; a < PROXY_WG_ANCHORS; ++a) acc[a] = 0.f;
-    for (int c0 = 0; c0 < e; c0 += 512) {
-      float yv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const int cc = c0 + lane + 64 * j; yv[j] = cc < e ? y[cc] : 0.f; }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int cc = c0 + lane + 64 * j;
-        if (cc < e) {
-#pragma unroll
-          for (int a = 0; a < PROXY_WG_ANCHORS; ++a) acc[a] = fmaf(A[a * e + cc], yv[j], acc[a]);
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < PROXY_WG_ANCHORS; ++a) {
-      const float v = wave_sum(acc[a]);
-      if (lane == 0) D[a * nb + r] = v;
-    }
-  }
+  anchor_dots<PROXY_WG_ANCHORS, PROXY_WG_ANCHORS, PairDotBody>(A, PROXY_WG_ANCHORS, P.others, nb, e, D);   // rows past na are zero
   __syncthreads();
   if (a0 + wave < na) proxy_row(D + wave * nb, P, a0 + wave, tot, lane);
   proxy_finish(P, tot);
@@ -282,57 +225,24 @@ __global__ __launch_bounds__(PROXY_THREADS) void proxy_sweep_kernel(ProxyParams 
   proxy_finish(P, tot);
 }
 
-// ---- backward: Out[r][col] = sum_j M(r, j) B[j][col] on the f64 matrix instructions -----------------------------------------------
-// grid (ceil(R/32), ceil(e/32)), 4 waves, each a 16 x 16 tile of the 32 x 32 block; j in chunks of 32 through LDS (pair_bwd's tiling
-// and lane map).  M(r, j) = G[r][j] (G is [R][J]) or, TRANS, G[j][r] (G is [J][R]); SCALE: times qv[j], an exact f64 product.
-// OutT float: one fp32 rounding of g * sum (g = *upstream, NULL = 1); double: the sum itself.  The sum runs over j in [jb, je).
+// ---- backward: rectangular products on pair_loss.h's mm_f64_tile ------------------------------------------------------------------
+// M(r, j) = G[r][j] or, TRANS, G[j][r]; SCALE: times qv[j].  OutT float: one fp32 rounding of g * sum (g = *upstream, NULL = 1);
+// double: the sum itself.  The sum runs over j in [jb, je).
+template <class OutT>
+struct ProxyMmOut {
+  static constexpr bool ROW_SUM = false;
+  const float* upstream; OutT* out;
+  __device__ double begin() const { return upstream ? (double)*upstream : 1.0; }
+  __device__ void put(double g, long at, double y, double) const {
+    if constexpr (sizeof(OutT) == 4) out[at] = (float)(g * y);
+    else out[at] = y;
+  }
+};
+
 template <bool TRANS, bool SCALE, class OutT>
 __device__ __forceinline__ void proxy_mm(const float* __restrict__ G, const float* __restrict__ qv, const float* __restrict__ B, int R,
                                          int J, int e, int jb, int je, const float* __restrict__ upstream, OutT* __restrict__ out) {
-  __shared__ float wa[32][33];                           // M[i0 + ii][j0 + jj]
-  __shared__ float xs[32][33];                           // B[j0 + jj][e0 + ee]
-  __shared__ float qs[32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
-  const int ro = 16 * (wave >> 1), co = 16 * (wave & 1);
-  const int lr = lane & 15, lk = lane >> 4;
-  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int j0 = jb; j0 < je; j0 += 32) {                 // (jb is a multiple of 32 and je of 32 or J: j < J guards the tail)
-    for (int t = tid; t < 1024; t += 256) {
-      const int r = t >> 5, cc = t & 31;
-      if constexpr (TRANS) {
-        const int j = j0 + r, i = i0 + cc;
-        wa[cc][r] = (i < R && j < J) ? G[(long)j * R + i] : 0.f;
-      } else {
-        const int i = i0 + r, j = j0 + cc;
-        wa[r][cc] = (i < R && j < J) ? G[(long)i * J + j] : 0.f;
-      }
-      const int jr = j0 + r, ec = e0 + cc;
-      xs[r][cc] = (jr < J && ec < e) ? B[(long)jr * e + ec] : 0.f;
-    }
-    if constexpr (SCALE) {
-      if (tid < 32) qs[tid] = j0 + tid < J ? qv[j0 + tid] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const int kx = 4 * kk + lk;
-      double av = (double)wa[ro + lr][kx];
-      if constexpr (SCALE) av *= (double)qs[kx];
-      const double bv = (double)xs[kx][co + lr];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  const int col = e0 + co + lr;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = i0 + ro + lk + 4 * r;
-    if (row < R && col < e) {
-      if constexpr (sizeof(OutT) == 4) out[(long)row * e + col] = (float)((upstream ? (double)*upstream : 1.0) * acc[r]);
-      else out[(long)row * e + col] = acc[r];
-    }
-  }
+  mm_f64_tile<TRANS ? MM_TRANS : MM_DIRECT, SCALE>(G, qv, B, R, J, e, jb, je, ProxyMmOut<OutT>{upstream, out});
 }
 
 template <bool TRANS>

@@ -137,6 +137,14 @@ def triplet_gather_loss(emb, triplets, count, margin):
 _FUSED_WS = {}
 
 
+def _ticket_workspace(cache, where, shape, bytes_fn, dtype, device):
+    """bytes_fn(*shape) bytes (32 where a shape is out of range and the call about to be refused), zero-filled on the first call
+    under where + shape and kept: the kernels re-arm the arrival ticket in it."""
+    if where + shape not in cache:
+        cache[where + shape] = torch.zeros(max(bytes_fn(*shape), 32) // dtype.itemsize, dtype=dtype, device=device)
+    return cache[where + shape]
+
+
 def fused_loss_supported(k_classes, k_samples, e):
     return bool(_lib.lib().embnet_fused_loss_supported(int(k_classes), int(k_samples), int(e)))
 
@@ -156,10 +164,8 @@ class _FusedTripletLoss(torch.autograd.Function):
         count = _new((1,), emb, torch.int32)
         sel = _new((max(p * (k * (k - 1) // 2), 1),), emb, torch.int32)
         loss, act, mean = _new((rows,), emb), _new((rows,), emb), _new((), emb)
-        key = (emb.device.index, stream(), p, k)
-        ws = _FUSED_WS.get(key)
-        if ws is None:                                      # zero-filled once; the kernel re-arms its counter itself
-            ws = _FUSED_WS[key] = torch.zeros(max(lib.embnet_fused_loss_workspace_bytes(p, k) // 4, 8), device=emb.device)
+        ws = _ticket_workspace(_FUSED_WS, (emb.device.index, stream()), (p, k), lib.embnet_fused_loss_workspace_bytes, torch.float32,
+                               emb.device)
         check(lib.embnet_fused_triplet_loss_fwd(ptr(emb), p, k, e, f32(margin), code, int(seed) & (2 ** 64 - 1),
                                                 seed_dev, ptr(trip),
                                                 ptr(count), ptr(sel), ptr(loss), ptr(act), ptr(mean), ptr(ws),
@@ -230,10 +236,7 @@ class _PairLoss(torch.autograd.Function):
         g = _new((n, n), emb)
         outs = [_new(shape, emb, dtype) for shape, dtype in outputs]
         mean = _new((), emb)
-        key = (loss, emb.device.index, stream(), p, k, e)
-        ws = _PAIR_WS.get(key)
-        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
-            ws = _PAIR_WS[key] = torch.zeros(max(getattr(lib, ws_bytes)(p, k, e) // 4, 4), device=emb.device)
+        ws = _ticket_workspace(_PAIR_WS, (loss, emb.device.index, stream()), (p, k, e), getattr(lib, ws_bytes), torch.float32, emb.device)
         check(getattr(lib, fwd)(ptr(emb), p, k, e, *scalars, paths[path], ptr(g), *map(ptr, outs), ptr(mean), ptr(ws),
                                 ws.numel() * 4, stream()))
         ctx.bwd = bwd
@@ -323,11 +326,8 @@ class _ProxyLoss(torch.autograd.Function):
         lib = _lib.lib()
         g = _new((c, n) if kind == 1 else (n, c), emb)
         q, counts, mean = _new((c,), emb), _new((3,), emb, torch.int32), _new((), emb)
-        key = (emb.device.index, stream(), n, c, e)
-        ws = _PROXY_WS.get(key)
-        if ws is None:                                      # zero-filled once; the kernels re-arm their counter themselves
-            ws = _PROXY_WS[key] = torch.zeros(max(lib.embnet_proxy_loss_workspace_bytes(n, c, e) // 8, 2), device=emb.device,
-                                              dtype=torch.float64)
+        ws = _ticket_workspace(_PROXY_WS, (emb.device.index, stream()), (n, c, e), lib.embnet_proxy_loss_workspace_bytes, torch.float64,
+                               emb.device)
         check(lib.embnet_proxy_loss_fwd(ptr(emb), ptr(proxies), ptr(labels), n, c, e, kind, f32(a), f32(b), PROXY_PATHS[path],
                                         ptr(g), ptr(q), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8, stream()))
         ctx.kind, ctx.ws = kind, ws

@@ -49,31 +49,41 @@ class TripletTrainer:
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5,
                  negatives_selection_mode="semihard", seed=0, reducer=None, graph=None, loss_params=None):
+        self.p, self.k, self.margin, self.mode = int(k_classes), int(k_samples), float(margin), negatives_selection_mode
+        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES):
+            raise KeyError(self.mode)
+        if loss_params and self.mode not in self.LOSS_PARAMS:
+            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity' or 'supcon', not {self.mode!r}")
+        self.loss_params = self._checked_loss_params(self.mode, loss_params)
+        # one gradient per parameter and step: kernels write the reducer's flat buffer in place
+        self._setup(base_model, optimizer, seed, reducer, graph, direct=True)
+        # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
+        self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
+
+    def _setup(self, model, optimizer, seed, reducer, graph, direct):
+        """What every trainer's constructor does behind its own argument checks.  direct: whether each parameter gets ONE
+        gradient contribution per step, so that the kernels may write the reducer's flat buffer in place."""
         env = os.environ.get("EMBNET_GRAPH", "0")
         self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
         self._graph, self._graph_failed = None, False
-        self.model, self.opt = base_model, optimizer
-        self.p, self.k, self.margin, self.mode = int(k_classes), int(k_samples), float(margin), negatives_selection_mode
+        self.model, self.opt = model, optimizer
         self.seed, self.step_no, self.reducer = int(seed), 0, reducer
-        self.ctx = L.StepContext(f"TripletTrainer@{id(self):x}")       # this trainer's fused hand-overs (layers.StepContext)
-        # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
-        self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
-        if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES):
-            raise KeyError(self.mode)
-        self.loss_params = dict(loss_params or {})
-        if self.loss_params and self.mode not in self.LOSS_PARAMS:
-            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity' or 'supcon', not {self.mode!r}")
-        unknown = set(self.loss_params) - set(self.LOSS_PARAMS.get(self.mode, ()))
-        if unknown:
-            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} for {self.mode!r} "
-                             f"({', '.join(self.LOSS_PARAMS[self.mode])})")
+        self.ctx = L.StepContext(f"{type(self).__name__}@{id(self):x}")    # this trainer's fused hand-overs (layers.StepContext)
+        self.fused_loss = False
         from .optimizers import KerasOptimizer
         self._keras_opt = isinstance(optimizer, KerasOptimizer)
         if self._keras_opt:
             # the regularisers' gradient (2*lambda*w) joins g inside the one optimizer launch; the loss keeps their value
-            optimizer.set_l2(L.regularized_kernels(base_model))
+            optimizer.set_l2(L.regularized_kernels(model))
             if reducer is not None:
-                reducer.direct(True)          # one gradient per parameter and step: kernels write the flat buffer in place
+                reducer.direct(direct)
+
+    def _checked_loss_params(self, mode, loss_params):
+        params = dict(loss_params or {})
+        unknown = set(params) - set(self.LOSS_PARAMS.get(mode, ()))
+        if unknown:
+            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} for {mode!r} ({', '.join(self.LOSS_PARAMS[mode])})")
+        return params
 
     def mine(self, emb):
         with torch.no_grad():
@@ -113,8 +123,10 @@ class TripletTrainer:
     def _graph_state_live(self):
         return getattr(self, "_state", None) is not None and torch.cuda.is_current_stream_capturing()
 
+    ANY_LOSS_CAPTURES = False       # this class: only the fused loss path and the pair losses run without the host
+
     def _graph_supported(self, images):
-        if not self._keras_opt or not (self.fused_loss or self.mode in ops.PAIR_LOSS_MODES):
+        if not self._keras_opt or not (self.ANY_LOSS_CAPTURES or self.fused_loss or self.mode in ops.PAIR_LOSS_MODES):
             return False
         return self.opt.rule != "radam" or self.opt.iterations >= 6      # RAdam switches kernels while it warms up
 
@@ -137,7 +149,7 @@ class TripletTrainer:
         self._ring_pos += 1
 
     def _capture(self, images):
-        dev = (images[0] if isinstance(images, (tuple, list)) else images).device
+        dev = self._tuple(images)[0].device
         self._state = torch.zeros(12, dtype=torch.float32, device=dev)           # lr, b1, b2, eps, c1, c2 | seed (uint64) | steps since capture (uint64) | pad
         self._ring = torch.zeros((256, 12), dtype=torch.float32).pin_memory()
         self._since_capture = 0
@@ -192,16 +204,22 @@ class TripletTrainer:
             for m, st in zip(self._drops, drop_steps):
                 m._step = st
 
-    # the step's inputs: one image batch here; SiameseTrainer packs (x1, x2, y)
+    # the step's inputs, as `loss` takes them: one image batch here; SiameseTrainer packs (x1, x2, y), ProxyTrainer (images, labels)
     @staticmethod
-    def _inputs_like(images):
-        return torch.empty_like(images)
+    def _tuple(inputs):
+        return tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
 
-    def _inputs_copy(self, images):
-        self._gx.copy_(images)
+    def _inputs_like(self, inputs):
+        like = tuple(torch.empty_like(t) for t in self._tuple(inputs))
+        return like if isinstance(inputs, (tuple, list)) else like[0]
 
-    def _inputs_match(self, images):
-        return images.shape == self._gx.shape
+    def _inputs_copy(self, inputs):
+        for d, t in zip(self._tuple(self._gx), self._tuple(inputs)):
+            d.copy_(t)
+
+    def _inputs_match(self, inputs):
+        new, held = self._tuple(inputs), self._tuple(self._gx)
+        return len(new) == len(held) and all(a.shape == b.shape for a, b in zip(new, held))
 
     def _replay(self, images):
         self._inputs_copy(images)
@@ -365,46 +383,21 @@ class SiameseTrainer(TripletTrainer):
     siamese_model: SiameseNet.model ([x1, x2] -> [distance, cls1, cls2]); loss_fn(y_true, distance) -> scalar (contrastive_loss).
     step(x1, x2, y) -> the loss of the step (detached)."""
 
+    ANY_LOSS_CAPTURES = True
+
     def __init__(self, siamese_model, optimizer, loss_fn=None, seed=0, reducer=None, graph=None):
-        from .optimizers import KerasOptimizer
-        env = os.environ.get("EMBNET_GRAPH", "0")
-        self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
-        self._graph, self._graph_failed = None, False
-        self.model, self.opt = siamese_model, optimizer
-        self.seed, self.step_no, self.reducer = int(seed), 0, reducer
-        self.ctx = L.StepContext(f"SiameseTrainer@{id(self):x}")
-        self.fused_loss = False
+        # two gradient contributions per shared parameter: autograd accumulates, no in-place sinks
+        self._setup(siamese_model, optimizer, seed, reducer, graph, direct=False)
         self.last_triplets = None
         if loss_fn is None:
             from .losses_and_accuracies import contrastive_loss as loss_fn
         self.loss_fn = loss_fn
-        self._keras_opt = isinstance(optimizer, KerasOptimizer)
-        if self._keras_opt:
-            optimizer.set_l2(L.regularized_kernels(siamese_model))
-            if reducer is not None:
-                reducer.direct(False)         # two gradient contributions per shared parameter: autograd accumulates, no in-place sinks
 
     def loss(self, inputs):
         x1, x2, y = inputs
         mean = self.loss_fn(y, self.model([x1, x2])[0])
         reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
         return (mean if reg is None else mean + reg), mean, None
-
-    def _graph_supported(self, inputs):
-        if not self._keras_opt:
-            return False
-        return self.opt.rule != "radam" or self.opt.iterations >= 6
-
-    @staticmethod
-    def _inputs_like(inputs):
-        return tuple(torch.empty_like(t) for t in inputs)
-
-    def _inputs_copy(self, inputs):
-        for d, t in zip(self._gx, inputs):
-            d.copy_(t)
-
-    def _inputs_match(self, inputs):
-        return len(inputs) == len(self._gx) and all(a.shape == b.shape for a, b in zip(inputs, self._gx))
 
     def step(self, x1, x2, y):
         return super().step((x1, x2, y))
@@ -426,31 +419,19 @@ class ProxyTrainer(TripletTrainer):
     ranks' gradients — what the reducer forms — is the gradient of the mean of the ranks' losses, for the proxies as for the
     backbone.  (Proxy-Anchor's 1/|C+| is each rank's own: the mean is over the ranks' losses, not the loss of the pooled batch.)"""
     LOSS_PARAMS = {mode: keys for mode, (_, keys) in ops.PROXY_LOSS_MODES.items()}
+    ANY_LOSS_CAPTURES = True
 
     def __init__(self, base_model, head, optimizer, loss="proxy_anchor", loss_params=None, seed=0, reducer=None, graph=None):
-        from .optimizers import KerasOptimizer
-        env = os.environ.get("EMBNET_GRAPH", "0")
-        self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
-        self._graph, self._graph_failed = None, False
         if loss not in ops.PROXY_LOSS_MODES:
             raise KeyError(loss)
-        self.loss_params = dict(loss_params or {})
-        unknown = set(self.loss_params) - set(self.LOSS_PARAMS[loss])
-        if unknown:
-            raise ValueError(f"loss_params: unknown keys {sorted(unknown)} for {loss!r} ({', '.join(self.LOSS_PARAMS[loss])})")
+        self.loss_params = self._checked_loss_params(loss, loss_params)
         if not any(q is head.proxies for g in optimizer.param_groups for q in g["params"]):
             raise ValueError("ProxyTrainer: the optimizer does not hold head.proxies (build it over the backbone's parameters "
                              "and the head's)")
-        self.model, self.head, self.opt, self.mode = base_model, head, optimizer, loss
-        self.seed, self.step_no, self.reducer = int(seed), 0, reducer
-        self.ctx = L.StepContext(f"ProxyTrainer@{id(self):x}")
-        self.fused_loss = False
+        self.head, self.mode = head, loss
+        # one gradient per parameter and step, the proxies' included
+        self._setup(base_model, optimizer, seed, reducer, graph, direct=True)
         self.last_triplets = None
-        self._keras_opt = isinstance(optimizer, KerasOptimizer)
-        if self._keras_opt:
-            optimizer.set_l2(L.regularized_kernels(base_model))
-            if reducer is not None:
-                reducer.direct(True)          # one gradient per parameter and step, the proxies' included
 
     def loss(self, inputs):
         images, labels = inputs
@@ -461,15 +442,6 @@ class ProxyTrainer(TripletTrainer):
         self.last_triplets = (None, count)
         reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
         return (mean if reg is None else mean + reg), mean, count
-
-    def _graph_supported(self, inputs):
-        if not self._keras_opt:
-            return False
-        return self.opt.rule != "radam" or self.opt.iterations >= 6
-
-    _inputs_like = staticmethod(SiameseTrainer._inputs_like)
-    _inputs_copy = SiameseTrainer._inputs_copy
-    _inputs_match = SiameseTrainer._inputs_match
 
     def step(self, images, labels):
         if labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:

@@ -215,6 +215,51 @@ def test_train_config_function_accepts_and_refuses_the_key():
         assert cfg["generator"]["k_classes"] == 8 and cfg["generator"]["k_samples"] == 4 and cfg["generator"]["n_batches"] == 20
 
 
+def test_loss_config_table_names_the_trainers_parameters_and_keeps_the_messages():
+    """tools/train.py's one table-driven validator: every mode's parameters are the ones its trainer takes, in its order, and
+    each kind of refusal keeps the text the three separate validators had."""
+    import importlib.util
+    from embeddingnet_amd.train_step import ProxyTrainer, TripletTrainer
+    spec = importlib.util.spec_from_file_location("embnet_tools_train", os.path.join(ROOT, "tools", "train.py"))
+    train = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(train)
+    assert set(train.LOSS_CONFIGS) == {"ms_loss", "supcon_loss", "proxy_loss"}
+    for table in train.LOSS_CONFIGS.values():
+        for mode, checks in table.items():
+            trainer = ProxyTrainer if mode in ProxyTrainer.LOSS_PARAMS else TripletTrainer
+            assert tuple(checks) == tuple(trainer.LOSS_PARAMS[mode])
+    assert train.MS_LOSS_KEYS == ("alpha", "beta", "base", "epsilon") and train.SUPCON_LOSS_KEYS == ("temperature", "denominator")
+    assert train.PROXY_LOSS_KEYS == {"proxy_anchor": ("alpha", "delta"), "proxy_softmax": ("scale", "margin")}
+    texts = [
+        (train.ms_loss_config, _cfg("semihard", ms_loss=dict(alpha=2.0)),
+         "GENERATOR.ms_loss sets the parameters of negatives_selection_mode 'multi_similarity'; this config trains with 'semihard': "
+         "drop the key or change the mode"),
+        (train.proxy_loss_config, _cfg("proxy_anchor", model_mode="siamese", proxy_loss=dict(alpha=2.0)),
+         "GENERATOR.proxy_loss sets the parameters of negatives_selection_mode 'proxy_anchor' or 'proxy_softmax'; this config trains "
+         "with the Siamese contrastive loss: drop the key or change the mode"),
+        (train.ms_loss_config, _cfg("multi_similarity", ms_loss=dict(gamma=1.0)),
+         "GENERATOR.ms_loss: a mapping with keys out of ('alpha', 'beta', 'base', 'epsilon') (got {'gamma': 1.0})"),
+        (train.proxy_loss_config, _cfg("proxy_softmax", proxy_loss=dict(alpha=1.0)),
+         "GENERATOR.proxy_loss: a mapping with keys out of ('scale', 'margin') for 'proxy_softmax' (got {'alpha': 1.0})"),
+        (train.ms_loss_config, _cfg("multi_similarity", ms_loss=dict(alpha=True)),
+         "GENERATOR.ms_loss: every value must be a number (got {'alpha': True})"),
+        (train.proxy_loss_config, _cfg("proxy_anchor", proxy_loss=dict(alpha=-1.0, delta="x")),
+         "GENERATOR.proxy_loss: every value must be a number (got {'alpha': -1.0, 'delta': 'x'})"),
+        (train.proxy_loss_config, _cfg("proxy_anchor", proxy_loss=dict(delta=0.1, alpha=0)),
+         "GENERATOR.proxy_loss: alpha must be positive (got 0)"),
+        (train.supcon_loss_config, _cfg("supcon", supcon_loss=dict(temperature="hot", denominator="none")),
+         "GENERATOR.supcon_loss: temperature must be a positive number (got 'hot')"),
+        (train.supcon_loss_config, _cfg("supcon", supcon_loss=dict(denominator="none")),
+         "GENERATOR.supcon_loss: denominator must be 'all' or 'negatives' (got 'none')"),
+    ]
+    for fn, cfg, text in texts:
+        with pytest.raises(ValueError) as err:
+            fn(cfg)
+        assert str(err.value) == text
+    assert train.ms_loss_config(_cfg("multi_similarity", ms_loss=dict(beta=40, alpha=1))) == dict(alpha=1.0, beta=40.0)
+    assert train.proxy_loss_config(_cfg("proxy_anchor", proxy_loss=dict(delta=-0.5))) == dict(delta=-0.5)
+
+
 def test_proxy_checkpoints_round_trip_and_refuse_other_classes(tmp_path):
     import importlib.util
     from embeddingnet_amd.proxies import ProxyHead

@@ -138,84 +138,64 @@ def device_augmentations(cfg, synthetic=0, rank=0):
     return aug
 
 
-MS_LOSS_KEYS = ('alpha', 'beta', 'base', 'epsilon')
+# The optional GENERATOR keys that set a loss's parameters: key -> {the negatives_selection_mode that reads it -> {parameter: check}}.
+# A check is 'number', 'positive' (a number, and > 0), 'positive number' (the same under one message) or the tuple of allowed values.
+LOSS_CONFIGS = {
+    'ms_loss': {'multi_similarity': dict(alpha='number', beta='number', base='number', epsilon='number')},
+    'supcon_loss': {'supcon': dict(temperature='positive number', denominator=('all', 'negatives'))},
+    'proxy_loss': {'proxy_anchor': dict(alpha='positive', delta='number'), 'proxy_softmax': dict(scale='positive', margin='number')},
+}
+MS_LOSS_KEYS = tuple(LOSS_CONFIGS['ms_loss']['multi_similarity'])
+SUPCON_LOSS_KEYS = tuple(LOSS_CONFIGS['supcon_loss']['supcon'])
+PROXY_LOSS_KEYS = {mode: tuple(checks) for mode, checks in LOSS_CONFIGS['proxy_loss'].items()}
 
 
-def ms_loss_config(cfg):
-    """GENERATOR.ms_loss (optional): {alpha, beta, base, epsilon}, any subset, of the multi-similarity loss -> the trainer's
-    loss_params (None without the key).  Only GENERATOR.negatives_selection_mode 'multi_similarity' of a triplet-mode model reads
-    it: given with anything else, or with other keys or non-numbers, it is a ValueError before training starts."""
-    value = cfg['generator'].get('ms_loss')
+def loss_config(name, cfg):
+    """GENERATOR.<name> (a key of LOSS_CONFIGS; optional): any subset of the parameters of the mode's loss -> the trainer's
+    loss_params (None without the key).  Only the key's own modes of a triplet-mode model read it: given with anything else, or
+    with other parameters or a value that fails its check, it is a ValueError before training starts."""
+    value = cfg['generator'].get(name)
     if value is None:
         return None
-    mode = cfg['generator'].get('negatives_selection_mode')
-    if cfg['model']['mode'] == 'siamese' or mode != 'multi_similarity':
-        raise ValueError(f"GENERATOR.ms_loss sets the parameters of negatives_selection_mode 'multi_similarity'; this config "
-                         f"trains with {'the Siamese contrastive loss' if cfg['model']['mode'] == 'siamese' else repr(mode)}: "
+    table, mode, siamese = LOSS_CONFIGS[name], cfg['generator'].get('negatives_selection_mode'), cfg['model']['mode'] == 'siamese'
+    if siamese or mode not in table:
+        raise ValueError(f"GENERATOR.{name} sets the parameters of negatives_selection_mode {' or '.join(map(repr, table))}; "
+                         f"this config trains with {'the Siamese contrastive loss' if siamese else repr(mode)}: "
                          "drop the key or change the mode")
-    if not isinstance(value, dict) or set(value) - set(MS_LOSS_KEYS):
-        raise ValueError(f"GENERATOR.ms_loss: a mapping with keys out of {MS_LOSS_KEYS} (got {value!r})")
-    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value.values()):
-        raise ValueError(f"GENERATOR.ms_loss: every value must be a number (got {value!r})")
-    return {k: float(v) for k, v in value.items()}
+    checks = table[mode]
+    if not isinstance(value, dict) or set(value) - set(checks):
+        raise ValueError(f"GENERATOR.{name}: a mapping with keys out of {tuple(checks)}{f' for {mode!r}' if len(table) > 1 else ''} "
+                         f"(got {value!r})")
 
-
-SUPCON_LOSS_KEYS = ('temperature', 'denominator')
-
-
-def supcon_loss_config(cfg):
-    """GENERATOR.supcon_loss (optional): {temperature, denominator}, any subset, of the SupCon / NT-Xent loss -> the trainer's
-    loss_params (None without the key).  Only GENERATOR.negatives_selection_mode 'supcon' of a triplet-mode model reads it: given
-    with anything else, or with other keys, a temperature that is no number or a denominator other than 'all' / 'negatives', it
-    is a ValueError before training starts."""
-    value = cfg['generator'].get('supcon_loss')
-    if value is None:
-        return None
-    mode = cfg['generator'].get('negatives_selection_mode')
-    if cfg['model']['mode'] == 'siamese' or mode != 'supcon':
-        raise ValueError(f"GENERATOR.supcon_loss sets the parameters of negatives_selection_mode 'supcon'; this config "
-                         f"trains with {'the Siamese contrastive loss' if cfg['model']['mode'] == 'siamese' else repr(mode)}: "
-                         "drop the key or change the mode")
-    if not isinstance(value, dict) or set(value) - set(SUPCON_LOSS_KEYS):
-        raise ValueError(f"GENERATOR.supcon_loss: a mapping with keys out of {SUPCON_LOSS_KEYS} (got {value!r})")
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float))
+    if not all(number(v) for k, v in value.items() if checks[k] in ('number', 'positive')):
+        raise ValueError(f"GENERATOR.{name}: every value must be a number (got {value!r})")
     out = {}
-    if 'temperature' in value:
-        t = value['temperature']
-        if isinstance(t, bool) or not isinstance(t, (int, float)) or not t > 0:
-            raise ValueError(f"GENERATOR.supcon_loss: temperature must be a positive number (got {t!r})")
-        out['temperature'] = float(t)
-    if 'denominator' in value:
-        if value['denominator'] not in ('all', 'negatives'):
-            raise ValueError(f"GENERATOR.supcon_loss: denominator must be 'all' or 'negatives' (got {value['denominator']!r})")
-        out['denominator'] = value['denominator']
+    for k, check in checks.items():
+        if k not in value:
+            continue
+        v = value[k]
+        if check == 'positive number' and not (number(v) and v > 0):
+            raise ValueError(f"GENERATOR.{name}: {k} must be a positive number (got {v!r})")
+        if check == 'positive' and not v > 0:
+            raise ValueError(f"GENERATOR.{name}: {k} must be positive (got {v!r})")
+        if isinstance(check, tuple) and v not in check:
+            raise ValueError(f"GENERATOR.{name}: {k} must be {' or '.join(map(repr, check))} (got {v!r})")
+        out[k] = v if isinstance(check, tuple) else float(v)
     return out
 
 
-PROXY_LOSS_KEYS = {'proxy_anchor': ('alpha', 'delta'), 'proxy_softmax': ('scale', 'margin')}
+def ms_loss_config(cfg):
+    return loss_config('ms_loss', cfg)
+
+
+def supcon_loss_config(cfg):
+    return loss_config('supcon_loss', cfg)
 
 
 def proxy_loss_config(cfg):
-    """GENERATOR.proxy_loss (optional): {alpha, delta} of negatives_selection_mode 'proxy_anchor' or {scale, margin} of
-    'proxy_softmax', any subset -> the trainer's loss_params (None without the key).  Only those two modes of a triplet-mode model
-    read it: given with anything else, or with other keys, non-numbers or a non-positive alpha / scale, it is a ValueError before
-    training starts.  The two modes themselves need a triplet-mode model."""
-    mode = cfg['generator'].get('negatives_selection_mode')
-    siamese = cfg['model']['mode'] == 'siamese'
-    value = cfg['generator'].get('proxy_loss')
-    if value is None:
-        return None
-    if siamese or mode not in PROXY_LOSS_KEYS:
-        raise ValueError(f"GENERATOR.proxy_loss sets the parameters of negatives_selection_mode 'proxy_anchor' or 'proxy_softmax'; "
-                         f"this config trains with {'the Siamese contrastive loss' if siamese else repr(mode)}: "
-                         "drop the key or change the mode")
-    keys = PROXY_LOSS_KEYS[mode]
-    if not isinstance(value, dict) or set(value) - set(keys):
-        raise ValueError(f"GENERATOR.proxy_loss: a mapping with keys out of {keys} for {mode!r} (got {value!r})")
-    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value.values()):
-        raise ValueError(f"GENERATOR.proxy_loss: every value must be a number (got {value!r})")
-    if keys[0] in value and not value[keys[0]] > 0:
-        raise ValueError(f"GENERATOR.proxy_loss: {keys[0]} must be positive (got {value[keys[0]]!r})")
-    return {k: float(v) for k, v in value.items()}
+    return loss_config('proxy_loss', cfg)
 
 
 def _proxies_path(weights_path):
