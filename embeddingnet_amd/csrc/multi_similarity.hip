@@ -35,9 +35,7 @@ namespace embnet {
 
 static_assert(EMBNET_MS_PER_CLASS == PAIR_PER_CLASS && EMBNET_MS_SIMILARITY_MATRIX == PAIR_MATRIX, "path constants");
 
-// one rounding order everywhere: t = fl(c * fl(s - base)), c = -alpha or +beta; monotone in s
-__device__ __forceinline__ float ms_t(float c, float s, float base) { return __fmul_rn(c, __fsub_rn(s, base)); }
-
+// (ms_t, ms_term and ms_side are pair_loss.h's: xbm.hip applies them to pair sets given by labels)
 struct MsBody : PairDotBody {
   struct Args { float alpha, beta, base, eps; };
   using Sum = float;
@@ -65,12 +63,12 @@ struct MsBody : PairDotBody {
     int cp = 0, cn = 0;
     for (int j = lane; j < k; j += 64) {                   // lane-strided, column order
       const float s = srow[lo + j];
-      if (j != ai && mxe > s) { sp += expf(__fsub_rn(ms_t(-alpha, s, base), mp)); ++cp; }
+      if (j != ai && mxe > s) { sp += ms_term(-alpha, s, base, mp); ++cp; }
     }
     for (int col = lane; col < n; col += 64) {
       if (col >= lo && col < lo + k) continue;
       const float s = srow[col];
-      if (__fadd_rn(s, eps) > mn) { sn += expf(__fsub_rn(ms_t(beta, s, base), mg)); ++cn; }
+      if (__fadd_rn(s, eps) > mn) { sn += ms_term(beta, s, base, mg); ++cn; }
     }
     const float dp = __fadd_rn(expf(-mp), wave_sum(sp));   // e^{-m} + sum e^{t - m}
     const float dn = __fadd_rn(expf(-mg), wave_sum(sn));
@@ -78,14 +76,14 @@ struct MsBody : PairDotBody {
       const float s = srow[col];
       float g = 0.f;
       if (col >= lo && col < lo + k) {
-        if (col - lo != ai && mxe > s) g = -__fdiv_rn(expf(__fsub_rn(ms_t(-alpha, s, base), mp)), dp);
+        if (col - lo != ai && mxe > s) g = -__fdiv_rn(ms_term(-alpha, s, base, mp), dp);
       } else if (__fadd_rn(s, eps) > mn) {
-        g = __fdiv_rn(expf(__fsub_rn(ms_t(beta, s, base), mg)), dn);
+        g = __fdiv_rn(ms_term(beta, s, base, mg), dn);
       }
       grow[col] = g;
     }
-    const float lp = __fdiv_rn(__fadd_rn(mp, logf(dp)), alpha);
-    const float ln = __fdiv_rn(__fadd_rn(mg, logf(dn)), beta);
+    const float lp = ms_side(mp, dp, alpha);
+    const float ln = ms_side(mg, dn, beta);
     return PairAnchorOut<float>{__fadd_rn(lp, ln), wave_sum(cp), wave_sum(cn)};
   }
   static __device__ int third(const PairAnchorOut<float>& o) { return o.c1 > 0; }   // active: it keeps a negative

@@ -54,6 +54,14 @@ __device__ __forceinline__ float wave_min(float v) {
   return v;
 }
 
+// Multi-similarity's per-pair pieces, stated once for multi_similarity.hip (pair sets by P x K contiguity) and xbm.hip (pair sets by
+// two label vectors).  One rounding order everywhere: t = fl(c * fl(s - base)), c = -alpha or +beta; monotone in s.
+__device__ __forceinline__ float ms_t(float c, float s, float base) { return __fmul_rn(c, __fsub_rn(s, base)); }
+// a kept pair's term of the stable side: e^{t - m}
+__device__ __forceinline__ float ms_term(float c, float s, float base, float m) { return expf(__fsub_rn(ms_t(c, s, base), m)); }
+// a side's loss from its maximum m and its denominator d = e^{-m} + sum e^{t - m} >= 1: (m + log d) / c
+__device__ __forceinline__ float ms_side(float m, float d, float c) { return __fdiv_rn(__fadd_rn(m, logf(d)), c); }
+
 template <class Sum>
 struct PairAnchorOut { Sum loss; int c0, c1; };
 

@@ -9,6 +9,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
   proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
   proxy_softmax_loss(head, scale, margin)(y_true, y_pred)   build-defined (CosFace / NormSoftmax against a ProxyHead's proxies) -> scalar
+  xbm_loss(memory, loss, **params)(y_true, y_pred)          build-defined (a batch against a cross-batch memory, xbm.py) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
 from . import ops
@@ -81,6 +82,25 @@ def proxy_softmax_loss(head, scale=64.0, margin=0.35):
 
     def loss_function(y_true, y_pred):
         return ops.proxy_softmax_loss(y_pred, head.proxies, y_true, scale, margin)[0]
+
+    return loss_function
+
+
+def xbm_loss(memory, loss="contrastive", **params):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_true is the int32 [N] tensor of class indices (negative: unlabelled),
+    y_pred the [N, E] embeddings, memory an xbm.CrossBatchMemory.  Each call first enqueues the batch (detached) and then scores
+    it against the whole memory with the rows' own slots excluded: the cross-batch memory loss of Wang et al. 2020 (build-defined,
+    not in the reference; include/embnet.h, embnet_xbm_loss_fwd).  loss: 'contrastive' (params: margin) or 'multi_similarity'
+    (alpha, beta, base, epsilon); other parameters are refused."""
+    if loss not in ops.XBM_LOSS_MODES:
+        raise KeyError(loss)
+    fn, keys = ops.XBM_LOSS_MODES[loss]
+    if set(params) - set(keys):
+        raise ValueError(f"xbm_loss: unknown parameters {sorted(set(params) - set(keys))} for {loss!r} ({', '.join(keys)})")
+
+    def loss_function(y_true, y_pred):
+        slots = memory.enqueue(y_pred, y_true)
+        return fn(y_pred, y_true, memory.feats, memory.labels, slots, **params)[0]
 
     return loss_function
 

@@ -379,6 +379,105 @@ PROXY_LOSS_MODES = {
 }
 
 
+# --------------------------------------------------------------------------- cross-batch memory (csrc/xbm.hip)
+XBM_KINDS = {"xbm_contrastive_loss": 1, "xbm_multi_similarity_loss": 2}      # EMBNET_XBM_CONTRASTIVE, EMBNET_XBM_MULTI_SIMILARITY
+_XBM_WS = {}
+
+
+def _xbm_labels(who, name, labels, n):
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise _lib.EmbnetError(f"{who}: {name} must be an int32 tensor of {n} entries")
+    return labels.contiguous()
+
+
+def xbm_enqueue(emb, labels, memory):
+    """The rows of emb [N,E] (detached) and their int32 labels [N] into the ring of `memory` (an xbm.CrossBatchMemory, or anything
+    with feats [M,E], labels [M], cursor [1], slots and a 16-byte zeroed `ticket`): row i goes to slot (cursor + i) mod M and the
+    cursor advances by N, all on the device (embnet_xbm_enqueue: one launch, the cursor read by the kernel, so a captured graph
+    replays on the ring's current state).  -> slots int32 [N] (memory.slots[:N]), no host synchronisation."""
+    emb = _prep(emb.detach())
+    n, e = emb.shape
+    m = memory.feats.shape[0]
+    if memory.feats.shape[1] != e:
+        raise _lib.EmbnetError(f"xbm_enqueue: embeddings of width {e} do not match a memory of width {memory.feats.shape[1]}")
+    if n > memory.slots.shape[0]:
+        raise _lib.EmbnetError(f"xbm_enqueue: a batch of {n} rows does not fit a memory of {m} slots")
+    labels = _xbm_labels("xbm_enqueue", "labels", labels, n)
+    slots = memory.slots[:n]
+    check(_lib.lib().embnet_xbm_enqueue(ptr(emb), ptr(labels), n, e, ptr(memory.feats), ptr(memory.labels), m, ptr(memory.cursor),
+                                        ptr(slots), ptr(memory.ticket), stream()))
+    return slots
+
+
+class _XbmLoss(torch.autograd.Function):
+    """embnet_xbm_loss_fwd / _bwd (include/embnet.h): S + sweep forward, one or two backward launches.  G [n,m] and the bank stay saved for
+    the backward; the bank is a constant."""
+
+    @staticmethod
+    def forward(ctx, emb, labels, mem, mem_labels, self_slots, loss, scalars):
+        emb, mem = _prep(emb), _prep(mem.detach())
+        n, e = emb.shape
+        if mem.dim() != 2 or mem.shape[1] != e:
+            raise _lib.EmbnetError(f"{loss}: a memory {tuple(mem.shape)} does not match embeddings of width {e}")
+        m = mem.shape[0]
+        labels = _xbm_labels(loss, "labels", labels, n)
+        mem_labels = _xbm_labels(loss, "mem_labels", mem_labels, m)
+        if self_slots is not None:
+            self_slots = _xbm_labels(loss, "self_slots", self_slots, n)
+        lib = _lib.lib()
+        g = _new((n, m), emb)
+        counts, mean = _new((4,), emb, torch.int32), _new((), emb)
+        ws = _ticket_workspace(_XBM_WS, (emb.device.index, stream()), (n, m, e), lib.embnet_xbm_loss_workspace_bytes, torch.float64,
+                               emb.device)
+        a, b, c, d = (tuple(map(f32, scalars)) + (0.0, 0.0, 0.0))[:4]
+        check(lib.embnet_xbm_loss_fwd(ptr(emb), ptr(labels), ptr(mem), ptr(mem_labels), ptr(self_slots), n, m, e, XBM_KINDS[loss],
+                                      a, b, c, d, ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8, stream()))
+        ctx.save_for_backward(mem, g)
+        ctx.shape, ctx.ws = (n, m, e), ws                   # the backward's scratch: S is not needed any more
+        ctx.mark_non_differentiable(counts, g)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return mean, counts, g
+
+    @staticmethod
+    def backward(ctx, dmean, *_):
+        if dmean is None:
+            return (None,) * 7
+        mem, g = ctx.saved_tensors
+        n, m, e = ctx.shape
+        demb = _new((n, e), g)
+        check(_lib.lib().embnet_xbm_loss_bwd(ptr(mem), n, m, e, ptr(g), ptr(_prep(dmean)), ptr(demb), ptr(ctx.ws),
+                                             ctx.ws.numel() * 8, stream()))
+        return (demb,) + (None,) * 6
+
+
+def xbm_contrastive_loss(emb, labels, mem, mem_labels, self_slots=None, margin=0.5, return_weights=False):
+    """The XBM paper's contrastive loss (Wang et al., CVPR 2020) of embeddings [N,E] with int32 labels [N] against a DETACHED bank
+    mem [M,E] with int32 mem_labels [M] (negative: an unlabelled row, an empty slot; they belong to no pair), on S = X mem^T:
+    l_i = sum over the same-label slots with 1 - S > 0 of (1 - S) + sum over the other-label slots with S > margin of S, mean over
+    all N rows; self_slots int32 [N] names each row's own copy in the bank (what xbm_enqueue returned), which is excluded.
+    -> (mean [autograd w.r.t. emb only], counts int32 [4] = kept positives, kept negatives, active anchors, labelled bank slots) on
+    the device, no host synchronisation; return_weights adds G [N,M] = dl_i/dS_ij (include/embnet.h)."""
+    out = _XbmLoss.apply(emb, labels, mem, mem_labels, self_slots, "xbm_contrastive_loss", (float(margin),))
+    return out if return_weights else out[:2]
+
+
+def xbm_multi_similarity_loss(emb, labels, mem, mem_labels, self_slots=None, alpha=2.0, beta=50.0, base=0.5, epsilon=0.1,
+                              return_weights=False):
+    """The multi-similarity loss of multi_similarity_loss — its mining rule, rounding forms and stable logarithms — with anchor i's
+    positives the same-label slots of a DETACHED bank and its negatives the other-label slots (arguments and results as
+    xbm_contrastive_loss; an anchor without a positive or without a negative keeps nothing)."""
+    out = _XbmLoss.apply(emb, labels, mem, mem_labels, self_slots, "xbm_multi_similarity_loss",
+                         (float(alpha), float(beta), float(base), float(epsilon)))
+    return out if return_weights else out[:2]
+
+
+# The memory losses of train_step.XbmTrainer:  mode: (function, the xbm_params it takes)
+XBM_LOSS_MODES = {
+    "contrastive": (xbm_contrastive_loss, ("margin",)),
+    "multi_similarity": (xbm_multi_similarity_loss, ("alpha", "beta", "base", "epsilon")),
+}
+
+
 # --------------------------------------------------------------------------- contrastive / accuracy
 class _Contrastive(torch.autograd.Function):
     @staticmethod

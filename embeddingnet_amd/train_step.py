@@ -100,7 +100,13 @@ class TripletTrainer:
         """-> (total loss incl. regularisers, triplet loss, live triplet count tensor)."""
         if images.shape[0] != self.p * self.k:
             raise ValueError(f"batch of {images.shape[0]} images != k_classes*k_samples = {self.p * self.k}")
-        emb = self.model(images)
+        mean, count = self.batch_loss(self.model(images))
+        reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
+        return (mean if reg is None else mean + reg), mean, count
+
+    def batch_loss(self, emb):
+        """The mode's loss of the class-contiguous embeddings [P*K, E] of one batch -> (mean, live count tensor); sets
+        last_triplets (and last_pair_counts).  XbmTrainer adds the memory's loss of the same embeddings to it."""
         if self.mode in ops.PAIR_LOSS_MODES:                # at every batch size and whatever EMBNET_FUSED_LOSS says
             fn, keys, at = ops.PAIR_LOSS_MODES[self.mode]
             mean, counts = fn(emb, self.p, self.k, **({"margin": self.margin} if keys is None else self.loss_params))[:2]
@@ -116,8 +122,7 @@ class TripletTrainer:
         else:
             trip, count = self.mine(emb)
             mean, _ = ops.triplet_gather_loss(emb, trip, count, self.margin)
-        reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
-        return (mean if reg is None else mean + reg), mean, count
+        return mean, count
 
     # ---- graph replay ---------------------------------------------------------------------------------------
     def _graph_state_live(self):
@@ -204,7 +209,7 @@ class TripletTrainer:
             for m, st in zip(self._drops, drop_steps):
                 m._step = st
 
-    # the step's inputs, as `loss` takes them: one image batch here; SiameseTrainer packs (x1, x2, y), ProxyTrainer (images, labels)
+    # the step's inputs, as `loss` takes them: one image batch here; SiameseTrainer packs (x1, x2, y), ProxyTrainer and XbmTrainer (images, labels)
     @staticmethod
     def _tuple(inputs):
         return tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
@@ -446,4 +451,80 @@ class ProxyTrainer(TripletTrainer):
     def step(self, images, labels):
         if labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
             raise ValueError(f"ProxyTrainer.step: labels must be int32 [{images.shape[0]}] (got {labels.dtype} {tuple(labels.shape)})")
+        return super().step((images, labels))
+
+
+class XbmTrainer(TripletTrainer):
+    """TripletTrainer with a cross-batch memory (xbm.CrossBatchMemory; Wang et al., CVPR 2020): the loss of a step is the parent
+    mode's in-batch loss — any negatives_selection_mode — plus `weight` times the loss of the SAME embeddings against the memory
+    (ops.XBM_LOSS_MODES: 'contrastive', the XBM paper's criterion, xbm_params = dict(margin), default 0.5; 'multi_similarity',
+    xbm_params = dict(alpha, beta, base, epsilon), defaults 2, 50, 0.5, 0.1; unknown keys are refused).  The XBM recipe: the batch's
+    detached embeddings are enqueued first, then the batch is scored against the whole ring with each sample's own slot excluded.
+    The ring, its write position and the enqueue live on the device (include/embnet.h): no host synchronisation, and with
+    graph=True / 'auto' the step — enqueue and memory loss included — is captured once and replayed like ProxyTrainer's, the labels
+    copied into a static buffer beside the images; a replayed step is bit-identical to an eager one.
+
+    step(images, labels): labels int32 device tensor [N] of global class indices, rows class-contiguous as for TripletTrainer.
+    While step_no < start_iteration nothing of the memory runs — no enqueue, no memory loss: the step is TripletTrainer's, bit for
+    bit, and runs eagerly (the capture waits until the memory is live).  last_pair_counts / last_triplets are the parent's;
+    last_xbm_counts = int32 [4]: kept positives, kept negatives, active anchors, labelled memory slots (None before the memory is live).
+    Under data parallelism each rank keeps a memory of its own batches: nothing is gathered, the reducer averages the ranks'
+    gradients as it does the in-batch loss's.  The memory is not checkpointed: after a resume it refills."""
+
+    def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5, negatives_selection_mode="semihard", seed=0,
+                 reducer=None, graph=None, loss_params=None, memory=None, xbm_loss="contrastive", xbm_params=None, weight=1.0,
+                 start_iteration=0):
+        super().__init__(base_model, optimizer, k_classes, k_samples, margin, negatives_selection_mode, seed, reducer, graph,
+                         loss_params)
+        if xbm_loss not in ops.XBM_LOSS_MODES:
+            raise KeyError(xbm_loss)
+        keys = ops.XBM_LOSS_MODES[xbm_loss][1]
+        unknown = set(xbm_params or {}) - set(keys)
+        if unknown:
+            raise ValueError(f"xbm_params: unknown keys {sorted(unknown)} for {xbm_loss!r} ({', '.join(keys)})")
+        if memory is None or not hasattr(memory, "enqueue"):
+            raise ValueError("XbmTrainer: memory must be an xbm.CrossBatchMemory")
+        if memory.size < self.p * self.k:
+            raise ValueError(f"XbmTrainer: a memory of {memory.size} slots is smaller than a batch of {self.p * self.k}")
+        if int(start_iteration) < 0:
+            raise ValueError(f"XbmTrainer: start_iteration={start_iteration} must not be negative")
+        self.memory, self.xbm_loss, self.xbm_params = memory, xbm_loss, dict(xbm_params or {})
+        self.weight, self.start_iteration = float(weight), int(start_iteration)
+        self.last_xbm_counts, self._xbm_live, self._g_xbm_counts = None, False, None
+
+    def loss(self, inputs):
+        images, labels = inputs
+        if images.shape[0] != self.p * self.k:
+            raise ValueError(f"batch of {images.shape[0]} images != k_classes*k_samples = {self.p * self.k}")
+        emb = self.model(images)
+        if emb.shape[1] != self.memory.embedding_size:
+            raise ValueError(f"XbmTrainer: embeddings of width {emb.shape[1]} do not match a memory of width "
+                             f"{self.memory.embedding_size}")
+        mean, count = self.batch_loss(emb)
+        if self._xbm_live:
+            slots = self.memory.enqueue(emb, labels)        # first the batch's own (detached) copies, then the whole ring
+            xbm_mean, self.last_xbm_counts = ops.XBM_LOSS_MODES[self.xbm_loss][0](
+                emb, labels, self.memory.feats, self.memory.labels, slots, **self.xbm_params)
+            mean = mean + self.weight * xbm_mean
+        reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)
+        return (mean if reg is None else mean + reg), mean, count
+
+    def _graph_supported(self, inputs):
+        return self.step_no >= self.start_iteration and super()._graph_supported(inputs)
+
+    def _capture(self, inputs):
+        super()._capture(inputs)
+        self._g_xbm_counts = self.last_xbm_counts           # the replayed step's (static) output tensor
+
+    def _replay(self, inputs):
+        out = super()._replay(inputs)
+        self.last_xbm_counts = self._g_xbm_counts           # an eager step in between re-bound it
+        return out
+
+    def step(self, images, labels):
+        if labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+            raise ValueError(f"XbmTrainer.step: labels must be int32 [{images.shape[0]}] (got {labels.dtype} {tuple(labels.shape)})")
+        self._xbm_live = self.step_no >= self.start_iteration
+        if not self._xbm_live:
+            return self._plain_step((images, labels))       # the parent's eager step; the capture waits for the memory
         return super().step((images, labels))

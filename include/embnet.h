@@ -1057,6 +1057,60 @@ int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int n, int c, 
                           const float* q, const float* upstream, float* demb, float* dproxies, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* Cross-Batch Memory (Wang et al., CVPR 2020, "XBM"): the detached embeddings of the last m samples kept in a ring on the device,
+ * and the pair losses of a batch against that ring (the reference has no memory): build-defined, selected as
+ * XbmTrainer(memory=..., xbm_loss="contrastive" | "multi_similarity").  Additions only: the ABI version stays 22.
+ *   The ring.  mem[m,e] fp32 and mem_labels[m] int32 belong to the caller, who initialises them ONCE to 0 and -1 (a negative bank
+ *     label marks an empty or unlabelled slot);  *cursor is a DEVICE int32, the next slot to write, initialised once to 0.
+ *     embnet_xbm_enqueue: row i of emb[n,e] goes to slot (cursor + i) mod m with labels[i], slots[i] receives that slot, and
+ *     afterwards *cursor = (cursor + n) mod m.  1 <= n <= m <= 65536, 1 <= e <= 4096.  The cursor is read from device memory by the
+ *     kernel at run time, never passed by value: a captured graph replays on the ring's current state.  It is advanced by the last
+ *     workgroup to arrive, after every workgroup has read it: no workgroup sees the advanced value.  One launch, no memset node,
+ *     vector stores only.  A cursor word outside [0, m) is taken modulo m as an unsigned number: no value of it addresses memory
+ *     outside the ring.  workspace: 16 bytes, 16-byte aligned (the arrival counter).
+ *   The loss.  emb[n,e] fp32 batch with labels[n] int32, mem[m,e] / mem_labels[m] the bank (DETACHED: it carries no gradient),
+ *     self_slots[n] int32 or NULL.
+ *   Similarity.  S_ij = sum_k x_ik y_jk, an fp32 dot product through embnet_dense_dgrad_f32 (a k-ordered chain per element: a rounded
+ *     product and a rounded addition per k).  Unit rows are not required.
+ *   Pair sets.  Labels are compared by value and never used as an index.  A NEGATIVE label marks an unlabelled batch row or an empty
+ *     or unlabelled bank slot: such a row or column belongs to no pair set, its entries of G are zero and it receives no gradient.
+ *     Column self_slots[i] is excluded for anchor i (the sample's own copy, just enqueued); a slot outside [0, m), or self_slots
+ *     NULL, excludes nothing.  For y_i >= 0:  P_i = {j : z_j = y_i, j != self_i},  N_i = {j : z_j >= 0, z_j != y_i}.
+ *   EMBNET_XBM_CONTRASTIVE (the XBM paper's own criterion as its released code has it; a = margin, the Python layers default to 0.5;
+ *     b, c, d are ignored).  A positive is kept iff fl(1 - S_ip) > 0 (one fp32 subtraction); its term is fl(1 - S_ip) and G_ip = -1.
+ *     A negative is kept iff S_in > margin; its term is S_in and G_in = +1.  l_i = the sum of the kept terms: the fp32 terms join an
+ *     f64 sum in a fixed order.  (The released code drops positives with S >= 1 - 1e-5 to get rid of the self pair; here the self
+ *     pair is excluded exactly by its slot, and the threshold is 1.)
+ *   EMBNET_XBM_MULTI_SIMILARITY (a, b, c, d = alpha > 0, beta > 0, base, epsilon >= 0; defaults 2, 50, 0.5, 0.1).  The mining rule
+ *     with its one rounding form, t+ / t-, the stable logarithms, l_i and G are embnet_ms_loss_fwd's, word for word, over P_i and
+ *     N_i as above (the kernels share the code: csrc/pair_loss.h).  An anchor with an empty P_i or an empty N_i keeps nothing.
+ *   Common.  *mean_loss = (1/n) sum_i l_i, n counting EVERY batch row.  pair_g[n][m] = dl_i/dS_ij (without the 1/n); every entry is
+ *     written.  Backward: demb_i = (g / n) sum_j G_ij y_j, g = *upstream (NULL = 1); there is no column role, the bank is a
+ *     constant.  The sum runs on the f64 matrix instructions: every element is one fp32 rounding of an f64 sum.
+ *   Counters.  counts[4], int32, exact on the device's fp32 S: {kept positives, kept negatives, active anchors (those that keep a
+ *     pair), labelled bank slots (z_j >= 0)}.
+ * Range: 2 <= n <= 4096, n <= m <= 65536, n m <= 2^26, 1 <= e <= 4096; kind one of the two; margin finite; alpha, beta finite and
+ * positive, base finite, epsilon finite and non-negative; anything else is rejected before a launch.  ONE forward path,
+ * EMBNET_XBM_SWEEP: S into the workspace, then a sweep launch in which one wave walks one anchor's row of S (a row of 65536 floats
+ * does not fit LDS, and at these sizes the rectangle never fits a workgroup the way the proxies' small path does);
+ * embnet_xbm_loss_path exists so that a second path can join.  The backward is one launch, two against a long bank: the slot sum
+ * is then split into slices whose f64 sums are added in slice order (a workspace of the forward's size holds them where S was).
+ * No floating-point atomics, every reduction in a fixed order: bitwise reproducible; no host synchronisation or allocation.
+ * workspace (embnet_xbm_loss_workspace_bytes, 16-byte aligned; 4 n m bytes and a few per anchor): zero-filled ONCE by the caller;
+ * every launch, the enqueue's included, leaves its arrival counter zeroed.  The backward uses it as scratch only, behind the
+ * counter and the partials: it may be the forward's (S is no longer needed) or another. */
+enum { EMBNET_XBM_CONTRASTIVE = 1, EMBNET_XBM_MULTI_SIMILARITY = 2 };
+enum { EMBNET_XBM_SWEEP = 1 };
+int embnet_xbm_enqueue(const float* emb, const int32_t* labels, int n, int e, float* mem, int32_t* mem_labels, int m,
+                       int32_t* cursor, int32_t* slots, void* workspace, void* stream);
+int embnet_xbm_loss_path(int n, int m, int e);            /* EMBNET_XBM_SWEEP; 0 outside the range */
+size_t embnet_xbm_loss_workspace_bytes(int n, int m, int e);      /* 0 outside the range */
+int embnet_xbm_loss_fwd(const float* emb, const int32_t* labels, const float* mem, const int32_t* mem_labels,
+                        const int32_t* self_slots, int n, int m, int e, int kind, float a, float b, float c, float d,
+                        float* pair_g, int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_xbm_loss_bwd(const float* mem, int n, int m, int e, const float* pair_g, const float* upstream, float* demb,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

@@ -7,7 +7,8 @@ For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2
 semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
-denominator beside ops.multi_similarity_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases()):
+denominator beside ops.multi_similarity_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
+xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -151,6 +152,125 @@ def proxy_cases(a, dev, out):
         print(json.dumps(row), flush=True)
 
 
+# the cross-batch memory: (name, n, e, m, kind)
+XBM_CASES = [(f"xbm_{kind}_e{e}_m{m}", 128, e, m, kind) for kind in ("contrastive", "multi_similarity") for e in (128, 256)
+             for m in (1024, 8192, 65536)]
+
+
+def torch_xbm_step(kind, x, labels, mem, mem_labels, cursor, params):
+    """Enqueue and loss composed from torch ops (index_copy_, matmul, where, logsumexp, autograd), everything on the device: the
+    yardstick of the xbm cases."""
+    n, m = x.shape[0], mem.shape[0]
+    slots = (cursor + torch.arange(n, device=x.device)) % m
+    mem.index_copy_(0, slots, x.detach())
+    mem_labels.index_copy_(0, slots, labels)
+    cursor.add_(n).remainder_(m)
+    s = x @ mem.T
+    ok = (labels >= 0)[:, None] & (mem_labels >= 0)[None, :] & (torch.arange(m, device=x.device)[None, :] != slots[:, None])
+    same = labels[:, None] == mem_labels[None, :]
+    pos, neg = ok & same, ok & ~same
+    zero = torch.zeros((), device=x.device)
+    if kind == "contrastive":
+        return (torch.where(pos & (1.0 - s > 0), 1.0 - s, zero).sum(1) + torch.where(neg & (s > params["margin"]), s, zero).sum(1)).mean()
+    al, be, ba, eps = params["alpha"], params["beta"], params["base"], params["epsilon"]
+    inf = torch.full((), float("inf"), device=x.device)
+    mn, mx = torch.where(pos, s, inf).min(1).values, torch.where(neg, s, -inf).max(1).values
+    kp, kn = pos & ((mx + eps)[:, None] > s), neg & ((s + eps) > mn[:, None])
+    z = torch.zeros((n, 1), device=x.device)
+    lp = torch.logsumexp(torch.cat([z, torch.where(kp, -al * (s - ba), -inf)], 1), 1) / al
+    ln = torch.logsumexp(torch.cat([z, torch.where(kn, be * (s - ba), -inf)], 1), 1) / be
+    return torch.where(kn.any(1), lp + ln, zero).mean()
+
+
+def xbm_cases(a, dev, out):
+    """ops.xbm_enqueue + ops.xbm_contrastive_loss / ops.xbm_multi_similarity_loss + backward at N = 128 against a full memory of M
+    slots, beside the same step composed from torch ops, in one process, alternating: device microseconds are medians of
+    alternating rounds of graph replays; launches and per-kernel times of the library leg come from the library's trace."""
+    from embeddingnet_amd.xbm import CrossBatchMemory
+    for name, n, e, m, kind in XBM_CASES:
+        if a.only and a.only not in name:
+            continue
+        g = torch.Generator(device=dev).manual_seed(7)
+        classes = 256
+        cen = torch.rand((classes, e), device=dev, generator=g)
+
+        def rows(lab):
+            r = (cen[lab.long()] + 0.25 * torch.randn((lab.shape[0], e), device=dev, generator=g)).abs()
+            return r / r.norm(dim=1, keepdim=True)
+        labels = torch.randperm(classes, device=dev, generator=g)[:n // 4].repeat_interleave(4).to(torch.int32)
+        x = rows(labels).requires_grad_(True)
+        bank_labels = torch.randint(0, classes, (m,), device=dev, generator=g).to(torch.int32)
+        memory = CrossBatchMemory(m, e, dev)
+        memory.feats.copy_(rows(bank_labels)); memory.labels.copy_(bank_labels)
+        t_mem, t_lab, t_cur = memory.feats.clone(), bank_labels.long(), torch.zeros(1, dtype=torch.long, device=dev)
+        fn, keys = ops.XBM_LOSS_MODES[kind]
+        params = dict(margin=0.5) if kind == "contrastive" else dict(alpha=2.0, beta=50.0, base=0.5, epsilon=0.1)
+        lab64 = labels.long()
+
+        def hip():
+            x.grad = None
+            fn(x, labels, memory.feats, memory.labels, memory.enqueue(x, labels), **params)[0].backward()
+
+        def composed():
+            x.grad = None
+            torch_xbm_step(kind, x, lab64, t_mem, t_lab, t_cur, params).backward()
+
+        trace = measure(hip, a.iters)
+        med = graph_rounds(dict(hip=hip, torch_composed=composed), rounds=15, reps=20)
+        row = dict(config=name, N=n, E=e, M=m, kind=kind, hip=trace, device_us_median=med,
+                   device_ratio_vs_torch_composed=round(med["hip"] / med["torch_composed"], 3))
+        out.append(row)
+        print(json.dumps(row), flush=True)
+
+
+def xbm_step_time(config, m, rounds=7, steps=10):
+    """One process, one leg: the training step of `config` ('simple2': simple2 64 x 64, 8 x 4, semihard; 'c2': ResNet18 224 x 224,
+    32 x 4, hardest; E = 256, graph-replayed) with a contrastive cross-batch memory of m slots (XbmTrainer) or, m = 0, without
+    (TripletTrainer), on eight resident random batches taken in turn, so that the in-batch loss stays live in both legs (a step
+    whose loss has died propagates zero gradients, and the backbone's backward kernels run measurably faster on zeros).
+    -> median, min and max milliseconds per step over `rounds` rounds of `steps` steps timed with events, and the live count."""
+    from embeddingnet_amd import backbones as B
+    from embeddingnet_amd.optimizers import KerasOptimizer
+    from embeddingnet_amd.train_step import TripletTrainer, XbmTrainer
+    from embeddingnet_amd.xbm import CrossBatchMemory
+    dev = torch.device("cuda:0")
+    backbone, image, p, k, mining = dict(simple2=("simple2", 64, 8, 4, "semihard"), c2=("resnet18", 224, 32, 4, "hardest"))[config]
+    g = torch.Generator(device=dev).manual_seed(3)
+    pool = [torch.rand((p * k, image, image, 3), device=dev, generator=g) for _ in range(8)]
+    y = torch.arange(p, dtype=torch.int32, device=dev).repeat_interleave(k)
+    tick = [0]
+
+    def x():
+        tick[0] += 1
+        return pool[tick[0] % 8]
+    base, _ = B.get_backbone((image, image, 3), encodings_len=256, backbone_name=backbone, backbone_weights=None, seed=1, device=dev)
+    opt = KerasOptimizer([q for q in base.parameters() if q.requires_grad], "adam", 1e-4)
+    if m:
+        tr = XbmTrainer(base, opt, p, k, negatives_selection_mode=mining, graph=True, memory=CrossBatchMemory(m, 256, dev))
+        step = lambda: tr.step(x(), y)
+    else:
+        tr = TripletTrainer(base, opt, p, k, negatives_selection_mode=mining, graph=True)
+        step = lambda: tr.step(x())
+    for _ in range(TripletTrainer.GRAPH_WARMUP + 6 + (m // (p * k) if config == "simple2" else 0)):     # captured; simple2: a full memory
+        step()
+    torch.cuda.synchronize()
+    times, live = [], []
+    for _ in range(rounds):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(steps):
+            step()
+        t1.record()
+        t1.synchronize()
+        times.append(t0.elapsed_time(t1) / steps)
+        live.append(int(tr.last_triplets[1].sum().item()))
+    row = dict(config=f"xbm_step_{config}", M=m, live_triplets_min=min(live), graph=tr._graph is not None, step_ms_median=round(sorted(times)[len(times) // 2], 4),
+               step_ms_min_max=[round(min(times), 4), round(max(times), 4)],
+               filled=None if not m else tr.memory.filled())
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def step_times(out, rounds=9, steps=10):
     """The simple2 64 x 64 training step, 8 x 4 batches, in proxy_anchor mode (ProxyTrainer, 100 classes) beside supcon mode
     (TripletTrainer), eager steps, alternating rounds of `steps` steps timed with events: median milliseconds per step."""
@@ -198,8 +318,15 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default=None, help="run only the cases whose name contains this")
+    ap.add_argument("--xbm-step", default=None, choices=["simple2", "c2"], help="time one training step leg (xbm_step_time) and exit")
+    ap.add_argument("--xbm-memory", type=int, default=0, help="--xbm-step: slots of the cross-batch memory, 0 = none")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.xbm_step:
+        row = xbm_step_time(a.xbm_step, a.xbm_memory)
+        if a.json:
+            json.dump([row], open(a.json, "w"), indent=1)
+        return
     out = []
     for name, p, k, e, mode in CASES:
         if a.only and a.only not in name:
@@ -272,6 +399,7 @@ def main():
         out.append(row)
         print(json.dumps(row), flush=True)
     proxy_cases(a, dev, out)
+    xbm_cases(a, dev, out)
     if a.only and a.only in "proxy_step_time":
         step_times(out)
     if a.json:

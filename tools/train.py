@@ -11,6 +11,10 @@ EarlyStopping(patience 10) (:84-86), best-only checkpoints weights/epoch_XXX.npz
 Multi-GPU: launch with torchrun; classes are sharded per rank and gradients all-reduced over RCCL.
 GENERATOR.negatives_selection_mode 'proxy_anchor' / 'proxy_softmax' train the backbone together with one learnable proxy per
 class (train_step.ProxyTrainer on the feeder's labelled batches); the proxies are checkpointed as proxies/epoch_XXX.npz.
+GENERATOR.xbm: {size, weight, start_iteration, loss, <that loss's parameters>} adds a cross-batch memory (train_step.XbmTrainer,
+embeddingnet_amd/xbm.py) to any triplet-mode negatives_selection_mode but the proxy ones: the loss of the batch against the detached
+embeddings of the last `size` samples, `weight` times, from step `start_iteration` on; `xbm_filled` and the kept pairs are logged
+per epoch.  Each rank keeps its own memory; it is not checkpointed, after --resume_from it refills.
 `--synthetic` swaps the file loader for an in-memory synthetic dataset (no dataset ships with the repo).
 """
 import argparse
@@ -198,6 +202,36 @@ def proxy_loss_config(cfg):
     return loss_config('proxy_loss', cfg)
 
 
+# GENERATOR.xbm (optional): the memory's own keys, and per memory loss (ops.XBM_LOSS_MODES) that loss's parameters.
+XBM_KEYS = dict(size='positive', weight='number', start_iteration='number', loss=('contrastive', 'multi_similarity'))
+XBM_LOSS_KEYS = {'contrastive': dict(margin='number'),
+                 'multi_similarity': dict(alpha='positive', beta='positive', base='number', epsilon='number')}
+XBM_DEFAULTS = dict(weight=1.0, start_iteration=0, loss='contrastive')
+XBM_MODES = ('semihard', 'hardest', 'random_hard', 'batch_hard', 'batch_all', 'multi_similarity', 'supcon')
+
+
+def xbm_config(cfg):
+    """GENERATOR.xbm (optional) -> dict(size, weight, start_iteration, loss, params) or None, checked by loss_config: the key goes
+    with every negatives_selection_mode of TripletTrainer and is refused (ValueError before training starts) with the proxy modes,
+    in Siamese mode, with keys that are neither the memory's nor its loss's, and with a memory smaller than a batch."""
+    value = cfg['generator'].get('xbm')
+    if value is None:
+        return None
+    loss = value.get('loss', XBM_DEFAULTS['loss']) if isinstance(value, dict) else XBM_DEFAULTS['loss']
+    checks = dict(XBM_KEYS, **XBM_LOSS_KEYS.get(loss, {}))
+    LOSS_CONFIGS['xbm'] = {mode: checks for mode in XBM_MODES}
+    out = dict(XBM_DEFAULTS, **loss_config('xbm', cfg))
+    if 'size' not in out or out['size'] != int(out['size']):
+        raise ValueError(f"GENERATOR.xbm: size, the number of slots, must be a whole number (got {value!r})")
+    if out['start_iteration'] != int(out['start_iteration']) or out['start_iteration'] < 0:
+        raise ValueError(f"GENERATOR.xbm: start_iteration must be a whole number >= 0 (got {value!r})")
+    batch = int(cfg['generator']['k_classes']) * int(cfg['generator']['k_samples'])
+    if out['size'] < batch:
+        raise ValueError(f"GENERATOR.xbm: a memory of {int(out['size'])} slots is smaller than a batch of {batch}")
+    return dict(size=int(out['size']), weight=float(out['weight']), start_iteration=int(out['start_iteration']), loss=out['loss'],
+                params={k: out[k] for k in XBM_LOSS_KEYS[out['loss']] if k in out})
+
+
 def _proxies_path(weights_path):
     """<project>/weights/epoch_007.npz -> <project>/proxies/epoch_007.npz (the class proxies of the proxy losses)."""
     d, f = os.path.split(os.path.abspath(weights_path))
@@ -291,6 +325,7 @@ def main():
     ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
     supcon_loss = supcon_loss_config(cfg)              # and GENERATOR.supcon_loss
     proxy_loss = proxy_loss_config(cfg)                # and GENERATOR.proxy_loss
+    xbm = xbm_config(cfg)                              # and GENERATOR.xbm (with a proxy mode, in Siamese mode, a memory below a batch)
     # each is refused with another's mode: at most one is set
     loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss) if v is not None), None)
     proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS
@@ -321,7 +356,7 @@ def main():
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
-    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss')}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss', 'xbm')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -393,9 +428,17 @@ def main():
         trainer = ProxyTrainer(model.base_model, head, opt, loss=p_gen['negatives_selection_mode'], loss_params=loss_params,
                                seed=rank, reducer=reducer)
     else:
-        trainer = TripletTrainer(
-            model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], margin=p_gen['margin'],
-            negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer, loss_params=loss_params)
+        kw = dict(margin=p_gen['margin'], negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer,
+                  loss_params=loss_params)
+        if xbm is not None:
+            # each rank keeps a memory of its own batches (nothing is gathered); it starts empty, after a resume too
+            from embeddingnet_amd.train_step import XbmTrainer
+            from embeddingnet_amd.xbm import CrossBatchMemory
+            memory = CrossBatchMemory(xbm['size'], p_model['encodings_len'], dev)
+            trainer = XbmTrainer(model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], memory=memory, xbm_loss=xbm['loss'],
+                                 xbm_params=xbm['params'], weight=xbm['weight'], start_iteration=xbm['start_iteration'], **kw)
+        else:
+            trainer = TripletTrainer(model.base_model, opt, gen_kw['k_classes'], p_gen['k_samples'], **kw)
     plateau = Plateau(persistent=bool(p_train.get('plateau_persistent', False)))
     history = {'loss': [], 'val_loss': []}
     for k in retrieval_ks:
@@ -423,16 +466,18 @@ def main():
             for g in opt.param_groups:
                 g['lr'] = lr
             trainable.train()
-            losses = []
+            losses, xbm_counts = [], []
             for _ in range(len(train_gen)):
                 if siamese:
                     (x1, x2), y = train_gen[0]
                     losses.append(trainer.step(torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev),
                                                torch.from_numpy(np.asarray(y, dtype=np.float32)).to(dev).reshape(-1, 1)))
                 else:
-                    if proxy_mode:
+                    if proxy_mode or xbm is not None:
                         xb, yb = feeder.next_labelled()
                         losses.append(trainer.step(xb, yb))
+                        if xbm is not None and trainer.last_xbm_counts is not None:
+                            xbm_counts.append(trainer.last_xbm_counts.clone())      # (a replayed step's counts are one buffer)
                     else:
                         xb = feeder.next()
                         losses.append(trainer.step(xb))
@@ -442,6 +487,9 @@ def main():
             msg = f'Epoch {epoch + 1}/{n_epochs} - lr {lr:.3g} - loss {epoch_loss:.4f}'
             if n_images:                                  # (the .item() above waited for the epoch's last step)
                 msg += f' - {n_images * world / (time.perf_counter() - t_epoch):.0f} images/s'
+            if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
+                kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
+                msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
             value = epoch_loss
             if val_gen is not None:
                 trainable.eval()
