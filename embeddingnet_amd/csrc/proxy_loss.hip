@@ -24,17 +24,11 @@
 #include <math.h>
 #include "common.h"
 #include "pair_loss.h"
+#include "proxy_loss.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
 
-constexpr int PROXY_MAX_N = 4096;
-constexpr int PROXY_MAX_C = 16384;
-constexpr int PROXY_MAX_E = 4096;
-constexpr int PROXY_THREADS = 256;                       // 4 waves: one anchor each
-constexpr int PROXY_WG_ANCHORS = PROXY_THREADS / 64;
-constexpr int PROXY_LDS_FLOATS = 16 * 1024;              // small path: 4 (e + nb) floats
-constexpr long PROXY_SMALL_MACS = 1L << 25;              // small path: n c e, every workgroup re-reads all of B from L2
 static_assert(EMBNET_PROXY_SMALL == 1 && EMBNET_PROXY_MATRIX == 2, "path constants");
 
 struct ProxyParams {
@@ -52,29 +46,19 @@ struct ProxyParams {
 
 struct ProxyAnchorOut { float lp, ln; int has, viol; };
 
-// ---- prep: q and the class sizes; one wave per class ------------------------------------------------------------------------------
-// The wave reads 64 consecutive elements of the row at a time (coalesced) and squares them in f64, which is exact; the chain over
-// k is contractual, so every lane then adds the 64 squares in lane order, taken from the other lanes one by one: the same f64
-// additions in the same order as a serial loop, and past the row's end exact zeros.  The labels are counted lane-strided (integers).
+// ---- prep: q (proxy_loss.h's proxy_row_q) and the class sizes; one wave per class; the labels are counted lane-strided (integers) --
 __global__ __launch_bounds__(PROXY_THREADS) void proxy_prep_kernel(const float* __restrict__ w, const int32_t* __restrict__ labels,
                                                                    int n, int c, int e, float* __restrict__ q,
                                                                    int32_t* __restrict__ cnt) {
   const int lane = threadIdx.x & 63;
   const int cl = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
   if (cl >= c) return;                                   // wave-uniform
-  const float* r = w + (long)cl * e;
-  double ss = 0.0;
-  for (int k0 = 0; k0 < e; k0 += 64) {
-    const double v = k0 + lane < e ? (double)r[k0 + lane] : 0.0;
-    const double v2 = v * v;
-#pragma unroll 8
-    for (int j = 0; j < 64; ++j) ss += __shfl(v2, j, 64);
-  }
+  const float qc = proxy_row_q(w + (long)cl * e, e, lane);
   int m = 0;
   for (int i = lane; i < n; i += 64) m += labels[i] == cl;
   m = wave_sum(m);
   if (lane == 0) {
-    q[cl] = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
+    q[cl] = qc;
     cnt[cl] = m;
   }
 }
@@ -332,6 +316,43 @@ inline void proxy_bwd_split(int n, int c, int e, int& splits, int& jchunk) {
   splits = cdiv(c, jchunk);
 }
 
+// The backward's launches on checked arguments, in two steps so that multi_proxy_loss.hip (the CosFace case over c kc rows) can add its
+// regulariser's term to Y between them.  products: demb, and Y = G^(T) X in f64 into y [c][e] (which first holds the slices' sums
+// where demb's class sum is split: proxy_bwd_split).  pa: G is [c][n] (transposed for demb's rows, direct for Y's), else [n][c].
+void proxy_bwd_products(const float* emb, const float* proxies, int n, int c, int e, bool pa, const float* pair_g, const float* q,
+                        const float* upstream, float* demb, double* y, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const double flop = 2.0 * n * c * e, gbytes = 4.0 * n * c;
+  const dim3 ge(cdiv(n, 32), cdiv(e, 32)), gy(cdiv(c, 32), cdiv(e, 32));
+  int splits, jchunk;
+  proxy_bwd_split(n, c, e, splits, jchunk);
+  {
+    EMBNET_TRACE_FLOP(splits == 1 ? "embnet::proxy_bwd_emb_kernel" : "embnet::proxy_bwd_emb_part_kernel", flop, gbytes + 4.0 * e * (c + n), stream);
+    if (splits == 1) {
+      if (pa) proxy_bwd_emb_kernel<true><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+      else proxy_bwd_emb_kernel<false><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+    } else {                                             // the slices' sums sit in Y's place until the next launch but one writes Y
+      const dim3 gz(ge.x, ge.y, splits);
+      if (pa) proxy_bwd_emb_part_kernel<true><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+      else proxy_bwd_emb_part_kernel<false><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+    }
+  }
+  if (splits > 1) {
+    EMBNET_TRACE("embnet::proxy_bwd_emb_sum_kernel", TRACE_BYTES, 8.0 * splits * n * e + 4.0 * n * e, stream);
+    proxy_bwd_emb_sum_kernel<<<cdiv((long)n * e, 256), 256, 0, s>>>(y, splits, (long)n * e, upstream, demb);
+  }
+  EMBNET_TRACE_FLOP("embnet::proxy_bwd_y_kernel", flop, gbytes + 4.0 * e * n + 8.0 * e * c, stream);
+  if (pa) proxy_bwd_y_kernel<false><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
+  else proxy_bwd_y_kernel<true><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
+}
+
+// project: dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c)
+void proxy_bwd_project(const double* y, const float* proxies, const float* q, int c, int e, const float* upstream, float* dproxies,
+                       void* stream) {
+  EMBNET_TRACE("embnet::proxy_bwd_proxies_kernel", TRACE_BYTES, 16.0 * c * e, stream);
+  proxy_bwd_proxies_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, (hipStream_t)stream>>>(y, proxies, q, c, e, upstream, dproxies);
+}
+
 inline int proxy_check_common(const char* what, bool pointers, int n, int c, int e, int kind, const void* workspace,
                               size_t workspace_bytes) {
   EMBNET_CHECK_ARG(pointers, "%s: null pointer", what);
@@ -405,34 +426,8 @@ extern "C" int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int
   const int rc = proxy_check_common(what, emb && proxies && pair_g && q && demb && dproxies && workspace, n, c, e, kind, workspace,
                                     workspace_bytes);
   if (rc != EMBNET_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
   double* y = (double*)((char*)workspace + ProxyWorkspace(n, c, e).y);
-  const bool pa = kind == EMBNET_PROXY_ANCHOR;               // G is [c][n]: transposed for demb's rows, direct for Y's
-  const double flop = 2.0 * n * c * e, gbytes = 4.0 * n * c;
-  const dim3 ge(cdiv(n, 32), cdiv(e, 32)), gy(cdiv(c, 32), cdiv(e, 32));
-  int splits, jchunk;
-  proxy_bwd_split(n, c, e, splits, jchunk);
-  {
-    EMBNET_TRACE_FLOP(splits == 1 ? "embnet::proxy_bwd_emb_kernel" : "embnet::proxy_bwd_emb_part_kernel", flop, gbytes + 4.0 * e * (c + n), stream);
-    if (splits == 1) {
-      if (pa) proxy_bwd_emb_kernel<true><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
-      else proxy_bwd_emb_kernel<false><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
-    } else {                                             // the slices' sums sit in Y's place until the next launch but one writes Y
-      const dim3 gz(ge.x, ge.y, splits);
-      if (pa) proxy_bwd_emb_part_kernel<true><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
-      else proxy_bwd_emb_part_kernel<false><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
-    }
-  }
-  if (splits > 1) {
-    EMBNET_TRACE("embnet::proxy_bwd_emb_sum_kernel", TRACE_BYTES, 8.0 * splits * n * e + 4.0 * n * e, stream);
-    proxy_bwd_emb_sum_kernel<<<cdiv((long)n * e, 256), 256, 0, s>>>(y, splits, (long)n * e, upstream, demb);
-  }
-  {
-    EMBNET_TRACE_FLOP("embnet::proxy_bwd_y_kernel", flop, gbytes + 4.0 * e * n + 8.0 * e * c, stream);
-    if (pa) proxy_bwd_y_kernel<false><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
-    else proxy_bwd_y_kernel<true><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
-  }
-  EMBNET_TRACE("embnet::proxy_bwd_proxies_kernel", TRACE_BYTES, 16.0 * c * e, stream);
-  proxy_bwd_proxies_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, s>>>(y, proxies, q, c, e, upstream, dproxies);
+  proxy_bwd_products(emb, proxies, n, c, e, kind == EMBNET_PROXY_ANCHOR, pair_g, q, upstream, demb, y, stream);
+  proxy_bwd_project(y, proxies, q, c, e, upstream, dproxies, stream);
   return check_launch(what);
 }

@@ -146,7 +146,7 @@ class ENDataGenerator:
 class TripletsDataGenerator(ENDataGenerator):
     # build-defined rules that exist only inside the fused step (train_step.TripletTrainer): accepted here so that a config
     # names them for tools/train.py, refused by the reference-structured mine_batch / __getitem__
-    STEP_ONLY_MODES = ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES) + tuple(ops.PROXY_LOSS_MODES)
+    STEP_ONLY_MODES = ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES) + tuple(ops.PROXY_LOSS_MODES) + tuple(ops.MULTI_PROXY_LOSS_MODES)
 
     def __init__(self, embedding_model, class_files_paths, class_names, n_batches=10, input_shape=None,
                  batch_size=32, augmentations=None, k_classes=5, k_samples=5, margin=0.5,

@@ -9,6 +9,8 @@ meaning), computing on the GPU through libembnet_hip.so.
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
   proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
   proxy_softmax_loss(head, scale, margin)(y_true, y_pred)   build-defined (CosFace / NormSoftmax against a ProxyHead's proxies) -> scalar
+  soft_triple_loss(head, scale, margin, gamma, tau)(y_true, y_pred)   build-defined (SoftTriple against a ProxyHead's centres) -> scalar
+  arcface_loss(head, scale, margin)(y_true, y_pred)         build-defined (sub-centre ArcFace against a ProxyHead's centres) -> scalar
   xbm_loss(memory, loss, **params)(y_true, y_pred)          build-defined (a batch against a cross-batch memory, xbm.py) -> scalar
 Inputs are torch CUDA tensors; outputs carry autograd.
 """
@@ -82,6 +84,28 @@ def proxy_softmax_loss(head, scale=64.0, margin=0.35):
 
     def loss_function(y_true, y_pred):
         return ops.proxy_softmax_loss(y_pred, head.proxies, y_true, scale, margin)[0]
+
+    return loss_function
+
+
+def soft_triple_loss(head, scale=20.0, margin=0.01, gamma=0.1, tau=0.2):
+    """Returns loss_function(y_true, y_pred) -> scalar; arguments as proxy_anchor_loss, head a proxies.ProxyHead with
+    centers_per_class centres per class.  SoftTriple (Qian et al. 2019), the centre regulariser included (build-defined, not in
+    the reference; include/embnet.h, embnet_multi_proxy_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.soft_triple_loss(y_pred, head.proxies, y_true, head.n_classes, scale, margin, gamma, tau)[0]
+
+    return loss_function
+
+
+def arcface_loss(head, scale=64.0, margin=0.5):
+    """Returns loss_function(y_true, y_pred) -> scalar; arguments as soft_triple_loss.  Sub-centre ArcFace (Deng et al. 2019 / 2020);
+    centers_per_class = 1 is ArcFace, margin = 0 NormSoftmax (build-defined, not in the reference; include/embnet.h,
+    embnet_multi_proxy_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.arcface_loss(y_pred, head.proxies, y_true, head.n_classes, scale, margin)[0]
 
     return loss_function
 

@@ -372,10 +372,95 @@ def proxy_softmax_loss(emb, proxies, labels, scale=64.0, margin=0.35, path="auto
     return out if return_weights else out[:2]
 
 
+# --------------------------------------------------------------------------- losses on several centres per class (csrc/multi_proxy_loss.hip)
+MPROXY_KINDS = {"soft_triple_loss": 1, "arcface_loss": 2}            # EMBNET_MPROXY_SOFT_TRIPLE, EMBNET_MPROXY_ARCFACE
+_MPROXY_WS = {}
+
+
+class _MultiProxyLoss(torch.autograd.Function):
+    """embnet_multi_proxy_loss_fwd / _bwd (include/embnet.h): a prep launch, the regulariser's where SoftTriple has one, and one
+    forward launch on the small path, D + sweep above it; the proxy losses' backward launches, one more with the regulariser.
+    G [n, c kc], q and the regulariser's H [c, kc, kc] stay saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, emb, centres, labels, loss, n_classes, a, b, gamma, tau, path):
+        emb, centres = _prep(emb), _prep(centres)
+        n, e = emb.shape
+        c = int(n_classes)
+        if centres.dim() != 2 or centres.shape[1] != e:
+            raise _lib.EmbnetError(f"{loss}: centres {tuple(centres.shape)} do not match embeddings of width {e}")
+        if c < 1 or centres.shape[0] % c:
+            raise _lib.EmbnetError(f"{loss}: {centres.shape[0]} centres are not a whole number per class of n_classes={n_classes}")
+        kc = centres.shape[0] // c
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+            raise _lib.EmbnetError(f"{loss}: labels must be an int32 tensor of {n} entries")
+        if path not in PROXY_PATHS:
+            raise _lib.EmbnetError(f"{loss}: path {path!r} is not one of {sorted(PROXY_PATHS)}")
+        labels = labels.contiguous()
+        kind = MPROXY_KINDS[loss]
+        lib = _lib.lib()
+        g, q = _new((n, c * kc), emb), _new((c * kc,), emb)
+        # H exists where the library launches the regulariser: it decides on tau as the float it receives
+        h = _new((c, kc, kc), emb) if kind == 1 and kc > 1 and ctypes.c_float(tau).value > 0 else None
+        counts, mean, reg = _new((3,), emb, torch.int32), _new((), emb), _new((), emb)
+        ws = _ticket_workspace(_MPROXY_WS, (emb.device.index, stream()), (n, c, kc, e), lib.embnet_multi_proxy_loss_workspace_bytes,
+                               torch.float64, emb.device)
+        check(lib.embnet_multi_proxy_loss_fwd(ptr(emb), ptr(centres), ptr(labels), n, c, kc, e, kind, f32(a), f32(b), f32(gamma),
+                                              f32(tau), PROXY_PATHS[path], ptr(g), ptr(q), ptr(h), ptr(counts), ptr(mean), ptr(reg),
+                                              ptr(ws), ws.numel() * 8, stream()))
+        ctx.shape, ctx.ws, ctx.has_h = (n, c, kc, e), ws, h is not None
+        ctx.save_for_backward(*((emb, centres, g, q) + ((h,) if h is not None else ())))
+        ctx.mark_non_differentiable(counts, g, reg)
+        ctx.set_materialize_grads(False)
+        return mean, counts, reg, g
+
+    @staticmethod
+    def backward(ctx, dmean, *_):
+        if dmean is None:
+            return (None,) * 10
+        emb, centres, g, q = ctx.saved_tensors[:4]
+        h = ctx.saved_tensors[4] if ctx.has_h else None
+        n, c, kc, e = ctx.shape
+        demb, dcentres = torch.empty_like(emb), torch.empty_like(centres)
+        check(_lib.lib().embnet_multi_proxy_loss_bwd(ptr(emb), ptr(centres), n, c, kc, e, ptr(g), ptr(q), ptr(h), ptr(_prep(dmean)),
+                                                     ptr(demb), ptr(dcentres), ptr(ctx.ws), ctx.ws.numel() * 8, stream()))
+        return (demb, dcentres) + (None,) * 8
+
+
+def soft_triple_loss(emb, centres, labels, n_classes, scale=20.0, margin=0.01, gamma=0.1, tau=0.2, path="auto", return_weights=False):
+    """SoftTriple (Qian et al., ICCV 2019) of embeddings [N,E] against learnable centres [C*kc,E] (class-major: kc consecutive rows
+    per class), labels int32 [N] as in proxy_anchor_loss.  S'_ic = sum_j softmax_j(S_icj / gamma) S_icj pools a class's kc
+    similarities, t_ic = scale (S'_ic - margin [c = y_i]), loss = mean over the labelled samples of lse_c t_ic - t_iy, plus the
+    centre regulariser reg = tau / (C kc (kc - 1)) sum_c sum_{s<t} sqrt(2 + 1e-5 - 2 cos(w_cs, w_ct)) (include/embnet.h has the
+    rounding and the stable forms).  -> (loss [autograd w.r.t. emb and centres], counts int32 [3] = labelled samples, violating
+    samples (another class pools at least as similar as the own), 0, reg) on the device, no host synchronisation; return_weights
+    adds G [N, C*kc] = dloss/dS.  path: 'auto', 'small' or 'matrix'."""
+    out = _MultiProxyLoss.apply(emb, centres, labels, "soft_triple_loss", n_classes, float(scale), float(margin), float(gamma),
+                                float(tau), path)
+    return out if return_weights else out[:3]
+
+
+def arcface_loss(emb, centres, labels, n_classes, scale=64.0, margin=0.5, path="auto", return_weights=False):
+    """Sub-centre ArcFace (Deng et al., CVPR 2019 / ECCV 2020) of embeddings [N,E] against learnable centres [C*kc,E] (class-major),
+    labels int32 [N] as in proxy_anchor_loss; kc = 1 is ArcFace, margin = 0 NormSoftmax.  S'_ic = max_j S_icj,
+    t_ic = scale cos(acos(S'_ic) + margin [c = y_i]) with the usual guard below cos(pi - margin), loss = mean over the labelled
+    samples of lse_c t_ic - t_iy (include/embnet.h has the rounding and the stable forms).  -> (loss [autograd w.r.t. emb and centres],
+    counts int32 [3] = labelled samples, violating samples, samples on the guard's branch) on the device, no host synchronisation;
+    return_weights adds G [N, C*kc] = dloss/dS.  path: 'auto', 'small' or 'matrix'."""
+    out = _MultiProxyLoss.apply(emb, centres, labels, "arcface_loss", n_classes, float(scale), float(margin), 1.0, 0.0, path)
+    return (out[0], out[1], out[3]) if return_weights else out[:2]
+
+
 # The training modes of train_step.ProxyTrainer:  mode: (function, the loss_params it takes)
 PROXY_LOSS_MODES = {
     "proxy_anchor": (proxy_anchor_loss, ("alpha", "delta")),
     "proxy_softmax": (proxy_softmax_loss, ("scale", "margin")),
+}
+# ... and its modes on several centres per class, in a table of their own: the function takes the number of classes behind the
+# labels, `centers` is no argument of it but must be the head's centers_per_class, and the violating samples are counts[1]
+MULTI_PROXY_LOSS_MODES = {
+    "soft_triple": (soft_triple_loss, ("scale", "margin", "gamma", "tau", "centers")),
+    "arcface": (arcface_loss, ("scale", "margin", "centers")),
 }
 
 

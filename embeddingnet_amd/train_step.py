@@ -409,40 +409,62 @@ class SiameseTrainer(TripletTrainer):
 
 
 class ProxyTrainer(TripletTrainer):
-    """The training step of the proxy / classification losses (ops.PROXY_LOSS_MODES: 'proxy_anchor' = Proxy-Anchor, Kim et al.
-    2020; 'proxy_softmax' = CosFace, Wang et al. 2018, with margin 0 NormSoftmax) with TripletTrainer's machinery: its own step
-    context, the weight-gradient slab sums deferred to one launch per flush, the KerasOptimizer's one-launch update — the proxies
-    are one more tensor of its single group — and, graph=True / 'auto', the whole step captured once into a HIP graph and replayed,
-    the labels copied into a static buffer beside the images.
+    """The training step of the proxy / classification losses with TripletTrainer's machinery: its own step context, the
+    weight-gradient slab sums deferred to one launch per flush, the KerasOptimizer's one-launch update — the proxies are one more
+    tensor of its single group — and, graph=True / 'auto', the whole step captured once into a HIP graph and replayed, the labels
+    copied into a static buffer beside the images.
 
-    base_model: images -> embeddings [N, E];  head: a proxies.ProxyHead(C, E) whose parameter the optimizer (and the reducer)
-    must hold;  loss_params: dict(alpha, delta), defaults 32 and 0.1, or dict(scale, margin), defaults 64 and 0.35; unknown keys
-    are refused.  step(images, labels) -> the loss of the step (detached); labels: int32 device tensor [N] of global class
-    indices in any order (outside [0, C): unlabelled).  last_pair_counts = int32 [3]: anchors with a positive term, labelled
-    samples, violating anchors (include/embnet.h); last_triplets = (None, violating anchors [1]).
+    base_model: images -> embeddings [N, E];  head: a proxies.ProxyHead whose parameter the optimizer (and the reducer) must hold;
+    loss_params: a dict out of the mode's keys below, unknown keys are refused.  step(images, labels) -> the loss of the step
+    (detached); labels: int32 device tensor [N] of global class indices in any order (outside [0, C): unlabelled).
+
+    One proxy per class (ops.PROXY_LOSS_MODES; head.centers_per_class must be 1):
+      'proxy_anchor'   Proxy-Anchor, Kim et al. 2020; dict(alpha, delta), defaults 32 and 0.1.
+      'proxy_softmax'  CosFace, Wang et al. 2018, with margin 0 NormSoftmax; dict(scale, margin), defaults 64 and 0.35.
+      last_pair_counts = int32 [3]: anchors with a positive term, labelled samples, violating anchors (include/embnet.h);
+      last_triplets = (None, violating anchors [1]);  last_reg = None.
+    Several centres per class (ops.MULTI_PROXY_LOSS_MODES; `centers`, where given, must be head.centers_per_class):
+      'soft_triple'    SoftTriple, Qian et al. 2019; dict(scale, margin, gamma, tau, centers), defaults 20, 0.01, 0.1, 0.2.
+      'arcface'        sub-centre ArcFace, Deng et al. 2019 / 2020; dict(scale, margin, centers), defaults 64, 0.5.
+      last_pair_counts = int32 [3]: labelled samples, violating samples, samples on ArcFace's guard branch (0 for SoftTriple);
+      last_triplets = (None, violating samples [1]);  last_reg = SoftTriple's centre regulariser (a device scalar, part of the
+      loss), None for ArcFace.
+
     Under data parallelism each rank's loss covers its own batch against ALL proxies; the proxies are replicated, so the mean of the
     ranks' gradients — what the reducer forms — is the gradient of the mean of the ranks' losses, for the proxies as for the
     backbone.  (Proxy-Anchor's 1/|C+| is each rank's own: the mean is over the ranks' losses, not the loss of the pooled batch.)"""
-    LOSS_PARAMS = {mode: keys for mode, (_, keys) in ops.PROXY_LOSS_MODES.items()}
+    LOSS_MODES = {**ops.PROXY_LOSS_MODES, **ops.MULTI_PROXY_LOSS_MODES}
+    LOSS_PARAMS = {mode: keys for mode, (_, keys) in LOSS_MODES.items()}
     ANY_LOSS_CAPTURES = True
 
     def __init__(self, base_model, head, optimizer, loss="proxy_anchor", loss_params=None, seed=0, reducer=None, graph=None):
-        if loss not in ops.PROXY_LOSS_MODES:
+        if loss not in self.LOSS_MODES:
             raise KeyError(loss)
         self.loss_params = self._checked_loss_params(loss, loss_params)
+        self.multi = loss in ops.MULTI_PROXY_LOSS_MODES
+        kc = self.loss_params.pop("centers", head.centers_per_class) if self.multi else 1
+        if kc != head.centers_per_class:
+            raise ValueError(f"ProxyTrainer: {loss!r} with {kc} centre(s) per class on a head of centers_per_class="
+                             f"{head.centers_per_class}")
         if not any(q is head.proxies for g in optimizer.param_groups for q in g["params"]):
             raise ValueError("ProxyTrainer: the optimizer does not hold head.proxies (build it over the backbone's parameters "
                              "and the head's)")
         self.head, self.mode = head, loss
         # one gradient per parameter and step, the proxies' included
         self._setup(base_model, optimizer, seed, reducer, graph, direct=True)
-        self.last_triplets = None
+        self.last_triplets = self.last_reg = None
 
     def loss(self, inputs):
         images, labels = inputs
         emb = self.model(images)
-        mean, counts = ops.PROXY_LOSS_MODES[self.mode][0](emb, self.head.proxies, labels, **self.loss_params)
-        count = counts[2:3]                                 # a slice view of the counts
+        fn = self.LOSS_MODES[self.mode][0]
+        if self.multi:                                      # violating samples are counts[1]; SoftTriple's loss carries its reg
+            mean, counts, *reg = fn(emb, self.head.proxies, labels, self.head.n_classes, **self.loss_params)
+            self.last_reg = reg[0] if reg else None
+            count = counts[1:2]
+        else:
+            mean, counts = fn(emb, self.head.proxies, labels, **self.loss_params)
+            count = counts[2:3]                             # a slice view of the counts
         self.last_pair_counts = counts
         self.last_triplets = (None, count)
         reg = L.regularization_loss(self.model, with_grad=not self._keras_opt)

@@ -1057,6 +1057,69 @@ int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int n, int c, 
                           const float* q, const float* upstream, float* demb, float* dproxies, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* SoftTriple (Qian et al., ICCV 2019) and sub-centre ArcFace (Deng et al., CVPR 2019; ECCV 2020): the losses of the Reality Check's
+ * table that score a batch against SEVERAL learnable centres per class (the reference has no such loss): build-defined, selected as
+ * ProxyTrainer(loss="soft_triple" | "arcface") on a ProxyHead(centers_per_class=kc).  A sample's kc similarities to one class's
+ * centres are pooled into one class similarity (ArcFace: their maximum; SoftTriple: their softmax-weighted mean), then a margin
+ * softmax runs over the c classes.  Additions only: the ABI version stays 22.
+ *   Inputs.  emb[n,e] fp32;  centres[c kc, e] fp32, class-major: row c' kc + j is centre j of class c';  labels[n] int32 with the
+ *     proxy losses' rules: a label outside [0, c) marks an UNLABELLED sample, its row of G is zero and it gets no loss and no
+ *     gradient; a label is used as an index only behind the range check (the guard in the kernels stays); no host check of labels.
+ *   Similarity, the proxy losses' form over the nb = c kc rows.  ss_r = sum_k w_rk^2 in f64, in k order;  q_r = (float)(1.0 /
+ *     sqrt(ss_r)), 0 when ss_r = 0;  D_ir = the fp32 dot product of x_i and w_r;  S_ir = fl(D_ir q_r).  Embedding rows are used as
+ *     they are.  q[c kc] is an output of the forward and an input of the backward.
+ *   Pooling, per sample i and class c' over j < kc (S_j = S_i,c'kc+j).  kc = 1: S' = S exactly, for both kinds.
+ *     EMBNET_MPROXY_ARCFACE:  S' = max_j S_j;  p_j = [j = the first j that attains the maximum] (ties go to the smaller j).
+ *     EMBNET_MPROXY_SOFT_TRIPLE:  z_j = fl(S_j / gamma),  zm = max_j z_j,  x_j = expf(fl(z_j - zm)),  den = the x_j added in j order
+ *       (fp32, >= 1: rows of norm 30 with gamma 0.1 cannot overflow),  num = the chain fma(x_j, S_j, num) in j order,
+ *       S' = fl(num / den);  p_j = fl(x_j / den);  dS'/dS_j = fl(p_j fl(1 + fl(fl(S_j - S') / gamma))).
+ *   Logits, for a labelled sample of class y.
+ *     SOFT_TRIPLE (a = lambda > 0, b = delta; the Python layers default to 20 and 0.01, gamma 0.1, tau 0.2):
+ *       t_ic' = fl(lambda fl(S'_iy - delta)) for c' = y and fl(lambda S'_ic') otherwise: with kc = 1 CosFace's rounding form.
+ *     ARCFACE (a = scale s > 0, b = margin m, 0 <= m < pi/2; the Python layers default to 64 and 0.5; gamma and tau are ignored):
+ *       t_ic' = fl(s S'_ic') off the own class and fl(s phi(S'_iy)) on it.  cm = cos m, sm = sin m, th = cos(pi - m),
+ *       mm = sin(pi - m) m are computed ONCE on the host in f64 from (double)m (pi = M_PI) and rounded to fp32.
+ *       S' > th:  r = sqrt(max(0, fl(1 - fl(S'^2)))) (a correctly rounded fp32 root),  phi = fl(fl(S' cm) - fl(r sm)); for S' >= 1 this
+ *         is S' cm: continuous, no clamp.  Otherwise (the usual non-easy-margin guard):  phi = fl(S' - mm).
+ *       phi' = fl(cm + fl(fl(S' sm) / max(r, 2^-10))) for S' > th and r > 0,  cm where r = 0,  1 for S' <= th: the floor on r is what
+ *       keeps a sample next to its centre from producing an infinite gradient.  m = 0 is NormSoftmax.
+ *   Loss.  l_i = log(sum_c' e^{t_ic' - M}) + (M - t_iy), M = max_c' t_ic' (CosFace's stable form, the logarithm's argument is >= 1);
+ *     *mean_loss = (float)((1/n_l) sum l_i + (double)*reg), the sum and the division in f64; the first term is 0 when n_l = 0.
+ *   G = pair_g, stored [n][c kc], every entry written:  with v = e^{t - M} / sum - [c' = y] in CosFace's form and k = fl(a / n_l),
+ *     G_i,c'j = fl(fl(k v) psi) dS'/dS_j: psi = phi'(S'_iy) multiplies the own class of ArcFace only, dS'/dS_j multiplies where kc > 1
+ *     (ArcFace: the whole weight on the argmax, exactly 0 on the others).
+ *   SoftTriple's regulariser (the authors' released form; kc > 1 and tau > 0, otherwise *reg = 0 and no launch; always 0 for ArcFace).
+ *     g_st = q_s q_t sum_k w_sk w_tk, the sum in f64 in k order;  coef = tau / (c kc (kc - 1));
+ *     R = coef sum_c' sum_{s<t} sqrt(max(0, 2 + 1e-5 - 2 g_st)), the pairs of a class added in (s, t) order, the classes in a fixed
+ *     order;  H_st = H_ts = -coef / sqrt(2 + 1e-5 - 2 g_st) (|g| <= (1 + 2^-24)^2: the argument stays positive), H_ss = 0.  Everything
+ *     in f64;  *reg = (float)R and reg_h[c][kc][kc] = (float)H are fp32 roundings.  reg_h is an output of the forward and an input of
+ *     the backward; it may be NULL where there is no regulariser.
+ *   Backward, g = *upstream (NULL = 1), Q_ir = q_r G_ir:  demb = g Q W;  Y_r = sum_i G_ir x_i + sum_{t != r, same class} H_rt q_t w_t
+ *     (reg_h NULL: no second term);  dcentres_r = g q_r (Y_r - q_r^2 (Y_r . w_r) w_r).  The sums run on the f64 matrix instructions
+ *     (the proxy losses' kernels with c := c kc); every output element is one fp32 rounding of an f64 expression.
+ *   Counters.  counts[3], int32, exact on the device's fp32 values:  counts[0] = labelled samples n_l;  counts[1] = violating
+ *     samples, max_{c' != y} S'_ic' >= S'_iy;  counts[2] = own-class lower-branch samples, S'_iy <= th (0 for SoftTriple).
+ * Range: 2 <= n <= 4096, 2 <= c, 1 <= kc <= 32, c kc <= 16384, 1 <= e <= 4096; a finite and > 0; SoftTriple: b finite, gamma finite
+ * and > 0, tau finite and >= 0; ArcFace: 0 <= b < pi/2; anything else is rejected before a launch.  path: 0 = auto
+ * (embnet_multi_proxy_loss_path), EMBNET_MPROXY_SMALL = a prep launch (q) and one launch in which a workgroup holds four samples and
+ * their rows of D in LDS (it needs e + c kc <= 4096 and n c kc e <= 2^25), EMBNET_MPROXY_MATRIX = prep, D through
+ * embnet_dense_dgrad_f32 into the workspace and a sweep launch in which one wave walks one sample's row of D; the regulariser is one
+ * more launch in front of either.  auto takes the small path where it fits AND c kc < 100 (from 100 centres on the matrix path
+ * measured faster at every shape tried).  No floating-point atomics, every reduction in a fixed order: bitwise reproducible; no host
+ * synchronisation or allocation, no memset node.
+ * workspace (embnet_multi_proxy_loss_workspace_bytes, either path and the backward, 16-byte aligned): zero-filled ONCE by the caller;
+ * every launch leaves its arrival counter zeroed.  The backward uses it as scratch only: it need not be the forward's. */
+enum { EMBNET_MPROXY_SOFT_TRIPLE = 1, EMBNET_MPROXY_ARCFACE = 2 };
+enum { EMBNET_MPROXY_SMALL = 1, EMBNET_MPROXY_MATRIX = 2 };
+int embnet_multi_proxy_loss_path(int n, int c, int kc, int e);            /* the path `auto` takes; 0 outside the range */
+size_t embnet_multi_proxy_loss_workspace_bytes(int n, int c, int kc, int e);      /* either path and the backward; 0 outside the range */
+int embnet_multi_proxy_loss_fwd(const float* emb, const float* centres, const int32_t* labels, int n, int c, int kc, int e, int kind,
+                                float a, float b, float gamma, float tau, int path, float* pair_g, float* q, float* reg_h,
+                                int32_t* counts, float* mean_loss, float* reg, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_multi_proxy_loss_bwd(const float* emb, const float* centres, int n, int c, int kc, int e, const float* pair_g,
+                                const float* q, const float* reg_h, const float* upstream, float* demb, float* dcentres,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Cross-Batch Memory (Wang et al., CVPR 2020, "XBM"): the detached embeddings of the last m samples kept in a ring on the device,
  * and the pair losses of a batch against that ring (the reference has no memory): build-defined, selected as
  * XbmTrainer(memory=..., xbm_loss="contrastive" | "multi_similarity").  Additions only: the ABI version stays 22.

@@ -8,7 +8,8 @@ semihard) the forward + backward of the loss path is run both ways on the same c
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
 denominator beside ops.multi_similarity_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
-xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time()):
+xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time(), the mproxy_* cases (SoftTriple and sub-centre
+ArcFace on several centres per class; `--only mproxy_`) at mproxy_cases()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
   fused:    ops.fused_triplet_loss (one forward launch) -> backward
 Reported per variant: library launches per pass and the sum of their device times (embnet_trace_*: HIP events on the
@@ -148,6 +149,87 @@ def proxy_cases(a, dev, out):
                    hip=trace, device_us_median=med,
                    device_ratio_vs_torch_composed=round(med["hip"] / med["torch_composed"], 3),
                    device_ratio_vs_multi_similarity=round(med["hip"] / med["multi_similarity"], 3))
+        out.append(row)
+        print(json.dumps(row), flush=True)
+
+
+# the losses on several centres per class: (name, p, k, e, classes, centres per class, mode), at the proxy cases' shapes with 1, 3 and
+# 10 centres (4096 classes with 10 centres are past the 16384 rows of the range)
+MPROXY_CASES = [(f"mproxy_{cfg}_{mode}_kc{kc}", p, k, e, 100, kc, mode) for mode in ("soft_triple", "arcface") for kc in (1, 3, 10)
+                for cfg, p, k, e in (("c1", 8, 4, 256), ("c2", 32, 4, 256), ("c5", 64, 4, 512))] + \
+               [(f"mproxy_c2_{mode}_c4096_kc3", 32, 4, 256, 4096, 3, mode) for mode in ("soft_triple", "arcface")]
+
+
+def torch_mproxy_loss(mode, x, w, labels, c, kc):
+    """The same loss composed from torch ops (matmul, softmax / max, logsumexp, autograd) at the layers' default parameters: the
+    yardstick of the mproxy cases."""
+    wn = w * torch.rsqrt((w * w).sum(1, keepdim=True))
+    s = (x @ wn.T).reshape(x.shape[0], c, kc)
+    pos = labels[:, None] == torch.arange(c, device=x.device)[None, :]
+    if mode == "soft_triple":
+        sp = (torch.softmax(s / 0.1, 2) * s).sum(2)
+        t = 20.0 * (sp - 0.01 * pos)
+        if kc == 1:                                         # no pairs of centres: no regulariser
+            return (torch.logsumexp(t, 1) - (t * pos).sum(1)).mean()
+        gram = wn.reshape(c, kc, -1) @ wn.reshape(c, kc, -1).transpose(1, 2)
+        iu = torch.triu_indices(kc, kc, 1, device=x.device)                # (no boolean gather: the leg is captured in a graph)
+        reg = 0.2 / (c * kc * (kc - 1)) * torch.sqrt(2.0 + 1e-5 - 2.0 * gram[:, iu[0], iu[1]]).sum()
+    else:
+        sp = s.max(2).values
+        m, th = 0.5, -0.8775825619
+        phi = torch.where(sp > th, sp * 0.8775825619 - torch.sqrt(torch.clamp(1.0 - sp * sp, min=1e-12)) * 0.4794255386, sp - 0.4794255386 * m)
+        t = 64.0 * torch.where(pos, phi, sp)
+        reg = 0.0
+    return (torch.logsumexp(t, 1) - (t * pos).sum(1)).mean() + reg
+
+
+def mproxy_cases(a, dev, out):
+    """ops.soft_triple_loss / ops.arcface_loss (forward + backward w.r.t. embeddings and centres, default parameters) beside the same
+    loss composed from torch ops and, where the shape fits both, beside the forward path that `auto` does not take, in one process,
+    alternating; measured as proxy_cases() measures.  Only with `--only mproxy...` or without `--only`."""
+    for name, p, k, e, c, kc, mode in MPROXY_CASES:
+        if a.only and not (a.only.startswith("mproxy") and a.only in name):
+            continue
+        n = p * k
+        g = torch.Generator(device=dev).manual_seed(7)
+        cen = torch.rand((p, e), device=dev, generator=g)
+        x = (cen.repeat_interleave(k, 0) + 0.25 * torch.randn((n, e), device=dev, generator=g)).abs()
+        x = (x / x.norm(dim=1, keepdim=True)).requires_grad_(True)
+        w = (torch.randn((c * kc, e), device=dev, generator=g) * (2.0 / (c * kc)) ** 0.5).requires_grad_(True)
+        labels = torch.randperm(c, device=dev, generator=g)[:p].repeat_interleave(k).to(torch.int32)
+        fn = ops.MULTI_PROXY_LOSS_MODES[mode][0]
+        lab64 = labels.long()
+
+        def hip():
+            x.grad = w.grad = None
+            fn(x, w, labels, c)[0].backward()
+
+        def composed():
+            x.grad = w.grad = None
+            torch_mproxy_loss(mode, x, w, lab64, c, kc).backward()
+
+        def hip_fwd():
+            fn(x, w, labels, c)
+
+        def composed_fwd():
+            torch_mproxy_loss(mode, x, w, lab64, c, kc)
+
+        def hip_other():
+            x.grad = w.grad = None
+            fn(x, w, labels, c, path=other)[0].backward()
+
+        def hip_other_fwd():
+            fn(x, w, labels, c, path=other)
+
+        path = {1: "small", 2: "matrix"}[_lib.lib().embnet_multi_proxy_loss_path(n, c, kc, e)]
+        other = "small" if path == "matrix" else "matrix"
+        legs = dict(hip=hip, torch_composed=composed, hip_forward=hip_fwd, torch_composed_forward=composed_fwd)
+        if other == "matrix" or (e + c * kc <= 4096 and n * c * kc * e <= 2 ** 25):          # the path `auto` does not take, where the shape allows it: the crossover's evidence
+            legs.update({f"hip_{other}": hip_other, f"hip_{other}_forward": hip_other_fwd})
+        trace = measure(hip, a.iters)
+        med = graph_rounds(legs, rounds=15, reps=20)
+        row = dict(config=name, N=n, E=e, C=c, KC=kc, mining=mode, path=path, hip=trace, device_us_median=med,
+                   device_ratio_vs_torch_composed=round(med["hip"] / med["torch_composed"], 3))
         out.append(row)
         print(json.dumps(row), flush=True)
 
@@ -399,6 +481,7 @@ def main():
         out.append(row)
         print(json.dumps(row), flush=True)
     proxy_cases(a, dev, out)
+    mproxy_cases(a, dev, out)
     xbm_cases(a, dev, out)
     if a.only and a.only in "proxy_step_time":
         step_times(out)

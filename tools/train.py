@@ -11,6 +11,7 @@ EarlyStopping(patience 10) (:84-86), best-only checkpoints weights/epoch_XXX.npz
 Multi-GPU: launch with torchrun; classes are sharded per rank and gradients all-reduced over RCCL.
 GENERATOR.negatives_selection_mode 'proxy_anchor' / 'proxy_softmax' train the backbone together with one learnable proxy per
 class (train_step.ProxyTrainer on the feeder's labelled batches); the proxies are checkpointed as proxies/epoch_XXX.npz.
+'soft_triple' / 'arcface' do the same with GENERATOR.proxy_loss.centers learnable centres per class (SoftTriple, sub-centre ArcFace).
 GENERATOR.xbm: {size, weight, start_iteration, loss, <that loss's parameters>} adds a cross-batch memory (train_step.XbmTrainer,
 embeddingnet_amd/xbm.py) to any triplet-mode negatives_selection_mode but the proxy ones: the loss of the batch against the detached
 embeddings of the last `size` samples, `weight` times, from step `start_iteration` on; `xbm_filled` and the kept pairs are logged
@@ -149,19 +150,28 @@ LOSS_CONFIGS = {
     'supcon_loss': {'supcon': dict(temperature='positive number', denominator=('all', 'negatives'))},
     'proxy_loss': {'proxy_anchor': dict(alpha='positive', delta='number'), 'proxy_softmax': dict(scale='positive', margin='number')},
 }
+# GENERATOR.proxy_loss with the modes on several centres per class (ops.MULTI_PROXY_LOSS_MODES): the same validator on a table of
+# their own (proxy_loss_config), so the messages about the key keep naming the two modes they always named
+MULTI_PROXY_LOSS_CONFIGS = {
+    'soft_triple': dict(scale='positive', margin='number', gamma='positive', tau='number', centers='positive'),
+    'arcface': dict(scale='positive', margin='number', centers='positive'),
+}
+MULTI_PROXY_DEFAULT_CENTERS = {'soft_triple': 10, 'arcface': 1}
 MS_LOSS_KEYS = tuple(LOSS_CONFIGS['ms_loss']['multi_similarity'])
 SUPCON_LOSS_KEYS = tuple(LOSS_CONFIGS['supcon_loss']['supcon'])
 PROXY_LOSS_KEYS = {mode: tuple(checks) for mode, checks in LOSS_CONFIGS['proxy_loss'].items()}
 
 
-def loss_config(name, cfg):
-    """GENERATOR.<name> (a key of LOSS_CONFIGS; optional): any subset of the parameters of the mode's loss -> the trainer's
+def loss_config(name, cfg, table=None):
+    """GENERATOR.<name> (a key of LOSS_CONFIGS, or with `table` that table's; optional): any subset of the parameters of the mode's loss -> the trainer's
     loss_params (None without the key).  Only the key's own modes of a triplet-mode model read it: given with anything else, or
     with other parameters or a value that fails its check, it is a ValueError before training starts."""
     value = cfg['generator'].get(name)
     if value is None:
         return None
-    table, mode, siamese = LOSS_CONFIGS[name], cfg['generator'].get('negatives_selection_mode'), cfg['model']['mode'] == 'siamese'
+    table = LOSS_CONFIGS[name] if table is None else table
+    mode = cfg['generator'].get('negatives_selection_mode')
+    siamese = cfg['model']['mode'] == 'siamese'
     if siamese or mode not in table:
         raise ValueError(f"GENERATOR.{name} sets the parameters of negatives_selection_mode {' or '.join(map(repr, table))}; "
                          f"this config trains with {'the Siamese contrastive loss' if siamese else repr(mode)}: "
@@ -199,7 +209,24 @@ def supcon_loss_config(cfg):
 
 
 def proxy_loss_config(cfg):
-    return loss_config('proxy_loss', cfg)
+    """GENERATOR.proxy_loss for the proxy modes; with 'soft_triple' / 'arcface' checked against MULTI_PROXY_LOSS_CONFIGS, and then:
+    centers a whole number in [1, 32], tau not negative, ArcFace's margin in [0, pi/2)."""
+    mode = cfg['generator'].get('negatives_selection_mode')
+    if mode not in MULTI_PROXY_LOSS_CONFIGS or cfg['model']['mode'] == 'siamese':
+        return loss_config('proxy_loss', cfg)
+    out = loss_config('proxy_loss', cfg, MULTI_PROXY_LOSS_CONFIGS)
+    if out is None:
+        return None
+    value = cfg['generator']['proxy_loss']
+    if 'centers' in out and (out['centers'] != int(out['centers']) or out['centers'] > 32):
+        raise ValueError(f"GENERATOR.proxy_loss: centers, the centres per class, must be a whole number in [1, 32] (got {value!r})")
+    if out.get('tau', 0.0) < 0:
+        raise ValueError(f"GENERATOR.proxy_loss: tau must not be negative (got {value!r})")
+    if mode == 'arcface' and not 0 <= out.get('margin', 0.5) < np.pi / 2:
+        raise ValueError(f"GENERATOR.proxy_loss: margin must lie in [0, pi/2) for 'arcface' (got {value!r})")
+    if 'centers' in out:
+        out['centers'] = int(out['centers'])
+    return out
 
 
 # GENERATOR.xbm (optional): the memory's own keys, and per memory loss (ops.XBM_LOSS_MODES) that loss's parameters.
@@ -240,12 +267,17 @@ def _proxies_path(weights_path):
 
 def save_proxies(path, head, class_names):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    np.savez(path, proxies=head.proxies.detach().cpu().numpy(), class_names=np.asarray(list(class_names), dtype=str))
+    np.savez(path, proxies=head.proxies.detach().cpu().numpy(), class_names=np.asarray(list(class_names), dtype=str),
+             centers_per_class=np.int64(head.centers_per_class))
 
 
 def load_proxies(path, head, class_names):
-    """The proxies of a checkpoint into `head`; a file for other classes (or another order of them) is refused."""
+    """The proxies of a checkpoint into `head`; a file for other classes (or another order of them), or with another number of
+    centres per class (a file without the key has one), is refused."""
     d = np.load(path, allow_pickle=False)
+    kc = int(d['centers_per_class']) if 'centers_per_class' in d.files else 1
+    if kc != head.centers_per_class:
+        raise ValueError(f"{path}: its centers_per_class is {kc}, this run's is {head.centers_per_class}")
     if [str(v) for v in d['class_names']] != [str(v) for v in class_names]:
         raise ValueError(f"{path}: its class_names differ from the dataset's: the proxies belong to other classes")
     if tuple(d['proxies'].shape) != tuple(head.proxies.shape):
@@ -328,7 +360,8 @@ def main():
     xbm = xbm_config(cfg)                              # and GENERATOR.xbm (with a proxy mode, in Siamese mode, a memory below a batch)
     # each is refused with another's mode: at most one is set
     loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss) if v is not None), None)
-    proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS
+    multi_proxy_mode = cfg['generator'].get('negatives_selection_mode') in MULTI_PROXY_LOSS_CONFIGS
+    proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS or multi_proxy_mode
     if proxy_mode and cfg['model']['mode'] == 'siamese':
         raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
@@ -383,7 +416,11 @@ def main():
     if proxy_mode:
         # one learnable proxy per class of the WHOLE dataset, replicated on every rank (seeded on the CPU: identical everywhere)
         from embeddingnet_amd.proxies import ProxyHead
-        head = ProxyHead(len(data_loader.class_names), p_model['encodings_len'], seed=0).to(dev)
+        centers = 1
+        if multi_proxy_mode:                          # ... or `centers` of them (the trainer checks the number against the head's)
+            loss_params = dict(loss_params or {})
+            centers = loss_params.setdefault('centers', MULTI_PROXY_DEFAULT_CENTERS[p_gen['negatives_selection_mode']])
+        head = ProxyHead(len(data_loader.class_names), p_model['encodings_len'], seed=0, centers_per_class=centers).to(dev)
         if args.resume_from is not None and os.path.exists(_proxies_path(args.resume_from)):
             load_proxies(_proxies_path(args.resume_from), head, data_loader.class_names)
             print(f'resumed proxies from {_proxies_path(args.resume_from)}')
@@ -466,7 +503,7 @@ def main():
             for g in opt.param_groups:
                 g['lr'] = lr
             trainable.train()
-            losses, xbm_counts = [], []
+            losses, xbm_counts, violating = [], [], []
             for _ in range(len(train_gen)):
                 if siamese:
                     (x1, x2), y = train_gen[0]
@@ -476,6 +513,8 @@ def main():
                     if proxy_mode or xbm is not None:
                         xb, yb = feeder.next_labelled()
                         losses.append(trainer.step(xb, yb))
+                        if multi_proxy_mode:
+                            violating.append(trainer.last_triplets[1].clone())      # (a replayed step's counts are one buffer)
                         if xbm is not None and trainer.last_xbm_counts is not None:
                             xbm_counts.append(trainer.last_xbm_counts.clone())      # (a replayed step's counts are one buffer)
                     else:
@@ -487,6 +526,10 @@ def main():
             msg = f'Epoch {epoch + 1}/{n_epochs} - lr {lr:.3g} - loss {epoch_loss:.4f}'
             if n_images:                                  # (the .item() above waited for the epoch's last step)
                 msg += f' - {n_images * world / (time.perf_counter() - t_epoch):.0f} images/s'
+            if violating:                                 # this rank's: violating samples per step, the last step's regulariser
+                msg += f' - violating {torch.stack(violating).float().mean().item():.1f}'
+                if trainer.last_reg is not None:
+                    msg += f' - reg {trainer.last_reg.item():.4f}'
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
