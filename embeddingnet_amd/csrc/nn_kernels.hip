@@ -283,6 +283,25 @@ __global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict_
   });
 }
 
+// Channel quad q of pixel p of a c-channel tensor (c % 4 != 0) read as if it had been widened to 4 * ceil(c / 4) channels
+// (pad_channels_kernel): the pad lanes are 0.  c == 3 is the image batch in front of the zoo ResNet stem.
+__device__ __forceinline__ float4 ld_pad4(const float* __restrict__ x, long p, int c, int q) {
+  const float* s = x + p * c + 4 * q;
+  if (c == 3) return make_float4(s[0], s[1], s[2], 0.f);
+  const int live = c - 4 * q;                             // >= 1
+  return make_float4(s[0], live > 1 ? s[1] : 0.f, live > 2 ? s[2] : 0.f, live > 3 ? s[3] : 0.f);
+}
+// bn_stats4_kernel over the WIDENED tensor without the widened copy: the geometry, the thread -> pixel map and the accumulation
+// are those of bn_stats4_kernel on [m, 4 * c4], so the partials are the same bits (a pad lane sums zeros).
+__global__ __launch_bounds__(256) void bn_stats_pad4_kernel(const float* __restrict__ x, long m, int c, int c4, ColGeom g,
+                                                            float* __restrict__ partial) {
+  col_reduce2_v4(m, c4, g, partial, [&](long r, int q, float4& a, float4& b) {
+    const float4 v = ld_pad4(x, r, c, q);
+    add4(a, v);
+    b.x = fmaf(v.x, v.x, b.x); b.y = fmaf(v.y, v.y, b.y); b.z = fmaf(v.z, v.z, b.z); b.w = fmaf(v.w, v.w, b.w);
+  });
+}
+
 // pmax [blocks][c]: the block's max |dz| per channel — what bounds the dx of the apply pass before it runs (dx_channel_bound)
 __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                              long m, int c4, ColGeom g, const float* __restrict__ mean,
@@ -668,6 +687,34 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
   }
 }
 
+// y [pixels, 4 * c4] = act(scale * widened(x) + shift) for a c-channel x (c % 4 != 0): pad_channels_kernel and the four-channel
+// branch of affine_act_kernel in one pass (4 c + 16 c4 B/pixel instead of 4 c + 48 c4) — its arithmetic per element, the range of
+// y from the bounds likewise; a pad lane is act(fma(0, scale, shift)).
+__global__ __launch_bounds__(256) void pad_affine_act_kernel(const float* __restrict__ x, long total4, int c, int c4,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             int act, float* __restrict__ y, const float* __restrict__ bound,
+                                                             uint32_t* __restrict__ range_out) {
+  const long stride = (long)gridDim.x * 256;
+  if (range_out && blockIdx.x == 0) {
+    const float b = tensor_bound(bound, 4 * c4);
+    if (threadIdx.x == 0) *range_out = __float_as_uint(b);
+  }
+  const bool fixed = stride % c4 == 0;
+  float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
+  if (fixed) {
+    const int q = (int)(((long)blockIdx.x * 256 + threadIdx.x) % c4);
+    sc = ld4(scale, q); sh = ld4(shift, q);
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+    const long p = c4 == 1 ? i : i / c4;
+    const int q = (int)(i - p * c4);
+    if (!fixed) { sc = ld4(scale, q); sh = ld4(shift, q); }
+    float4 o = affine4(ld_pad4(x, p, c, q), sc, sh);
+    if (act) o = act_apply4(act, o);
+    st4(y, i, o);
+  }
+}
+
 // backward reductions: dbeta = sum dz, dgamma = sum dz*xhat, dz = dy * [x*scale+shift > 0]   (8 B/elem)
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             long m, int c, ColGeom g, const float* __restrict__ mean,
@@ -991,22 +1038,10 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_reduce4_kernel(
   });
 }
 
-// dx over the input pixels: da rebuilt from the covering windows, then the BN-backward formula
-__global__ __launch_bounds__(256) void pool_bn_bwd_apply4_kernel(
-    const float* __restrict__ dy, const uint8_t* __restrict__ argmax, const float* __restrict__ x, int n, int h, int w,
-    int c4, int k, int stride, int pad, int oh, int ow, float inv_m, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ dbeta, const float* __restrict__ dgamma, int act, int training, float* __restrict__ dx,
-    uint32_t* __restrict__ range_slot) {
-  const long total = (long)n * h * w * c4;
-  const long i0 = (long)blockIdx.x * 256 + threadIdx.x;
-  const bool valid = i0 < total;                         // (no early return: every lane takes part in the range's wave maximum)
-  const long i = valid ? i0 : total - 1;
-  const int q = (int)(i % c4);
-  long t = i / c4;
-  const int iw = (int)(t % w); t /= w;
-  const int ih = (int)(t % h);
-  const int b = (int)(t / h);
+// dx of input pixel (b, ih, iw), channel quad q (element i of x): da rebuilt from the covering windows, then the BN-backward formula
+__device__ __forceinline__ float4 pool_bn_dx4(const float* __restrict__ dy, const uint8_t* __restrict__ argmax, const float* __restrict__ x,
+                                              long i, int b, int ih, int iw, int q, int c4, int k, int stride, int pad, int oh, int ow,
+                                              const BnConsts& kc, float inv_m, int act, int training) {
   const float4 xv = ld4(x, i);
   float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
   if (k <= 2 * stride) {
@@ -1030,10 +1065,63 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply4_kernel(
   } else {
     g = pool_taps_grad4(dy, argmax, b, ih, iw, q, c4, k, stride, pad, oh, ow);
   }
+  return bn_dx4(act_grad4(act, xv, kc.sc, kc.sh, g), xv, kc, inv_m, training);
+}
+
+// dx over the input pixels, one thread per channel quad of the tensor
+__global__ __launch_bounds__(256) void pool_bn_bwd_apply4_kernel(
+    const float* __restrict__ dy, const uint8_t* __restrict__ argmax, const float* __restrict__ x, int n, int h, int w,
+    int c4, int k, int stride, int pad, int oh, int ow, float inv_m, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ dbeta, const float* __restrict__ dgamma, int act, int training, float* __restrict__ dx,
+    uint32_t* __restrict__ range_slot) {
+  const long total = (long)n * h * w * c4;
+  const long i0 = (long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i0 < total;                         // (no early return: every lane takes part in the range's wave maximum)
+  const long i = valid ? i0 : total - 1;
+  const int q = (int)(i % c4);
+  long t = i / c4;
+  const int iw = (int)(t % w); t /= w;
+  const int ih = (int)(t % h);
+  const int b = (int)(t / h);
   const BnConsts kc = bn_consts(q, scale, shift, mean, rstd, dbeta, dgamma, training);
-  const float4 o = bn_dx4(act_grad4(act, xv, kc.sc, kc.sh, g), xv, kc, inv_m, training);
+  const float4 o = pool_bn_dx4(dy, argmax, x, i, b, ih, iw, q, c4, k, stride, pad, oh, ow, kc, inv_m, act, training);
   if (valid) st4(dx, i, o);
   if (range_slot) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, valid ? amax4(0.f, o) : 0.f);
+}
+
+// The same dx on row bands: a workgroup owns one 256-quad segment of the input row (16 pixels x 16 quads on the stem) over `band`
+// consecutive rows of the [n * h] row sequence and walks down it, so the pooled dy / argmax rows that vertically neighbouring
+// input rows share (each pooled row serves k input rows) are re-read by the CU that fetched them.  Per element the arithmetic is
+// pool_bn_dx4 as above; the range partial is the maximum over the workgroup's band (the slot's word 0 is a maximum of maxima).
+__global__ __launch_bounds__(256) void pool_bn_bwd_apply_band4_kernel(
+    const float* __restrict__ dy, const uint8_t* __restrict__ argmax, const float* __restrict__ x, long rows, int h, int w,
+    int c4, int k, int stride, int pad, int oh, int ow, int segs, int band, float inv_m, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ dbeta, const float* __restrict__ dgamma, int act, int training, float* __restrict__ dx,
+    uint32_t* __restrict__ range_slot) {
+  const int seg = (int)(blockIdx.x % (unsigned)segs);
+  const long r0 = (long)(blockIdx.x / (unsigned)segs) * band;
+  const long r1 = min(r0 + band, rows);                  // (a ragged last band)
+  const int w4 = w * c4, e = seg * 256 + (int)threadIdx.x;   // e: this thread's quad of the row
+  float amax = 0.f;
+  if (e < w4) {
+    const int q = e % c4, iw = e / c4;
+    const BnConsts kc = bn_consts(q, scale, shift, mean, rstd, dbeta, dgamma, training);
+    int b = (int)(r0 / h), ih = (int)(r0 - (long)b * h);
+    for (long r = r0; r < r1; ++r) {
+      const long i = r * w4 + e;
+      // (1 / m made opaque per row: with a loop-invariant 1 / m the compiler hoists dbeta / m and dgamma / m out of the loop as
+      // rounded products, where the one-row kernel contracts them into fmas — dx would differ in the last bit)
+      float im = inv_m;
+      asm volatile("" : "+v"(im));
+      const float4 o = pool_bn_dx4(dy, argmax, x, i, b, ih, iw, q, c4, k, stride, pad, oh, ow, kc, im, act, training);
+      st4(dx, i, o);
+      amax = amax4(amax, o);
+      if (++ih == h) { ih = 0; ++b; }
+    }
+  }
+  if (range_slot) range_emit_block(range_slot + 1 + blockIdx.x % RANGE_PARTIALS, amax);
 }
 
 // y[n,c] = mean over hw.  Workgroup = one sample x 64 channels (16 channel-quad lanes x 16 pixel lanes).
@@ -1478,6 +1566,27 @@ extern "C" int embnet_bn_train_fwd_ex(const float* x, long m, int c, const float
                            partial_in, partial_rows, workspace, workspace_bytes, y_bound, y_range, stream, xhat_bound);
 }
 
+// BatchNorm (training) of a c-channel tensor (c % 4 != 0) whose OUTPUT has cp = 4 * ceil(c / 4) channels, in two passes over x:
+// what embnet_pad_channels + embnet_bn_train_fwd_ex compute in four (the widened copy written, read for the statistics, read and
+// written by the apply pass), bit for bit.  Every per-channel array has cp entries.
+extern "C" int embnet_bn_train_fwd_pad_ex(const float* x, long m, int c, int cp, const float* gamma, const float* beta, float eps,
+                                          float momentum, int act, float* y, float* save_mean, float* save_rstd, float* scale,
+                                          float* shift, float* moving_mean, float* moving_var, void* workspace,
+                                          size_t workspace_bytes, float* y_bound, uint32_t* y_range, float* xhat_bound, void* stream) {
+  EMBNET_CHECK_ARG(x && y && save_mean && save_rstd && scale && shift && workspace, "bn_train_fwd_pad: null pointer");
+  EMBNET_CHECK_ARG(m > 0 && c > 0 && (c & 3) && cp == (c + 3) / 4 * 4, "bn_train_fwd_pad: m=%ld c=%d cp=%d", m, c, cp);
+  EMBNET_CHECK_ARG(!y_range || (y_bound && !(reinterpret_cast<uintptr_t>(y_range) & 3)),
+                   "bn_train_fwd_pad: y_range (the range slot of y) goes with y_bound");
+  if (const int e = bn_workspace_check("bn_train_fwd_pad", workspace_bytes, m, cp)) return e;
+  const int c4 = cp / 4;
+  const ColGeom g4 = col_geom(m, c4);
+  { EMBNET_TRACE("embnet::bn_stats_pad4_kernel", TRACE_BYTES, 4.0 * m * c, stream); bn_stats_pad4_kernel<<<g4.blocks, 256, 0, S(stream)>>>(x, m, c, c4, g4, (float*)workspace); }
+  { EMBNET_TRACE("embnet::bn_finalize_kernel", TRACE_BYTES, 8.0 * g4.blocks * cp, stream); bn_finalize_kernel<<<cp, 256, 0, S(stream)>>>((const float*)workspace, g4.blocks, m, cp, gamma, beta, eps, momentum, save_mean,
+                                                          save_rstd, scale, shift, moving_mean, moving_var, 0, y_bound, xhat_bound); }
+  { EMBNET_TRACE("embnet::pad_affine_act_kernel", TRACE_BYTES, 4.0 * m * (c + cp), stream); pad_affine_act_kernel<<<ew_blocks_c4(m * c4, c4), 256, 0, S(stream)>>>(x, m * c4, c, c4, scale, shift, act, y, y_bound, y_range); }
+  return check_launch("bn_train_fwd_pad");
+}
+
 extern "C" int embnet_bn_infer_fwd(const float* x, long m, int c, const float* gamma, const float* beta,
                                    const float* moving_mean, const float* moving_var, float eps, int relu, float* y,
                                    float* scale, float* shift, void* stream) {
@@ -1913,7 +2022,7 @@ static int bn_act_maxpool_bwd_impl(const float* dy, const uint8_t* argmax, const
                                    int k, int stride, int pad, int oh, int ow, const float* save_mean,
                                    const float* save_rstd, const float* scale, const float* shift, int act,
                                    int training, const float* xwin, float* dx, float* dgamma, float* dbeta,
-                                   void* workspace, size_t workspace_bytes, uint32_t* emit, void* stream) {
+                                   void* workspace, size_t workspace_bytes, uint32_t* emit, void* stream, int band_rows = 0) {
   EMBNET_CHECK_ARG(!emit || (save_mean && save_rstd && !(reinterpret_cast<uintptr_t>(emit) & 3)),
                    "bn_act_maxpool_bwd: a range of dx was requested without saved statistics (or the slot is not 4-byte aligned)");
   EMBNET_CHECK_ARG(dy && argmax && x && scale && shift && dx && dgamma && dbeta && workspace, "bn_act_maxpool_bwd: null pointer");
@@ -1931,6 +2040,15 @@ static int bn_act_maxpool_bwd_impl(const float* dy, const uint8_t* argmax, const
     zero2_kernel<<<cdiv(c, 256), 256, 0, S(stream)>>>(dbeta, dgamma, c);
   }
   const long total = (long)n * h * w * (c / 4);
+  if (band_rows > 0) {                      // row bands (see the kernel): segs 256-quad segments per input row x bands of band_rows rows
+    const long rows = (long)n * h, w4 = (long)w * (c / 4), segs = cdiv(w4, 256), bands = cdiv(rows, band_rows);
+    EMBNET_CHECK_ARG(w4 < (1l << 31) - 256 && segs * bands < (1l << 31), "bn_act_maxpool_bwd: %ld x %ld workgroups", segs, bands);
+    EMBNET_TRACE("embnet::pool_bn_bwd_apply_band4_kernel", TRACE_BYTES, 32.0 * total + 5.0 * mp * c, stream);
+    pool_bn_bwd_apply_band4_kernel<<<(unsigned)(segs * bands), 256, 0, S(stream)>>>(dy, argmax, x, rows, h, w, c / 4, k, stride, pad, oh, ow,
+                                                                                   (int)segs, band_rows, 1.f / (float)((long)n * h * w),
+                                                                                   save_mean, save_rstd, scale, shift, dbeta, dgamma, act,
+                                                                                   training, dx, emit);
+  } else
   { EMBNET_TRACE("embnet::pool_bn_bwd_apply4_kernel", TRACE_BYTES, 32.0 * total + 5.0 * mp * c, stream); pool_bn_bwd_apply4_kernel<<<cdiv(total, 256), 256, 0, S(stream)>>>(dy, argmax, x, n, h, w, c / 4, k, stride, pad, oh, ow,
                                                                     1.f / (float)((long)n * h * w), save_mean, save_rstd,
                                                                     scale, shift, dbeta, dgamma, act, training, dx, emit); }
@@ -1953,6 +2071,17 @@ extern "C" int embnet_bn_act_maxpool_bwd_ex(const float* dy, const uint8_t* argm
   (void)take_emit_slot();
   return bn_act_maxpool_bwd_impl(dy, argmax, x, n, h, w, c, k, stride, pad, oh, ow, save_mean, save_rstd, scale, shift, act, training,
                                  xwin, dx, dgamma, dbeta, workspace, workspace_bytes, dx_range, stream);
+}
+
+extern "C" int embnet_bn_act_maxpool_bwd_band_ex(const float* dy, const uint8_t* argmax, const float* x, int n, int h, int w, int c,
+                                                 int k, int stride, int pad, int oh, int ow, const float* save_mean,
+                                                 const float* save_rstd, const float* scale, const float* shift, int act,
+                                                 int training, const float* xwin, float* dx, float* dgamma, float* dbeta,
+                                                 void* workspace, size_t workspace_bytes, uint32_t* dx_range, int band_rows, void* stream) {
+  (void)take_emit_slot();
+  EMBNET_CHECK_ARG(band_rows >= 0, "bn_act_maxpool_bwd: band_rows=%d", band_rows);
+  return bn_act_maxpool_bwd_impl(dy, argmax, x, n, h, w, c, k, stride, pad, oh, ow, save_mean, save_rstd, scale, shift, act, training,
+                                 xwin, dx, dgamma, dbeta, workspace, workspace_bytes, dx_range, stream, band_rows);
 }
 
 extern "C" int embnet_gap_fwd(const float* x, int n, int hw, int c, float* y, void* stream) {

@@ -1887,8 +1887,6 @@ class _InputBNConvFn(torch.autograd.Function):
         m = n * h * wd
         cp = (c + 3) // 4 * 4                      # widen 3 -> 4 channels: 16-byte gathers in the stem conv
         if cp != c:
-            xp = torch.empty((n, h, wd, cp), device=x.device, dtype=torch.float32)
-            check(lib.embnet_pad_channels(ptr(x), m, c, cp, ptr(xp), stream()))
             # persistent padded copies of the three BN vectors and of the kernel (zero taps / zero offset for the pad
             # channel), refreshed by plain copies: no cat / pad / fill launches per step
             # (kept on the kernel Parameter object, like its planes: an address-keyed cache would hand a new model the pads
@@ -1905,10 +1903,18 @@ class _InputBNConvFn(torch.autograd.Function):
             beta_p[:c].copy_(beta.detach()); mm_p[:c].copy_(moving_mean); mv_p[:c].copy_(moving_var)
             w_p[:, :, :c, :].copy_(w.detach())
         else:
-            xp, beta_p, mm_p, mv_p, w_p = x, beta, moving_mean, moving_var, w
-        a = torch.empty_like(xp)
+            beta_p, mm_p, mv_p, w_p = beta, moving_mean, moving_var, w
+        a = torch.empty((n, h, wd, cp), device=x.device, dtype=torch.float32)
         ranged = w_range is not None and cp % 4 == 0
-        stats, st = _bn_stats(xp, m, cp, 6 if ranged else 4, None, beta_p, eps, momentum, 0, True, mm_p, mv_p, None, a, ranged)
+        if cp != c:                                # two passes over x (statistics, then a written widened): no padded copy of x
+            stats = torch.empty((6 if ranged else 4, cp), device=x.device, dtype=torch.float32)
+            st = _StatsRows(stats)
+            ws = workspace(lib.embnet_bn_workspace_bytes(m, cp), x.device)
+            check(lib.embnet_bn_train_fwd_pad_ex(ptr(x), m, c, cp, None, ptr(beta_p), eps, momentum, 0, ptr(a), st.mean, st.rstd,
+                                                 st.scale, st.shift, ptr(mm_p), ptr(mv_p), ptr(ws), ws.numel() * 4, st.bound,
+                                                 st.range if ranged else None, st.xhat, stream()))
+        else:
+            stats, st = _bn_stats(x, m, cp, 6 if ranged else 4, None, beta_p, eps, momentum, 0, True, mm_p, mv_p, None, a, ranged)
         a_range = (stats, st.range) if ranged else None
         if cp != c:                                # the pad channel is identically 0 after BN (x=0, beta=0)
             moving_mean.copy_(mm_p[:c])
@@ -2121,11 +2127,17 @@ class _BNActMaxPoolFn(torch.autograd.Function):
         st = _StatsRows(stats)
         mean, rstd = (st.mean, st.rstd) if training else (None, None)
         dxr = _emit_dx_range(dx) if ctx.emit_dx_range else None
-        check(lib.embnet_bn_act_maxpool_bwd_ex(ptr(dy), ptr(arg), ptr(x), n, h, w, c, k, stride, pad, oh, ow, mean, rstd, st.scale,
-                                               st.shift, act, int(training), ptr(xwin) if training else None, ptr(dx), ptr(tg),
-                                               ptr(tb), ptr(ws), ws.numel() * 4, ptr(dxr), stream()))
+        check(lib.embnet_bn_act_maxpool_bwd_band_ex(ptr(dy), ptr(arg), ptr(x), n, h, w, c, k, stride, pad, oh, ow, mean, rstd,
+                                                    st.scale, st.shift, act, int(training), ptr(xwin) if training else None,
+                                                    ptr(dx), ptr(tg), ptr(tb), ptr(ws), ws.numel() * 4, ptr(dxr),
+                                                    POOL_BWD_BAND_ROWS, stream()))
         dgamma, dbeta = finish()
         return (dx, dgamma, dbeta) + (None,) * 11
+
+
+# input rows per workgroup of the fused pool's dx pass (embnet_bn_act_maxpool_bwd_band_ex): 4, 8, 16 and 32 measured within noise of
+# each other in the ResNet18 step, all ahead of one thread per quad (profiles/stem_pool_passes_ab.md)
+POOL_BWD_BAND_ROWS = 8
 
 
 def bn_act_maxpool(x, bn, pool):

@@ -639,6 +639,15 @@ int embnet_bn_train_fwd_ex(const float* x, long m, int c, const float* gamma, co
                            float* shift, float* moving_mean, float* moving_var, const float* partial_in,
                            int partial_rows, void* workspace, size_t workspace_bytes, float* y_bound, uint32_t* y_range,
                            float* xhat_bound, void* stream);
+/* BatchNormalization (training) of x[m,c] with c % 4 != 0 whose output y[m,cp] has cp = 4 * ceil(c / 4) channels (the image batch
+ * in front of the zoo ResNet stem, 3 -> 4): two passes over x — statistics, then act(scale x + shift) written widened — with the
+ * results of embnet_pad_channels followed by embnet_bn_train_fwd_ex on the widened copy, bit for bit, without that copy.
+ * gamma / beta / the moving statistics / every output row have cp entries (the pad channels' statistics are those of zeros);
+ * workspace >= embnet_bn_workspace_bytes(m, cp); y is required. */
+int embnet_bn_train_fwd_pad_ex(const float* x, long m, int c, int cp, const float* gamma, const float* beta, float eps,
+                               float momentum, int act, float* y, float* save_mean, float* save_rstd, float* scale,
+                               float* shift, float* moving_mean, float* moving_var, void* workspace, size_t workspace_bytes,
+                               float* y_bound, uint32_t* y_range, float* xhat_bound, void* stream);
 int embnet_bn_infer_fwd(const float* x, long m, int c, const float* gamma, const float* beta,
                         const float* moving_mean, const float* moving_var, float eps, int relu, float* y,
                         float* scale, float* shift, void* stream);
@@ -756,6 +765,13 @@ int embnet_bn_act_maxpool_bwd_ex(const float* dy, const uint8_t* argmax, const f
                                  const float* scale, const float* shift, int act, int training, const float* xwin, float* dx,
                                  float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, uint32_t* dx_range,
                                  void* stream);
+/* _band_ex: band_rows > 0 runs the dx pass on bands of that many consecutive input rows per workgroup (the pooled rows that
+ * neighbouring input rows share stay in one CU's cache); 0 is _ex.  dx, dgamma, dbeta and dx_range do not depend on it. */
+int embnet_bn_act_maxpool_bwd_band_ex(const float* dy, const uint8_t* argmax, const float* x, int n, int h, int w, int c, int k,
+                                      int stride, int pad, int oh, int ow, const float* save_mean, const float* save_rstd,
+                                      const float* scale, const float* shift, int act, int training, const float* xwin,
+                                      float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                      uint32_t* dx_range, int band_rows, void* stream);
 
 /* GlobalAveragePooling2D (backbones.py:111): x[n,hw,c] -> y[n,c]. */
 /* act(x*scale + shift) -> y AND its per-image channel means -> gap[n,c], one pass (the BatchNormalization + swish in front
