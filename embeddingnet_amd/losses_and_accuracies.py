@@ -7,6 +7,8 @@ meaning), computing on the GPU through libembnet_hip.so.
   batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
   multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
+  fast_ap_loss(P, K, bins)(y_true, y_pred)                  build-defined (FastAP over a [P*K, E] block) -> scalar
+  smooth_ap_loss(P, K, temperature)(y_true, y_pred)         build-defined (Smooth-AP over a [P*K, E] block) -> scalar
   proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
   proxy_softmax_loss(head, scale, margin)(y_true, y_pred)   build-defined (CosFace / NormSoftmax against a ProxyHead's proxies) -> scalar
   soft_triple_loss(head, scale, margin, gamma, tau)(y_true, y_pred)   build-defined (SoftTriple against a ProxyHead's centres) -> scalar
@@ -63,6 +65,29 @@ def supcon_loss(k_classes, k_samples, temperature=0.1, denominator="all"):
 
     def loss_function(y_true, y_pred):
         return ops.supcon_loss(y_pred, k_classes, k_samples, temperature, denominator)[0]
+
+    return loss_function
+
+
+def fast_ap_loss(k_classes, k_samples, bins=10):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] block of
+    L2-normalised embeddings, y_true is ignored (Keras signature).  FastAP (Cakir et al. 2019; build-defined, not in the
+    reference): average precision over each anchor's soft-binned distance histograms (include/embnet.h,
+    embnet_fast_ap_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.fast_ap_loss(y_pred, k_classes, k_samples, bins)[0]
+
+    return loss_function
+
+
+def smooth_ap_loss(k_classes, k_samples, temperature=0.01):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] embedding
+    block, y_true is ignored (Keras signature).  Smooth-AP (Brown et al. 2020; build-defined, not in the reference): average
+    precision with sigmoid ranks at a temperature (include/embnet.h, embnet_smooth_ap_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.smooth_ap_loss(y_pred, k_classes, k_samples, temperature)[0]
 
     return loss_function
 

@@ -195,6 +195,7 @@ BATCH_ALL_PATHS = {"auto": 0, "per_class": 1, "distance_matrix": 2}
 MS_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 SUPCON_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 SUPCON_DENOMINATORS = {"all": 1, "negatives": 2}
+AP_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 
 
 def _supcon_scalars(temperature, denominator):
@@ -216,6 +217,10 @@ _PAIR_LOSSES = {
                               lambda *abbe: tuple(map(f32, abbe)), (((4,), torch.int32),), "embnet_ms_loss_bwd", False),
     "supcon_loss": ("embnet_supcon_loss_fwd", "embnet_supcon_loss_workspace_bytes", SUPCON_PATHS, _supcon_scalars,
                     (((2,), torch.int32),), "embnet_ms_loss_bwd", False),     # demb = (g / N)(G + G^T) X is MS's backward
+    "fast_ap_loss": ("embnet_fast_ap_loss_fwd", "embnet_fast_ap_loss_workspace_bytes", AP_PATHS, lambda bins: (bins,),
+                     (((2,), torch.int32),), "embnet_ms_loss_bwd", False),
+    "smooth_ap_loss": ("embnet_smooth_ap_loss_fwd", "embnet_smooth_ap_loss_workspace_bytes", AP_PATHS,
+                       lambda temperature: (f32(temperature),), (((2,), torch.int32),), "embnet_ms_loss_bwd", False),
 }
 _PAIR_WS = {}
 
@@ -289,6 +294,31 @@ def supcon_loss(emb, k_classes, k_samples, temperature=0.1, denominator="all", p
     return out if return_weights else out[:2]
 
 
+def fast_ap_loss(emb, k_classes, k_samples, bins=10, path="auto", return_weights=False):
+    """FastAP (Cakir et al., CVPR 2019) over a class-contiguous [P*K, E] block of L2-normalised rows: each anchor's distances
+    d = 2 - 2 S, S = X X^T, are soft-binned into histograms h+ / h- over the bins + 1 centres l * 4 / bins (triangular pulse), and
+    l_i = 1 - (1/(K-1)) sum_l h+_l H+_l / H_l with H+, H the running sums; mean over all N anchors (include/embnet.h has the
+    rounding form and the pair weights).  bins: a whole number in [2, 64].  -> (mean [autograd], counts int32 [2] = positive
+    pairs, violating anchors: those whose hardest negative is at least as similar as their hardest positive) on the device, no
+    host synchronisation; return_weights adds the pair-weight matrix G [N,N] the backward uses.  path: 'auto', 'per_class' or
+    'similarity_matrix'."""
+    if isinstance(bins, bool) or int(bins) != bins:
+        raise _lib.EmbnetError(f"fast_ap_loss: bins={bins!r} is not a whole number")
+    out = _PairLoss.apply(emb, "fast_ap_loss", int(k_classes), int(k_samples), (int(bins),), path)
+    return out if return_weights else out[:2]
+
+
+def smooth_ap_loss(emb, k_classes, k_samples, temperature=0.01, path="auto", return_weights=False):
+    """Smooth-AP (Brown et al., ECCV 2020) over a class-contiguous [P*K, E] block: the ranks in average precision with the step
+    replaced by a sigmoid of temperature tau, l_i = 1 - (1/(K-1)) sum_p R_p / Q_p, R_p = 1 + sum_{q != p} sigma((S_iq - S_ip) / tau)
+    over the other positives and Q_p the same sum over every other column; mean over all N anchors (include/embnet.h has the
+    rounding form and the pair weights).  K <= 65.  -> (mean [autograd], counts int32 [2] = positive pairs, violating anchors) on
+    the device, no host synchronisation; return_weights adds the pair-weight matrix G [N,N] the backward uses.  path: 'auto',
+    'per_class' or 'similarity_matrix'."""
+    out = _PairLoss.apply(emb, "smooth_ap_loss", int(k_classes), int(k_samples), (float(temperature),), path)
+    return out if return_weights else out[:2]
+
+
 # The training modes (TripletTrainer's negatives_selection_mode) whose loss is one of the above over the whole batch; they have no
 # triplet rows, a device count stands where the triplet count does.
 #   mode: (function, the loss_params it takes or None = it takes `margin`, the element of its counts that is that count or
@@ -297,6 +327,8 @@ PAIR_LOSS_MODES = {
     "batch_all": (batch_all_triplet_loss, None, None),                                          # n_active
     "multi_similarity": (multi_similarity_loss, ("alpha", "beta", "base", "epsilon"), 3),       # kept pairs
     "supcon": (supcon_loss, ("temperature", "denominator"), 1),                                 # violating anchors
+    "fast_ap": (fast_ap_loss, ("bins",), 1),                                                    # violating anchors
+    "smooth_ap": (smooth_ap_loss, ("temperature",), 1),                                         # violating anchors
 }
 
 

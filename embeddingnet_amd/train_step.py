@@ -31,7 +31,7 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon); anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon / fast_ap / smooth_ap); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
     all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
     negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
@@ -41,8 +41,10 @@ class TripletTrainer:
     used; last_triplets = (None, kept pairs [1]) and last_pair_counts = int32 [4]: kept positives, kept negatives, active
     anchors, kept pairs) or 'supcon' (the softmax / InfoNCE family of ops.supcon_loss with loss_params = dict(temperature,
     denominator), defaults 0.1 and 'all' = SupCon, 'negatives' = NT-Xent; `margin` is not used; last_triplets = (None, violating
-    anchors [1]) and last_pair_counts = int32 [2]: positive pairs, violating anchors).  Under data parallelism every mode mines
-    and normalises per rank."""
+    anchors [1]) and last_pair_counts = int32 [2]: positive pairs, violating anchors) or 'fast_ap' / 'smooth_ap' (the ranking
+    family: ops.fast_ap_loss with loss_params = dict(bins), default 10, and ops.smooth_ap_loss with loss_params =
+    dict(temperature), default 0.01; `margin` is not used; last_triplets and last_pair_counts as for 'supcon').  Under data
+    parallelism every mode mines and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     LOSS_PARAMS = {mode: keys for mode, (_, keys, _) in ops.PAIR_LOSS_MODES.items() if keys is not None}
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
@@ -53,7 +55,8 @@ class TripletTrainer:
         if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES):
             raise KeyError(self.mode)
         if loss_params and self.mode not in self.LOSS_PARAMS:
-            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity' or 'supcon', not {self.mode!r}")
+            raise ValueError(f"loss_params belong to negatives_selection_mode='multi_similarity', 'supcon', 'fast_ap' or 'smooth_ap', "
+                             f"not {self.mode!r}")
         self.loss_params = self._checked_loss_params(self.mode, loss_params)
         # one gradient per parameter and step: kernels write the reducer's flat buffer in place
         self._setup(base_model, optimizer, seed, reducer, graph, direct=True)

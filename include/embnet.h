@@ -1019,6 +1019,58 @@ size_t embnet_supcon_loss_workspace_bytes(int p, int k, int e);   /* sized for e
 int embnet_supcon_loss_fwd(const float* emb, int p, int k, int e, float temperature, int denominator, int path, float* pair_g,
                            int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
 
+/* FastAP and Smooth-AP (the ranking family of the Reality Check's loss table: smooth surrogates of the average precision of each
+ * anchor's ranked list, the quantity embnet_retrieval_* reports as MAP@R; the reference has no such loss): build-defined,
+ * selected as TripletTrainer(negatives_selection_mode="fast_ap" | "smooth_ap").  Additions only: the ABI version stays 22.
+ *   Inputs.  emb[n,e] fp32, n = p*k; rows c*k .. c*k+k-1 are class c.  S = X X^T, computed as embnet_ms_loss_fwd computes it.
+ *   Pair sets of anchor i.  Positives P_i: the other rows of its class, |P_i| = k-1.  Negatives N_i: the rows of other classes.
+ *   FastAP (Cakir et al., CVPR 2019).  bins = L, a whole number in [2, 64]; the Python layers default to 10.  Rows are expected
+ *     L2-normalised, so that d = 2 - 2 S lies in [0, 4]; nothing requires it.
+ *     Position of a pair, ONE rounding form: inv = L / 4 (exact in fp32), d = fl(2 - 2 S_ij), u = fl(d inv), l0 = floor(u),
+ *     f = u - l0 (exact).  The pair adds fl(1 - f) to bin l0 and f to bin l0 + 1 of the anchor's histogram h+ (j in P_i) or h-
+ *     (j in N_i); the bins are 0 .. L and a bin index outside that range is dropped.  This is the triangular pulse
+ *     max(0, 1 - |d - l Delta| / Delta), Delta = 4 / L, used as it is for a d outside [0, 4]; a d exactly on a centre belongs to
+ *     the interval on its right.
+ *     Hp_l, Hn_l: the running sums of h+, h- from bin 0 up; H_l = Hp_l + Hn_l.
+ *     F_i = sum_{l : H_l > 0} h+_l Hp_l / H_l,   l_i = 1 - F_i / (k-1).
+ *     b_l = h+_l Hp_l / H_l^2,  c_l = h+_l Hn_l / H_l^2 (this is h+_l / H_l - b_l, formed without the subtraction); both are 0
+ *     where H_l = 0, which is every bin below the anchor's smallest distance.
+ *     A-_m = -sum_{l >= m} b_l,   A+_m = Hp_m / H_m + sum_{l >= m} c_l (the quotient 0 where H_m = 0);  A outside 0 .. L is 0.
+ *     G_ij = dl_i/dS_ij = (2 inv / (k-1)) (A^c_{l0+1} - A^c_{l0}),  c = + for j in P_i, - for j in N_i;  G_ii = 0.
+ *     A pair whose u is within the rounding of S of a whole number may take either neighbouring interval: the histogram is
+ *     continuous across a centre, the pair's own G_ij is not.  The rows of G do not sum to zero.
+ *   Smooth-AP (Brown et al., ECCV 2020).  temperature tau, positive and finite, with fl(1/tau) a normal fp32 number; the Python
+ *     layers default to 0.01.  k <= 65 (k-1 <= 64 positives; anything above is rejected).
+ *     r = fl(1/tau), one correctly rounded division taken once per call.  For a positive p and a column j not in {i, p}:
+ *     z_pj = fl(fl(S_ij - S_ip) r),  t = e^{-|z|},  s_pj = sigma(z) = 1 / (1 + t) for z >= 0 and t / (1 + t) otherwise,
+ *     s'_pj = r t / (1 + t)^2.  The subtraction 1 - s is never used.
+ *     R_p = 1 + sum_{q in P_i, q != p} s_pq,  Nn_p = sum_{n in N_i} s_pn,  Q_p = R_p + Nn_p  (the ranks of p among the positives and
+ *     among all),  U_p = sum_{q in P_i, q != p} s'_pq,  Tn_p = sum_{n in N_i} s'_pn,  T_p = U_p + Tn_p.
+ *     l_i = 1 - (1/(k-1)) sum_p R_p / Q_p.
+ *     G_ij = (1/(k-1)) [ sum_{p in P_i, p != j} s'_pj (R_p / Q_p^2 - [j in P_i] / Q_p) + [j in P_i] (U_j / Q_j - R_j T_j / Q_j^2) ],
+ *     G_ii = 0, evaluated as R_p / Q_p^2 - 1 / Q_p = -Nn_p / Q_p^2 and U_j / Q_j - R_j T_j / Q_j^2 = (U_j Nn_j - R_j Tn_j) / Q_j^2.
+ *     Every row of G sums to zero in exact arithmetic.
+ *   Common.  *mean_loss = (1/n) sum_i l_i.  pair_g[n][n] = G (without the 1/n); all n*n entries are written.  Backward:
+ *     demb_i = (g / n) sum_j (G_ij + G_ji) x_j, g = *upstream (NULL = 1) — this is embnet_ms_loss_bwd's contract, and
+ *     embnet_ms_loss_bwd(emb, n, e, pair_g, upstream, demb, stream) is the backward.
+ *   Counters.  counts[2], int32, exact: counts[0] = positive pairs n (k-1); counts[1] = violating anchors, the anchors with
+ *     max_{n in N_i} S_in >= min_{p in P_i} S_ip on the device's fp32 S (embnet_supcon_loss_fwd's counter).
+ * Range: p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096, and the parameter ranges above; anything else is rejected before a launch.
+ * path: 0 = auto (embnet_*_ap_loss_path), EMBNET_AP_PER_CLASS, EMBNET_AP_SIMILARITY_MATRIX: the two forward paths, the fit rule and
+ * the workspace of embnet_ms_loss_fwd (the kernels share one skeleton, csrc/pair_loss.h).  No floating-point atomics, every sum
+ * in a fixed order: bitwise reproducible; no host synchronisation or allocation.
+ * workspace (embnet_*_ap_loss_workspace_bytes, either path, 16-byte aligned): zero-filled ONCE by the caller; every launch leaves
+ * its arrival counter zeroed. */
+enum { EMBNET_AP_PER_CLASS = 1, EMBNET_AP_SIMILARITY_MATRIX = 2 };
+int embnet_fast_ap_loss_path(int p, int k, int e);        /* the path `auto` takes; 0 outside the range */
+size_t embnet_fast_ap_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_fast_ap_loss_fwd(const float* emb, int p, int k, int e, int bins, int path, float* pair_g, int32_t* counts,
+                            float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_smooth_ap_loss_path(int p, int k, int e);      /* the path `auto` takes; 0 outside the range */
+size_t embnet_smooth_ap_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_smooth_ap_loss_fwd(const float* emb, int p, int k, int e, float temperature, int path, float* pair_g, int32_t* counts,
+                              float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Proxy-Anchor (Kim et al., CVPR 2020) and CosFace / NormSoftmax (Wang et al., CVPR 2018; Zhai & Wu, BMVC 2019): the proxy /
  * classification family of the Reality Check's loss table, a batch scored against one learnable vector per class (the reference
  * has no such loss): build-defined, selected as ProxyTrainer(loss="proxy_anchor" | "proxy_softmax").  Additions only: the ABI

@@ -7,7 +7,8 @@ For C1 (8x4 = 32 rows, E = 256, semihard), C2 (32x4 = 128, E = 256, hardest), C2
 semihard) the forward + backward of the loss path is run both ways on the same clustered embeddings (the *_batch_all cases
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
-denominator beside ops.multi_similarity_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
+denominator beside ops.multi_similarity_loss, the *_fast_ap / *_smooth_ap cases (`--only _ap`) ops.fast_ap_loss / ops.smooth_ap_loss at
+their defaults beside ops.supcon_loss('all'); the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
 xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time(), the mproxy_* cases (SoftTriple and sub-centre
 ArcFace on several centres per class; `--only mproxy_`) at mproxy_cases()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
@@ -34,7 +35,9 @@ CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batc
          ("c5_batch_all", 64, 4, 512, "batch_all"),
          ("c1_multi_similarity", 8, 4, 256, "multi_similarity"), ("c2_multi_similarity", 32, 4, 256, "multi_similarity"),
          ("c5_multi_similarity", 64, 4, 512, "multi_similarity"),
-         ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")]
+         ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")] + \
+        [(f"{cfg}_{mode}", p, k, e, mode) for mode in ("fast_ap", "smooth_ap")
+         for cfg, p, k, e in (("c1", 8, 4, 256), ("c2", 32, 4, 256), ("c5", 64, 4, 512))]
 
 
 # the losses on class proxies: (name, p, k, e, classes, mode)
@@ -451,6 +454,20 @@ def main():
                 ops.supcon_loss(x, p, k, 0.1, denominator)[0].backward()
             return leg
 
+        def ap_loss():
+            x.grad = None
+            (ops.fast_ap_loss if mode == "fast_ap" else ops.smooth_ap_loss)(x, p, k)[0].backward()
+
+        if mode in ("fast_ap", "smooth_ap"):                # the two legs alternate in one process, at one shape, twice over
+            row = dict(config=name, N=n, E=e, mining=mode)
+            for rnd in (1, 2):
+                row[f"{mode}_{rnd}"] = measure(ap_loss, a.iters)
+                row[f"supcon_all_{rnd}"] = measure(supcon("all"), a.iters)
+            row[f"device_ratio_{mode}_vs_supcon_all"] = round(min(row[f"{mode}_1"]["device_us"], row[f"{mode}_2"]["device_us"])
+                                                              / min(row["supcon_all_1"]["device_us"], row["supcon_all_2"]["device_us"]), 3)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if mode == "supcon":                                # the three legs alternate in one process, at one shape
             row = dict(config=name, N=n, E=e, mining=mode, supcon_all=measure(supcon("all"), a.iters),
                        supcon_negatives=measure(supcon("negatives"), a.iters),

@@ -150,6 +150,8 @@ LOSS_CONFIGS = {
     'supcon_loss': {'supcon': dict(temperature='positive number', denominator=('all', 'negatives'))},
     'proxy_loss': {'proxy_anchor': dict(alpha='positive', delta='number'), 'proxy_softmax': dict(scale='positive', margin='number')},
 }
+# GENERATOR.ap_loss with the ranking modes: the same validator on a table of its own, as for the modes below (ap_loss_config)
+AP_LOSS_CONFIGS = {'fast_ap': dict(bins='positive'), 'smooth_ap': dict(temperature='positive number')}
 # GENERATOR.proxy_loss with the modes on several centres per class (ops.MULTI_PROXY_LOSS_MODES): the same validator on a table of
 # their own (proxy_loss_config), so the messages about the key keep naming the two modes they always named
 MULTI_PROXY_LOSS_CONFIGS = {
@@ -160,6 +162,7 @@ MULTI_PROXY_DEFAULT_CENTERS = {'soft_triple': 10, 'arcface': 1}
 MS_LOSS_KEYS = tuple(LOSS_CONFIGS['ms_loss']['multi_similarity'])
 SUPCON_LOSS_KEYS = tuple(LOSS_CONFIGS['supcon_loss']['supcon'])
 PROXY_LOSS_KEYS = {mode: tuple(checks) for mode, checks in LOSS_CONFIGS['proxy_loss'].items()}
+AP_LOSS_KEYS = {mode: tuple(checks) for mode, checks in AP_LOSS_CONFIGS.items()}
 
 
 def loss_config(name, cfg, table=None):
@@ -208,6 +211,16 @@ def supcon_loss_config(cfg):
     return loss_config('supcon_loss', cfg)
 
 
+def ap_loss_config(cfg):
+    """GENERATOR.ap_loss for the ranking modes: {bins} with 'fast_ap', a whole number in [2, 64]; {temperature} with 'smooth_ap'."""
+    out = loss_config('ap_loss', cfg, AP_LOSS_CONFIGS)
+    if out is not None and 'bins' in out:
+        if out['bins'] != int(out['bins']) or not 2 <= out['bins'] <= 64:
+            raise ValueError(f"GENERATOR.ap_loss: bins must be a whole number in [2, 64] (got {cfg['generator']['ap_loss']!r})")
+        out['bins'] = int(out['bins'])
+    return out
+
+
 def proxy_loss_config(cfg):
     """GENERATOR.proxy_loss for the proxy modes; with 'soft_triple' / 'arcface' checked against MULTI_PROXY_LOSS_CONFIGS, and then:
     centers a whole number in [1, 32], tau not negative, ArcFace's margin in [0, pi/2)."""
@@ -234,7 +247,8 @@ XBM_KEYS = dict(size='positive', weight='number', start_iteration='number', loss
 XBM_LOSS_KEYS = {'contrastive': dict(margin='number'),
                  'multi_similarity': dict(alpha='positive', beta='positive', base='number', epsilon='number')}
 XBM_DEFAULTS = dict(weight=1.0, start_iteration=0, loss='contrastive')
-XBM_MODES = ('semihard', 'hardest', 'random_hard', 'batch_hard', 'batch_all', 'multi_similarity', 'supcon')
+XBM_MODES = ('semihard', 'hardest', 'random_hard', 'batch_hard', 'batch_all', 'multi_similarity', 'supcon', 'fast_ap',
+             'smooth_ap')
 
 
 def xbm_config(cfg):
@@ -357,11 +371,13 @@ def main():
     ms_loss = ms_loss_config(cfg)                      # likewise GENERATOR.ms_loss with another mode
     supcon_loss = supcon_loss_config(cfg)              # and GENERATOR.supcon_loss
     proxy_loss = proxy_loss_config(cfg)                # and GENERATOR.proxy_loss
+    ap_loss = ap_loss_config(cfg)                      # and GENERATOR.ap_loss
     xbm = xbm_config(cfg)                              # and GENERATOR.xbm (with a proxy mode, in Siamese mode, a memory below a batch)
     # each is refused with another's mode: at most one is set
-    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss) if v is not None), None)
+    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss, ap_loss) if v is not None), None)
     multi_proxy_mode = cfg['generator'].get('negatives_selection_mode') in MULTI_PROXY_LOSS_CONFIGS
     proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS or multi_proxy_mode
+    ap_mode = cfg['generator'].get('negatives_selection_mode') in AP_LOSS_KEYS and cfg['model']['mode'] != 'siamese'
     if proxy_mode and cfg['model']['mode'] == 'siamese':
         raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
@@ -389,7 +405,8 @@ def main():
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
-    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss', 'xbm')}
+    gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss',
+                                                       'ap_loss', 'xbm')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -513,22 +530,24 @@ def main():
                     if proxy_mode or xbm is not None:
                         xb, yb = feeder.next_labelled()
                         losses.append(trainer.step(xb, yb))
-                        if multi_proxy_mode:
+                        if multi_proxy_mode or ap_mode:
                             violating.append(trainer.last_triplets[1].clone())      # (a replayed step's counts are one buffer)
                         if xbm is not None and trainer.last_xbm_counts is not None:
                             xbm_counts.append(trainer.last_xbm_counts.clone())      # (a replayed step's counts are one buffer)
                     else:
                         xb = feeder.next()
                         losses.append(trainer.step(xb))
+                        if ap_mode:                       # the violating anchors (a replayed step's counts are one buffer)
+                            violating.append(trainer.last_triplets[1].clone())
                     n_images += xb.shape[0]
             epoch_loss = all_reduce_mean(float(torch.stack(losses).mean().item()))     # mean over ranks (logging + monitor)
             history['loss'].append(epoch_loss)
             msg = f'Epoch {epoch + 1}/{n_epochs} - lr {lr:.3g} - loss {epoch_loss:.4f}'
             if n_images:                                  # (the .item() above waited for the epoch's last step)
                 msg += f' - {n_images * world / (time.perf_counter() - t_epoch):.0f} images/s'
-            if violating:                                 # this rank's: violating samples per step, the last step's regulariser
+            if violating:                                 # this rank's: violating samples (anchors) per step, the last step's regulariser
                 msg += f' - violating {torch.stack(violating).float().mean().item():.1f}'
-                if trainer.last_reg is not None:
+                if multi_proxy_mode and trainer.last_reg is not None:
                     msg += f' - reg {trainer.last_reg.item():.4f}'
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
