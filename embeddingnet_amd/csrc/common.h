@@ -37,15 +37,17 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // the first time it runs there: bit d of the kernel's own word says device d is done, so a launch costs hipGetDevice and one load.
 // Two threads may both find the bit clear and both set the attribute (the same value); the acquire / release pair orders the one
 // that finds it set behind the call that set it.  A device number past the word is never remembered, only slower.
+// STATIC_BYTES: the LDS the kernel declares statically besides; the two together must stay within the CU's, or the runtime
+// refuses the attribute (and leaves its error for the next hipGetLastError).
 constexpr int BIG_LDS_BYTES = 160 * 1024;
-template <auto Kernel>
+template <auto Kernel, int STATIC_BYTES = 0>
 inline void allow_big_lds() {
   static std::atomic<uint64_t> done{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   const uint64_t bit = (unsigned)dev < 64 ? 1ull << dev : 0;
   if (done.load(std::memory_order_acquire) & bit) return;
-  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES - STATIC_BYTES);
   done.fetch_or(bit, std::memory_order_release);
 }
 

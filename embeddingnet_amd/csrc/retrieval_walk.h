@@ -48,6 +48,8 @@ __device__ __forceinline__ int half_wave_sum(int c) {
 //   row(rt)               what E needs per row (rt = walk_row, the row in the tile), handed back to every visit of that row
 //   visit(slot value, rt, row value, column value, key, live, same) -> the new slot value
 //   half_wave(v), commit(rt, v)   the reduction over the row's lanes; what their first lane does with it for a row below nq
+//   tile_done(count)      called by every thread behind the visits of a gallery tile, count = the visited tiles of this walk so
+//                         far; without FILTER every wave gets here for every tile, so E may put a barrier in it
 // The barrier behind the row prologue also publishes the LDS rows the calling kernel filled for E before the call.
 template <class G, bool VEC, class E>
 __device__ __forceinline__ void retrieval_walk(const WalkParams& p, const E ep) {
@@ -113,6 +115,7 @@ __device__ __forceinline__ void retrieval_walk(const WalkParams& p, const E ep) 
           out[im * 16 + r] = ep.visit(out[im * 16 + r], rt, rv, cx[in], k, live, cl[in] == rl);
         }
       }
+    ep.tile_done(t - t0 + 1);
   }
 
 #pragma unroll
@@ -135,6 +138,7 @@ struct WalkEpilogue {
   __device__ __forceinline__ int row(int) const { return 0; }
   __device__ static __forceinline__ int half_wave(int c) { return half_wave_sum(c); }
   __device__ __forceinline__ void commit(int, int) const {}
+  __device__ __forceinline__ void tile_done(int) const {}
 };
 
 // Tile and split choice.  128x128 tiles where they alone put >= 384 workgroups' worth of work on the chip (cross_dist's

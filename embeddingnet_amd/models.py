@@ -206,6 +206,15 @@ class EmbeddingNet:
         encodings, labels, kw = self._encode_validation("calculate_map_at_r", data_loader, gallery, batch_size)
         return retrieval_map_metrics(encodings, labels, **kw)
 
+    def calculate_verification_metrics(self, data_loader, fars=(1e-1, 1e-2, 1e-3), bins=4096, gallery='val', batch_size=256):
+        """ROC AUC / EER / TAR@FAR over all pairs of data_loader.val_data (verification.verification_metrics: a pair is "same"
+        when the classes agree).  gallery='val': every unordered pair within the validation set; gallery='train': every
+        (validation item, training item) pair.  batch_size as in calculate_retrieval_metrics; the validation items are encoded
+        the same way."""
+        from .verification import verification_metrics
+        encodings, labels, kw = self._encode_validation("calculate_verification_metrics", data_loader, gallery, batch_size)
+        return verification_metrics(encodings, labels, fars=fars, bins=bins, **kw)
+
     def calculate_clustering_metrics(self, data_loader, n_clusters=None, seed=0, n_init=1, batch_size=256):
         """NMI (and homogeneity, completeness, purity) of a k-means clustering of data_loader.val_data's encodings against
         their class labels (clustering.clustering_metrics).  n_clusters None: the number of validation classes.  The

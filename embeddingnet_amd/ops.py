@@ -1011,3 +1011,39 @@ def kmeans_pp_pick(mind2, seed, draw):
     check(_lib.lib().embnet_kmeans_pp_pick(ptr(mind2), mind2.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), ptr(index), ptr(u),
                                            stream()))
     return index, u
+
+
+# --------------------------------------------------------------------------- verification histograms (csrc/verification.hip)
+VERIFICATION_MAX_BINS = 4096
+
+
+def verification_all_pairs(q, q_labels, x=None, x_labels=None, bins=4096, d2_max=4.0, flush_tiles=0):
+    """Every (query, gallery) pair counted by its squared distance, without the [nq,n] matrix (include/embnet.h, "verification").
+
+    q [nq,e], q_labels [nq]; x [n,e], x_labels [n] the gallery, or None: leave-one-out on q — pair (i, i) is skipped and every
+    unordered pair is counted twice.  bins: a power of two in [2, 4096] over [0, d2_max), d2_max a power of two; a pair beyond
+    the range (or with a NaN distance) sits in the last bin.  -> (hist_same, hist_other) int64 [bins] on the device, exact.
+    flush_tiles: how often a workgroup empties its LDS counters (0: as rarely as is safe); the result does not depend on it."""
+    q, ql, x, xl, self_exclude, nq, n, e = _retrieval_blocks("verification_all_pairs", q, q_labels, x, x_labels)
+    lib = _lib.lib()
+    ws = _new((max(lib.embnet_verification_all_pairs_workspace_bytes(nq, n) // 8, 2),), q, torch.float64)
+    hist = _new((2, int(bins)) if int(bins) > 0 else (2, 1), q, torch.int64)
+    check(lib.embnet_verification_all_pairs(ptr(q), ptr(ql), nq, None if self_exclude else ptr(x), None if self_exclude else ptr(xl),
+                                            n, e, int(bins), f32(d2_max), int(flush_tiles), ptr(hist[0]), ptr(hist[1]),
+                                            ptr(ws), ws.numel() * 8, stream()))
+    return hist[0], hist[1]
+
+
+def verification_values(values, same, lo=0.0, w=1.0, bins=4096):
+    """Per-pair values (distances or scores) counted into a same-pair and an other-pair histogram of `bins` bins of width w (a
+    power of two) from lo: bin = clamp(floor((v - lo) / w), 0, bins - 1), NaN to the last bin.  values [m] float32, same [m]
+    (non-zero: a same-class pair); m = 0 yields zeros.  -> (hist_same, hist_other) int64 [bins] on the device, exact."""
+    values = _prep(values.detach()).reshape(-1)
+    same = same.to(device=values.device, dtype=torch.int32).contiguous().reshape(-1)
+    if same.numel() != values.numel():
+        raise _lib.EmbnetError(f"verification_values: {values.numel()} values but {same.numel()} flags")
+    m = values.numel()
+    hist = _new((2, int(bins)) if int(bins) > 0 else (2, 1), values, torch.int64)
+    check(_lib.lib().embnet_verification_values(ptr(values) if m else None, ptr(same) if m else None, m, f32(lo), f32(w), int(bins),
+                                                ptr(hist[0]), ptr(hist[1]), stream()))
+    return hist[0], hist[1]

@@ -245,6 +245,45 @@ int embnet_kmeans_update(const float* x, const int32_t* labels, int n, const flo
 int embnet_kmeans_pp_update(const float* x, int n, int e, const int32_t* index, int first, float* mind2, void* stream);
 int embnet_kmeans_pp_pick(const float* mind2, int n, uint64_t seed, int draw, int32_t* index, double* u, void* stream);
 
+/* ---- verification (ROC AUC, EER, TAR@FAR): every pair of encodings counted into a same-class and an other-class histogram of its
+ * distance, without the [nq,n] matrix and without a sort (csrc/verification.hip).  Additions only: the ABI version stays 22.
+ *   Bin contract.  A histogram has `bins` bins over [lo, lo + bins * w): bins a power of two in [2, EMBNET_VERIFICATION_MAX_BINS],
+ *     w a positive power of two (a normal float), lo finite (0 for distances).
+ *       bin(v) = clamp((int)floorf((v - lo) * (1 / w)), 0, bins - 1),   bin(NaN) = bins - 1   (as the walk's "NaN counts as +inf")
+ *     1 / w is a power of two, so the product is exact: the bin is an EXACT function of the fp32 value v (of v - lo, which is v
+ *     for distances), not a second rounding, and a host restatement in float32 gives the same integer.  Thresholds are the edges
+ *     t_j = lo + j * w, j = 0 .. bins; a pair is accepted as "same" at threshold t_j iff its bin is below j, that is iff v < t_j
+ *     (for j < bins; everything from the last edge on, +inf and NaN included, sits in the last bin).
+ *   Outputs: hist_same[bins], hist_other[bins], uint64, 8-byte aligned.  The call zeroes them with a kernel of its own (not a
+ *     memset node), then adds exact integers with integer atomics: the result does not depend on scheduling and is bitwise
+ *     reproducible across runs, streams and graph replay.
+ * embnet_verification_all_pairs: one walk of the fp32 distance GEMM of embnet_retrieval_first_positive — the same d2 =
+ *     max(|q|^2 + |x|^2 - 2 q.x, 0), NaN -> +inf, the same tile and split plan (both geometries) and loaders (16-byte; scalar for
+ *     unaligned pointers or e % 4 != 0) — whose epilogue counts bin(d2) of every pair (query r, gallery column c) into hist_same
+ *     when the labels agree and into hist_other otherwise; lo = 0, w = d2_max / bins, d2_max a positive power of two.
+ *     x == NULL (then x_labels must be NULL and n == nq): leave-one-out, the gallery IS the query block and pair (i, i) is
+ *     skipped; every unordered pair is then counted TWICE (as (i, j) and as (j, i)), and halving is the caller's.
+ *     A gallery that IS the query block (x == q, or q a part of x) is an ordinary gallery: all nq * n pairs count, the
+ *     d2 = 0 self pairs among the same-class ones.
+ *     A workgroup counts into a private LDS histogram with 32-bit counters and adds its non-zero bins to the outputs every
+ *     `flush_tiles` gallery tiles and at the end of its walk.  flush_tiles = 0: the largest interval that cannot overflow a
+ *     counter, (2^32 - 1) / (BM * BN) for the plan's BM x BN tile; a positive value above that is refused, any other is honoured
+ *     (the result is the same for every value).  Workspace: >= embnet_verification_all_pairs_workspace_bytes(nq, n) bytes
+ *     (0 for nq <= 0 or n <= 0), 16-byte aligned, no initialisation needed, short -> -3.  Refused with -1: a null pointer, bins or
+ *     d2_max outside the contract, sizes the walk refuses (a block of 2 GiB or more, nq, n, e <= 0), too large a flush_tiles.
+ *     2*nq*n*e FLOP, O(nq + n) bytes of workspace.  No allocation and no synchronisation inside.
+ * embnet_verification_values: the same bin function and LDS histogram over a vector: values[m] f32, same[m] int32 (non-zero:
+ *     a same-class pair).  m = 0 is accepted and yields zeros.  It serves explicit pair lists (the distances of
+ *     embnet_pair_distance_fwd) and similarity scores.  Refused with -1: a null pointer, m < 0, bins, w or lo outside the contract. */
+#define EMBNET_VERIFICATION_MAX_BINS 4096
+size_t embnet_verification_all_pairs_workspace_bytes(int nq, int n);
+int embnet_verification_all_pairs(const float* q, const int32_t* q_labels, int nq,
+                                  const float* x, const int32_t* x_labels, int n, int e, int bins, float d2_max, int flush_tiles,
+                                  uint64_t* hist_same, uint64_t* hist_other,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int embnet_verification_values(const float* values, const int32_t* same, int m, float lo, float w, int bins,
+                               uint64_t* hist_same, uint64_t* hist_other, void* stream);
+
 /* ------------------------------------------------------------------ backbone layers
  * Stand-ins for the Keras layers that backbones.py:19-121 instantiates (TensorFlow kernels in the
  * reference).  All NHWC fp32. */

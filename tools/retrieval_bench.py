@@ -26,7 +26,13 @@ positive), for classes of `--per-class` members (default 20 and 512), next to
   (b) materialised_ms   ops.cross_distances(squared) + torch.sort(dim=1) + a gather of the labels, where the matrix fits
 the three alternating round by round in one process; `pass2_over_counting` = device time of map_walk_kernel<2> over that of
 retrieval_walk_kernel<2> from the library's event trace — what counting EVERY positive's negatives costs over counting the
-first's."""
+first's.
+
+`--verification`: device time of the verification histogram walk (ops.verification_all_pairs, bins 1024 and 4096) next to the two
+walks of ops.retrieval_first_positive at the same shape (the same GEMM under a minimum epilogue; `--floor-lib` names another
+build of the library to take them from) and to ops.cross_distances + torch.histc where the matrix fits: verification_mode.
+`--verification --contention`: the epilogue's terms priced one by one — a collapsed input whose pairs all share one bin, 64 / 1024 /
+4096 bins at equal atomics, one flush per tile against one per walk: verification_contention_mode."""
 import argparse
 import json
 import os
@@ -148,6 +154,166 @@ def map_mode(args):
     return results
 
 
+def _bind(path):
+    """A second copy of the library (another build) next to the one the package loaded: every symbol the header declares and
+    this build has, with its own event trace."""
+    import ctypes
+    from embeddingnet_amd import _lib
+    l = ctypes.CDLL(path)
+    for name, (res, argtypes) in _lib.parse_header().items():
+        if hasattr(l, name):
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = res, argtypes
+    return l
+
+
+def _trace_us(l, fn):
+    """{kernel: device microseconds} of one call of fn under library l's event trace."""
+    import ctypes
+    l.embnet_trace_enable(1)
+    l.embnet_trace_reset()
+    fn()
+    torch.cuda.synchronize()
+    name = ctypes.create_string_buffer(160)
+    ms, work, unit, nbytes = ctypes.c_float(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
+    per = {}
+    for i in range(l.embnet_trace_count()):
+        l.embnet_trace_get(i, ctypes.addressof(name), 160, ctypes.addressof(ms), ctypes.addressof(work), ctypes.addressof(unit),
+                           ctypes.addressof(nbytes))
+        per[name.value.decode().split("::")[-1]] = round(1e3 * ms.value, 1)
+    l.embnet_trace_enable(0)
+    l.embnet_trace_reset()
+    return per
+
+
+def verification_mode(args):
+    """ops.verification_all_pairs (bins 1024 and 4096, leave-one-out, shuffled labels: nothing for a label filter to skip) next to
+      (a) the two walks of embnet_retrieval_first_positive at the same shape — the same GEMM under a minimum epilogue (pass 1: a
+          64-bit minimum per row, pass 2: a count per row) — from `--floor-lib` (a build of another commit) when given, else
+          from the loaded library; per-kernel device time from that library's event trace
+      (b) ops.cross_distances(squared) + torch.histc per label class, where the [n, n] matrix fits: wall time between events
+    the legs alternating round by round in one process; the medians of `--rounds` traced calls."""
+    from embeddingnet_amd import _lib, ops
+    from embeddingnet_amd._lib import ptr, stream
+    dev = torch.device("cuda:0")
+    cur = _lib.lib()
+    floor = _bind(args.floor_lib) if args.floor_lib else cur
+
+    def first(x, labels, ws, outs):
+        n, e = x.shape
+        rc = floor.embnet_retrieval_first_positive(ptr(x), ptr(labels), n, ptr(x), ptr(labels), n, e, 1, ptr(outs[0]), ptr(outs[1]),
+                                                   ptr(outs[2]), ptr(ws), ws.numel() * 8, stream())
+        assert rc == 0, floor.embnet_last_error()
+
+    def composed(x, labels, bins):
+        d = ops.cross_distances(x, x, squared=True)
+        same = labels[:, None] == labels[None, :]
+        hs = torch.histc(d[same], bins=bins, min=0.0, max=4.0)
+        ho = torch.histc(d[~same], bins=bins, min=0.0, max=4.0)
+        return hs, ho
+
+    warm, wl = clustered(512, 64, dev, "shuffled")
+    ops.verification_all_pairs(warm, wl, bins=1024), composed(warm, wl, 1024)
+    results = []
+    for e in args.dims:
+        for n in args.sizes:
+            x, labels = clustered(n, e, dev, "shuffled")
+            ws = torch.empty(max(floor.embnet_retrieval_workspace_bytes(n, n) // 8, 2), dtype=torch.float64, device=dev)
+            outs = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                    torch.empty(n, device=dev))
+            both = 4.0 * n * n <= args.max_matrix_gib * 2 ** 30 / 3      # the two masked copies besides the matrix
+            run_v = {b: (lambda b=b: ops.verification_all_pairs(x, labels, bins=b, d2_max=4.0)) for b in (1024, 4096)}
+            run_f = lambda: first(x, labels, ws, outs)
+            run_f(), [r() for r in run_v.values()]
+            t_v, t_f1, t_f2, t_c, t_prep = {1024: [], 4096: []}, [], [], {1024: [], 4096: []}, []
+            for _ in range(args.rounds):
+                for b in (1024, 4096):
+                    per = _trace_us(cur, run_v[b])
+                    t_v[b].append(per["verif_walk_kernel"])
+                    t_prep.append(per["verif_prep_kernel"])
+                    per = _trace_us(floor, run_f)
+                    t_f1.append(per["retrieval_walk_kernel<1>"])
+                    t_f2.append(per["retrieval_walk_kernel<2>"])
+                    if both:
+                        t_c[b].append(1e3 * timed(lambda: composed(x, labels, b))[0])
+                        torch.cuda.empty_cache()
+            hs, ho = run_v[4096]()
+            f1, f2 = float(np.median(t_f1)), float(np.median(t_f2))
+            tile = 128 if ((n + 127) // 128) ** 2 >= 384 else 64
+            res = {"mode": "verification", "n": n, "e": e, "tile": tile, "label_order": "shuffled", "leave_one_out": True,
+                   "device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "floor_lib": args.floor_lib or "loaded library",
+                   "floor_pass1_us": round(f1, 1), "floor_pass1_us_min_max": [min(t_f1), max(t_f1)],
+                   "floor_pass2_us": round(f2, 1), "floor_pass2_us_min_max": [min(t_f2), max(t_f2)],
+                   "prep_us": round(float(np.median(t_prep)), 1), "pairs": int((hs.sum() + ho.sum()).item()),
+                   "same_pairs": int(hs.sum().item())}
+            for b in (1024, 4096):
+                v = float(np.median(t_v[b]))
+                res.update({f"walk_us_{b}": round(v, 1), f"walk_us_{b}_min_max": [min(t_v[b]), max(t_v[b])],
+                            f"walk_{b}_over_pass1": round(v / f1, 3), f"walk_{b}_over_pass2": round(v / f2, 3),
+                            f"walk_{b}_tflops": round(2.0 * n * n * e / (v * 1e-6) / 1e12, 2)})
+                if both:
+                    c = float(np.median(t_c[b]))
+                    res.update({f"composed_us_{b}": round(c, 1), f"walk_{b}_over_composed": round(v / c, 4)})
+            print(json.dumps(res), flush=True)
+            results.append(res)
+            del x, labels, ws, outs
+            torch.cuda.empty_cache()
+    return results
+
+
+def verification_contention_mode(args):
+    """What the histogram epilogue costs beyond the walk, term by term (device µs of verif_walk_kernel, median of `--rounds`):
+      collapsed   every row the same unit vector up to 1e-4 of noise: all d2 fall into bin 0, so the 64 LDS atomics of a wave
+                  instruction aim at one address (two with mixed labels) — the worst case for same-address LDS atomics; next to
+                  the clustered input of the same shape, whose d2 spreads over many bins
+      bins        64 / 1024 / 4096 on the clustered input: the same atomics, a growing clear + scan + flush per workgroup
+      flush       flush_tiles = 1 against 0 (one flush per walk): the price of one flush per gallery tile, divided by the number
+                  of extra flushes a workgroup does (tiles_per_split - 1, from the library's plan)"""
+    from embeddingnet_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    cur = _lib.lib()
+
+    def walk_us(x, labels, bins, flush_tiles=0):
+        run = lambda: ops.verification_all_pairs(x, labels, bins=bins, d2_max=4.0, flush_tiles=flush_tiles)
+        run()
+        t = [_trace_us(cur, run)["verif_walk_kernel"] for _ in range(args.rounds)]
+        return round(float(np.median(t)), 1), [min(t), max(t)]
+
+    def plan(n):
+        big = ((n + 127) // 128) ** 2 >= 384
+        b = 128 if big else 64
+        tiles = (n + b - 1) // b
+        want = min(-(-512 // tiles), tiles)
+        return b, -(-tiles // want)
+
+    results = []
+    for e in args.dims:
+        for n in args.sizes:
+            x, labels = clustered(n, e, dev, "shuffled")
+            g = torch.Generator(device=dev).manual_seed(1)
+            c = torch.randn(1, e, device=dev, generator=g) + 1e-4 * torch.randn(n, e, device=dev, generator=g)
+            c = (c / c.norm(dim=1, keepdim=True)).contiguous()
+            tile, tps = plan(n)
+            res = {"mode": "verification_contention", "n": n, "e": e, "tile": tile, "tiles_per_split": tps,
+                   "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
+            hs, ho = ops.verification_all_pairs(c, labels, bins=4096, d2_max=4.0)
+            res["collapsed_share_in_bin0"] = round(float((hs[0] + ho[0]).item()) / float((hs.sum() + ho.sum()).item()), 4)
+            for bins in (64, 1024, 4096):
+                res[f"clustered_us_{bins}"], res[f"clustered_us_{bins}_min_max"] = walk_us(x, labels, bins)
+                res[f"collapsed_us_{bins}"], res[f"collapsed_us_{bins}_min_max"] = walk_us(c, labels, bins)
+                res[f"collapsed_over_clustered_{bins}"] = round(res[f"collapsed_us_{bins}"] / res[f"clustered_us_{bins}"], 3)
+            for bins in (1024, 4096):
+                every, _ = walk_us(x, labels, bins, flush_tiles=1)
+                res[f"flush_every_tile_us_{bins}"] = every
+                if tps > 1:
+                    res[f"us_per_extra_flush_{bins}"] = round((every - res[f"clustered_us_{bins}"]) / (tps - 1), 3)
+            print(json.dumps(res), flush=True)
+            results.append(res)
+            del x, labels, c
+            torch.cuda.empty_cache()
+    return results
+
+
 def write_out(args, results):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -165,9 +331,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--map", action="store_true", help="time the MAP@R primitive (see the module docstring)")
     ap.add_argument("--per-class", type=int, nargs="+", default=[20, 512], help="--map: members per class")
+    ap.add_argument("--verification", action="store_true", help="time the verification histogram walk (see verification_mode)")
+    ap.add_argument("--contention", action="store_true",
+                    help="--verification: price the epilogue's terms instead (see verification_contention_mode)")
+    ap.add_argument("--floor-lib", default=None, help="--verification: another build of libembnet_hip.so for the floor leg")
     args = ap.parse_args()
     if args.rounds < 3:
         ap.error("--rounds must be at least 3")
+    if args.verification:
+        return write_out(args, verification_contention_mode(args) if args.contention else verification_mode(args))
     if args.map:
         if args.sizes == ap.get_default("sizes"):
             args.sizes = [6100, 32768, 131072]

@@ -326,13 +326,65 @@ def clustering_nmi_config(p_train, validate):
     return on
 
 
+VERIFICATION_DEFAULTS = {'fars': [1e-1, 1e-2, 1e-3], 'bins': 4096}
+LOWER_IS_BETTER = ('val_eer',)                             # monitored evaluation values that improve downwards
+
+
+def verification_config(p_train, validate):
+    """TRAIN.verification (optional, default off) -> None or {'fars': [...], 'bins': int}: after each epoch's validation, ROC AUC,
+    equal error rate and TAR@FAR over all pairs of the validation set (EmbeddingNet.calculate_verification_metrics) join the
+    history as val_auc / val_eer / val_tar@far=f, f written as repr(f).  `true` takes the defaults; a mapping may set `fars`
+    (each in (0, 1)) and `bins` (a power of two in [2, 4096]); any other sub-key is refused."""
+    raw = p_train.get('verification')
+    if raw is None or raw is False:
+        return None
+    if raw is True:
+        raw = {}
+    if not isinstance(raw, dict):
+        raise ValueError(f"TRAIN.verification: true, false or a mapping with fars / bins (got {raw!r})")
+    unknown = sorted(set(raw) - set(VERIFICATION_DEFAULTS))
+    if unknown:
+        raise ValueError(f"TRAIN.verification: unknown keys {unknown} (fars, bins)")
+    out = dict(VERIFICATION_DEFAULTS, **raw)
+    bins = out['bins']
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 2 <= bins <= 4096 or bins & (bins - 1):
+        raise ValueError(f"TRAIN.verification: bins must be a power of two in [2, 4096] (got {bins!r})")
+    fars = out['fars']
+    if isinstance(fars, (int, float)) and not isinstance(fars, bool):
+        fars = [fars]
+    if not isinstance(fars, (list, tuple)) or not fars:
+        raise ValueError(f"TRAIN.verification: fars must be a non-empty list (got {fars!r})")
+    for f in fars:
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0.0 < float(f) < 1.0:
+            raise ValueError(f"TRAIN.verification: every far must lie in (0, 1) (got {f!r})")
+    if not validate:
+        raise ValueError("TRAIN.verification evaluates the validation set: it needs DATALOADER.validate (validation is off)")
+    return {'fars': [float(f) for f in fars], 'bins': bins}
+
+
+def verification_names(verification):
+    """The history names (without 'val_') of a verification_config result, in logging order."""
+    return ['auc', 'eer'] + [f'tar@far={f!r}' for f in verification['fars']] if verification else []
+
+
+def monitored_value(monitor, history, epoch_loss):
+    """What plateau, early stop and best checkpoint minimise: the monitored entry itself where lower is better (the losses,
+    val_eer), 1 - it for every other evaluation value."""
+    if monitor == 'loss':
+        return epoch_loss
+    last = history[monitor][-1]
+    return last if monitor == 'val_loss' or monitor in LOWER_IS_BETTER else 1.0 - last
+
+
 def monitor_config(p_train, validate):
     """TRAIN.retrieval_ks / TRAIN.monitor (both optional) -> (the K's of the per-epoch retrieval evaluation, the monitored name).
     retrieval_ks: after each epoch's validation, Recall@K and MRR of the validation set (leave-one-out,
     EmbeddingNet.calculate_retrieval_metrics) join the history as val_recall@K / val_mrr.  monitor: what plateau, early stop and
     best checkpoint follow — 'val_loss' ('loss' without validation) by default, or 'loss', 'val_recall@K' with K in
     retrieval_ks, 'val_mrr', with TRAIN.retrieval_map (retrieval_map_config) 'val_map@r' / 'val_r_precision', and with
-    TRAIN.clustering_nmi (clustering_nmi_config) 'val_nmi' — larger is better for all of those.  Anything that cannot be honoured is a ValueError before training starts."""
+    TRAIN.clustering_nmi (clustering_nmi_config) 'val_nmi' — larger is better for all of those —, and with TRAIN.verification
+    (verification_config) 'val_auc', 'val_tar@far=f' (larger is better) or 'val_eer' (LOWER is better: monitored_value does not
+    flip it).  Anything that cannot be honoured is a ValueError before training starts."""
     ks = p_train.get('retrieval_ks') or []
     if isinstance(ks, (int, float)):
         ks = [ks]
@@ -357,9 +409,16 @@ def monitor_config(p_train, validate):
     elif monitor == 'val_nmi':
         if not clustering_nmi_config(p_train, validate):
             raise ValueError("TRAIN.monitor: 'val_nmi' needs TRAIN.clustering_nmi")
+    elif monitor in ('val_auc', 'val_eer') or monitor.startswith('val_tar@far='):
+        verification = verification_config(p_train, validate)
+        if not verification:
+            raise ValueError(f"TRAIN.monitor: {monitor!r} needs TRAIN.verification")
+        if monitor[4:] not in verification_names(verification):
+            raise ValueError(f"TRAIN.monitor: {monitor!r} names a far that TRAIN.verification.fars {verification['fars']} does not "
+                             "compute")
     elif monitor not in ('loss', 'val_loss'):
         raise ValueError(f"TRAIN.monitor: unknown name {monitor!r} (loss, val_loss, val_recall@K, val_mrr, val_map@r, "
-                         "val_r_precision, val_nmi)")
+                         "val_r_precision, val_nmi, val_auc, val_eer, val_tar@far=f)")
     return ks, monitor
 
 
@@ -382,6 +441,7 @@ def main():
         raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     clustering_nmi_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
+    verification_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
     p_train, p_model, p_loader, p_gen = cfg['train'], cfg['model'], cfg['dataloader'], cfg['generator']
     apply_gpu_ids(cfg['general'].get('gpu_ids'))
     paths = create_save_folders(cfg['general'])
@@ -405,6 +465,7 @@ def main():
     retrieval_ks, monitor = monitor_config(p_train, bool(data_loader.validate))
     retrieval_map = retrieval_map_config(p_train, bool(data_loader.validate))
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
+    verification = verification_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss',
                                                        'ap_loss', 'xbm')}
 
@@ -503,6 +564,8 @@ def main():
         history['val_map@r'], history['val_r_precision'] = [], []
     if clustering_nmi:
         history['val_nmi'] = []
+    for name in verification_names(verification):
+        history['val_' + name] = []
     n_epochs = min(p_train['n_epochs'], args.max_epochs or p_train['n_epochs'])
 
     # triplet mode: batches are planned on this thread and decoded / uploaded ahead of the step (input_pipeline.Feeder: the
@@ -587,10 +650,14 @@ def main():
                         found = model.calculate_clustering_metrics(data_loader)
                     history['val_nmi'].append(all_reduce_mean(float(found['nmi'])))
                     msg += f" - val_nmi {history['val_nmi'][-1]:.4f}"
-                if monitor == 'loss':
-                    value = epoch_loss
-                elif monitor != 'val_loss':
-                    value = 1.0 - history[monitor][-1]    # lower is better for plateau, early stop and best checkpoint
+                if verification:
+                    with torch.no_grad():
+                        found = model.calculate_verification_metrics(data_loader, fars=verification['fars'],
+                                                                     bins=verification['bins'])
+                    for name in verification_names(verification):
+                        history['val_' + name].append(all_reduce_mean(float(found[name])))
+                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                value = monitored_value(monitor, history, epoch_loss)    # lower is better for plateau, early stop, best checkpoint
             if rank == 0:
                 print(msg, flush=True)
             improved, stop, lr_end = plateau.update(value, lr)   # `value` is the all-reduced mean: same decisions on every rank
