@@ -1,4 +1,4 @@
-// What every walk of the streaming distance GEMM shares (retrieval.hip: Recall@K, MAP@R; kmeans.hip: nearest centre): the key,
+// What every walk of the streaming distance GEMM shares (retrieval.hip: Recall@K, MAP@R; kmeans.hip: nearest centre; verification.hip: pair histograms; knn_search.hip: top-k): the key,
 // the walk and its epilogue contract, the tile and split plan, the workspace carver and the traced dispatch.
 #pragma once
 #include "gemm_engine.h"
@@ -144,14 +144,17 @@ struct WalkEpilogue {
 // Tile and split choice.  128x128 tiles where they alone put >= 384 workgroups' worth of work on the chip (cross_dist's
 // rule), 64x64 below.  The gallery is cut into `splits` ranges of whole tiles so that (query tiles) x splits reaches ~512
 // workgroups on the 256 CUs; with many query tiles splits = 1 and a row sees one atomic per wave column per pass.
-static void retrieval_plan(int nq, int n, bool& big, int& splits, int& tiles_per_split) {
-  big = (long)cdiv(nq, 128) * cdiv(n, 128) >= 384;
-  const int b = big ? 128 : 64;
+// (plan_splits: the split rule for b x b tiles, for a walk that has one geometry only — knn_search.hip)
+static void plan_splits(int nq, int n, int b, int& splits, int& tiles_per_split) {
   const int tiles_m = cdiv(nq, b), tiles_n = cdiv(n, b);
   int want = cdiv(512, tiles_m);
   if (want > tiles_n) want = tiles_n;
   tiles_per_split = cdiv(tiles_n, want);
   splits = cdiv(tiles_n, tiles_per_split);
+}
+static void retrieval_plan(int nq, int n, bool& big, int& splits, int& tiles_per_split) {
+  big = (long)cdiv(nq, 128) * cdiv(n, 128) >= 384;
+  plan_splits(nq, n, big ? 128 : 64, splits, tiles_per_split);
 }
 
 // A workspace handed out from the front in 16-byte steps.  Without a base it only adds up, so the constructor that carves a

@@ -110,15 +110,16 @@ class EmbeddingNet:
             self.encoded_training_data = pickle.load(f)
         return self.fit_knn(knn_k)
 
-    def fit_knn(self, knn_k=1, encoded_training_data=None):
+    def fit_knn(self, knn_k=1, encoded_training_data=None, algorithm='matrix'):
         """Build encoded_training_data['knn_classifier'] — the entry predict_knn reads (reference :134-137);
-        the reference leaves its construction to external code."""
+        the reference leaves its construction to external code.  algorithm: KNNClassifier's ('matrix', or 'stream' for the
+        search that forms no distance matrix)."""
         from .knn import KNNClassifier
         if encoded_training_data is not None:
             self.encoded_training_data = encoded_training_data
         d = self.encoded_training_data
         dev = next(self.base_model.parameters()).device if self.base_model is not None else None
-        d['knn_classifier'] = KNNClassifier(n_neighbors=knn_k, device=dev).fit(d['encodings'], d['labels'])
+        d['knn_classifier'] = KNNClassifier(n_neighbors=knn_k, device=dev, algorithm=algorithm).fit(d['encodings'], d['labels'])
         return d['knn_classifier']
 
     def predict_knn(self, image, with_top5=False):

@@ -780,6 +780,51 @@ def retrieval_reduce(rank, ks):
     return hits, n_valid, s
 
 
+# --------------------------------------------------------------------------- evaluation: k-nearest-neighbour search
+KNN_K_MAX = 128                                            # EMBNET_KNN_K_MAX (include/embnet.h)
+KNN_SELECT = {"all": 0, "same": 1, "other": 2}
+
+
+def knn_search(q, x=None, k=1, q_labels=None, x_labels=None, select="all", squared=True):
+    """The k nearest gallery items of every query, without the [nq,n] distance matrix (include/embnet.h, "k-nearest-neighbour
+    search").
+
+    q [nq,e]; x [n,e] the gallery, None: leave-one-out on q (column i is skipped for query i).  select: 'all' — every gallery
+    item (labels may be omitted); 'same' / 'other' — only items with the query's label / with another label (q_labels, and
+    x_labels with a gallery, are needed).  1 <= k <= KNN_K_MAX; k may exceed n.
+    -> (dist float32 [nq,k], idx int32 [nq,k], found int32 [nq]), on the device: ascending in (d2, index); found = min(k, eligible
+    items); entries from found on are idx = -1, dist = +inf.  squared=False: dist is the square root of the kernel's d2 (one
+    elementwise pass on the way out)."""
+    if select not in KNN_SELECT:
+        raise _lib.EmbnetError(f"knn_search: select must be one of {sorted(KNN_SELECT)} (got {select!r})")
+    k = int(k)
+    if not 1 <= k <= KNN_K_MAX:
+        raise _lib.EmbnetError(f"knn_search: k = {k} must be in [1, {KNN_K_MAX}]")
+    if q_labels is None:
+        if select != "all":
+            raise _lib.EmbnetError(f"knn_search: select={select!r} needs labels")
+        if x_labels is not None:
+            raise _lib.EmbnetError("knn_search: gallery labels without query labels")
+        q = _prep(q.detach())
+        self_exclude = x is None
+        x = q if self_exclude else _prep(x.detach())
+        if q.dim() != 2 or x.dim() != 2 or q.shape[0] == 0 or x.shape[0] == 0:
+            raise _lib.EmbnetError(f"knn_search: need non-empty [rows, e] blocks (got {tuple(q.shape)}, {tuple(x.shape)})")
+        if x.shape[1] != q.shape[1]:
+            raise _lib.EmbnetError(f"knn_search: widths differ ({q.shape[1]} vs {x.shape[1]})")
+        ql = xl = None
+        (nq, e), n = q.shape, x.shape[0]
+    else:
+        q, ql, x, xl, self_exclude, nq, n, e = _retrieval_blocks("knn_search", q, q_labels, x, x_labels)
+    lib = _lib.lib()
+    ws = _new((max(lib.embnet_knn_search_workspace_bytes(nq, n, k) // 8, 2),), q, torch.float64)
+    idx, found = _new((nq, k), q, torch.int32), _new((nq,), q, torch.int32)
+    d2 = _new((nq, k), q)
+    check(lib.embnet_knn_search(ptr(q), ptr(ql), nq, ptr(x), ptr(xl), n, e, int(self_exclude), KNN_SELECT[select], k, ptr(idx),
+                                ptr(d2), ptr(found), ptr(ws), ws.numel() * 8, stream()))
+    return (d2 if squared else d2.sqrt_()), idx, found
+
+
 # --------------------------------------------------------------------------- softmax pre-training head
 class _SoftmaxXent(torch.autograd.Function):
     @staticmethod

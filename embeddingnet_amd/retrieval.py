@@ -13,6 +13,10 @@ the positives with pos <= R, ap@r = (1 / R) * the sum of j / pos(p_j) over those
 (retrieval_map_metrics; ops.retrieval_positive_ranks keeps every positive's key in pass 1 and counts the negatives in front of
 each in pass 2, ops.retrieval_map_reduce sums).  Out of scope: a query set that is a strict subset of its gallery (leave-one-out
 needs queries and gallery to be the same rows in the same order), and classes above ops.R_MAX = 4096 positives per query.
+
+nearest_neighbors answers the other question — WHICH gallery items are nearest to a query: the k smallest (distance, index)
+per query among all items, the same-class ones or the other-class ones, from one walk of the same GEMM whose epilogue keeps
+each row's candidates in LDS (ops.knn_search, csrc/knn_search.hip).  No [nq, n] matrix is formed there either.
 """
 import numpy as np
 import torch
@@ -146,3 +150,46 @@ def retrieval_map_metrics(encodings, labels=None, gallery=None, gallery_labels=N
     out['ap@r'] = ap_at_r.cpu().numpy()
     out['r'] = r.cpu().numpy().astype(np.int32, copy=False)
     return out
+
+
+def nearest_neighbors(encodings, k, labels=None, gallery=None, gallery_labels=None, select='all', squared=False, device=None):
+    """-> {'distances': np.ndarray[float32] [nq, k], 'indices': np.ndarray[int32] [nq, k], 'found': np.ndarray[int32] [nq]}: the k
+    nearest gallery items of every query, nearest first, ties to the smaller gallery index.
+
+    The inputs are retrieval_metrics': arrays, tensors or the encodings dict; labels any hashables; gallery None = leave-one-out
+    within `encodings` (a query never returns itself).  select: 'all' — every gallery item (labels may be omitted); 'same' —
+    only items with the query's label; 'other' — only items with another label.  found[r] = min(k, eligible items of query r);
+    the entries of a row from found[r] on are index -1 and distance +inf.  1 <= k <= ops.KNN_K_MAX = 128.  The search runs on the
+    streaming distance walk (ops.knn_search): no [nq, n] matrix is formed, so the gallery can be a whole training set.
+
+    The k hardest negatives of every training sample, over the whole dataset:
+
+        hard = nearest_neighbors(train_encodings, 10, labels=train_labels, select='other')
+        hard['indices'][i]        # the 10 samples of other classes nearest to sample i, nearest first
+
+    and its nearest positives (a class with fewer than k + 1 members gives found < k):
+
+        pos = nearest_neighbors(train_encodings, 5, labels=train_labels, select='same')
+        pos['indices'][i, :pos['found'][i]]
+    """
+    who = "nearest_neighbors"
+    encodings, labels, gallery, gallery_labels = _unpack(encodings, labels, gallery, gallery_labels)
+    if select not in ops.KNN_SELECT:
+        raise ValueError(f"{who}: select must be one of {sorted(ops.KNN_SELECT)} (got {select!r})")
+    if int(k) != k or not 1 <= int(k) <= ops.KNN_K_MAX:
+        raise ValueError(f"{who}: k must be an integer in [1, {ops.KNN_K_MAX}] (got {k})")
+    if select == 'all' and gallery is not None and gallery_labels is None:
+        labels = None                                       # nothing to compare them with: the search reads no label
+    if labels is None:
+        if select != 'all':
+            raise ValueError(f"{who}: select={select!r} needs labels")
+        n_rows = encodings.shape[0] if hasattr(encodings, 'shape') else len(encodings)
+        dummy = [0] * n_rows
+        g_rows = 0 if gallery is None else (gallery.shape[0] if hasattr(gallery, 'shape') else len(gallery))
+        q, _, x, _, _ = _blocks(who, encodings, dummy, gallery, None if gallery is None else [0] * g_rows, device)
+        ql = xl = None
+    else:
+        q, ql, x, xl, _ = _blocks(who, encodings, labels, gallery, gallery_labels, device)
+    dist, idx, found = ops.knn_search(q, x, int(k), ql, xl, select=select, squared=squared)
+    return {'distances': dist.cpu().numpy(), 'indices': idx.cpu().numpy().astype(np.int32, copy=False),
+            'found': found.cpu().numpy().astype(np.int32, copy=False)}

@@ -284,6 +284,37 @@ int embnet_verification_all_pairs(const float* q, const int32_t* q_labels, int n
 int embnet_verification_values(const float* values, const int32_t* same, int m, float lo, float w, int bins,
                                uint64_t* hist_same, uint64_t* hist_other, void* stream);
 
+/* ---- k-nearest-neighbour search: the k nearest gallery items of every query, computed without the [nq,n] distance matrix
+ * (csrc/knn_search.hip).  Additions only: the ABI version stays 22.
+ *   Distance, order, exclusion: exactly those of embnet_retrieval_first_positive above — d2 = max(rn + cn - 2 acc, 0) from the
+ *     same fp32 chain, NaN -> +inf; lexicographic order on (d2, gallery index), ties to the smaller index (embnet_topk_smallest's
+ *     rule); self_exclude != 0 needs nq == n (row i of q is row i of x) and skips column i for query i.
+ *   Eligible columns of query r, by `select`: 0 every non-excluded column; 1 only those with x_labels[c] == q_labels[r] (nearest
+ *     positives); 2 only those with another label (hard negatives).  select == 0: the label arrays may be NULL (they are not
+ *     read); select != 0: both are required.
+ *   Outputs, 1 <= k <= EMBNET_KNN_K_MAX:
+ *       found[nq] int32   found[r] = min(k, number of eligible columns of r)
+ *       idx[nq,k] int32   the first found[r] entries: the eligible columns with the smallest (d2, index), ascending in that order
+ *       d2[nq,k] float    their squared distances
+ *     Entries from found[r] on are idx = -1, d2 = +inf.  A NaN distance is a real entry: d2 = +inf with its index >= 0, behind
+ *     every finite one.  k may exceed n (the rows are padded).
+ *   Properties.  One walk of the distance GEMM (2*nq*n*e FLOP) whose epilogue keeps the candidates of a tile's rows in LDS and
+ *     writes each row's k best per gallery split; a second kernel merges the splits.  Keys are unique, so the k smallest do not
+ *     depend on the order in which they are met: the outputs are bitwise reproducible across runs, streams and graph replay.
+ *     Workspace: >= embnet_knn_search_workspace_bytes(nq, n, k) bytes (0 for a refused shape), 16-byte aligned, no initialisation
+ *     needed, short -> -3; O(n + nq + splits * nq * k) bytes with splits * ceil(nq / 64) <= 512 + ceil(nq / 64) — never O(nq * n).
+ *     Both loaders (16-byte; scalar for unaligned pointers or e % 4 != 0) compute the same arithmetic; the walk runs on 64x64
+ *     tiles.  Refused with -1: a null pointer, nq, n, e <= 0, a block of 2 GiB or more, k outside [1, EMBNET_KNN_K_MAX], select
+ *     outside {0, 1, 2}, select != 0 without both label arrays, self_exclude with nq != n, an unaligned workspace.
+ *     No allocation and no synchronisation inside. */
+#define EMBNET_KNN_K_MAX 128
+size_t embnet_knn_search_workspace_bytes(int nq, int n, int k);
+int embnet_knn_search(const float* q, const int32_t* q_labels, int nq,
+                      const float* x, const int32_t* x_labels, int n, int e,
+                      int self_exclude, int select, int k,
+                      int32_t* idx, float* d2, int32_t* found,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone layers
  * Stand-ins for the Keras layers that backbones.py:19-121 instantiates (TensorFlow kernels in the
  * reference).  All NHWC fp32. */

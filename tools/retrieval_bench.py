@@ -32,7 +32,10 @@ first's.
 walks of ops.retrieval_first_positive at the same shape (the same GEMM under a minimum epilogue; `--floor-lib` names another
 build of the library to take them from) and to ops.cross_distances + torch.histc where the matrix fits: verification_mode.
 `--verification --contention`: the epilogue's terms priced one by one — a collapsed input whose pairs all share one bin, 64 / 1024 /
-4096 bins at equal atomics, one flush per tile against one per walk: verification_contention_mode."""
+4096 bins at equal atomics, one flush per tile against one per walk: verification_contention_mode.
+
+`--knn`: the streaming k-nearest-neighbour search (ops.knn_search) at the nq,n,e,k of `--knn-cases`, next to the matrix path
+(ops.cross_distances + ops.topk_smallest) where its matrix fits and to one plain walk of the same shape: knn_mode."""
 import argparse
 import json
 import os
@@ -314,6 +317,74 @@ def verification_contention_mode(args):
     return results
 
 
+def knn_mode(args):
+    """ops.knn_search (the top-k epilogue on the distance walk, select 'all') at each nq,n,e,k of `--knn-cases`, next to
+      (a) matrix_ms   ops.cross_distances(squared) + ops.topk_smallest(k) — what KNNClassifier(algorithm='matrix') runs — where
+                      k <= 64 and the [nq, n] fp32 matrix is at most `--max-matrix-gib`: wall time between events
+      (b) floor_us    ONE plain walk at the same shape: the counting pass of ops.retrieval_first_positive
+                      (retrieval_walk_kernel<2>: every tile, an integer count per row) on shuffled labels — the floor of what any
+                      epilogue on this walk can reach; it runs on the plan's own tiles (128x128 where they fill the chip), the
+                      search on 64x64: `floor_tile`
+    the legs alternating round by round in one process; medians of `--rounds`.  stream_ms: wall time between events around the
+    whole call (norms, walk, merge; workspace and outputs allocated inside); walk_us / merge_us / floor_us: device time of the
+    kernels from the library's event trace."""
+    from embeddingnet_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    cur = _lib.lib()
+    warm, wl = clustered(512, 64, dev, "shuffled")
+    ops.knn_search(warm, warm, 10), ops.topk_smallest(ops.cross_distances(warm, warm, squared=True), 10)
+    ops.retrieval_first_positive(warm, wl, warm, wl)
+    results = []
+    for nq, n, e, k in args.knn_cases:
+        x, xl = clustered(n, e, dev, "shuffled")
+        q, ql = clustered(nq, e, dev, "shuffled", seed=1)
+        both = k <= 64 and 4.0 * nq * n <= args.max_matrix_gib * 2 ** 30
+        run_s = lambda: ops.knn_search(q, x, k)
+        run_m = lambda: ops.topk_smallest(ops.cross_distances(q, x, squared=True), k)
+        run_f = lambda: ops.retrieval_first_positive(q, ql, x, xl)
+        run_s(), run_f()
+        if both:
+            run_m()
+            torch.cuda.empty_cache()
+        t_s, t_m, t_w, t_g, t_f = [], [], [], [], []
+        for _ in range(args.rounds):
+            t_s.append(timed(run_s)[0])
+            if both:
+                t_m.append(timed(run_m)[0])
+                torch.cuda.empty_cache()
+            per = _trace_us(cur, run_s)
+            t_w.append(per["knn_walk_kernel"])
+            t_g.append(per["knn_merge_kernel"])
+            t_f.append(_trace_us(cur, run_f)["retrieval_walk_kernel<2>"])
+        s_ms, w_us, f_us = float(np.median(t_s)), float(np.median(t_w)), float(np.median(t_f))
+        flop = 2.0 * nq * n * e
+        tiles_m = -(-nq // 64)
+        want = min(-(-512 // tiles_m), -(-n // 64))
+        tps = -(-(-(-n // 64)) // want)
+        res = {"mode": "knn", "nq": nq, "n": n, "e": e, "k": k, "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
+               "splits": -(-(-(-n // 64)) // tps), "tiles_per_split": tps,
+               "stream_ms": round(s_ms, 3), "stream_ms_min_max": [round(min(t_s), 3), round(max(t_s), 3)],
+               "walk_us": round(w_us, 1), "walk_us_min_max": [min(t_w), max(t_w)], "merge_us": round(float(np.median(t_g)), 1),
+               "walk_tflops": round(flop / (w_us * 1e-6) / 1e12, 2), "walk_share_of_peak": round(flop / (w_us * 1e-6) / PEAK, 3),
+               "floor_us": round(f_us, 1), "floor_us_min_max": [min(t_f), max(t_f)],
+               "floor_tile": 128 if (-(-nq // 128)) * (-(-n // 128)) >= 384 else 64, "walk_over_floor": round(w_us / f_us, 3),
+               "matrix_gib": round(4.0 * nq * n / 2 ** 30, 2)}
+        if both:
+            m_ms = float(np.median(t_m))
+            res.update({"matrix_ms": round(m_ms, 3), "matrix_ms_min_max": [round(min(t_m), 3), round(max(t_m), 3)],
+                        "stream_over_matrix": round(s_ms / m_ms, 3)})
+        print(json.dumps(res), flush=True)
+        results.append(res)
+        del x, xl, q, ql
+        torch.cuda.empty_cache()
+    return results
+
+
+def _knn_case(text):
+    nq, n, e, k = (int(v) for v in text.split(","))
+    return nq, n, e, k
+
+
 def write_out(args, results):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -335,9 +406,15 @@ def main():
     ap.add_argument("--contention", action="store_true",
                     help="--verification: price the epilogue's terms instead (see verification_contention_mode)")
     ap.add_argument("--floor-lib", default=None, help="--verification: another build of libembnet_hip.so for the floor leg")
+    ap.add_argument("--knn", action="store_true", help="time the streaming k-nearest-neighbour search (see knn_mode)")
+    ap.add_argument("--knn-cases", type=_knn_case, nargs="+", metavar="NQ,N,E,K",
+                    default=[(2048, 32768, 256, 10), (2048, 32768, 256, 64), (2048, 32768, 256, 128), (32768, 32768, 256, 10),
+                             (8192, 262144, 512, 10), (8192, 262144, 512, 128), (50000, 262144, 512, 10)])
     args = ap.parse_args()
     if args.rounds < 3:
         ap.error("--rounds must be at least 3")
+    if args.knn:
+        return write_out(args, knn_mode(args))
     if args.verification:
         return write_out(args, verification_contention_mode(args) if args.contention else verification_mode(args))
     if args.map:
