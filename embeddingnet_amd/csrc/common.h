@@ -29,6 +29,13 @@ inline int check_launch(const char* what) {
   return EMBNET_OK;
 }
 
+// A caller's workspace: 16-byte aligned and at least `need` bytes.  `what` is the entry point's name without `embnet_`.
+inline int check_workspace(const char* what, const void* workspace, size_t workspace_bytes, size_t need) {
+  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+  return EMBNET_OK;
+}
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- dynamic LDS beyond the 64 KB a launch gets by default ----------------
@@ -128,6 +135,28 @@ __device__ __forceinline__ T block_sum256(T v) {
   __syncthreads();
   if (threadIdx.x == 0) v = wave_s[0] + wave_s[1] + wave_s[2] + wave_s[3];
   return v;
+}
+// NV integer totals over a 256-thread workgroup from one pass of the caller's, the same in every thread.  ONCE per kernel: the
+// array belongs to the function and no barrier follows the reads, so a second call's writes could overtake the first's reads.
+template <int NV>
+__device__ __forceinline__ void block_total256(int (&v)[NV]) {
+  __shared__ int wave_t[NV][4];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) wave_t[j][threadIdx.x >> 6] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = wave_t[j][0] + wave_t[j][1] + wave_t[j][2] + wave_t[j][3];
+}
+__device__ __forceinline__ int block_total256(int v) {   // (scalar, not through the array form: the callers' kernels keep their code)
+  __shared__ int wave_t[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) wave_t[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return wave_t[0] + wave_t[1] + wave_t[2] + wave_t[3];
 }
 
 // Arrival ticket: whether the calling workgroup is the last of its grid to get here (every thread calls; the answer is

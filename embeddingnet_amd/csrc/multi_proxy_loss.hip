@@ -2,28 +2,22 @@
 // kc learnable centres per class.  Build-defined: the reference has no such loss.  Semantics: include/embnet.h.
 //
 //   X [n, e] fp32 embeddings, W [c kc, e] fp32 centres, class-major (row c' kc + j is centre j of class c'), y [n] int32 labels (any
-//   order; outside [0, c) = unlabelled).  q_r, D and S = fl(D q_r) are proxy_loss.hip's over the nb = c kc rows.
-//   It is CosFace's rectangle (anchors = samples, one wave owns one sample's row of D) with a TWO-LEVEL row: a lane owns the classes
-//   lane, lane + 64, ... and walks each class's kc consecutive columns itself, so pooling S_ic'j -> S'_ic' needs no cross-lane traffic;
-//   the margin softmax over the c pooled similarities is then CosFace's three passes (extrema, sum, weights), each of which pools again:
-//   a row may reach 16384 floats, and the pooled values have nowhere to wait.
+//   order; outside [0, c) = unlabelled).  q_r = (float)(1 / sqrt(sum_k w_rk^2)), D = fp32 dot products, S = fl(D q_r) over the
+//   nb = c kc rows.  One wave owns one sample's row of D.  The row is TWO-LEVEL: a lane owns the classes lane, lane + 64, ... and
+//   walks each class's kc columns itself, so pooling S_ic'j -> S'_ic' needs no cross-lane traffic; the margin softmax over the c
+//   pooled similarities is three passes (extrema, sum, weights), each of which pools again: a row may reach 16384 floats.  At kc = 1
+//   (and, for ArcFace, margin 0) the row gives CosFace's bits: tests/test_rect_loss_identities_gpu.py.
 //   prep launch (a wave per centre): q.   regulariser launch (SoftTriple with kc > 1 and tau > 0 only; a workgroup per class): the
 //     class's pairs in f64, H, a per-class partial, and the last workgroup to arrive adds the partials up to *reg.
-//   small path (it fits where e + c kc <= 4096 and n c kc e <= 2^25; `auto` takes it below 100 centres only: at 100, 300 and 1000
-//     centres the matrix path's forward measured 1.6 to 9 times faster), ONE more launch: a workgroup holds four
-//     samples and their four rows of D in LDS (pair_loss.h's anchor_dots), one wave per sample runs the body.
-//   matrix path, TWO more launches: D through embnet_dense_dgrad_f32 into the workspace, then a sweep: one wave per sample walks its
-//     row of D from L2.
-//   per-sample partials, the arrival ticket, pair_loss.h's fixed-order f64 reduction by the last workgroup; n_l is counted from the
-//     labels by every workgroup (integers, any order).
-//   backward: proxy_loss.hip's launches (proxy_loss.h) with c := c kc, and between Y and the projection one launch that adds the
-//     regulariser's term  sum_t H_rt q_t w_t  to Y in f64.
+//   forward: the small kernel or D + sweep (rect_loss.h's rect_launch), partials, ticket and fixed-order f64 reduction as in
+//     proxy_loss.hip.  The small path fits where e + c kc <= 4096 and n c kc e <= 2^25; `auto` takes it below 100 centres only: at
+//     100, 300 and 1000 centres the matrix path's forward measured 1.6 to 9 times faster.
+//   backward: the proxies' launches (rect_loss.h declares them) with c := c kc, and between Y and the projection one launch that adds
+//     the regulariser's term  sum_t H_rt q_t w_t  to Y in f64.
 // A label is compared, and used as an index (the sample's own class) only behind the range check that makes it a class index.  Nothing
 // is atomic in floating point, every reduction has a fixed order: bitwise reproducible.  No host synchronisation, no allocation.
 #include <math.h>
-#include "common.h"
-#include "pair_loss.h"
-#include "proxy_loss.h"
+#include "rect_loss.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
@@ -52,9 +46,9 @@ struct MProxyParams {
 struct MProxyPool { float s, zm, den; };                 // S', and SoftTriple's pooling maximum and denominator
 
 // ---- prep: q; one wave per centre -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PROXY_THREADS) void mproxy_prep_kernel(const float* __restrict__ w, int nb, int e, float* __restrict__ q) {
+__global__ __launch_bounds__(RECT_THREADS) void mproxy_prep_kernel(const float* __restrict__ w, int nb, int e, float* __restrict__ q) {
   const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
+  const int r = blockIdx.x * RECT_WG_ANCHORS + (threadIdx.x >> 6);
   if (r >= nb) return;                                   // wave-uniform
   const float qr = proxy_row_q(w + (long)r * e, e, lane);
   if (lane == 0) q[r] = qr;
@@ -66,19 +60,19 @@ __global__ __launch_bounds__(PROXY_THREADS) void mproxy_prep_kernel(const float*
 // H_st = H_ts = -coef / sqrt(2 + 1e-5 - 2 g), coef = tau / (c kc (kc - 1)); |g| <= (1 + 2^-24)^2, so the root's argument stays above
 // 9e-6.  Thread 0 adds the class's terms in pair order (s, t lexicographic); the last workgroup to arrive adds the classes' partials
 // (thread-strided, butterfly, waves in order) and writes *reg = (float)(coef total).
-__global__ __launch_bounds__(PROXY_THREADS) void mproxy_reg_kernel(const float* __restrict__ w, const float* __restrict__ q, int c, int kc,
+__global__ __launch_bounds__(RECT_THREADS) void mproxy_reg_kernel(const float* __restrict__ w, const float* __restrict__ q, int c, int kc,
                                                                    int e, float tau, float* __restrict__ h, double* __restrict__ part,
                                                                    int* ticket, float* __restrict__ reg) {
   __shared__ float tile[MPROXY_MAX_KC][65];
   __shared__ double term[MPROXY_MAX_PAIRS];
-  __shared__ double wsum[PROXY_THREADS / 64];
+  __shared__ double wsum[RECT_THREADS / 64];
   const int tid = threadIdx.x, cl = blockIdx.x, r0 = cl * kc;
   const int pairs = kc * (kc - 1) / 2;
   int ps[2], pt[2];
   double acc[2] = {0.0, 0.0};
 #pragma unroll
   for (int u = 0; u < 2; ++u) {                          // pair tid + 256 u -> (s, t), s < t
-    int p = tid + PROXY_THREADS * u, s = 0;
+    int p = tid + RECT_THREADS * u, s = 0;
     ps[u] = pt[u] = -1;
     if (p < pairs) {
       while (p >= kc - 1 - s) { p -= kc - 1 - s; ++s; }
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(PROXY_THREADS) void mproxy_reg_kernel(const float* 
     }
   }
   for (int k0 = 0; k0 < e; k0 += 64) {
-    for (int i = tid; i < kc * 64; i += PROXY_THREADS) {
+    for (int i = tid; i < kc * 64; i += RECT_THREADS) {
       const int r = i >> 6, kk = i & 63;
       tile[r][kk] = k0 + kk < e ? w[(long)(r0 + r) * e + k0 + kk] : 0.f;
     }
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(PROXY_THREADS) void mproxy_reg_kernel(const float* 
     if (ps[u] >= 0) {
       const double g = (double)q[r0 + ps[u]] * (double)q[r0 + pt[u]] * acc[u];
       const double arg = 2.0 + MPROXY_REG_EPS - 2.0 * g;
-      term[tid + PROXY_THREADS * u] = sqrt(fmax(0.0, arg));
+      term[tid + RECT_THREADS * u] = sqrt(fmax(0.0, arg));
       const float hv = (float)(-coef / sqrt(arg));
       h[((long)r0 + ps[u]) * kc + pt[u]] = hv;
       h[((long)r0 + pt[u]) * kc + ps[u]] = hv;
@@ -120,13 +114,13 @@ __global__ __launch_bounds__(PROXY_THREADS) void mproxy_reg_kernel(const float* 
   }
   if (!last_workgroup_to_arrive(ticket)) return;
   double s = 0.0;
-  for (int i = tid; i < c; i += PROXY_THREADS) s += __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int i = tid; i < c; i += RECT_THREADS) s += __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   s = wave_sum(s);
   if ((tid & 63) == 0) wsum[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
     double t = 0.0;
-    for (int wv = 0; wv < PROXY_THREADS / 64; ++wv) t += wsum[wv];
+    for (int wv = 0; wv < RECT_THREADS / 64; ++wv) t += wsum[wv];
     *reg = (float)(coef * t);
   }
 }
@@ -148,16 +142,9 @@ __global__ __launch_bounds__(256) void mproxy_bwd_reg_kernel(const float* __rest
 // ---- the row body -----------------------------------------------------------------------------------------------------------------------
 // labelled samples, the same in every thread of the workgroup
 __device__ __forceinline__ int mproxy_labelled(const int32_t* __restrict__ labels, int n, int c) {
-  __shared__ int sl[PROXY_WG_ANCHORS];
   int l = 0;
-  for (int i = threadIdx.x; i < n; i += PROXY_THREADS) l += (unsigned)labels[i] < (unsigned)c;
-  l = wave_sum(l);
-  if ((threadIdx.x & 63) == 0) sl[threadIdx.x >> 6] = l;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < PROXY_WG_ANCHORS; ++w) t += sl[w];
-  return t;
+  for (int i = threadIdx.x; i < n; i += RECT_THREADS) l += (unsigned)labels[i] < (unsigned)c;
+  return block_total256(l);
 }
 
 // One class's kc similarities pooled into S' (one thread).  ArcFace: the maximum.  SoftTriple: z_j = fl(S_j / gamma), zm = max z,
@@ -267,7 +254,7 @@ __device__ __forceinline__ void mproxy_finish(const MProxyParams& P) {
   if (!last_workgroup_to_arrive(P.ticket)) return;
   double ts[1];
   int tc[3];
-  if (reduce_partials<PROXY_THREADS>(P.part_loss, P.part_cnt, P.n, ts, tc)) {
+  if (reduce_partials<RECT_THREADS>(P.part_loss, P.part_cnt, P.n, ts, tc)) {
     P.counts[0] = tc[0];                                 // labelled samples: at most 4096
     P.counts[1] = tc[1];
     P.counts[2] = tc[2];
@@ -279,26 +266,26 @@ __device__ __forceinline__ void mproxy_finish(const MProxyParams& P) {
 }
 
 // ---- forward, small path: grid = ceil(n / 4) workgroups -----------------------------------------------------------------------------
-__global__ __launch_bounds__(PROXY_THREADS) void mproxy_small_fwd_kernel(MProxyParams P) {
-  __shared__ __attribute__((aligned(16))) float lds[PROXY_LDS_FLOATS];
+__global__ __launch_bounds__(RECT_THREADS) void mproxy_small_fwd_kernel(MProxyParams P) {
+  __shared__ __attribute__((aligned(16))) float lds[RECT_LDS_FLOATS];
   const int n = P.n, nb = P.c * P.kc, e = P.e;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a0 = blockIdx.x * PROXY_WG_ANCHORS;
+  const int a0 = blockIdx.x * RECT_WG_ANCHORS;
   const int nl = mproxy_labelled(P.labels, n, P.c);
   float* A = lds;                                        // [4][e] the workgroup's samples (zero rows past n)
-  float* D = lds + PROXY_WG_ANCHORS * e;                 // [4][nb] their rows of D
-  for (int i = tid; i < PROXY_WG_ANCHORS * e; i += PROXY_THREADS) A[i] = a0 + i / e < n ? P.emb[(long)a0 * e + i] : 0.f;
+  float* D = lds + RECT_WG_ANCHORS * e;                 // [4][nb] their rows of D
+  for (int i = tid; i < RECT_WG_ANCHORS * e; i += RECT_THREADS) A[i] = a0 + i / e < n ? P.emb[(long)a0 * e + i] : 0.f;
   __syncthreads();
-  anchor_dots<PROXY_WG_ANCHORS, PROXY_WG_ANCHORS, PairDotBody>(A, PROXY_WG_ANCHORS, P.centres, nb, e, D);
+  anchor_dots<RECT_WG_ANCHORS, RECT_WG_ANCHORS, PairDotBody>(A, RECT_WG_ANCHORS, P.centres, nb, e, D);
   __syncthreads();
   if (a0 + wave < n) mproxy_row(D + wave * nb, P, a0 + wave, nl, lane);
   mproxy_finish(P);
 }
 
 // ---- forward, matrix path: grid = ceil(n / 4) workgroups, one wave walks one row of D from L2 ---------------------------------------
-__global__ __launch_bounds__(PROXY_THREADS) void mproxy_sweep_kernel(MProxyParams P) {
+__global__ __launch_bounds__(RECT_THREADS) void mproxy_sweep_kernel(MProxyParams P) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int a = blockIdx.x * PROXY_WG_ANCHORS + wave;
+  const int a = blockIdx.x * RECT_WG_ANCHORS + wave;
   const int nl = mproxy_labelled(P.labels, P.n, P.c);
   if (a < P.n) mproxy_row(P.d + (long)a * P.c * P.kc, P, a, nl, lane);
   mproxy_finish(P);
@@ -311,8 +298,7 @@ inline bool mproxy_range_ok(int n, int c, int kc, int e) {
 }
 
 inline bool mproxy_small_fits(int n, int c, int kc, int e) {
-  const long nb = (long)c * kc;
-  return PROXY_WG_ANCHORS * (e + nb) <= PROXY_LDS_FLOATS && (long)n * nb * e <= PROXY_SMALL_MACS;
+  return rect_small_fits(n, (long)c * kc, e);
 }
 
 // [16 B ticket][n f64 partial losses][n int4 partial counts][c f64 regulariser partials][n*nb f32 D][nb*e f64 Y], nb = c kc
@@ -337,10 +323,7 @@ inline int mproxy_check_common(const char* what, bool pointers, int n, int c, in
   EMBNET_CHECK_ARG(kc >= 1 && kc <= MPROXY_MAX_KC, "%s: kc=%d outside [1, %d]", what, kc, MPROXY_MAX_KC);
   EMBNET_CHECK_ARG((long)c * kc <= PROXY_MAX_C, "%s: c*kc=%ld above %d", what, (long)c * kc, PROXY_MAX_C);
   EMBNET_CHECK_ARG(e >= 1 && e <= PROXY_MAX_E, "%s: e=%d outside [1, %d]", what, e, PROXY_MAX_E);
-  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-  const size_t need = MProxyWorkspace(n, c, kc, e).bytes;
-  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-  return EMBNET_OK;
+  return check_workspace(what, workspace, workspace_bytes, MProxyWorkspace(n, c, kc, e).bytes);
 }
 
 }  // namespace embnet
@@ -397,23 +380,14 @@ extern "C" int embnet_multi_proxy_loss_fwd(const float* emb, const float* centre
   P.ticket = (int*)ws; P.part_loss = (double*)(ws + L.part_loss); P.part_cnt = (int4*)(ws + L.part_cnt); P.d = d;
   {
     EMBNET_TRACE("embnet::mproxy_prep_kernel", TRACE_BYTES, 4.0 * nb * e + 4.0 * nb, stream);
-    mproxy_prep_kernel<<<cdiv(nb, PROXY_WG_ANCHORS), PROXY_THREADS, 0, s>>>(centres, nb, e, q);
+    mproxy_prep_kernel<<<cdiv(nb, RECT_WG_ANCHORS), RECT_THREADS, 0, s>>>(centres, nb, e, q);
   }
   if (has_reg) {
     EMBNET_TRACE_FLOP("embnet::mproxy_reg_kernel", 1.0 * c * kc * (kc - 1) * e, 4.0 * nb * e + 4.0 * nb * kc, stream);
-    mproxy_reg_kernel<<<c, PROXY_THREADS, 0, s>>>(centres, q, c, kc, e, tau, reg_h, (double*)(ws + L.part_reg), (int*)ws, reg);
+    mproxy_reg_kernel<<<c, RECT_THREADS, 0, s>>>(centres, q, c, kc, e, tau, reg_h, (double*)(ws + L.part_reg), (int*)ws, reg);
   }
-  const int grid = cdiv(n, PROXY_WG_ANCHORS);
-  if (path == EMBNET_MPROXY_SMALL) {
-    EMBNET_TRACE_FLOP("embnet::mproxy_small_fwd_kernel", 2.0 * n * nb * e, 4.0 * e * (n + (double)grid * nb) + 4.0 * n * nb, stream);
-    mproxy_small_fwd_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
-    return check_launch(what);
-  }
-  const int rg = embnet_dense_dgrad_f32(emb, centres, d, n, nb, e, stream);
-  if (rg != EMBNET_OK) return rg;
-  EMBNET_TRACE("embnet::mproxy_sweep_kernel", TRACE_BYTES, 16.0 * n * nb, stream);
-  mproxy_sweep_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
-  return check_launch(what);
+  return rect_launch(what, mproxy_small_fwd_kernel, "embnet::mproxy_small_fwd_kernel", mproxy_sweep_kernel,
+                     "embnet::mproxy_sweep_kernel", path == EMBNET_MPROXY_SMALL, P, emb, centres, d, n, nb, e, stream);
 }
 
 extern "C" int embnet_multi_proxy_loss_bwd(const float* emb, const float* centres, int n, int c, int kc, int e, const float* pair_g,

@@ -29,9 +29,10 @@
 // pair_sweep_fwd / pair_bwd, and pair_launch launches them.  Nothing is atomic in floating point, every reduction has a fixed
 // order; no host synchronisation, no allocation.
 //
-// Four pieces here know nothing of P x K and serve proxy_loss.hip's rectangle as well: the arrival ticket (common.h's
-// last_workgroup_to_arrive), reduce_partials (the last workgroup's fixed-order totals), anchor_dots (rows of B against a few
-// anchors in LDS) and mm_f64_tile (the 32 x 32 f64 matrix-instruction product).  The P x K skeleton proper is the Body, PairParams,
+// Four pieces here know nothing of P x K: the arrival ticket (common.h's last_workgroup_to_arrive), reduce_partials (the last
+// workgroup's fixed-order totals), anchor_dots (rows of B against a few anchors in LDS) and mm_f64_tile (the 32 x 32 f64
+// matrix-instruction product).  rect_loss.h builds the rectangle losses' skeleton (a batch against proxies, centres or the memory
+// bank) on the same four.  The P x K skeleton proper is the Body, PairParams,
 // pair_class_fwd / pair_sweep_fwd / pair_finish / pair_bwd, the fit rule, the workspace layout, the checks and pair_launch.
 #pragma once
 #include "common.h"
@@ -357,9 +358,7 @@ inline int pair_check_path_and_workspace(const char* what, int p, int k, int e, 
   EMBNET_CHECK_ARG(path >= 0 && path <= PAIR_MATRIX, "%s: unknown path %d", what, path);
   EMBNET_CHECK_ARG(path != PAIR_PER_CLASS || pair_class_path_fits(p, k, e), "%s: p=%d k=%d e=%d does not fit the per-class path",
                    what, p, k, e);
-  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-  return EMBNET_OK;
+  return check_workspace(what, workspace, workspace_bytes, need);
 }
 
 inline int pair_check_bwd(const char* what, bool pointers, int n, int e) {

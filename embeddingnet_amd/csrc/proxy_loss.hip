@@ -6,25 +6,19 @@
 //   Both losses are ONE rectangle seen from its two sides: anchors A [na, e] meet others B [nb, e], one wave owns one anchor's row.
 //     Proxy-Anchor: the anchors are the proxies (na = c, nb = n), G is [c][n];  a row's positives are the samples of its class.
 //     CosFace:      the anchors are the samples (na = n, nb = c), G is [n][c];  a row's positive is the sample's own class.
-//   prep launch (a wave per class): q, the class sizes cnt[c] (every workgroup of the forward adds them up to |C+| and n_l:
-//     integers, any order).
+//   prep launch (a wave per class): q, the class sizes cnt[c] (every workgroup of the forward adds them up to |C+| and n_l).
 //   small path (e + max(n, c) <= 4096 and n c e <= 2^25), ONE more launch: a workgroup holds four anchors and their four rows of D
-//     in LDS (pair_loss.h's anchor_dots), one wave per anchor runs the body.
-//   matrix path, TWO more launches: D through embnet_dense_dgrad_f32 (the exact-fp32 matrix-instruction GEMM, a k-ordered chain
-//     per element) into the workspace, then a sweep: one wave per anchor walks its row of D from L2 in three passes (extrema, sums,
-//     weights).  A CosFace row reaches 16384 floats = 64 KiB, four times pair_sweep_fwd's per-wave LDS row: it is not staged at all.
+//     in LDS (pair_loss.h's anchor_dots); matrix path, TWO more (rect_loss.h's rect_launch): D into the workspace, then a sweep from
+//     L2 (a CosFace row reaches 16384 floats: not staged).  One wave per anchor runs the body in three passes (extrema, sums, weights).
 //   per-anchor partials, the arrival ticket, pair_loss.h's fixed-order f64 reduction by the last workgroup.
-//   backward, three launches (four with demb's class sum split, see proxy_bwd_split) on the f64 matrix instructions
-//     (pair_loss.h's mm_f64_tile): demb = g Q^(T) W,
-//     Y = G^(T) X in f64 into the workspace, then a wave per class: dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c), every output
-//     one fp32 rounding of an f64 expression.
+//   backward, three launches (four with demb's class sum split, rect_loss.h's split product) on the f64 matrix instructions:
+//     demb = g Q^(T) W, Y = G^(T) X in f64 into the workspace, then a wave per class: dproxies_c = g q_c (Y_c - q_c^2 (Y_c . w_c) w_c),
+//     every output one fp32 rounding of an f64 expression.
 // A label is compared, and used as an index (CosFace: the sample's own column) only behind the range check that makes it a class
 // index; an unlabelled value addresses nothing.  Nothing is atomic in floating point, every reduction has a fixed order: bitwise
 // reproducible.  No host synchronisation, no allocation: capturable in a graph.
 #include <math.h>
-#include "common.h"
-#include "pair_loss.h"
-#include "proxy_loss.h"
+#include "rect_loss.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
@@ -46,12 +40,12 @@ struct ProxyParams {
 
 struct ProxyAnchorOut { float lp, ln; int has, viol; };
 
-// ---- prep: q (proxy_loss.h's proxy_row_q) and the class sizes; one wave per class; the labels are counted lane-strided (integers) --
-__global__ __launch_bounds__(PROXY_THREADS) void proxy_prep_kernel(const float* __restrict__ w, const int32_t* __restrict__ labels,
+// ---- prep: q (rect_loss.h's proxy_row_q) and the class sizes; one wave per class; the labels are counted lane-strided (integers) --
+__global__ __launch_bounds__(RECT_THREADS) void proxy_prep_kernel(const float* __restrict__ w, const int32_t* __restrict__ labels,
                                                                    int n, int c, int e, float* __restrict__ q,
                                                                    int32_t* __restrict__ cnt) {
   const int lane = threadIdx.x & 63;
-  const int cl = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
+  const int cl = blockIdx.x * RECT_WG_ANCHORS + (threadIdx.x >> 6);
   if (cl >= c) return;                                   // wave-uniform
   const float qc = proxy_row_q(w + (long)cl * e, e, lane);
   int m = 0;
@@ -65,16 +59,11 @@ __global__ __launch_bounds__(PROXY_THREADS) void proxy_prep_kernel(const float* 
 
 // (classes with a sample, labelled samples), the same in every thread of the workgroup
 __device__ __forceinline__ int2 proxy_totals(const int32_t* __restrict__ cnt, int c) {
-  __shared__ int sp[PROXY_WG_ANCHORS], sl[PROXY_WG_ANCHORS];
-  int p = 0, l = 0;
-  for (int i = threadIdx.x; i < c; i += PROXY_THREADS) { const int v = cnt[i]; p += v > 0; l += v; }
-  p = wave_sum(p); l = wave_sum(l);
-  if ((threadIdx.x & 63) == 0) { sp[threadIdx.x >> 6] = p; sl[threadIdx.x >> 6] = l; }
-  __syncthreads();
-  int tp = 0, tl = 0;
-#pragma unroll
-  for (int w = 0; w < PROXY_WG_ANCHORS; ++w) { tp += sp[w]; tl += sl[w]; }
-  return make_int2(tp, tl);
+  int p = 0, l = 0;                                      // both from one pass over the class sizes
+  for (int i = threadIdx.x; i < c; i += RECT_THREADS) { const int v = cnt[i]; p += v > 0; l += v; }
+  int t[2] = {p, l};
+  block_total256(t);
+  return make_int2(t[0], t[1]);
 }
 
 // one rounding order: t = fl(c fl(s + o)); monotone in s for either sign of c
@@ -175,7 +164,7 @@ __device__ __forceinline__ void proxy_finish(const ProxyParams& P, int2 tot) {
   if (!last_workgroup_to_arrive(P.ticket)) return;
   double ts[2];
   int tc[2];
-  if (reduce_partials<PROXY_THREADS>((const double*)P.part_loss, P.part_cnt, P.na, ts, tc)) {
+  if (reduce_partials<RECT_THREADS>((const double*)P.part_loss, P.part_cnt, P.na, ts, tc)) {
     P.counts[0] = tc[0];                                 // |C+| or n_l: at most 16384
     P.counts[1] = tot.y;                                 // labelled samples: at most 4096
     P.counts[2] = tc[1];
@@ -184,91 +173,67 @@ __device__ __forceinline__ void proxy_finish(const ProxyParams& P, int2 tot) {
 }
 
 // ---- forward, small path: grid = ceil(na / 4) workgroups -------------------------------------------------------------------------
-__global__ __launch_bounds__(PROXY_THREADS) void proxy_small_fwd_kernel(ProxyParams P) {
-  __shared__ __attribute__((aligned(16))) float lds[PROXY_LDS_FLOATS];
+__global__ __launch_bounds__(RECT_THREADS) void proxy_small_fwd_kernel(ProxyParams P) {
+  __shared__ __attribute__((aligned(16))) float lds[RECT_LDS_FLOATS];
   const int na = P.na, nb = P.nb, e = P.e;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a0 = blockIdx.x * PROXY_WG_ANCHORS;
+  const int a0 = blockIdx.x * RECT_WG_ANCHORS;
   const int2 tot = proxy_totals(P.cnt, P.c);
   float* A = lds;                                        // [4][e] the workgroup's anchors (zero rows past na)
-  float* D = lds + PROXY_WG_ANCHORS * e;                 // [4][nb] their rows of D
-  for (int i = tid; i < PROXY_WG_ANCHORS * e; i += PROXY_THREADS) A[i] = a0 + i / e < na ? P.anchors[(long)a0 * e + i] : 0.f;
+  float* D = lds + RECT_WG_ANCHORS * e;                 // [4][nb] their rows of D
+  for (int i = tid; i < RECT_WG_ANCHORS * e; i += RECT_THREADS) A[i] = a0 + i / e < na ? P.anchors[(long)a0 * e + i] : 0.f;
   __syncthreads();
-  anchor_dots<PROXY_WG_ANCHORS, PROXY_WG_ANCHORS, PairDotBody>(A, PROXY_WG_ANCHORS, P.others, nb, e, D);   // rows past na are zero
+  anchor_dots<RECT_WG_ANCHORS, RECT_WG_ANCHORS, PairDotBody>(A, RECT_WG_ANCHORS, P.others, nb, e, D);   // rows past na are zero
   __syncthreads();
   if (a0 + wave < na) proxy_row(D + wave * nb, P, a0 + wave, tot, lane);
   proxy_finish(P, tot);
 }
 
 // ---- forward, matrix path: grid = ceil(na / 4) workgroups, one wave walks one row of D from L2 -----------------------------------
-__global__ __launch_bounds__(PROXY_THREADS) void proxy_sweep_kernel(ProxyParams P) {
+__global__ __launch_bounds__(RECT_THREADS) void proxy_sweep_kernel(ProxyParams P) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int a = blockIdx.x * PROXY_WG_ANCHORS + wave;
+  const int a = blockIdx.x * RECT_WG_ANCHORS + wave;
   const int2 tot = proxy_totals(P.cnt, P.c);
   if (a < P.na) proxy_row(P.d + (long)a * P.nb, P, a, tot, lane);
   proxy_finish(P, tot);
 }
 
 // ---- backward: rectangular products on pair_loss.h's mm_f64_tile ------------------------------------------------------------------
-// M(r, j) = G[r][j] or, TRANS, G[j][r]; SCALE: times qv[j].  OutT float: one fp32 rounding of g * sum (g = *upstream, NULL = 1);
-// double: the sum itself.  The sum runs over j in [jb, je).
-template <class OutT>
-struct ProxyMmOut {
-  static constexpr bool ROW_SUM = false;
-  const float* upstream; OutT* out;
-  __device__ double begin() const { return upstream ? (double)*upstream : 1.0; }
-  __device__ void put(double g, long at, double y, double) const {
-    if constexpr (sizeof(OutT) == 4) out[at] = (float)(g * y);
-    else out[at] = y;
-  }
-};
-
-template <bool TRANS, bool SCALE, class OutT>
-__device__ __forceinline__ void proxy_mm(const float* __restrict__ G, const float* __restrict__ qv, const float* __restrict__ B, int R,
-                                         int J, int e, int jb, int je, const float* __restrict__ upstream, OutT* __restrict__ out) {
-  mm_f64_tile<TRANS ? MM_TRANS : MM_DIRECT, SCALE>(G, qv, B, R, J, e, jb, je, ProxyMmOut<OutT>{upstream, out});
-}
-
+// The left operand is G[r][j] or, TRANS, G[j][r]; demb's is scaled by q[j].  demb = (float)(g sum), g = *upstream (NULL = 1).
 template <bool TRANS>
 __global__ __launch_bounds__(256) void proxy_bwd_emb_kernel(const float* __restrict__ G, const float* __restrict__ q,
                                                             const float* __restrict__ proxies, int n, int c, int e,
                                                             const float* __restrict__ upstream, float* __restrict__ demb) {
-  proxy_mm<TRANS, true, float>(G, q, proxies, n, c, e, 0, c, upstream, demb);
+  mm_f64_tile<TRANS ? MM_TRANS : MM_DIRECT, true>(G, q, proxies, n, c, e, 0, c, RectScaledOut<false>{upstream, n, demb});
 }
 
 // Few samples against many classes leave the grid above ceil(n/32) ceil(e/32) workgroups with c / 32 serial rounds each: the
-// classes are then split over blockIdx.z in chunks of `jchunk` (a multiple of 32), every slice writes its f64 sums, and
-// proxy_bwd_emb_sum_kernel adds the slices in slice order, scales by g and rounds once.
+// classes are then split (rect_loss.h's split product).
 template <bool TRANS>
 __global__ __launch_bounds__(256) void proxy_bwd_emb_part_kernel(const float* __restrict__ G, const float* __restrict__ q,
                                                                  const float* __restrict__ proxies, int n, int c, int e, int jchunk,
                                                                  double* __restrict__ part) {
-  const int jb = blockIdx.z * jchunk;
-  proxy_mm<TRANS, true, double>(G, q, proxies, n, c, e, jb, min(c, jb + jchunk), nullptr, part + (long)blockIdx.z * n * e);
+  rect_mm_part<TRANS ? MM_TRANS : MM_DIRECT, true>(G, q, proxies, n, c, e, jchunk, part);
 }
 
 __global__ __launch_bounds__(256) void proxy_bwd_emb_sum_kernel(const double* __restrict__ part, int splits, long ne,
                                                                 const float* __restrict__ upstream, float* __restrict__ demb) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= ne) return;
-  double s = 0.0;
-  for (int z = 0; z < splits; ++z) s += part[z * ne + i];
-  demb[i] = (float)((upstream ? (double)*upstream : 1.0) * s);
+  rect_mm_sum<false>(part, splits, ne, 1, upstream, demb);
 }
 
 template <bool TRANS>
 __global__ __launch_bounds__(256) void proxy_bwd_y_kernel(const float* __restrict__ G, const float* __restrict__ emb, int n, int c,
                                                           int e, double* __restrict__ y) {
-  proxy_mm<TRANS, false, double>(G, nullptr, emb, c, n, e, 0, n, nullptr, y);
+  mm_f64_tile<TRANS ? MM_TRANS : MM_DIRECT, false>(G, nullptr, emb, c, n, e, 0, n, RectF64Out{y});
 }
 
 // a wave per class: t = Y_c . w_c (lane-strided f64 chains + butterfly), dproxies_c = g q (Y_c - q^2 t w_c)
-__global__ __launch_bounds__(PROXY_THREADS) void proxy_bwd_proxies_kernel(const double* __restrict__ y, const float* __restrict__ proxies,
-                                                                          const float* __restrict__ q, int c, int e,
-                                                                          const float* __restrict__ upstream,
-                                                                          float* __restrict__ dproxies) {
+__global__ __launch_bounds__(RECT_THREADS) void proxy_bwd_proxies_kernel(const double* __restrict__ y, const float* __restrict__ proxies,
+                                                                         const float* __restrict__ q, int c, int e,
+                                                                         const float* __restrict__ upstream,
+                                                                         float* __restrict__ dproxies) {
   const int lane = threadIdx.x & 63;
-  const int cl = blockIdx.x * PROXY_WG_ANCHORS + (threadIdx.x >> 6);
+  const int cl = blockIdx.x * RECT_WG_ANCHORS + (threadIdx.x >> 6);
   if (cl >= c) return;                                   // wave-uniform
   const double* yr = y + (long)cl * e;
   const float* wr = proxies + (long)cl * e;
@@ -286,8 +251,8 @@ inline bool proxy_range_ok(int n, int c, int e) {
   return n >= 2 && n <= PROXY_MAX_N && c >= 2 && c <= PROXY_MAX_C && e >= 1 && e <= PROXY_MAX_E;
 }
 
-inline bool proxy_small_fits(int n, int c, int e) {
-  return PROXY_WG_ANCHORS * (e + (n > c ? n : c)) <= PROXY_LDS_FLOATS && (long)n * c * e <= PROXY_SMALL_MACS;
+inline bool proxy_small_fits(int n, int c, int e) {       // either side of the rectangle as the anchors
+  return rect_small_fits(n < c ? n : c, n > c ? n : c, e);
 }
 
 // [16 B ticket][c int32 class sizes][m double2 partial losses][m int4 partial counts][c*n f32 D][c*e f64 Y], m = max(n, c)
@@ -304,44 +269,29 @@ struct ProxyWorkspace {
   }
 };
 
-// demb's class split: none while the unsplit grid has 1024 workgroups or a slice would hold fewer than 256 classes; the slices'
-// f64 sums (splits n e doubles) live where Y will be written afterwards (c e doubles), so splits n <= c.  -> (splits, jchunk)
-inline void proxy_bwd_split(int n, int c, int e, int& splits, int& jchunk) {
-  const int base = cdiv(n, 32) * cdiv(e, 32);
-  int s = cdiv(1024, base);
-  if (s > c / 256) s = c / 256;
-  if (s > c / n) s = c / n;
-  if (s < 1) s = 1;
-  jchunk = cdiv(cdiv(c, s), 32) * 32;
-  splits = cdiv(c, jchunk);
-}
-
 // The backward's launches on checked arguments, in two steps so that multi_proxy_loss.hip (the CosFace case over c kc rows) can add its
-// regulariser's term to Y between them.  products: demb, and Y = G^(T) X in f64 into y [c][e] (which first holds the slices' sums
-// where demb's class sum is split: proxy_bwd_split).  pa: G is [c][n] (transposed for demb's rows, direct for Y's), else [n][c].
+// regulariser's term to Y between them.  products: demb, and Y = G^(T) X in f64 into y [c][e].  pa: G is [c][n] (transposed for
+// demb's rows, direct for Y's), else [n][c].  demb's class sum is split towards 1024 workgroups; the slices' f64 sums (splits n e
+// doubles) live where Y is written afterwards (c e doubles), so splits n <= c.
 void proxy_bwd_products(const float* emb, const float* proxies, int n, int c, int e, bool pa, const float* pair_g, const float* q,
                         const float* upstream, float* demb, double* y, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const double flop = 2.0 * n * c * e, gbytes = 4.0 * n * c;
-  const dim3 ge(cdiv(n, 32), cdiv(e, 32)), gy(cdiv(c, 32), cdiv(e, 32));
+  const double flop = 2.0 * n * c * e, gbytes = 4.0 * n * c, ebytes = gbytes + 4.0 * e * (c + n);
   int splits, jchunk;
-  proxy_bwd_split(n, c, e, splits, jchunk);
-  {
-    EMBNET_TRACE_FLOP(splits == 1 ? "embnet::proxy_bwd_emb_kernel" : "embnet::proxy_bwd_emb_part_kernel", flop, gbytes + 4.0 * e * (c + n), stream);
-    if (splits == 1) {
-      if (pa) proxy_bwd_emb_kernel<true><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
-      else proxy_bwd_emb_kernel<false><<<ge, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
-    } else {                                             // the slices' sums sit in Y's place until the next launch but one writes Y
-      const dim3 gz(ge.x, ge.y, splits);
-      if (pa) proxy_bwd_emb_part_kernel<true><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
-      else proxy_bwd_emb_part_kernel<false><<<gz, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
-    }
-  }
-  if (splits > 1) {
-    EMBNET_TRACE("embnet::proxy_bwd_emb_sum_kernel", TRACE_BYTES, 8.0 * splits * n * e + 4.0 * n * e, stream);
-    proxy_bwd_emb_sum_kernel<<<cdiv((long)n * e, 256), 256, 0, s>>>(y, splits, (long)n * e, upstream, demb);
-  }
+  rect_mm_split(n, c, e, 1024, c / n, splits, jchunk);
+  rect_mm_launch({"embnet::proxy_bwd_emb_kernel", "embnet::proxy_bwd_emb_part_kernel", "embnet::proxy_bwd_emb_sum_kernel"}, flop, ebytes,
+                 ebytes, n, e, splits, stream,
+                 [&](dim3 grid) {
+                   if (pa) proxy_bwd_emb_kernel<true><<<grid, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+                   else proxy_bwd_emb_kernel<false><<<grid, 256, 0, s>>>(pair_g, q, proxies, n, c, e, upstream, demb);
+                 },
+                 [&](dim3 grid) {
+                   if (pa) proxy_bwd_emb_part_kernel<true><<<grid, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+                   else proxy_bwd_emb_part_kernel<false><<<grid, 256, 0, s>>>(pair_g, q, proxies, n, c, e, jchunk, y);
+                 },
+                 [&](int grid) { proxy_bwd_emb_sum_kernel<<<grid, 256, 0, s>>>(y, splits, (long)n * e, upstream, demb); });
   EMBNET_TRACE_FLOP("embnet::proxy_bwd_y_kernel", flop, gbytes + 4.0 * e * n + 8.0 * e * c, stream);
+  const dim3 gy(cdiv(c, 32), cdiv(e, 32));
   if (pa) proxy_bwd_y_kernel<false><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
   else proxy_bwd_y_kernel<true><<<gy, 256, 0, s>>>(pair_g, emb, n, c, e, y);
 }
@@ -350,7 +300,7 @@ void proxy_bwd_products(const float* emb, const float* proxies, int n, int c, in
 void proxy_bwd_project(const double* y, const float* proxies, const float* q, int c, int e, const float* upstream, float* dproxies,
                        void* stream) {
   EMBNET_TRACE("embnet::proxy_bwd_proxies_kernel", TRACE_BYTES, 16.0 * c * e, stream);
-  proxy_bwd_proxies_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, (hipStream_t)stream>>>(y, proxies, q, c, e, upstream, dproxies);
+  proxy_bwd_proxies_kernel<<<cdiv(c, RECT_WG_ANCHORS), RECT_THREADS, 0, (hipStream_t)stream>>>(y, proxies, q, c, e, upstream, dproxies);
 }
 
 inline int proxy_check_common(const char* what, bool pointers, int n, int c, int e, int kind, const void* workspace,
@@ -360,10 +310,7 @@ inline int proxy_check_common(const char* what, bool pointers, int n, int c, int
   EMBNET_CHECK_ARG(c >= 2 && c <= PROXY_MAX_C, "%s: c=%d outside [2, %d]", what, c, PROXY_MAX_C);
   EMBNET_CHECK_ARG(e >= 1 && e <= PROXY_MAX_E, "%s: e=%d outside [1, %d]", what, e, PROXY_MAX_E);
   EMBNET_CHECK_ARG(kind == EMBNET_PROXY_ANCHOR || kind == EMBNET_PROXY_SOFTMAX, "%s: unknown kind %d", what, kind);
-  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-  const size_t need = ProxyWorkspace(n, c, e).bytes;
-  if (workspace_bytes < need) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-  return EMBNET_OK;
+  return check_workspace(what, workspace, workspace_bytes, ProxyWorkspace(n, c, e).bytes);
 }
 
 }  // namespace embnet
@@ -404,19 +351,10 @@ extern "C" int embnet_proxy_loss_fwd(const float* emb, const float* proxies, con
                 (int*)ws, (double2*)(ws + L.part_loss), (int4*)(ws + L.part_cnt), d};
   {
     EMBNET_TRACE("embnet::proxy_prep_kernel", TRACE_BYTES, 4.0 * c * e + 4.0 * n + 8.0 * c, stream);
-    proxy_prep_kernel<<<cdiv(c, PROXY_WG_ANCHORS), PROXY_THREADS, 0, s>>>(proxies, labels, n, c, e, q, cnt);
+    proxy_prep_kernel<<<cdiv(c, RECT_WG_ANCHORS), RECT_THREADS, 0, s>>>(proxies, labels, n, c, e, q, cnt);
   }
-  const int grid = cdiv(na, PROXY_WG_ANCHORS);
-  if (path == EMBNET_PROXY_SMALL) {
-    EMBNET_TRACE_FLOP("embnet::proxy_small_fwd_kernel", 2.0 * n * c * e, 4.0 * e * (na + (double)grid * nb) + 4.0 * n * c, stream);
-    proxy_small_fwd_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
-    return check_launch(what);
-  }
-  const int rg = embnet_dense_dgrad_f32(P.anchors, P.others, d, na, nb, e, stream);
-  if (rg != EMBNET_OK) return rg;
-  EMBNET_TRACE("embnet::proxy_sweep_kernel", TRACE_BYTES, 16.0 * n * c, stream);
-  proxy_sweep_kernel<<<grid, PROXY_THREADS, 0, s>>>(P);
-  return check_launch(what);
+  return rect_launch(what, proxy_small_fwd_kernel, "embnet::proxy_small_fwd_kernel", proxy_sweep_kernel, "embnet::proxy_sweep_kernel",
+                     path == EMBNET_PROXY_SMALL, P, P.anchors, P.others, d, na, nb, e, stream);
 }
 
 extern "C" int embnet_proxy_loss_bwd(const float* emb, const float* proxies, int n, int c, int e, int kind, const float* pair_g,

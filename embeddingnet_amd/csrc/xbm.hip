@@ -6,27 +6,24 @@
 //   workgroup has read it by then and drained what it stored, so none sees the advanced value.  The cursor is read from device memory
 //   by the kernel: a captured graph replays with the ring's current state.  One launch, no memset.
 //   loss: X [n, e] batch, y [n] labels, Y [m, e] bank, z [m] bank labels (negative = belongs to no set), self_slots [n] (the column
-//   that is the anchor's own copy, excluded).  S = X Y^T through embnet_dense_dgrad_f32 (the exact-fp32 matrix-instruction GEMM, a
-//   k-ordered chain per element) into the workspace, then a sweep: one wave owns one anchor and walks its row of S from L2 in
-//   lane-strided trips, as proxy_loss.hip's proxy_sweep_kernel does (a row of 65 536 floats is 256 KiB: it is not staged in LDS, and
-//   for the same reason the rectangle never fits a workgroup the way the proxies' small path does: ONE forward path,
-//   EMBNET_XBM_SWEEP; embnet_xbm_loss_path exists so that a second one can join).  The two kinds are Bodies of that sweep; the
-//   predicate "same label, labelled, not my own slot" stands where the P x K losses test [lo, lo + k).
+//   that is the anchor's own copy, excluded).  The anchors are the batch, the others the bank: S = X Y^T into the workspace and
+//   then the sweep (rect_loss.h's rect_sweep_launch), one wave per anchor walking its row of S from L2 (a row of 65 536 floats is
+//   256 KiB, so the rectangle never fits a workgroup the way the proxies' small path does: ONE forward path, EMBNET_XBM_SWEEP;
+//   embnet_xbm_loss_path exists so that a second one can join).  The two kinds are Bodies of that sweep; the predicate "same label, labelled, not my own slot" stands where the P x K losses test
+//   [lo, lo + k).
 //     contrastive (the XBM paper's criterion): one pass, the kept terms join a per-lane f64 chain (exact products are not needed:
 //       the terms are fp32 numbers, the chain has ceil(m / 64) f64 additions and the butterfly six).
 //     multi-similarity: MsBody's mining comparisons, pair_loss.h's t, term and side, three passes over the row (extrema, sums, weights).
 //   per-anchor partials, the arrival ticket, pair_loss.h's fixed-order f64 reduction by the last workgroup, which also counts the
 //   labelled bank slots (integers, any order).
-//   backward: demb = (g / n) G Y on the f64 matrix instructions (pair_loss.h's mm_f64_tile<MM_DIRECT>); the bank is detached and
-//   there is no column role.  A batch against a long bank leaves the grid ceil(n/32) ceil(e/32) workgroups with m / 32 serial
-//   rounds each (128 x 128 against 8192 slots: 16 workgroups, 256 rounds, 0.56 ms measured): the slots are then split over
-//   blockIdx.z in chunks of a multiple of 32, every slice writes its f64 sums where the forward kept S, and a second launch adds the
-//   slices in slice order, scales and rounds once (proxy_loss.hip's demb split).
+//   backward: demb = (g / n) G Y on the f64 matrix instructions; the bank is detached and there is no column role.  A batch against a
+//   long bank leaves the grid ceil(n/32) ceil(e/32) workgroups with m / 32 serial rounds each (128 x 128 against 8192 slots: 16
+//   workgroups, 256 rounds, 0.56 ms measured): the slots are then split (rect_loss.h's split product), the slices where the forward
+//   kept S.
 // A label is only ever compared, never used as an index; a self slot is only ever compared with a column index.  Nothing is atomic
 // in floating point, every reduction has a fixed order: bitwise reproducible.  No host synchronisation, no allocation: capturable.
 #include <math.h>
-#include "common.h"
-#include "pair_loss.h"
+#include "rect_loss.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
@@ -37,6 +34,7 @@ constexpr int XBM_MAX_E = 4096;
 constexpr long XBM_MAX_PAIRS = 1L << 26;                 // n m: S and G are 256 MiB each at most
 constexpr int XBM_THREADS = 256;                         // 4 waves: one row (enqueue) or one anchor (sweep) each
 constexpr int XBM_WG_ROWS = XBM_THREADS / 64;
+static_assert(XBM_THREADS == RECT_THREADS, "rect_sweep_launch launches the sweeps");
 
 // ---- the ring: grid = ceil(n / 4) workgroups, one wave copies one row ---------------------------------------------------------------
 __global__ __launch_bounds__(XBM_THREADS) void xbm_enqueue_kernel(const float* __restrict__ emb, const int32_t* __restrict__ labels,
@@ -156,16 +154,9 @@ struct XbmMsBody {
 
 // labelled bank slots, the same in every thread of the workgroup (integers: any order)
 __device__ __forceinline__ int xbm_labelled_slots(const int32_t* __restrict__ mem_labels, int m) {
-  __shared__ int sl[XBM_WG_ROWS];
   int l = 0;
   for (int j = threadIdx.x; j < m; j += XBM_THREADS) l += mem_labels[j] >= 0;
-  l = wave_sum(l);
-  if ((threadIdx.x & 63) == 0) sl[threadIdx.x >> 6] = l;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < XBM_WG_ROWS; ++w) t += sl[w];
-  return t;
+  return block_total256(l);
 }
 
 // grid = ceil(n / 4) workgroups, one wave walks one anchor's row of S from L2
@@ -203,41 +194,20 @@ __device__ __forceinline__ void xbm_sweep(const XbmParams& P) {
 __global__ __launch_bounds__(XBM_THREADS) void xbm_contrastive_sweep_kernel(XbmParams P) { xbm_sweep<XbmContrastiveBody>(P); }
 __global__ __launch_bounds__(XBM_THREADS) void xbm_ms_sweep_kernel(XbmParams P) { xbm_sweep<XbmMsBody>(P); }
 
-// ---- backward: demb = (g / n) G Y ---------------------------------------------------------------------------------------------------
-struct XbmBwdOut {
-  static constexpr bool ROW_SUM = false;
-  const float* upstream; int n; float* demb;
-  __device__ double begin() const { return (upstream ? (double)*upstream : 1.0) / (double)n; }
-  __device__ void put(double scale, long at, double y, double) const { demb[at] = (float)(scale * y); }
-};
-
+// ---- backward: demb = (g / n) G Y, split over the slots where the bank is long (rect_loss.h's split product) ---------------------------
 __global__ __launch_bounds__(256) void xbm_bwd_kernel(const float* __restrict__ G, const float* __restrict__ mem, int n, int m, int e,
                                                       const float* __restrict__ upstream, float* __restrict__ demb) {
-  mm_f64_tile<MM_DIRECT, false>(G, nullptr, mem, n, m, e, 0, m, XbmBwdOut{upstream, n, demb});
+  mm_f64_tile<MM_DIRECT, false>(G, nullptr, mem, n, m, e, 0, m, RectScaledOut<true>{upstream, n, demb});
 }
-
-// the split form: slice blockIdx.z sums the slots [z jchunk, (z + 1) jchunk) into part[z][n][e] (f64, unscaled) ...
-struct XbmPartOut {
-  static constexpr bool ROW_SUM = false;
-  double* part;
-  __device__ double begin() const { return 0.0; }
-  __device__ void put(double, long at, double y, double) const { part[at] = y; }
-};
 
 __global__ __launch_bounds__(256) void xbm_bwd_part_kernel(const float* __restrict__ G, const float* __restrict__ mem, int n, int m,
                                                            int e, int jchunk, double* __restrict__ part) {
-  const int jb = blockIdx.z * jchunk;
-  mm_f64_tile<MM_DIRECT, false>(G, nullptr, mem, n, m, e, jb, min(m, jb + jchunk), XbmPartOut{part + (long)blockIdx.z * n * e});
+  rect_mm_part<MM_DIRECT, false>(G, nullptr, mem, n, m, e, jchunk, part);
 }
 
-// ... and the slices are added in slice order, scaled by g / n and rounded once
 __global__ __launch_bounds__(256) void xbm_bwd_sum_kernel(const double* __restrict__ part, int splits, long ne, int n,
                                                           const float* __restrict__ upstream, float* __restrict__ demb) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= ne) return;
-  double s = 0.0;
-  for (int z = 0; z < splits; ++z) s += part[z * ne + i];
-  demb[i] = (float)((upstream ? (double)*upstream : 1.0) / (double)n * s);
+  rect_mm_sum<true>(part, splits, ne, n, upstream, demb);
 }
 
 // ---- host side: range, workspace layout ---------------------------------------------------------------------------------------------
@@ -255,17 +225,6 @@ struct XbmWorkspace {
     bytes = s + pair_align16((size_t)n * m * 4);
   }
 };
-
-// demb's slot split: none while a slice would hold fewer than 256 slots; otherwise towards 2048 workgroups; the slices' f64 sums
-// (splits n e doubles) live in S's place (n m floats), so splits <= m / (2 e).  -> (splits, jchunk)
-inline void xbm_bwd_split(int n, int m, int e, int& splits, int& jchunk) {
-  int s = cdiv(2048, (long)cdiv(n, 32) * cdiv(e, 32));
-  if (s > m / 256) s = m / 256;
-  if (s > m / (2 * e)) s = m / (2 * e);
-  if (s < 1) s = 1;
-  jchunk = cdiv(cdiv(m, s), 32) * 32;
-  splits = cdiv(m, jchunk);
-}
 
 inline int xbm_check_range(const char* what, int n, int m, int e) {
   EMBNET_CHECK_ARG(n >= 2 && n <= XBM_MAX_N, "%s: n=%d outside [2, %d]", what, n, XBM_MAX_N);
@@ -316,24 +275,19 @@ extern "C" int embnet_xbm_loss_fwd(const float* emb, const int32_t* labels, cons
     EMBNET_CHECK_ARG(isfinite(c), "%s: base=%g must be finite", what, (double)c);
     EMBNET_CHECK_ARG(isfinite(d) && d >= 0.f, "%s: epsilon=%g must be finite and non-negative", what, (double)d);
   }
-  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
   const XbmWorkspace L(n, m);
-  if (workspace_bytes < L.bytes) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, L.bytes);
+  const int rw = check_workspace(what, workspace, workspace_bytes, L.bytes);
+  if (rw != EMBNET_OK) return rw;
   char* ws = (char*)workspace;
   float* s = (float*)(ws + L.s);
-  const int rg = embnet_dense_dgrad_f32(emb, mem, s, n, m, e, stream);
-  if (rg != EMBNET_OK) return rg;
   XbmParams P{labels, mem_labels, self_slots, n, m, kind, a, b, c, d, pair_g, counts, mean_loss,
               (int*)ws, (double*)(ws + L.part_loss), (int4*)(ws + L.part_cnt), s};
   const int grid = cdiv(n, XBM_WG_ROWS);
-  if (kind == EMBNET_XBM_CONTRASTIVE) {
-    EMBNET_TRACE("embnet::xbm_contrastive_sweep_kernel", TRACE_BYTES, 8.0 * n * m + 4.0 * m * (grid + 1.0), stream);
-    xbm_contrastive_sweep_kernel<<<grid, XBM_THREADS, 0, (hipStream_t)stream>>>(P);
-  } else {
-    EMBNET_TRACE("embnet::xbm_ms_sweep_kernel", TRACE_BYTES, 16.0 * n * m + 4.0 * m * (3.0 * grid + 1.0), stream);
-    xbm_ms_sweep_kernel<<<grid, XBM_THREADS, 0, (hipStream_t)stream>>>(P);
-  }
-  return check_launch(what);
+  if (kind == EMBNET_XBM_CONTRASTIVE)
+    return rect_sweep_launch(what, xbm_contrastive_sweep_kernel, "embnet::xbm_contrastive_sweep_kernel",
+                             8.0 * n * m + 4.0 * m * (grid + 1.0), P, emb, mem, s, n, m, e, stream);
+  return rect_sweep_launch(what, xbm_ms_sweep_kernel, "embnet::xbm_ms_sweep_kernel", 16.0 * n * m + 4.0 * m * (3.0 * grid + 1.0), P, emb,
+                           mem, s, n, m, e, stream);
 }
 
 extern "C" int embnet_xbm_loss_bwd(const float* mem, int n, int m, int e, const float* pair_g, const float* upstream, float* demb,
@@ -342,25 +296,20 @@ extern "C" int embnet_xbm_loss_bwd(const float* mem, int n, int m, int e, const 
   EMBNET_CHECK_ARG(mem && pair_g && demb && workspace, "%s: null pointer", what);
   const int rc = xbm_check_range(what, n, m, e);
   if (rc != EMBNET_OK) return rc;
-  EMBNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
   const XbmWorkspace L(n, m);
-  if (workspace_bytes < L.bytes) return fail(EMBNET_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, L.bytes);
+  const int rw = check_workspace(what, workspace, workspace_bytes, L.bytes);
+  if (rw != EMBNET_OK) return rw;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(cdiv(n, 32), cdiv(e, 32));
   const double flop = 2.0 * n * m * e, bytes = 4.0 * ((double)n * m + (double)m * e + (double)n * e);
+  // towards 2048 workgroups; the slices' f64 sums (splits n e doubles) live in S's place (n m floats, not needed any more), so
+  // splits <= m / (2 e)
   int splits, jchunk;
-  xbm_bwd_split(n, m, e, splits, jchunk);
-  if (splits == 1) {
-    EMBNET_TRACE_FLOP("embnet::xbm_bwd_kernel", flop, bytes, stream);
-    xbm_bwd_kernel<<<grid, 256, 0, s>>>(pair_g, mem, n, m, e, upstream, demb);
-    return check_launch(what);
-  }
-  double* part = (double*)((char*)workspace + L.s);      // splits n e doubles <= n m floats: S is not needed any more
-  {
-    EMBNET_TRACE_FLOP("embnet::xbm_bwd_part_kernel", flop, bytes + 8.0 * splits * n * e, stream);
-    xbm_bwd_part_kernel<<<dim3(grid.x, grid.y, splits), 256, 0, s>>>(pair_g, mem, n, m, e, jchunk, part);
-  }
-  EMBNET_TRACE("embnet::xbm_bwd_sum_kernel", TRACE_BYTES, 8.0 * splits * n * e + 4.0 * n * e, stream);
-  xbm_bwd_sum_kernel<<<cdiv((long)n * e, 256), 256, 0, s>>>(part, splits, (long)n * e, n, upstream, demb);
+  rect_mm_split(n, m, e, 2048, m / (2 * e), splits, jchunk);
+  double* part = (double*)((char*)workspace + L.s);
+  rect_mm_launch({"embnet::xbm_bwd_kernel", "embnet::xbm_bwd_part_kernel", "embnet::xbm_bwd_sum_kernel"}, flop, bytes,
+                 bytes + 8.0 * splits * n * e, n, e, splits, stream,
+                 [&](dim3 grid) { xbm_bwd_kernel<<<grid, 256, 0, s>>>(pair_g, mem, n, m, e, upstream, demb); },
+                 [&](dim3 grid) { xbm_bwd_part_kernel<<<grid, 256, 0, s>>>(pair_g, mem, n, m, e, jchunk, part); },
+                 [&](int grid) { xbm_bwd_sum_kernel<<<grid, 256, 0, s>>>(part, splits, (long)n * e, n, upstream, demb); });
   return check_launch(what);
 }

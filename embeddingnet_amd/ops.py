@@ -338,6 +338,24 @@ PROXY_KINDS = {"proxy_anchor_loss": 1, "proxy_softmax_loss": 2}      # EMBNET_PR
 _PROXY_WS = {}
 
 
+def _int32_labels(who, name, labels, n):
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise _lib.EmbnetError(f"{who}: {name} must be an int32 tensor of {n} entries")
+    return labels.contiguous()
+
+
+def _proxy_width(loss, name, w, e):                         # the first check of the losses on proxies and on centres ...
+    if w.dim() != 2 or w.shape[1] != e:
+        raise _lib.EmbnetError(f"{loss}: {name} {tuple(w.shape)} do not match embeddings of width {e}")
+
+
+def _proxy_labels_and_path(loss, labels, n, path):          # ... and their last two -> the labels, contiguous
+    labels = _int32_labels(loss, "labels", labels, n)
+    if path not in PROXY_PATHS:
+        raise _lib.EmbnetError(f"{loss}: path {path!r} is not one of {sorted(PROXY_PATHS)}")
+    return labels
+
+
 class _ProxyLoss(torch.autograd.Function):
     """embnet_proxy_loss_fwd / _bwd (include/embnet.h): a prep launch and one forward launch on the small path, prep + D + sweep
     above it; three backward launches.  G [c,n] (Proxy-Anchor) or [n,c] (CosFace) and q stay saved for the backward."""
@@ -347,13 +365,8 @@ class _ProxyLoss(torch.autograd.Function):
         emb, proxies = _prep(emb), _prep(proxies)
         n, e = emb.shape
         c = proxies.shape[0]
-        if proxies.dim() != 2 or proxies.shape[1] != e:
-            raise _lib.EmbnetError(f"{loss}: proxies {tuple(proxies.shape)} do not match embeddings of width {e}")
-        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-            raise _lib.EmbnetError(f"{loss}: labels must be an int32 tensor of {n} entries")
-        if path not in PROXY_PATHS:
-            raise _lib.EmbnetError(f"{loss}: path {path!r} is not one of {sorted(PROXY_PATHS)}")
-        labels = labels.contiguous()
+        _proxy_width(loss, "proxies", proxies, e)
+        labels = _proxy_labels_and_path(loss, labels, n, path)
         kind = PROXY_KINDS[loss]
         lib = _lib.lib()
         g = _new((c, n) if kind == 1 else (n, c), emb)
@@ -419,16 +432,11 @@ class _MultiProxyLoss(torch.autograd.Function):
         emb, centres = _prep(emb), _prep(centres)
         n, e = emb.shape
         c = int(n_classes)
-        if centres.dim() != 2 or centres.shape[1] != e:
-            raise _lib.EmbnetError(f"{loss}: centres {tuple(centres.shape)} do not match embeddings of width {e}")
+        _proxy_width(loss, "centres", centres, e)
         if c < 1 or centres.shape[0] % c:
             raise _lib.EmbnetError(f"{loss}: {centres.shape[0]} centres are not a whole number per class of n_classes={n_classes}")
         kc = centres.shape[0] // c
-        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-            raise _lib.EmbnetError(f"{loss}: labels must be an int32 tensor of {n} entries")
-        if path not in PROXY_PATHS:
-            raise _lib.EmbnetError(f"{loss}: path {path!r} is not one of {sorted(PROXY_PATHS)}")
-        labels = labels.contiguous()
+        labels = _proxy_labels_and_path(loss, labels, n, path)
         kind = MPROXY_KINDS[loss]
         lib = _lib.lib()
         g, q = _new((n, c * kc), emb), _new((c * kc,), emb)
@@ -501,12 +509,6 @@ XBM_KINDS = {"xbm_contrastive_loss": 1, "xbm_multi_similarity_loss": 2}      # E
 _XBM_WS = {}
 
 
-def _xbm_labels(who, name, labels, n):
-    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-        raise _lib.EmbnetError(f"{who}: {name} must be an int32 tensor of {n} entries")
-    return labels.contiguous()
-
-
 def xbm_enqueue(emb, labels, memory):
     """The rows of emb [N,E] (detached) and their int32 labels [N] into the ring of `memory` (an xbm.CrossBatchMemory, or anything
     with feats [M,E], labels [M], cursor [1], slots and a 16-byte zeroed `ticket`): row i goes to slot (cursor + i) mod M and the
@@ -519,7 +521,7 @@ def xbm_enqueue(emb, labels, memory):
         raise _lib.EmbnetError(f"xbm_enqueue: embeddings of width {e} do not match a memory of width {memory.feats.shape[1]}")
     if n > memory.slots.shape[0]:
         raise _lib.EmbnetError(f"xbm_enqueue: a batch of {n} rows does not fit a memory of {m} slots")
-    labels = _xbm_labels("xbm_enqueue", "labels", labels, n)
+    labels = _int32_labels("xbm_enqueue", "labels", labels, n)
     slots = memory.slots[:n]
     check(_lib.lib().embnet_xbm_enqueue(ptr(emb), ptr(labels), n, e, ptr(memory.feats), ptr(memory.labels), m, ptr(memory.cursor),
                                         ptr(slots), ptr(memory.ticket), stream()))
@@ -537,10 +539,10 @@ class _XbmLoss(torch.autograd.Function):
         if mem.dim() != 2 or mem.shape[1] != e:
             raise _lib.EmbnetError(f"{loss}: a memory {tuple(mem.shape)} does not match embeddings of width {e}")
         m = mem.shape[0]
-        labels = _xbm_labels(loss, "labels", labels, n)
-        mem_labels = _xbm_labels(loss, "mem_labels", mem_labels, m)
+        labels = _int32_labels(loss, "labels", labels, n)
+        mem_labels = _int32_labels(loss, "mem_labels", mem_labels, m)
         if self_slots is not None:
-            self_slots = _xbm_labels(loss, "self_slots", self_slots, n)
+            self_slots = _int32_labels(loss, "self_slots", self_slots, n)
         lib = _lib.lib()
         g = _new((n, m), emb)
         counts, mean = _new((4,), emb, torch.int32), _new((), emb)
