@@ -221,4 +221,37 @@ __host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t a, 
   return (uint32_t)(mix64(mix64(seed ^ (a * 0xD6E8FEB86659FD93ull)) + b) >> 32);
 }
 
+// Hermans batch-hard for anchor row a of the class that owns columns [lo, lo + k), by the calling wave, on the anchor's distance
+// row (n floats, global memory or LDS): ip = the farthest same-class column other than a, in_ = the closest other-class column,
+// the first index on ties; the same in every lane.  A NaN never compares, +inf never wins among the negatives.  When no column of
+// a set compares (a non-finite embedding row), the set's first column is taken — NumPy's arg-max / arg-min on an all-NaN or
+// all-inf set — so both indices lie in [0, n) whatever the row holds.  Needs k >= 2 and n >= 2 k.
+__device__ __forceinline__ void batch_hard_select(const float* row, int n, int k, int a, int lo, int& ip, int& in_) {
+  const int lane = threadIdx.x & 63, hi = lo + k;
+  float bp = -INFINITY, bn = INFINITY;
+  ip = in_ = 0x7fffffff;
+  for (int c0 = lane; c0 < n; c0 += 4 * 64) {              // four loads in flight per lane; ascending columns per lane
+    float vv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) vv[u] = c0 + 64 * u < n ? row[c0 + 64 * u] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = c0 + 64 * u;
+      if (c >= n) break;
+      const float v = vv[u];
+      if (c >= lo && c < hi) { if (c != a && v > bp) { bp = v; ip = c; } }
+      else if (v < bn) { bn = v; in_ = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bp, o, 64); const int oi = __shfl_xor(ip, o, 64);
+    if (ov > bp || (ov == bp && oi < ip)) { bp = ov; ip = oi; }
+    const float nv = __shfl_xor(bn, o, 64); const int ni = __shfl_xor(in_, o, 64);
+    if (nv < bn || (nv == bn && ni < in_)) { bn = nv; in_ = ni; }
+  }
+  if (ip == 0x7fffffff) ip = a == lo ? lo + 1 : lo;        // no positive compared: the first same-class row other than the anchor
+  if (in_ == 0x7fffffff) in_ = lo > 0 ? 0 : hi;            // no negative compared: the first other-class row
+}
+
 }  // namespace embnet

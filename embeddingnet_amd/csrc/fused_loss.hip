@@ -112,20 +112,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_triplet_loss_fwd_kernel(F
   if (q.mode == EMBNET_MINE_BATCH_HARD) {
     // Hermans batch-hard (build-defined): per anchor the farthest positive and the closest negative; slot = anchor
     for (int a = wave; a < k; a += NW) {
-      const float* row = D + a * n;
-      float bp = -INFINITY, bn = INFINITY; int ip = 0x7fffffff, in_ = 0x7fffffff;
-      for (int col = lane; col < n; col += 64) {
-        const float v = row[col];
-        if (col >= lo && col < lo + k) { if (col != lo + a && v > bp) { bp = v; ip = col; } }
-        else if (v < bn) { bn = v; in_ = col; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bp, o, 64); const int oi = __shfl_xor(ip, o, 64);
-        if (ov > bp || (ov == bp && oi < ip)) { bp = ov; ip = oi; }
-        const float nv = __shfl_xor(bn, o, 64); const int ni = __shfl_xor(in_, o, 64);
-        if (nv < bn || (nv == bn && ni < in_)) { bn = nv; in_ = ni; }
-      }
+      int ip, in_;
+      batch_hard_select(D + a * n, n, k, lo + a, lo, ip, in_);
       const float b = hinge_term(A + a * e, A + (ip - lo) * e, q.emb + (long)in_ * e, e, lane, q.margin);
       if (lane == 0) {
         int* t = q.triplets + 3 * (long)(lo + a);

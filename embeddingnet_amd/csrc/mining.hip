@@ -297,29 +297,8 @@ __global__ __launch_bounds__(256) void batch_hard_kernel(const float* __restrict
   const int lane = threadIdx.x & 63;
   if (a == 0 && lane == 0 && count) *count = n;
   if (a >= n) return;
-  const int lo = (a / k) * k, hi = lo + k;
-  const float* row = D + (long)a * n;
-  float bp = -INFINITY, bn = INFINITY; int ip = 0x7fffffff, in_ = 0x7fffffff;
-  for (int c0 = lane; c0 < n; c0 += 4 * 64) {              // four loads in flight per lane; columns visited in the same order
-    float vv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) vv[u] = c0 + 64 * u < n ? row[c0 + 64 * u] : 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 64 * u;
-      if (c >= n) break;
-      const float v = vv[u];
-      if (c >= lo && c < hi) { if (c != a && v > bp) { bp = v; ip = c; } }
-      else if (v < bn) { bn = v; in_ = c; }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bp, o, 64); const int oi = __shfl_xor(ip, o, 64);
-    if (ov > bp || (ov == bp && oi < ip)) { bp = ov; ip = oi; }
-    const float nv = __shfl_xor(bn, o, 64); const int ni = __shfl_xor(in_, o, 64);
-    if (nv < bn || (nv == bn && ni < in_)) { bn = nv; in_ = ni; }
-  }
+  int ip, in_;
+  batch_hard_select(D + (long)a * n, n, k, a, (a / k) * k, ip, in_);
   if (lane == 0) { int* t = triplets + 3 * (long)a; t[0] = a; t[1] = ip; t[2] = in_; }
 }
 

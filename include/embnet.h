@@ -68,14 +68,22 @@ int embnet_pairwise_dist_f32(const float* x, int n, int e, float* dist, int squa
  * fallback triplet (n-2,n-1,0) when nothing qualifies).  triplets must hold
  * embnet_mine_max_triplets(p,k) rows; selected[pairs] receives the chosen negative row or -1;
  * cand_mask (optional, [pairs][ceil((n-k)/32)] words) receives the candidate set of each pair as
- * a bitmask over the ascending out-of-class columns.  seed drives the two random rules. */
+ * a bitmask over the ascending out-of-class columns.  seed drives the two random rules.
+ * Non-finite distances (a NaN or inf embedding row): the loss value (dist[i,j] - dist[i,neg]) + margin is compared as it
+ * comes out, so a NaN distance (either operand) is never a candidate and never the arg-max of `hardest`, and a +inf
+ * distance to a negative (value -inf) disqualifies that negative; a pair left without a candidate selects -1.  Every
+ * index written lies in [0, n). */
 int embnet_mine_max_triplets(int p, int k);
 int embnet_mine_triplets(const float* dist, int p, int k, float margin, int mode, uint64_t seed,
                          int32_t* triplets, int32_t* count, int32_t* selected, uint32_t* cand_mask,
                          void* stream);
 
 /* Hermans batch-hard selection (README.md:112 cites it; no reference code): per anchor the
- * farthest same-class and the closest other-class row.  triplets[n,3]; *count = n (optional). */
+ * farthest same-class and the closest other-class row, the first index on ties.  triplets[n,3]; *count = n (optional).
+ * Non-finite distances: a NaN never compares and +inf never wins among the negatives; when no column of a set compares
+ * (the anchor's row is NaN), the set's first column is taken: the first same-class row other than the anchor, the first
+ * other-class row (NumPy's arg-max / arg-min on an all-NaN set).  Both indices lie in [0, n) whatever dist holds; the same
+ * rule holds for EMBNET_MINE_BATCH_HARD in embnet_fused_triplet_loss_fwd. */
 int embnet_batch_hard(const float* dist, int p, int k, int32_t* triplets, int32_t* count, void* stream);
 
 /* losses_and_accuracies.py:26-42 loss_function(y_true, y_pred): y_pred[t,3e] = concat(a,p,n);

@@ -177,6 +177,12 @@ def test_mining_random_pick_is_uniform(golden, dev):
     assert chi2 < chi2dist.ppf(0.999, ncand - 1), (chi2, counts)
 
 
+def _picks_by_pair(trip, p, k):
+    """triplets -> the negative of every positive pair in pair order, -1 where the pair has none"""
+    sel = {(int(a), int(b)): int(n) for a, b, n in trip}
+    return np.array([sel.get((c * k + a, c * k + b), -1) for c in range(p) for a in range(k) for b in range(a + 1, k)])
+
+
 def test_mining_end_to_end_from_embeddings(golden, dev):
     """GPU distance matrix + GPU mining vs the reference's triplets on tie-free inputs."""
     from embeddingnet_amd import ops
@@ -189,11 +195,12 @@ def test_mining_end_to_end_from_embeddings(golden, dev):
         ref = g[f"{name}/hardest/triplets"]
         if got.shape == ref.shape and np.array_equal(got, ref):
             continue
-        # any difference must sit on an fp32-borderline decision of the reference's loss values
+        # every differing pair must itself sit on an fp32-borderline decision of the reference's loss values
         lv = g[f"{name}/hardest/loss_values"]
         srt = np.sort(lv, axis=1)
         border = (np.abs(srt[:, -1]) < 1e-4) | (srt[:, -1] - srt[:, -2] < 1e-4)
-        assert border.any(), f"{name}: triplets differ without a borderline pair"
+        diff = np.flatnonzero(_picks_by_pair(got, p, k) != _picks_by_pair(ref, p, k))
+        assert border[diff].all(), f"{name}: pairs {diff[~border[diff]]} differ without being borderline: {lv[diff[~border[diff]]]}"
 
 
 def test_batch_hard_vs_oracle(dev):
@@ -293,7 +300,9 @@ def test_fused_loss_path_golden(golden, dev, case, mode):
         assert np.array_equal(got, ref_trip)
     elif mode == "hardest":
         if not (got.shape == ref_trip.shape and np.array_equal(got, ref_trip)):
-            assert _borderline(g[f"{key}/loss_values"]).any(), f"{name}: triplets differ without a borderline pair"
+            border = _borderline(g[f"{key}/loss_values"])                # every differing pair must itself be borderline
+            diff = np.flatnonzero(_picks_by_pair(got, p, k) != _picks_by_pair(ref_trip, p, k))
+            assert border[diff].all(), f"{name}: pairs {diff[~border[diff]]} differ without being borderline"
     else:
         cand = g[f"{key}/candidates"]
         ppc = k * (k - 1) // 2
