@@ -1,4 +1,5 @@
-// The skeleton the losses over a class-contiguous P x K batch share (batch_all.hip, multi_similarity.hip, supcon.hip): what
+// The skeleton the losses over a class-contiguous P x K batch share (batch_all.hip, multi_similarity.hip, supcon.hip, ap_loss.hip,
+// circle_loss.hip): what
 // differs between them is what ONE WAVE does with ONE ANCHOR's row of the pair matrix, the Body.
 //
 //   X [N, E] fp32, N = P*K, rows c*K .. c*K+K-1 are class c;  the pair matrix S is X X^T (similarities) or the squared distances.
@@ -35,6 +36,7 @@
 // bank) on the same four.  The P x K skeleton proper is the Body, PairParams,
 // pair_class_fwd / pair_sweep_fwd / pair_finish / pair_bwd, the fit rule, the workspace layout, the checks and pair_launch.
 #pragma once
+#include <math.h>
 #include "common.h"
 #include "../../include/embnet.h"
 
@@ -62,6 +64,82 @@ __device__ __forceinline__ float ms_t(float c, float s, float base) { return __f
 __device__ __forceinline__ float ms_term(float c, float s, float base, float m) { return expf(__fsub_rn(ms_t(c, s, base), m)); }
 // a side's loss from its maximum m and its denominator d = e^{-m} + sum e^{t - m} >= 1: (m + log d) / c
 __device__ __forceinline__ float ms_side(float m, float d, float c) { return __fdiv_rn(__fadd_rn(m, logf(d)), c); }
+
+// Circle loss's per-pair pieces and its row, stated once for circle_loss.hip (pair sets by P x K contiguity, the row in LDS) and
+// xbm.hip (pair sets by two label vectors, the row in global memory).  One rounding order everywhere (include/embnet.h):
+//   alpha+ = max(fl(O+ - s), 0),  a+ = fl(-gamma fl(alpha+ fl(s - D+)));   alpha- = max(fl(s - O-), 0),  a- = fl(gamma fl(alpha- fl(s - D-)))
+struct CircleArgs { float gamma, op, on, dp, dn; };      // gamma, O+ = fl(1 + m), O- = -m, D+ = fl(1 - m), D- = m
+__device__ __forceinline__ float circle_alpha(int role, float s, const CircleArgs& a) {
+  return fmaxf(role > 0 ? __fsub_rn(a.op, s) : __fsub_rn(s, a.on), 0.f);
+}
+__device__ __forceinline__ float circle_logit(int role, float alpha, float s, const CircleArgs& a) {
+  return role > 0 ? __fmul_rn(-a.gamma, __fmul_rn(alpha, __fsub_rn(s, a.dp))) : __fmul_rn(a.gamma, __fmul_rn(alpha, __fsub_rn(s, a.dn)));
+}
+
+struct CircleRowOut { float loss; int viol, cp, cn, active; };   // cp / cn: the side's pairs with alpha > 0
+
+// One wave, one anchor's row srow[cols] of S; role(col) = +1 a positive, -1 a negative, 0 neither.  Three lane-strided passes in
+// column order: the sides' largest logits and the extreme similarities; the sums e^{a - M} (>= 1: the largest logit gives e^0) and
+// the counters; all `cols` entries of the row of G.  An empty side (min over no positive = +inf, max over no negative = -inf)
+// leaves a zero row and no loss.  The same result in every lane.
+template <class Role>
+__device__ __forceinline__ CircleRowOut circle_row(const float* __restrict__ srow, int cols, const Role& role, const CircleArgs& a,
+                                                   float* __restrict__ grow, int lane) {
+  float mn = INFINITY, mx = -INFINITY, Mp = -INFINITY, Mn = -INFINITY;
+  for (int col = lane; col < cols; col += 64) {
+    const int r = role(col);
+    if (r == 0) continue;
+    const float s = srow[col];
+    const float t = circle_logit(r, circle_alpha(r, s, a), s, a);
+    if (r > 0) { mn = fminf(mn, s); Mp = fmaxf(Mp, t); }
+    else { mx = fmaxf(mx, s); Mn = fmaxf(Mn, t); }
+  }
+  mn = wave_min(mn);                                     // min over the positives (+inf: none)
+  mx = wave_max(mx);                                     // max over the negatives (-inf: none)
+  if (mn == INFINITY || mx == -INFINITY) {               // an empty side (wave-uniform)
+    for (int col = lane; col < cols; col += 64) grow[col] = 0.f;
+    return CircleRowOut{0.f, 0, 0, 0, 0};
+  }
+  Mp = wave_max(Mp);
+  Mn = wave_max(Mn);
+  float sp = 0.f, sn = 0.f;
+  int cp = 0, cn = 0;
+  for (int col = lane; col < cols; col += 64) {
+    const int r = role(col);
+    if (r == 0) continue;
+    const float s = srow[col];
+    const float al = circle_alpha(r, s, a);
+    const float t = circle_logit(r, al, s, a);
+    if (r > 0) { sp += expf(__fsub_rn(t, Mp)); cp += al > 0.f; }
+    else { sn += expf(__fsub_rn(t, Mn)); cn += al > 0.f; }
+  }
+  const float dp = wave_sum(sp), dn = wave_sum(sn);      // >= 1 each
+  const float z = __fadd_rn(__fadd_rn(Mp, logf(dp)), __fadd_rn(Mn, logf(dn)));
+  const float t1 = expf(-fabsf(z));                      // softplus and sigmoid from e^{-|z|} <= 1
+  const float d1 = __fadd_rn(1.f, t1);
+  const float sg = __fmul_rn(__fdiv_rn(z >= 0.f ? 1.f : t1, d1), a.gamma);      // sigma gamma
+  const float wp = __fdiv_rn(sg, dp), wn = __fdiv_rn(sg, dn);
+  for (int col = lane; col < cols; col += 64) {
+    const int r = role(col);
+    float g = 0.f;
+    if (r != 0) {
+      const float s = srow[col];
+      const float al = circle_alpha(r, s, a);
+      const float t = circle_logit(r, al, s, a);
+      g = r > 0 ? -__fmul_rn(wp, __fmul_rn(al, expf(__fsub_rn(t, Mp)))) : __fmul_rn(wn, __fmul_rn(al, expf(__fsub_rn(t, Mn))));
+    }
+    grow[col] = g;
+  }
+  return CircleRowOut{__fadd_rn(fmaxf(z, 0.f), logf(d1)), mx >= mn, wave_sum(cp), wave_sum(cn), 1};
+}
+
+// The parameters on the host: m in [0, 1] and gamma > 0, both finite -> the five constants, each one fp32 operation.
+inline int circle_args(const char* what, float m, float gamma, CircleArgs& a) {
+  EMBNET_CHECK_ARG(isfinite(m) && m >= 0.f && m <= 1.f, "%s: m=%g must be finite and in [0, 1]", what, (double)m);
+  EMBNET_CHECK_ARG(isfinite(gamma) && gamma > 0.f, "%s: gamma=%g must be finite and positive", what, (double)gamma);
+  a = CircleArgs{gamma, 1.f + m, -m, 1.f - m, m};
+  return EMBNET_OK;
+}
 
 template <class Sum>
 struct PairAnchorOut { Sum loss; int c0, c1; };

@@ -14,6 +14,7 @@
 //     contrastive (the XBM paper's criterion): one pass, the kept terms join a per-lane f64 chain (exact products are not needed:
 //       the terms are fp32 numbers, the chain has ceil(m / 64) f64 additions and the butterfly six).
 //     multi-similarity: MsBody's mining comparisons, pair_loss.h's t, term and side, three passes over the row (extrema, sums, weights).
+//     circle (an entry point of its own, embnet_xbm_circle_loss_fwd): pair_loss.h's circle_row, the row of circle_loss.hip.
 //   per-anchor partials, the arrival ticket, pair_loss.h's fixed-order f64 reduction by the last workgroup, which also counts the
 //   labelled bank slots (integers, any order).
 //   backward: demb = (g / n) G Y on the f64 matrix instructions; the bank is detached and there is no column role.  A batch against a
@@ -62,13 +63,13 @@ struct XbmParams {
   const int32_t* mem_labels;                             // [m]
   const int32_t* self_slots;                             // [n] or NULL
   int n, m, kind;
-  float a, b, c, d;                                      // margin | alpha, beta, base, epsilon
+  float a, b, c, d;                                      // margin | alpha, beta, base, epsilon | gamma, O+, D+, m (Circle)
   float* g; int32_t* counts; float* mean;
   int* ticket; double* part_loss; int4* part_cnt;        // workspace: arrival counter (zero between launches), partials
   const float* s;                                        // S [n][m]
 };
 
-struct XbmAnchorOut { double loss; int cp, cn; };
+struct XbmAnchorOut { double loss; int cp, cn; int act = -1; };       // act: whether the anchor is active; -1 = iff it keeps a pair
 
 // What a column is to an anchor of label yi >= 0 whose own copy sits in column self: +1 a positive, -1 a negative, 0 neither.
 __device__ __forceinline__ int xbm_role(int z, int col, int yi, int self) {
@@ -152,6 +153,21 @@ struct XbmMsBody {
   }
 };
 
+// Circle loss over the label sets: pair_loss.h's circle_row, the row circle_loss.hip runs in LDS, here on the row in global memory.
+// An anchor is active when it has a positive and a negative, whether or not any of them still has alpha > 0.
+struct XbmCircleRole {
+  const int32_t* __restrict__ z; int yi, self;
+  __device__ int operator()(int col) const { return xbm_role(z[col], col, yi, self); }
+};
+
+struct XbmCircleBody {
+  static __device__ XbmAnchorOut anchor(const float* __restrict__ srow, const XbmParams& P, int yi, int self, float* __restrict__ grow,
+                                        int lane) {
+    const CircleRowOut o = circle_row(srow, P.m, XbmCircleRole{P.mem_labels, yi, self}, CircleArgs{P.a, P.b, -P.d, P.c, P.d}, grow, lane);
+    return XbmAnchorOut{(double)o.loss, o.cp, o.cn, o.active};
+  }
+};
+
 // labelled bank slots, the same in every thread of the workgroup (integers: any order)
 __device__ __forceinline__ int xbm_labelled_slots(const int32_t* __restrict__ mem_labels, int m) {
   int l = 0;
@@ -175,7 +191,7 @@ __device__ __forceinline__ void xbm_sweep(const XbmParams& P) {
     }
     if (lane == 0) {
       P.part_loss[a] = o.loss;
-      P.part_cnt[a] = make_int4(o.cp, o.cn, o.cp + o.cn > 0, 0);
+      P.part_cnt[a] = make_int4(o.cp, o.cn, o.act < 0 ? o.cp + o.cn > 0 : o.act, 0);
     }
   }
   if (!last_workgroup_to_arrive(P.ticket)) return;
@@ -193,6 +209,7 @@ __device__ __forceinline__ void xbm_sweep(const XbmParams& P) {
 
 __global__ __launch_bounds__(XBM_THREADS) void xbm_contrastive_sweep_kernel(XbmParams P) { xbm_sweep<XbmContrastiveBody>(P); }
 __global__ __launch_bounds__(XBM_THREADS) void xbm_ms_sweep_kernel(XbmParams P) { xbm_sweep<XbmMsBody>(P); }
+__global__ __launch_bounds__(XBM_THREADS) void xbm_circle_sweep_kernel(XbmParams P) { xbm_sweep<XbmCircleBody>(P); }
 
 // ---- backward: demb = (g / n) G Y, split over the slots where the bank is long (rect_loss.h's split product) ---------------------------
 __global__ __launch_bounds__(256) void xbm_bwd_kernel(const float* __restrict__ G, const float* __restrict__ mem, int n, int m, int e,
@@ -288,6 +305,28 @@ extern "C" int embnet_xbm_loss_fwd(const float* emb, const int32_t* labels, cons
                              8.0 * n * m + 4.0 * m * (grid + 1.0), P, emb, mem, s, n, m, e, stream);
   return rect_sweep_launch(what, xbm_ms_sweep_kernel, "embnet::xbm_ms_sweep_kernel", 16.0 * n * m + 4.0 * m * (3.0 * grid + 1.0), P, emb,
                            mem, s, n, m, e, stream);
+}
+
+extern "C" int embnet_xbm_circle_loss_fwd(const float* emb, const int32_t* labels, const float* mem, const int32_t* mem_labels,
+                                          const int32_t* self_slots, int n, int m_slots, int e, float m, float gamma, float* pair_g,
+                                          int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* what = "xbm_circle_loss_fwd";
+  EMBNET_CHECK_ARG(emb && labels && mem && mem_labels && pair_g && counts && mean_loss && workspace, "%s: null pointer", what);
+  const int rc = xbm_check_range(what, n, m_slots, e);
+  if (rc != EMBNET_OK) return rc;
+  CircleArgs a;
+  const int ra = circle_args(what, m, gamma, a);
+  if (ra != EMBNET_OK) return ra;
+  const XbmWorkspace L(n, m_slots);
+  const int rw = check_workspace(what, workspace, workspace_bytes, L.bytes);
+  if (rw != EMBNET_OK) return rw;
+  char* ws = (char*)workspace;
+  float* s = (float*)(ws + L.s);
+  XbmParams P{labels, mem_labels, self_slots, n, m_slots, 0, a.gamma, a.op, a.dp, a.dn, pair_g, counts, mean_loss,
+              (int*)ws, (double*)(ws + L.part_loss), (int4*)(ws + L.part_cnt), s};
+  const int grid = cdiv(n, XBM_WG_ROWS);
+  return rect_sweep_launch(what, xbm_circle_sweep_kernel, "embnet::xbm_circle_sweep_kernel",
+                           16.0 * n * m_slots + 4.0 * m_slots * (3.0 * grid + 1.0), P, emb, mem, s, n, m_slots, e, stream);
 }
 
 extern "C" int embnet_xbm_loss_bwd(const float* mem, int n, int m, int e, const float* pair_g, const float* upstream, float* demb,

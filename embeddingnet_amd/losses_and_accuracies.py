@@ -7,6 +7,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   batch_all_triplet_loss(P, K, margin)(y_true, y_pred)   build-defined (batch-all over a [P*K, E] block) -> scalar
   multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
+  circle_loss(P, K, m, gamma)(y_true, y_pred)               build-defined (Circle loss over a [P*K, E] block) -> scalar
   fast_ap_loss(P, K, bins)(y_true, y_pred)                  build-defined (FastAP over a [P*K, E] block) -> scalar
   smooth_ap_loss(P, K, temperature)(y_true, y_pred)         build-defined (Smooth-AP over a [P*K, E] block) -> scalar
   proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
@@ -65,6 +66,18 @@ def supcon_loss(k_classes, k_samples, temperature=0.1, denominator="all"):
 
     def loss_function(y_true, y_pred):
         return ops.supcon_loss(y_pred, k_classes, k_samples, temperature, denominator)[0]
+
+    return loss_function
+
+
+def circle_loss(k_classes, k_samples, m=0.4, gamma=80.0):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] embedding
+    block, y_true is ignored (Keras signature).  Circle loss (Sun et al. 2020, the pair-wise form; build-defined, not in the
+    reference): every pair weighted by its distance from its optimum, relaxation m and scale gamma (include/embnet.h,
+    embnet_circle_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.circle_loss(y_pred, k_classes, k_samples, m, gamma)[0]
 
     return loss_function
 
@@ -140,7 +153,7 @@ def xbm_loss(memory, loss="contrastive", **params):
     y_pred the [N, E] embeddings, memory an xbm.CrossBatchMemory.  Each call first enqueues the batch (detached) and then scores
     it against the whole memory with the rows' own slots excluded: the cross-batch memory loss of Wang et al. 2020 (build-defined,
     not in the reference; include/embnet.h, embnet_xbm_loss_fwd).  loss: 'contrastive' (params: margin) or 'multi_similarity'
-    (alpha, beta, base, epsilon); other parameters are refused."""
+    (alpha, beta, base, epsilon) or 'circle' (m, gamma; embnet_xbm_circle_loss_fwd); other parameters are refused."""
     if loss not in ops.XBM_LOSS_MODES:
         raise KeyError(loss)
     fn, keys = ops.XBM_LOSS_MODES[loss]

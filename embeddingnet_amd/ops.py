@@ -196,6 +196,7 @@ MS_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 SUPCON_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 SUPCON_DENOMINATORS = {"all": 1, "negatives": 2}
 AP_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
+CIRCLE_PATHS = {"auto": 0, "per_class": 1, "similarity_matrix": 2}
 
 
 def _supcon_scalars(temperature, denominator):
@@ -221,6 +222,8 @@ _PAIR_LOSSES = {
                      (((2,), torch.int32),), "embnet_ms_loss_bwd", False),
     "smooth_ap_loss": ("embnet_smooth_ap_loss_fwd", "embnet_smooth_ap_loss_workspace_bytes", AP_PATHS,
                        lambda temperature: (f32(temperature),), (((2,), torch.int32),), "embnet_ms_loss_bwd", False),
+    "circle_loss": ("embnet_circle_loss_fwd", "embnet_circle_loss_workspace_bytes", CIRCLE_PATHS,
+                    lambda m, gamma: (f32(m), f32(gamma)), (((3,), torch.int32),), "embnet_ms_loss_bwd", False),
 }
 _PAIR_WS = {}
 
@@ -319,6 +322,19 @@ def smooth_ap_loss(emb, k_classes, k_samples, temperature=0.01, path="auto", ret
     return out if return_weights else out[:2]
 
 
+def circle_loss(emb, k_classes, k_samples, m=0.4, gamma=80.0, path="auto", return_weights=False):
+    """Circle loss (Sun et al., CVPR 2020; the pair-wise form) over a class-contiguous [P*K, E] block, on S = X X^T: every pair is
+    weighted by its distance from its optimum, alpha+ = [1 + m - S_ip]+ and alpha- = [S_in + m]+ (constants of the backward), and
+    l_i = softplus(lse_p(-gamma alpha+ (S_ip - (1 - m))) + lse_n(gamma alpha- (S_in - m))), mean over all N anchors
+    (include/embnet.h has the rounding and the stable forms).  0 <= m <= 1, gamma > 0; the defaults are pytorch-metric-learning's,
+    the paper's face setting is 0.25 / 256.  -> (mean [autograd], counts int32 [3] = positive pairs, violating anchors: those
+    whose hardest negative is at least as similar as their hardest positive, negatives with alpha- > 0) on the device, no host
+    synchronisation; return_weights adds the pair-weight matrix G [N,N] the backward uses.  path: 'auto', 'per_class' or
+    'similarity_matrix'."""
+    out = _PairLoss.apply(emb, "circle_loss", int(k_classes), int(k_samples), (float(m), float(gamma)), path)
+    return out if return_weights else out[:2]
+
+
 # The training modes (TripletTrainer's negatives_selection_mode) whose loss is one of the above over the whole batch; they have no
 # triplet rows, a device count stands where the triplet count does.
 #   mode: (function, the loss_params it takes or None = it takes `margin`, the element of its counts that is that count or
@@ -329,6 +345,7 @@ PAIR_LOSS_MODES = {
     "supcon": (supcon_loss, ("temperature", "denominator"), 1),                                 # violating anchors
     "fast_ap": (fast_ap_loss, ("bins",), 1),                                                    # violating anchors
     "smooth_ap": (smooth_ap_loss, ("temperature",), 1),                                         # violating anchors
+    "circle": (circle_loss, ("m", "gamma"), 1),                                                 # violating anchors
 }
 
 
@@ -529,8 +546,8 @@ def xbm_enqueue(emb, labels, memory):
 
 
 class _XbmLoss(torch.autograd.Function):
-    """embnet_xbm_loss_fwd / _bwd (include/embnet.h): S + sweep forward, one or two backward launches.  G [n,m] and the bank stay saved for
-    the backward; the bank is a constant."""
+    """embnet_xbm_loss_fwd (Circle loss: embnet_xbm_circle_loss_fwd) / _bwd (include/embnet.h): S + sweep forward, one or two backward
+    launches.  G [n,m] and the bank stay saved for the backward; the bank is a constant."""
 
     @staticmethod
     def forward(ctx, emb, labels, mem, mem_labels, self_slots, loss, scalars):
@@ -548,9 +565,14 @@ class _XbmLoss(torch.autograd.Function):
         counts, mean = _new((4,), emb, torch.int32), _new((), emb)
         ws = _ticket_workspace(_XBM_WS, (emb.device.index, stream()), (n, m, e), lib.embnet_xbm_loss_workspace_bytes, torch.float64,
                                emb.device)
-        a, b, c, d = (tuple(map(f32, scalars)) + (0.0, 0.0, 0.0))[:4]
-        check(lib.embnet_xbm_loss_fwd(ptr(emb), ptr(labels), ptr(mem), ptr(mem_labels), ptr(self_slots), n, m, e, XBM_KINDS[loss],
-                                      a, b, c, d, ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8, stream()))
+        if loss == "xbm_circle_loss":                       # an entry point of its own: (m, gamma) where the kinds take a, b, c, d
+            check(lib.embnet_xbm_circle_loss_fwd(ptr(emb), ptr(labels), ptr(mem), ptr(mem_labels), ptr(self_slots), n, m, e,
+                                                 *map(f32, scalars), ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8,
+                                                 stream()))
+        else:
+            a, b, c, d = (tuple(map(f32, scalars)) + (0.0, 0.0, 0.0))[:4]
+            check(lib.embnet_xbm_loss_fwd(ptr(emb), ptr(labels), ptr(mem), ptr(mem_labels), ptr(self_slots), n, m, e, XBM_KINDS[loss],
+                                          a, b, c, d, ptr(g), ptr(counts), ptr(mean), ptr(ws), ws.numel() * 8, stream()))
         ctx.save_for_backward(mem, g)
         ctx.shape, ctx.ws = (n, m, e), ws                   # the backward's scratch: S is not needed any more
         ctx.mark_non_differentiable(counts, g)
@@ -590,10 +612,20 @@ def xbm_multi_similarity_loss(emb, labels, mem, mem_labels, self_slots=None, alp
     return out if return_weights else out[:2]
 
 
+def xbm_circle_loss(emb, labels, mem, mem_labels, self_slots=None, m=0.4, gamma=80.0, return_weights=False):
+    """The Circle loss of circle_loss — its weights, rounding forms and stable logarithms — with anchor i's positives the same-label
+    slots of a DETACHED bank and its negatives the other-label slots (arguments and results as xbm_contrastive_loss; an anchor
+    without a positive or without a negative has no loss).  counts int32 [4] = positives with alpha+ > 0, negatives with
+    alpha- > 0, active anchors (a positive and a negative), labelled bank slots."""
+    out = _XbmLoss.apply(emb, labels, mem, mem_labels, self_slots, "xbm_circle_loss", (float(m), float(gamma)))
+    return out if return_weights else out[:2]
+
+
 # The memory losses of train_step.XbmTrainer:  mode: (function, the xbm_params it takes)
 XBM_LOSS_MODES = {
     "contrastive": (xbm_contrastive_loss, ("margin",)),
     "multi_similarity": (xbm_multi_similarity_loss, ("alpha", "beta", "base", "epsilon")),
+    "circle": (xbm_circle_loss, ("m", "gamma")),
 }
 
 

@@ -31,7 +31,7 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon / fast_ap / smooth_ap); anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon / fast_ap / smooth_ap / circle); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
     all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
     negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
@@ -43,7 +43,10 @@ class TripletTrainer:
     denominator), defaults 0.1 and 'all' = SupCon, 'negatives' = NT-Xent; `margin` is not used; last_triplets = (None, violating
     anchors [1]) and last_pair_counts = int32 [2]: positive pairs, violating anchors) or 'fast_ap' / 'smooth_ap' (the ranking
     family: ops.fast_ap_loss with loss_params = dict(bins), default 10, and ops.smooth_ap_loss with loss_params =
-    dict(temperature), default 0.01; `margin` is not used; last_triplets and last_pair_counts as for 'supcon').  Under data
+    dict(temperature), default 0.01; `margin` is not used; last_triplets and last_pair_counts as for 'supcon') or 'circle' (Sun et
+    al.: ops.circle_loss with loss_params = dict(m, gamma), defaults 0.4 and 80; `margin` is not used; last_triplets = (None,
+    violating anchors [1]) and last_pair_counts = int32 [3]: positive pairs, violating anchors, negatives that still carry
+    gradient).  Under data
     parallelism every mode mines and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     LOSS_PARAMS = {mode: keys for mode, (_, keys, _) in ops.PAIR_LOSS_MODES.items() if keys is not None}
@@ -483,7 +486,8 @@ class XbmTrainer(TripletTrainer):
     """TripletTrainer with a cross-batch memory (xbm.CrossBatchMemory; Wang et al., CVPR 2020): the loss of a step is the parent
     mode's in-batch loss — any negatives_selection_mode — plus `weight` times the loss of the SAME embeddings against the memory
     (ops.XBM_LOSS_MODES: 'contrastive', the XBM paper's criterion, xbm_params = dict(margin), default 0.5; 'multi_similarity',
-    xbm_params = dict(alpha, beta, base, epsilon), defaults 2, 50, 0.5, 0.1; unknown keys are refused).  The XBM recipe: the batch's
+    xbm_params = dict(alpha, beta, base, epsilon), defaults 2, 50, 0.5, 0.1; 'circle', xbm_params = dict(m, gamma), defaults 0.4
+    and 80, whose first two counts are the pairs with a positive weight; unknown keys are refused).  The XBM recipe: the batch's
     detached embeddings are enqueued first, then the batch is scored against the whole ring with each sample's own slot excluded.
     The ring, its write position and the enqueue live on the device (include/embnet.h): no host synchronisation, and with
     graph=True / 'auto' the step — enqueue and memory loss included — is captured once and replayed like ProxyTrainer's, the labels

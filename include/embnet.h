@@ -1320,6 +1320,55 @@ int embnet_xbm_loss_fwd(const float* emb, const int32_t* labels, const float* me
 int embnet_xbm_loss_bwd(const float* mem, int n, int m, int e, const float* pair_g, const float* upstream, float* demb,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Circle loss (Sun et al., CVPR 2020, "Circle Loss: A Unified Perspective of Pair Similarity Optimization"; the pair-wise form, as
+ * pytorch-metric-learning's CircleLoss has it; the reference has no such loss): build-defined, in-batch selected as
+ * TripletTrainer(negatives_selection_mode="circle") and against the cross-batch memory as XbmTrainer(xbm_loss="circle").
+ * Additions only: the ABI version stays 22.
+ *   Parameters.  The relaxation m, finite, 0 <= m <= 1; the scale gamma, finite and positive.  The Python layers default to 0.4 and
+ *     80 (pytorch-metric-learning's; the paper's face setting is 0.25 / 256).  Derived ONCE per call on the host, one fp32 operation
+ *     each:  O+ = fl(1 + m),  O- = -m,  D+ = fl(1 - m),  D- = m.
+ *   Similarity.  In-batch: emb[n,e] fp32, n = p*k, rows c*k .. c*k+k-1 are class c; S = X X^T, computed as embnet_ms_loss_fwd
+ *     computes it.  Ring: S = X Mem^T through embnet_dense_dgrad_f32, as embnet_xbm_loss_fwd computes it.  Unit rows are not required.
+ *   Pair sets of anchor i.  In-batch: P_i the other rows of its class, N_i the rows of other classes.  Ring: by label value, with
+ *     negative labels and self_slots, embnet_xbm_loss_fwd's P_i and N_i word for word.
+ *   Logits, in ONE rounding form (every fl one fp32 operation):
+ *     alpha+_p = max(fl(O+ - S_ip), 0),   a+_p = fl(-gamma fl(alpha+_p fl(S_ip - D+)));
+ *     alpha-_n = max(fl(S_in - O-), 0),   a-_n = fl( gamma fl(alpha-_n fl(S_in - D-))).
+ *     A pair with alpha = 0 stays in its sum with logit 0 (the paper and the published implementations).
+ *   Per-anchor loss.  L+ = lse_p a+_p,  L- = lse_n a-_n, each as M + log sum e^{a - M} with M the side's largest logit, so the
+ *     logarithm's argument is >= 1;  z = fl(L+ + L-);  l_i = softplus(z) = max(z, 0) + log(1 + t), t = e^{-|z|}.  An anchor with an
+ *     empty P_i or an empty N_i (the ring only) has l_i = 0 and a zero row of G.  *mean_loss = (1/n) sum_i l_i, n counting EVERY
+ *     batch row.  The results are finite whenever every logit is finite in fp32.
+ *   Pair weights.  alpha is a CONSTANT of the backward (the authors' code and pytorch-metric-learning detach it; this gives the
+ *     paper's gradient).  sigma = sigmoid(z) = 1 / (1 + t) for z >= 0, t / (1 + t) otherwise.  With w+ = fl(fl(sigma gamma) / sum+)
+ *     and w- = fl(fl(sigma gamma) / sum-), sum the side's sum of e^{a - M}:
+ *     G_ip = -fl(w+ fl(alpha+_p e^{a+_p - M+})),   G_in = +fl(w- fl(alpha-_n e^{a-_n - M-})),   0 elsewhere, the diagonal or the
+ *     self slot included; every entry of pair_g ([n][n] resp. [n][m_slots], without the 1/n) is written.  G is therefore NOT the
+ *     derivative of l_i with alpha free: it lacks the term through d alpha / dS.
+ *   Backward.  No entry point of its own.  In-batch: demb_i = (g / n) sum_j (G_ij + G_ji) x_j, embnet_ms_loss_bwd's contract, and
+ *     embnet_ms_loss_bwd(emb, n, e, pair_g, upstream, demb, stream) is the backward.  Ring: demb_i = (g / n) sum_j G_ij y_j,
+ *     embnet_xbm_loss_bwd as it stands.
+ *   Counters, int32, exact on the device's fp32 S.  In-batch counts[3]: {positive pairs n (k-1) <= 4096 * 2047; violating
+ *     anchors, max_{n in N_i} S_in >= min_{p in P_i} S_ip (embnet_supcon_loss_fwd's counter) <= n; negatives with alpha- > 0, the
+ *     ones that still carry gradient, <= n (n - k) < 2^24}.  Ring counts[4]: {positives with alpha+ > 0, negatives with
+ *     alpha- > 0, both over the active anchors and <= n m_slots <= 2^26; active anchors (P_i and N_i both non-empty); labelled
+ *     bank slots}.
+ * Range.  In-batch: embnet_ms_loss_fwd's (p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096), with its two forward paths
+ * (EMBNET_CIRCLE_PER_CLASS, EMBNET_CIRCLE_SIMILARITY_MATRIX; path 0 = auto, embnet_circle_loss_path), its fit rule and its
+ * workspace (embnet_circle_loss_workspace_bytes).  Ring: embnet_xbm_loss_fwd's (2 <= n <= 4096, n <= m_slots <= 65536,
+ * n m_slots <= 2^26, 1 <= e <= 4096), its one path and its workspace (embnet_xbm_loss_workspace_bytes).  Anything else, a
+ * non-finite or out-of-range m or gamma included, is rejected before a launch.  No floating-point atomics, every reduction in a
+ * fixed order: bitwise reproducible; no host synchronisation or allocation; capturable in a graph.  Either workspace (16-byte
+ * aligned): zero-filled ONCE by the caller; every launch leaves its arrival counter zeroed. */
+enum { EMBNET_CIRCLE_PER_CLASS = 1, EMBNET_CIRCLE_SIMILARITY_MATRIX = 2 };
+int embnet_circle_loss_path(int p, int k, int e);         /* the path `auto` takes; 0 outside the range */
+size_t embnet_circle_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_circle_loss_fwd(const float* emb, int p, int k, int e, float m, float gamma, int path, float* pair_g, int32_t* counts,
+                           float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_xbm_circle_loss_fwd(const float* emb, const int32_t* labels, const float* mem, const int32_t* mem_labels,
+                               const int32_t* self_slots, int n, int m_slots, int e, float m, float gamma, float* pair_g,
+                               int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

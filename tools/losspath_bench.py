@@ -8,7 +8,8 @@ semihard) the forward + backward of the loss path is run both ways on the same c
 run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape instead, the *_multi_similarity cases
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
 denominator beside ops.multi_similarity_loss, the *_fast_ap / *_smooth_ap cases (`--only _ap`) ops.fast_ap_loss / ops.smooth_ap_loss at
-their defaults beside ops.supcon_loss('all'); the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
+their defaults beside ops.supcon_loss('all'), the *_circle cases (`--only circle`, which also takes the xbm_circle cases) ops.circle_loss
+at its defaults beside ops.supcon_loss('all'); the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
 xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time(), the mproxy_* cases (SoftTriple and sub-centre
 ArcFace on several centres per class; `--only mproxy_`) at mproxy_cases()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
@@ -36,7 +37,7 @@ CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batc
          ("c1_multi_similarity", 8, 4, 256, "multi_similarity"), ("c2_multi_similarity", 32, 4, 256, "multi_similarity"),
          ("c5_multi_similarity", 64, 4, 512, "multi_similarity"),
          ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")] + \
-        [(f"{cfg}_{mode}", p, k, e, mode) for mode in ("fast_ap", "smooth_ap")
+        [(f"{cfg}_{mode}", p, k, e, mode) for mode in ("fast_ap", "smooth_ap", "circle")
          for cfg, p, k, e in (("c1", 8, 4, 256), ("c2", 32, 4, 256), ("c5", 64, 4, 512))]
 
 
@@ -238,7 +239,7 @@ def mproxy_cases(a, dev, out):
 
 
 # the cross-batch memory: (name, n, e, m, kind)
-XBM_CASES = [(f"xbm_{kind}_e{e}_m{m}", 128, e, m, kind) for kind in ("contrastive", "multi_similarity") for e in (128, 256)
+XBM_CASES = [(f"xbm_{kind}_e{e}_m{m}", 128, e, m, kind) for kind in ("contrastive", "multi_similarity", "circle") for e in (128, 256)
              for m in (1024, 8192, 65536)]
 
 
@@ -257,8 +258,13 @@ def torch_xbm_step(kind, x, labels, mem, mem_labels, cursor, params):
     zero = torch.zeros((), device=x.device)
     if kind == "contrastive":
         return (torch.where(pos & (1.0 - s > 0), 1.0 - s, zero).sum(1) + torch.where(neg & (s > params["margin"]), s, zero).sum(1)).mean()
-    al, be, ba, eps = params["alpha"], params["beta"], params["base"], params["epsilon"]
     inf = torch.full((), float("inf"), device=x.device)
+    if kind == "circle":
+        mr, ga = params["m"], params["gamma"]
+        lp = torch.logsumexp(torch.where(pos, -ga * (1.0 + mr - s).clamp(min=0).detach() * (s - (1.0 - mr)), -inf), 1)
+        ln = torch.logsumexp(torch.where(neg, ga * (s + mr).clamp(min=0).detach() * (s - mr), -inf), 1)
+        return torch.where(pos.any(1) & neg.any(1), torch.nn.functional.softplus(lp + ln), zero).mean()
+    al, be, ba, eps = params["alpha"], params["beta"], params["base"], params["epsilon"]
     mn, mx = torch.where(pos, s, inf).min(1).values, torch.where(neg, s, -inf).max(1).values
     kp, kn = pos & ((mx + eps)[:, None] > s), neg & ((s + eps) > mn[:, None])
     z = torch.zeros((n, 1), device=x.device)
@@ -268,7 +274,7 @@ def torch_xbm_step(kind, x, labels, mem, mem_labels, cursor, params):
 
 
 def xbm_cases(a, dev, out):
-    """ops.xbm_enqueue + ops.xbm_contrastive_loss / ops.xbm_multi_similarity_loss + backward at N = 128 against a full memory of M
+    """ops.xbm_enqueue + ops.xbm_contrastive_loss / ops.xbm_multi_similarity_loss / ops.xbm_circle_loss + backward at N = 128 against a full memory of M
     slots, beside the same step composed from torch ops, in one process, alternating: device microseconds are medians of
     alternating rounds of graph replays; launches and per-kernel times of the library leg come from the library's trace."""
     from embeddingnet_amd.xbm import CrossBatchMemory
@@ -289,7 +295,8 @@ def xbm_cases(a, dev, out):
         memory.feats.copy_(rows(bank_labels)); memory.labels.copy_(bank_labels)
         t_mem, t_lab, t_cur = memory.feats.clone(), bank_labels.long(), torch.zeros(1, dtype=torch.long, device=dev)
         fn, keys = ops.XBM_LOSS_MODES[kind]
-        params = dict(margin=0.5) if kind == "contrastive" else dict(alpha=2.0, beta=50.0, base=0.5, epsilon=0.1)
+        params = dict(contrastive=dict(margin=0.5), multi_similarity=dict(alpha=2.0, beta=50.0, base=0.5, epsilon=0.1),
+                      circle=dict(m=0.4, gamma=80.0))[kind]
         lab64 = labels.long()
 
         def hip():
@@ -456,9 +463,9 @@ def main():
 
         def ap_loss():
             x.grad = None
-            (ops.fast_ap_loss if mode == "fast_ap" else ops.smooth_ap_loss)(x, p, k)[0].backward()
+            dict(fast_ap=ops.fast_ap_loss, smooth_ap=ops.smooth_ap_loss, circle=ops.circle_loss)[mode](x, p, k)[0].backward()
 
-        if mode in ("fast_ap", "smooth_ap"):                # the two legs alternate in one process, at one shape, twice over
+        if mode in ("fast_ap", "smooth_ap", "circle"):                # the two legs alternate in one process, at one shape, twice over
             row = dict(config=name, N=n, E=e, mining=mode)
             for rnd in (1, 2):
                 row[f"{mode}_{rnd}"] = measure(ap_loss, a.iters)

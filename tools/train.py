@@ -16,6 +16,8 @@ GENERATOR.xbm: {size, weight, start_iteration, loss, <that loss's parameters>} a
 embeddingnet_amd/xbm.py) to any triplet-mode negatives_selection_mode but the proxy ones: the loss of the batch against the detached
 embeddings of the last `size` samples, `weight` times, from step `start_iteration` on; `xbm_filled` and the kept pairs are logged
 per epoch.  Each rank keeps its own memory; it is not checkpointed, after --resume_from it refills.
+GENERATOR.circle_loss: {m, gamma} sets Circle loss's parameters for negatives_selection_mode 'circle' (and `loss: 'circle'` with the
+same two keys under GENERATOR.xbm scores the memory with it); the violating anchors are logged per epoch.
 `--synthetic` swaps the file loader for an in-memory synthetic dataset (no dataset ships with the repo).
 """
 import argparse
@@ -152,6 +154,8 @@ LOSS_CONFIGS = {
 }
 # GENERATOR.ap_loss with the ranking modes: the same validator on a table of its own, as for the modes below (ap_loss_config)
 AP_LOSS_CONFIGS = {'fast_ap': dict(bins='positive'), 'smooth_ap': dict(temperature='positive number')}
+# GENERATOR.circle_loss with 'circle': likewise (circle_loss_config)
+CIRCLE_LOSS_CONFIGS = {'circle': dict(m='number', gamma='positive')}
 # GENERATOR.proxy_loss with the modes on several centres per class (ops.MULTI_PROXY_LOSS_MODES): the same validator on a table of
 # their own (proxy_loss_config), so the messages about the key keep naming the two modes they always named
 MULTI_PROXY_LOSS_CONFIGS = {
@@ -163,6 +167,7 @@ MS_LOSS_KEYS = tuple(LOSS_CONFIGS['ms_loss']['multi_similarity'])
 SUPCON_LOSS_KEYS = tuple(LOSS_CONFIGS['supcon_loss']['supcon'])
 PROXY_LOSS_KEYS = {mode: tuple(checks) for mode, checks in LOSS_CONFIGS['proxy_loss'].items()}
 AP_LOSS_KEYS = {mode: tuple(checks) for mode, checks in AP_LOSS_CONFIGS.items()}
+CIRCLE_LOSS_KEYS = tuple(CIRCLE_LOSS_CONFIGS['circle'])
 
 
 def loss_config(name, cfg, table=None):
@@ -211,6 +216,19 @@ def supcon_loss_config(cfg):
     return loss_config('supcon_loss', cfg)
 
 
+def _circle_m(name, out, value):
+    """Circle loss's relaxation lies in [0, 1] (include/embnet.h); the validator's checks know numbers and signs only."""
+    if out is not None and not 0 <= out.get('m', 0.4) <= 1:
+        raise ValueError(f"GENERATOR.{name}: m must lie in [0, 1] (got {value!r})")
+    return out
+
+
+def circle_loss_config(cfg):
+    """GENERATOR.circle_loss for 'circle': {m in [0, 1], gamma > 0}; `margin` is not used and embeddings_normalization should be
+    on (the optima 1 - m and m are cosine similarities)."""
+    return _circle_m('circle_loss', loss_config('circle_loss', cfg, CIRCLE_LOSS_CONFIGS), cfg['generator'].get('circle_loss'))
+
+
 def ap_loss_config(cfg):
     """GENERATOR.ap_loss for the ranking modes: {bins} with 'fast_ap', a whole number in [2, 64]; {temperature} with 'smooth_ap'."""
     out = loss_config('ap_loss', cfg, AP_LOSS_CONFIGS)
@@ -243,12 +261,13 @@ def proxy_loss_config(cfg):
 
 
 # GENERATOR.xbm (optional): the memory's own keys, and per memory loss (ops.XBM_LOSS_MODES) that loss's parameters.
-XBM_KEYS = dict(size='positive', weight='number', start_iteration='number', loss=('contrastive', 'multi_similarity'))
+XBM_KEYS = dict(size='positive', weight='number', start_iteration='number', loss=('contrastive', 'multi_similarity', 'circle'))
 XBM_LOSS_KEYS = {'contrastive': dict(margin='number'),
-                 'multi_similarity': dict(alpha='positive', beta='positive', base='number', epsilon='number')}
+                 'multi_similarity': dict(alpha='positive', beta='positive', base='number', epsilon='number'),
+                 'circle': dict(m='number', gamma='positive')}
 XBM_DEFAULTS = dict(weight=1.0, start_iteration=0, loss='contrastive')
 XBM_MODES = ('semihard', 'hardest', 'random_hard', 'batch_hard', 'batch_all', 'multi_similarity', 'supcon', 'fast_ap',
-             'smooth_ap')
+             'smooth_ap', 'circle')
 
 
 def xbm_config(cfg):
@@ -262,6 +281,8 @@ def xbm_config(cfg):
     checks = dict(XBM_KEYS, **XBM_LOSS_KEYS.get(loss, {}))
     LOSS_CONFIGS['xbm'] = {mode: checks for mode in XBM_MODES}
     out = dict(XBM_DEFAULTS, **loss_config('xbm', cfg))
+    if out['loss'] == 'circle':
+        _circle_m('xbm', out, value)
     if 'size' not in out or out['size'] != int(out['size']):
         raise ValueError(f"GENERATOR.xbm: size, the number of slots, must be a whole number (got {value!r})")
     if out['start_iteration'] != int(out['start_iteration']) or out['start_iteration'] < 0:
@@ -431,12 +452,14 @@ def main():
     supcon_loss = supcon_loss_config(cfg)              # and GENERATOR.supcon_loss
     proxy_loss = proxy_loss_config(cfg)                # and GENERATOR.proxy_loss
     ap_loss = ap_loss_config(cfg)                      # and GENERATOR.ap_loss
+    circle_loss = circle_loss_config(cfg)              # and GENERATOR.circle_loss
     xbm = xbm_config(cfg)                              # and GENERATOR.xbm (with a proxy mode, in Siamese mode, a memory below a batch)
     # each is refused with another's mode: at most one is set
-    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss, ap_loss) if v is not None), None)
+    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss, ap_loss, circle_loss) if v is not None), None)
     multi_proxy_mode = cfg['generator'].get('negatives_selection_mode') in MULTI_PROXY_LOSS_CONFIGS
     proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS or multi_proxy_mode
-    ap_mode = cfg['generator'].get('negatives_selection_mode') in AP_LOSS_KEYS and cfg['model']['mode'] != 'siamese'
+    # the modes whose log line carries the violating anchors: the ranking losses and Circle loss
+    ap_mode = cfg['generator'].get('negatives_selection_mode') in tuple(AP_LOSS_KEYS) + ('circle',) and cfg['model']['mode'] != 'siamese'
     if proxy_mode and cfg['model']['mode'] == 'siamese':
         raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
@@ -467,7 +490,7 @@ def main():
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
     verification = verification_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss',
-                                                       'ap_loss', 'xbm')}
+                                                       'ap_loss', 'circle_loss', 'xbm')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
