@@ -8,6 +8,7 @@ meaning), computing on the GPU through libembnet_hip.so.
   multi_similarity_loss(P, K, alpha, beta, base, epsilon)(y_true, y_pred)   build-defined (MS loss over a [P*K, E] block) -> scalar
   supcon_loss(P, K, temperature, denominator)(y_true, y_pred)   build-defined (SupCon / NT-Xent over a [P*K, E] block) -> scalar
   circle_loss(P, K, m, gamma)(y_true, y_pred)               build-defined (Circle loss over a [P*K, E] block) -> scalar
+  margin_loss(P, K, beta, alpha, cutoff, nonzero_loss_cutoff, seed)(y_true, y_pred)   build-defined (distance-weighted sampling + margin loss) -> scalar
   fast_ap_loss(P, K, bins)(y_true, y_pred)                  build-defined (FastAP over a [P*K, E] block) -> scalar
   smooth_ap_loss(P, K, temperature)(y_true, y_pred)         build-defined (Smooth-AP over a [P*K, E] block) -> scalar
   proxy_anchor_loss(head, alpha, delta)(y_true, y_pred)     build-defined (Proxy-Anchor against a ProxyHead's proxies) -> scalar
@@ -78,6 +79,18 @@ def circle_loss(k_classes, k_samples, m=0.4, gamma=80.0):
 
     def loss_function(y_true, y_pred):
         return ops.circle_loss(y_pred, k_classes, k_samples, m, gamma)[0]
+
+    return loss_function
+
+
+def margin_loss(k_classes, k_samples, beta=1.2, alpha=0.2, cutoff=0.5, nonzero_loss_cutoff=1.4, seed=0):
+    """Returns loss_function(y_true, y_pred) -> scalar; y_pred is the class-contiguous [k_classes*k_samples, E] block of
+    L2-normalised embeddings, y_true is ignored (Keras signature).  Distance-weighted sampling with the margin loss (Wu et al.
+    2017; build-defined, not in the reference): one negative per positive drawn with the inverse of the unit sphere's distance
+    density, two hinges around the boundary beta; the draws are keyed by `seed` (include/embnet.h, embnet_margin_loss_fwd)."""
+
+    def loss_function(y_true, y_pred):
+        return ops.margin_loss(y_pred, k_classes, k_samples, beta, alpha, cutoff, nonzero_loss_cutoff, seed=seed)[0]
 
     return loss_function
 

@@ -335,8 +335,78 @@ def circle_loss(emb, k_classes, k_samples, m=0.4, gamma=80.0, path="auto", retur
     return out if return_weights else out[:2]
 
 
+MARGIN_PATHS = {"auto": 0, "per_class": 1, "distance_matrix": 2}
+
+
+class _MarginLoss(torch.autograd.Function):
+    """embnet_margin_loss_fwd / _bwd (include/embnet.h): the sampler and the loss in one forward launch on the per-class path,
+    distance matrix + sweep above it; one backward launch.  Beside _PairLoss because of the seed, the triplet rows and sample_w."""
+
+    @staticmethod
+    def forward(ctx, emb, p, k, scalars, seed, seed_dev, path, with_sample_w):
+        emb = _prep(emb)
+        n, e = emb.shape
+        if n != p * k:
+            raise _lib.EmbnetError(f"margin_loss: {n} rows != k_classes*k_samples = {p}*{k}")
+        if path not in MARGIN_PATHS:
+            raise _lib.EmbnetError(f"margin_loss: path {path!r} is not one of {sorted(MARGIN_PATHS)}")
+        lib = _lib.lib()
+        w = _new((n, n), emb)
+        sample_w = _new((n, n), emb) if with_sample_w else None
+        counts = _new((3,), emb, torch.int32)
+        trip = _new((n * max(k - 1, 0), 3), emb, torch.int32)
+        mean = _new((), emb)
+        ws = _ticket_workspace(_PAIR_WS, ("margin_loss", emb.device.index, stream()), (p, k, e), lib.embnet_margin_loss_workspace_bytes,
+                               torch.float32, emb.device)
+        check(lib.embnet_margin_loss_fwd(ptr(emb), p, k, e, *map(f32, scalars), int(seed) & (2 ** 64 - 1), seed_dev, MARGIN_PATHS[path],
+                                         ptr(w), ptr(counts), ptr(trip), ptr(sample_w), ptr(mean), ptr(ws), ws.numel() * 4, stream()))
+        ctx.save_for_backward(emb, w, counts)
+        outs = (counts, trip, w) + ((sample_w,) if with_sample_w else ())
+        ctx.mark_non_differentiable(*outs)
+        ctx.set_materialize_grads(False)                    # no zero tensors for the outputs nobody differentiates
+        return (mean, *outs)
+
+    @staticmethod
+    def backward(ctx, dmean, *_):
+        if dmean is None:
+            return (None,) * 8
+        emb, w, counts = ctx.saved_tensors
+        n, e = emb.shape
+        demb = torch.empty_like(emb)
+        check(_lib.lib().embnet_margin_loss_bwd(ptr(emb), n, e, ptr(w), ptr(counts), ptr(_prep(dmean)), ptr(demb), stream()))
+        return (demb,) + (None,) * 7
+
+
+def margin_loss(emb, k_classes, k_samples, beta=1.2, alpha=0.2, cutoff=0.5, nonzero_loss_cutoff=1.4, seed=0, seed_dev=None,
+                path="auto", return_weights=False):
+    """Distance-weighted sampling with the margin loss (Wu et al., ICCV 2017) over a class-contiguous [P*K, E] block of unit rows:
+    every anchor draws one negative per positive, with replacement, from the other-class rows at Euclidean distance D <
+    nonzero_loss_cutoff with weight 1 / q(max(D, cutoff)), q the density of pairwise distances on the unit sphere, and pays
+    [D_ap - beta + alpha]+ + [beta - D_an + alpha]+; the mean runs over the A positive hinges (include/embnet.h has the rounding
+    form, the draws' keying and the sampler's summation order).  0 < cutoff < nonzero_loss_cutoff < 2, alpha >= 0; the defaults are
+    the paper's.  seed: the draws' key; seed_dev: device address of a uint64 that overrides it (graph replays).
+    -> (mean [autograd], counts int32 [3] = active positive hinges, active negative hinges, A, triplets int32 [N (K-1), 3] =
+    (anchor, positive, drawn negative)) on the device, no host synchronisation; return_weights adds the pair-weight matrix W [N,N]
+    the backward uses and the sampling weights [N,N] (a row of zeros: the anchor had no eligible negative and drew uniformly).
+    path: 'auto', 'per_class' or 'distance_matrix'."""
+    out = _MarginLoss.apply(emb, int(k_classes), int(k_samples),
+                            (float(beta), float(alpha), float(cutoff), float(nonzero_loss_cutoff)), int(seed), seed_dev, path,
+                            bool(return_weights))
+    return out if return_weights else out[:3]
+
+
+def distance_weighted_triplets(emb, k_classes, k_samples, cutoff=0.5, nonzero_loss_cutoff=1.4, seed=0):
+    """The miner of margin_loss on its own: -> (triplets int32 [N (K-1), 3], count int32 [1] = N (K-1)), no gradient; the rows
+    are fit for triplet_gather_loss.  The draws depend on the embeddings, the two cutoffs and the seed only, so they equal
+    margin_loss's for the same seed."""
+    with torch.no_grad():
+        trip = margin_loss(emb.detach(), k_classes, k_samples, cutoff=cutoff, nonzero_loss_cutoff=nonzero_loss_cutoff, seed=seed)[2]
+    return trip, torch.full((1,), trip.shape[0], dtype=torch.int32, device=trip.device)
+
+
 # The training modes (TripletTrainer's negatives_selection_mode) whose loss is one of the above over the whole batch; they have no
-# triplet rows, a device count stands where the triplet count does.
+# triplet rows ('distance_weighted' apart: its third result is the rows it drew, and it takes the step's seed), a device count stands
+# where the triplet count does.
 #   mode: (function, the loss_params it takes or None = it takes `margin`, the element of its counts that is that count or
 #          None = the counts are the count; with an element the trainer keeps all of them as last_pair_counts)
 PAIR_LOSS_MODES = {
@@ -346,6 +416,7 @@ PAIR_LOSS_MODES = {
     "fast_ap": (fast_ap_loss, ("bins",), 1),                                                    # violating anchors
     "smooth_ap": (smooth_ap_loss, ("temperature",), 1),                                         # violating anchors
     "circle": (circle_loss, ("m", "gamma"), 1),                                                 # violating anchors
+    "distance_weighted": (margin_loss, ("beta", "alpha", "cutoff", "nonzero_loss_cutoff"), 2),  # active hinges A
 }
 
 

@@ -31,7 +31,7 @@ class TripletTrainer:
     ~200 (simple2), for the batch sizes where the host cannot keep up with the GPU.  The step-dependent scalars (the
     optimizer's bias corrections, the mining seed) live in device memory and are refreshed by a 32-byte copy before
     each replay (dropout layers add a device-side step counter to their seeds); results are bit-identical to eager steps.
-    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon / fast_ap / smooth_ap / circle); anything else, or a failed capture, falls back to eager steps.
+    Needs: the KerasOptimizer and the fused loss path (or batch_all / multi_similarity / supcon / fast_ap / smooth_ap / circle / distance_weighted); anything else, or a failed capture, falls back to eager steps.
     With a gradient reducer (N > 1) the step is two graphs — forward + backward, optimizer — with the bucketed gradient
     all-reduce issued between them as ordinary collectives.  Steps taken while the kernel trace is on run eagerly.
     negatives_selection_mode: 'semihard' | 'hardest' | 'random_hard' (the reference's rules, ops.MINING_MODES), 'batch_hard'
@@ -46,7 +46,10 @@ class TripletTrainer:
     dict(temperature), default 0.01; `margin` is not used; last_triplets and last_pair_counts as for 'supcon') or 'circle' (Sun et
     al.: ops.circle_loss with loss_params = dict(m, gamma), defaults 0.4 and 80; `margin` is not used; last_triplets = (None,
     violating anchors [1]) and last_pair_counts = int32 [3]: positive pairs, violating anchors, negatives that still carry
-    gradient).  Under data
+    gradient) or 'distance_weighted' (Wu et al.: distance-weighted sampling with the margin loss, ops.margin_loss with loss_params =
+    dict(beta, alpha, cutoff, nonzero_loss_cutoff), defaults 1.2, 0.2, 0.5, 1.4; `margin` is not used; the draws are keyed by the
+    step's seed, from device memory in a replayed step, as the fused path's; last_triplets = (the N (K-1) drawn triplets, active
+    hinges A [1]) and last_pair_counts = int32 [3]: active positive hinges, active negative hinges, A).  Under data
     parallelism every mode mines and normalises per rank."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     LOSS_PARAMS = {mode: keys for mode, (_, keys, _) in ops.PAIR_LOSS_MODES.items() if keys is not None}
@@ -115,11 +118,17 @@ class TripletTrainer:
         last_triplets (and last_pair_counts).  XbmTrainer adds the memory's loss of the same embeddings to it."""
         if self.mode in ops.PAIR_LOSS_MODES:                # at every batch size and whatever EMBNET_FUSED_LOSS says
             fn, keys, at = ops.PAIR_LOSS_MODES[self.mode]
-            mean, counts = fn(emb, self.p, self.k, **({"margin": self.margin} if keys is None else self.loss_params))[:2]
+            kwargs = {"margin": self.margin} if keys is None else dict(self.loss_params)
+            draws = self.mode == "distance_weighted"        # the one whole-batch loss that samples: the fused path's seed
+            if draws:
+                kwargs.update(seed=(self.seed << 20) + self.step_no,
+                              seed_dev=self._state.data_ptr() + 24 if self._graph_state_live() else None)
+            out = fn(emb, self.p, self.k, **kwargs)
+            mean, counts = out[:2]
             count = counts if at is None else counts[at:at + 1]             # a slice view of the counts
             if at is not None:
                 self.last_pair_counts = counts
-            self.last_triplets = (None, count)
+            self.last_triplets = (out[2] if draws else None, count)
         elif self.fused_loss and ops.fused_loss_supported(self.p, self.k, emb.shape[1]):
             seed_dev = self._state.data_ptr() + 24 if self._graph_state_live() else None     # uint64 behind the 6 floats
             mean, _, trip, count = ops.fused_triplet_loss(emb, self.p, self.k, self.margin, self.mode,

@@ -1369,6 +1369,64 @@ int embnet_xbm_circle_loss_fwd(const float* emb, const int32_t* labels, const fl
                                const int32_t* self_slots, int n, int m_slots, int e, float m, float gamma, float* pair_g,
                                int32_t* counts, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Distance-weighted sampling and the margin loss (Wu, Manmatha, Smola, Kraehenbuehl, ICCV 2017, "Sampling Matters in Deep
+ * Embedding Learning"; pytorch-metric-learning's DistanceWeightedMiner and MarginLoss; the reference has no such loss):
+ * build-defined, selected as TripletTrainer(negatives_selection_mode="distance_weighted").  Additions only: the ABI version stays 22.
+ *   Inputs.  emb[n,e] fp32, n = p*k, rows c*k .. c*k+k-1 are class c; the method assumes unit rows (the weights are the inverse
+ *     of the density of pairwise distances on the unit sphere S^(e-1)), the kernels do not require them.
+ *   Distance.  d2(i,j) = sum_c (x_ic - x_jc)^2 exactly as embnet_batch_all_loss_fwd forms it on either path (difference form
+ *     per class; embnet_pairwise_dist_f32(squared), Gram form, on the matrix path).  D = sqrtf(max(d2, 0)), one fp32 sqrtf; a NaN
+ *     stays a NaN.  On the matrix path the Gram form's clamp would turn the NaN of a non-finite row into 0: there a pair with a row
+ *     whose squared norm (embnet_pairwise_dist_f32's own) is NaN or infinite has D = NaN.
+ *   Parameters.  beta finite; alpha >= 0 finite; cutoff = c_lo and nonzero_loss_cutoff = c_hi finite with 0 < c_lo < c_hi < 2, so
+ *     the second logarithm's argument below is positive.  The Python layers default to 1.2, 0.2, 0.5, 1.4 (the paper's).
+ *   Weights of anchor i (global row).  An other-class column n is ELIGIBLE iff D_in is not NaN and D_in < c_hi.  In ONE rounding
+ *     form, every fl one fp32 operation, logf / expf the device's:
+ *       D~ = max(D_in, c_lo),   t = fl(1 - fl(0.25 fl(D~ D~))),   lw_n = fl(fl(a1 logf(D~)) - fl(a2 logf(t))),
+ *       a1 = 2 - e and a2 = (e - 3) / 2, both exact in fp32;   M = max lw over the eligible columns, taken exactly;
+ *       w_n = expf(fl(lw_n - M)) on eligible columns, exactly 0 elsewhere (own class, the anchor, ineligible).
+ *     The maximal column has w = 1 exactly, so total >= 1 whenever a column is eligible; other weights may underflow to 0.
+ *   Draws.  The anchor's k-1 positives in ascending column order have ordinals j = 0 .. k-2; each gets one negative, drawn
+ *     independently and with replacement:  u_ij = (((rng(seed, i, 2j) << 32) | rng(seed, i, 2j+1)) >> 11) 2^-53  (rng = the
+ *     counter generator of the mining rules; the 53-bit form of embnet_kmeans_pp_pick).  Prefix sums in f64, in this order: the
+ *     row in chunks of 64 columns ascending (columns >= n weigh 0); inside chunk c the inclusive scan s of the chunk's weights in
+ *     column order by doubling steps 1, 2, 4, .. 32 (column l adds the value held l - step columns below it);
+ *     P_col = fl(carry_c + s_col), carry_0 = 0, carry_(c+1) = fl(carry_c + s_(c,63)); total = the carry behind the last chunk.
+ *     The pick is the first column, in ascending order, with w > 0 and P_col > fl(u total); if rounding leaves none, the last
+ *     column with w > 0.  total = 0 (no eligible column): the pick is the floor(u (n-k))-th other-class column in ascending order
+ *     (the authors' uniform fall-back).  A zero-weight column is never drawn while total > 0, and every index written lies in
+ *     [0, n) whatever the row holds.  seed_dev (NULL or a device uint64) overrides `seed` exactly as in
+ *     embnet_fused_triplet_loss_fwd, so a captured step draws new negatives at every replay.
+ *   Loss.  l+_ip = max(fl(fl(D_ip - beta) + alpha), 0) for every positive; l-_ij = max(fl(fl(beta - D_in) + alpha), 0) for draw
+ *     j's negative n (a NaN distance gives 0).  c+ = #{l+ > 0}, c- = #{l- > 0} over the batch, a draw counting each time it is
+ *     drawn; A = c+ + c-.  *mean_loss = (sum l+ + sum l-) / max(A, 1), the sums in f64: per anchor, lane (j mod 64) adds l+ then
+ *     l- of ordinal j in ascending j, the 64 lanes fold by the xor butterfly 32, 16, .. 1; then the skeleton's fixed order over
+ *     anchors and classes.  counts[3] = {c+, c-, A}: each of c+, c- is at most n (k-1) <= 4096 * 2047 < 2^23, so every partial
+ *     and A fit an int32.
+ *   Pair weights, pair_w[n][n], every entry written:  W[i,p] = +[l+_ip > 0] fl(1 / D_ip);  W[i,n] = -fl(m / D_in), m = the number
+ *     of draws of i that picked n, where l-(D_in) > 0 (the hinge depends on the column alone);  a pair with D = 0 or NaN carries
+ *     weight 0 (coincident rows have no direction) and still counts in c+ / c- if its hinge is positive;  0 elsewhere.
+ *   Other outputs.  triplets[n (k-1)][3] int32 = (i, p_j, n_ij) in (anchor, ordinal) order, always n (k-1) rows, fit for
+ *     embnet_triplet_gather_fwd as they are.  sample_w[n][n] fp32 (NULL skips it): the weights w as the sampler used them; a row of
+ *     zeros marks a fall-back anchor.
+ *   bwd, A held constant: with dD_ij/dx_i = (x_i - x_j) / D_ij,  demb_i = (g / max(A,1)) sum_j (W_ij + W_ji) (x_i - x_j),
+ *     g = *upstream (NULL = 1); A is read from counts[2] in device memory.  One launch on the f64 matrix instructions: every
+ *     product of an fp32 weight and an fp32 x is exact in f64.
+ * Range: embnet_ms_loss_fwd's (p >= 2, k >= 2, n <= 4096, 1 <= e <= 4096), embnet_batch_all_loss_fwd's two forward paths and fit
+ * rule (EMBNET_MARGIN_PER_CLASS, EMBNET_MARGIN_DISTANCE_MATRIX; path 0 = auto, embnet_margin_loss_path).  Anything else, a
+ * non-finite or out-of-range parameter included, is rejected before a launch.  No floating-point atomics, every reduction in a
+ * fixed order: the same seed gives the same bits; no host synchronisation or allocation; capturable in a graph.
+ * workspace (embnet_margin_loss_workspace_bytes, either path, 16-byte aligned): zero-filled ONCE by the caller; every launch
+ * leaves its arrival counter zeroed. */
+enum { EMBNET_MARGIN_PER_CLASS = 1, EMBNET_MARGIN_DISTANCE_MATRIX = 2 };
+int embnet_margin_loss_path(int p, int k, int e);         /* the path `auto` takes; 0 outside the range */
+size_t embnet_margin_loss_workspace_bytes(int p, int k, int e);   /* sized for either path; 0 outside the range */
+int embnet_margin_loss_fwd(const float* emb, int p, int k, int e, float beta, float alpha, float cutoff, float nonzero_loss_cutoff,
+                           uint64_t seed, const uint64_t* seed_dev, int path, float* pair_w, int32_t* counts, int32_t* triplets,
+                           float* sample_w, float* mean_loss, void* workspace, size_t workspace_bytes, void* stream);
+int embnet_margin_loss_bwd(const float* emb, int n, int e, const float* pair_w, const int32_t* counts, const float* upstream,
+                           float* demb, void* stream);
+
 /* ------------------------------------------------------------------ t-SNE of saved encodings
  * utils.py:36-91 plot_tsne / plot_tsne_interactive: `TSNE().fit_transform(encodings['encodings'])` (scikit-learn).  The
  * entries below are scikit-learn's EXACT method (TSNE(method='exact', n_components=2), sklearn/manifold/_t_sne.py and

@@ -9,7 +9,8 @@ run ops.batch_all_triplet_loss beside the fused `hardest` path at the same shape
 ops.multi_similarity_loss beside the fused `hardest` path and beside batch-all, the *_supcon cases ops.supcon_loss with either
 denominator beside ops.multi_similarity_loss, the *_fast_ap / *_smooth_ap cases (`--only _ap`) ops.fast_ap_loss / ops.smooth_ap_loss at
 their defaults beside ops.supcon_loss('all'), the *_circle cases (`--only circle`, which also takes the xbm_circle cases) ops.circle_loss
-at its defaults beside ops.supcon_loss('all'); the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
+at its defaults beside ops.supcon_loss('all'), the *_distance_weighted cases (`--only distance_weighted`) ops.margin_loss at its defaults
+beside ops.batch_all_triplet_loss and ops.circle_loss; the *_proxy_anchor / *_proxy_softmax cases are described at proxy_cases(), the
 xbm_* cases (the cross-batch memory) at xbm_cases(), `--xbm-step` at xbm_step_time(), the mproxy_* cases (SoftTriple and sub-centre
 ArcFace on several centres per class; `--only mproxy_`) at mproxy_cases()):
   separate: ops.pairwise_distances -> ops.mine_triplets / ops.batch_hard -> ops.triplet_gather_loss -> backward
@@ -37,7 +38,7 @@ CASES = [("c1", 8, 4, 256, "semihard"), ("c2", 32, 4, 256, "hardest"), ("c2_batc
          ("c1_multi_similarity", 8, 4, 256, "multi_similarity"), ("c2_multi_similarity", 32, 4, 256, "multi_similarity"),
          ("c5_multi_similarity", 64, 4, 512, "multi_similarity"),
          ("c1_supcon", 8, 4, 256, "supcon"), ("c2_supcon", 32, 4, 256, "supcon"), ("c5_supcon", 64, 4, 512, "supcon")] + \
-        [(f"{cfg}_{mode}", p, k, e, mode) for mode in ("fast_ap", "smooth_ap", "circle")
+        [(f"{cfg}_{mode}", p, k, e, mode) for mode in ("fast_ap", "smooth_ap", "circle", "distance_weighted")
          for cfg, p, k, e in (("c1", 8, 4, 256), ("c2", 32, 4, 256), ("c5", 64, 4, 512))]
 
 
@@ -472,6 +473,26 @@ def main():
                 row[f"supcon_all_{rnd}"] = measure(supcon("all"), a.iters)
             row[f"device_ratio_{mode}_vs_supcon_all"] = round(min(row[f"{mode}_1"]["device_us"], row[f"{mode}_2"]["device_us"])
                                                               / min(row["supcon_all_1"]["device_us"], row["supcon_all_2"]["device_us"]), 3)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            continue
+        if mode == "distance_weighted":                     # beside batch-all and Circle loss: the same skeleton, so the rest is the sampler
+            def margin():
+                x.grad = None
+                ops.margin_loss(x, p, k, seed=1)[0].backward()
+
+            def circle():
+                x.grad = None
+                ops.circle_loss(x, p, k)[0].backward()
+
+            row = dict(config=name, N=n, E=e, mining=mode)
+            for rnd in (1, 2):                              # the three legs alternate in one process, at one shape, twice over
+                row[f"distance_weighted_{rnd}"] = measure(margin, a.iters)
+                row[f"batch_all_{rnd}"] = measure(batch_all, a.iters)
+                row[f"circle_{rnd}"] = measure(circle, a.iters)
+            best = {leg: min(row[f"{leg}_1"]["device_us"], row[f"{leg}_2"]["device_us"]) for leg in ("distance_weighted", "batch_all", "circle")}
+            row["device_ratio_vs_batch_all"] = round(best["distance_weighted"] / best["batch_all"], 3)
+            row["device_ratio_vs_circle"] = round(best["distance_weighted"] / best["circle"], 3)
             out.append(row)
             print(json.dumps(row), flush=True)
             continue

@@ -18,6 +18,8 @@ embeddings of the last `size` samples, `weight` times, from step `start_iteratio
 per epoch.  Each rank keeps its own memory; it is not checkpointed, after --resume_from it refills.
 GENERATOR.circle_loss: {m, gamma} sets Circle loss's parameters for negatives_selection_mode 'circle' (and `loss: 'circle'` with the
 same two keys under GENERATOR.xbm scores the memory with it); the violating anchors are logged per epoch.
+GENERATOR.margin_loss: {beta, alpha, cutoff, nonzero_loss_cutoff} sets the margin loss's boundary and margin and the sampler's two
+cutoffs for negatives_selection_mode 'distance_weighted' (Wu et al., ICCV 2017); the active pairs per step are logged per epoch.
 `--synthetic` swaps the file loader for an in-memory synthetic dataset (no dataset ships with the repo).
 """
 import argparse
@@ -156,6 +158,8 @@ LOSS_CONFIGS = {
 AP_LOSS_CONFIGS = {'fast_ap': dict(bins='positive'), 'smooth_ap': dict(temperature='positive number')}
 # GENERATOR.circle_loss with 'circle': likewise (circle_loss_config)
 CIRCLE_LOSS_CONFIGS = {'circle': dict(m='number', gamma='positive')}
+# GENERATOR.margin_loss with 'distance_weighted': likewise (margin_loss_config)
+MARGIN_LOSS_CONFIGS = {'distance_weighted': dict(beta='number', alpha='number', cutoff='positive', nonzero_loss_cutoff='positive')}
 # GENERATOR.proxy_loss with the modes on several centres per class (ops.MULTI_PROXY_LOSS_MODES): the same validator on a table of
 # their own (proxy_loss_config), so the messages about the key keep naming the two modes they always named
 MULTI_PROXY_LOSS_CONFIGS = {
@@ -168,6 +172,8 @@ SUPCON_LOSS_KEYS = tuple(LOSS_CONFIGS['supcon_loss']['supcon'])
 PROXY_LOSS_KEYS = {mode: tuple(checks) for mode, checks in LOSS_CONFIGS['proxy_loss'].items()}
 AP_LOSS_KEYS = {mode: tuple(checks) for mode, checks in AP_LOSS_CONFIGS.items()}
 CIRCLE_LOSS_KEYS = tuple(CIRCLE_LOSS_CONFIGS['circle'])
+MARGIN_LOSS_KEYS = tuple(MARGIN_LOSS_CONFIGS['distance_weighted'])
+MARGIN_LOSS_DEFAULTS = dict(beta=1.2, alpha=0.2, cutoff=0.5, nonzero_loss_cutoff=1.4)
 
 
 def loss_config(name, cfg, table=None):
@@ -229,6 +235,20 @@ def circle_loss_config(cfg):
     return _circle_m('circle_loss', loss_config('circle_loss', cfg, CIRCLE_LOSS_CONFIGS), cfg['generator'].get('circle_loss'))
 
 
+def margin_loss_config(cfg):
+    """GENERATOR.margin_loss for 'distance_weighted': {beta, alpha >= 0, 0 < cutoff < nonzero_loss_cutoff < 2} (include/embnet.h);
+    `margin` is not used and embeddings_normalization should be on (the weights are those of the unit sphere)."""
+    out = loss_config('margin_loss', cfg, MARGIN_LOSS_CONFIGS)
+    if out is None:
+        return None
+    value, full = cfg['generator']['margin_loss'], dict(MARGIN_LOSS_DEFAULTS, **out)
+    if not 0 < full['cutoff'] < full['nonzero_loss_cutoff'] < 2:
+        raise ValueError(f"GENERATOR.margin_loss: need 0 < cutoff < nonzero_loss_cutoff < 2 (got {value!r})")
+    if full['alpha'] < 0:
+        raise ValueError(f"GENERATOR.margin_loss: alpha must not be negative (got {value!r})")
+    return out
+
+
 def ap_loss_config(cfg):
     """GENERATOR.ap_loss for the ranking modes: {bins} with 'fast_ap', a whole number in [2, 64]; {temperature} with 'smooth_ap'."""
     out = loss_config('ap_loss', cfg, AP_LOSS_CONFIGS)
@@ -267,7 +287,7 @@ XBM_LOSS_KEYS = {'contrastive': dict(margin='number'),
                  'circle': dict(m='number', gamma='positive')}
 XBM_DEFAULTS = dict(weight=1.0, start_iteration=0, loss='contrastive')
 XBM_MODES = ('semihard', 'hardest', 'random_hard', 'batch_hard', 'batch_all', 'multi_similarity', 'supcon', 'fast_ap',
-             'smooth_ap', 'circle')
+             'smooth_ap', 'circle', 'distance_weighted')
 
 
 def xbm_config(cfg):
@@ -453,13 +473,16 @@ def main():
     proxy_loss = proxy_loss_config(cfg)                # and GENERATOR.proxy_loss
     ap_loss = ap_loss_config(cfg)                      # and GENERATOR.ap_loss
     circle_loss = circle_loss_config(cfg)              # and GENERATOR.circle_loss
+    margin_loss = margin_loss_config(cfg)              # and GENERATOR.margin_loss
     xbm = xbm_config(cfg)                              # and GENERATOR.xbm (with a proxy mode, in Siamese mode, a memory below a batch)
     # each is refused with another's mode: at most one is set
-    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss, ap_loss, circle_loss) if v is not None), None)
+    loss_params = next((v for v in (ms_loss, supcon_loss, proxy_loss, ap_loss, circle_loss, margin_loss) if v is not None), None)
     multi_proxy_mode = cfg['generator'].get('negatives_selection_mode') in MULTI_PROXY_LOSS_CONFIGS
     proxy_mode = cfg['generator'].get('negatives_selection_mode') in PROXY_LOSS_KEYS or multi_proxy_mode
     # the modes whose log line carries the violating anchors: the ranking losses and Circle loss
     ap_mode = cfg['generator'].get('negatives_selection_mode') in tuple(AP_LOSS_KEYS) + ('circle',) and cfg['model']['mode'] != 'siamese'
+    # the mode whose log line carries the active pairs per step: the margin loss's positive hinges
+    margin_mode = cfg['generator'].get('negatives_selection_mode') == 'distance_weighted' and cfg['model']['mode'] != 'siamese'
     if proxy_mode and cfg['model']['mode'] == 'siamese':
         raise ValueError(f"negatives_selection_mode {cfg['generator']['negatives_selection_mode']!r} needs a triplet-mode model")
     retrieval_map_config(cfg['train'], bool(cfg['dataloader'].get('validate', True)))
@@ -490,7 +513,7 @@ def main():
     clustering_nmi = clustering_nmi_config(p_train, bool(data_loader.validate))
     verification = verification_config(p_train, bool(data_loader.validate))
     gen_kw = {k: v for k, v in p_gen.items() if k not in ('device_augmentations', 'augment_seed', 'ms_loss', 'supcon_loss', 'proxy_loss',
-                                                       'ap_loss', 'circle_loss', 'xbm')}
+                                                       'ap_loss', 'circle_loss', 'margin_loss', 'xbm')}
 
     siamese = p_model['mode'] == 'siamese'
     if siamese:
@@ -606,7 +629,7 @@ def main():
             for g in opt.param_groups:
                 g['lr'] = lr
             trainable.train()
-            losses, xbm_counts, violating = [], [], []
+            losses, xbm_counts, violating, active_pairs = [], [], [], []
             for _ in range(len(train_gen)):
                 if siamese:
                     (x1, x2), y = train_gen[0]
@@ -618,6 +641,8 @@ def main():
                         losses.append(trainer.step(xb, yb))
                         if multi_proxy_mode or ap_mode:
                             violating.append(trainer.last_triplets[1].clone())      # (a replayed step's counts are one buffer)
+                        if margin_mode:
+                            active_pairs.append(trainer.last_triplets[1].clone())
                         if xbm is not None and trainer.last_xbm_counts is not None:
                             xbm_counts.append(trainer.last_xbm_counts.clone())      # (a replayed step's counts are one buffer)
                     else:
@@ -625,6 +650,8 @@ def main():
                         losses.append(trainer.step(xb))
                         if ap_mode:                       # the violating anchors (a replayed step's counts are one buffer)
                             violating.append(trainer.last_triplets[1].clone())
+                        if margin_mode:                   # the positive hinges, likewise
+                            active_pairs.append(trainer.last_triplets[1].clone())
                     n_images += xb.shape[0]
             epoch_loss = all_reduce_mean(float(torch.stack(losses).mean().item()))     # mean over ranks (logging + monitor)
             history['loss'].append(epoch_loss)
@@ -635,6 +662,8 @@ def main():
                 msg += f' - violating {torch.stack(violating).float().mean().item():.1f}'
                 if multi_proxy_mode and trainer.last_reg is not None:
                     msg += f' - reg {trainer.last_reg.item():.4f}'
+            if active_pairs:                              # this rank's: hinges above zero per step, positives' and drawn negatives'
+                msg += f' - active_pairs {torch.stack(active_pairs).float().mean().item():.1f}'
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
