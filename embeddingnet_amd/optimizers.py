@@ -9,6 +9,12 @@ static chunk list.  The table is re-uploaded only when a gradient pointer change
 caching allocator they normally do not).  A parameter without a gradient is skipped, as Keras does.
 The classes are torch.optim.Optimizer subclasses, so param_groups[...]['lr'] scheduling and state_dict() work
 as usual.  GPU tensors only (the library has no CPU path).
+
+Beyond the reference: parameter groups with a rate multiplier and a decoupled weight decay each, SGD momentum, and gradient
+clipping by value or by global norm — what the proxy losses' papers train with (Proxy-Anchor: AdamW, the proxies at 100 x the
+backbone's rate, clipped gradients; SoftTriple: centres at 1e-2 against 1e-4; ArcFace / CosFace: SGD, momentum 0.9, decay 5e-4).
+An optimizer that uses any of them steps through `embnet_optimizer_step_groups` (still one launch; `global_clipnorm` puts
+`embnet_optimizer_grad_norm` in front of it); one group with none of them issues the call it always issued.
 """
 import math
 
@@ -20,30 +26,84 @@ from ._lib import check
 from . import layers as L
 
 RULE = {"sgd": 0, "rms_prop": 1, "adam": 2, "radam": 3}
+MAX_GROUPS = 8               # EMBNET_OPT_MAX_GROUPS
+MOMENTUM_RULE = 5            # EMBNET_OPT_MOMENTUM: 'sgd' with a momentum
 
 
 class KerasOptimizer(torch.optim.Optimizer):
-    """rule: 'sgd' | 'rms_prop' | 'adam' | 'radam' (the names utils.get_optimizer dispatches on)."""
+    """rule: 'sgd' | 'rms_prop' | 'adam' | 'radam' (the names utils.get_optimizer dispatches on).
 
-    def __init__(self, params, rule, lr, beta_1=0.9, beta_2=0.999, rho=0.9, epsilon=1e-7):
+    params: a parameter list, or torch-style groups (at most 8) with the keys
+      lr            the group's base rate (default: `lr`); a schedule may overwrite it at any time
+      lr_mult       default 1: the group steps at lr * lr_mult, so a schedule that writes one `lr` into every group keeps the ratio
+      weight_decay  default 0: decoupled decay in Keras AdamW's form, variable -= variable * weight_decay * (lr * lr_mult), applied
+                    before the rule (with 'adam' this is AdamW; it is not the l2 regulariser of set_l2, which joins the gradient)
+    momentum, nesterov: Keras' SGD momentum (rule 'sgd' only): v = momentum v - lr g;  w += nesterov ? momentum v - lr g : v.
+    clipvalue c: every gradient element is clamped to [-c, c].  global_clipnorm c: all gradients are scaled by
+    c / max(norm, c), norm the 2-norm over every gradient of the step (TensorFlow's clip_by_global_norm); `grad_norm` then holds
+    the norm before clipping.  The two are exclusive.  Both act on the gradient after the l2 regularisers' part joined it.
+    Under data parallelism step() runs after the gradient all-reduce, so every rank holds the same gradients and computes the
+    same norm in the same order: no extra collective, and the ranks' weights stay bitwise equal."""
+
+    def __init__(self, params, rule, lr, beta_1=0.9, beta_2=0.999, rho=0.9, epsilon=1e-7, momentum=0.0, nesterov=False,
+                 clipvalue=None, global_clipnorm=None):
         if rule not in RULE:
             raise KeyError(rule)
-        super().__init__(params, dict(lr=float(lr)))
+        if momentum < 0 or (clipvalue is not None and clipvalue < 0) or (global_clipnorm is not None and global_clipnorm < 0):
+            raise ValueError("momentum, clipvalue and global_clipnorm must not be negative")
+        if clipvalue and global_clipnorm:
+            raise ValueError("clipvalue and global_clipnorm are exclusive")
+        if nesterov and not momentum:
+            raise ValueError("nesterov needs a momentum")
+        if momentum and rule != "sgd":
+            raise ValueError(f"momentum belongs to rule 'sgd', not {rule!r}")
+        super().__init__(params, dict(lr=float(lr), lr_mult=1.0, weight_decay=0.0))
         self.rule, self.b1, self.b2, self.rho, self.eps = rule, beta_1, beta_2, rho, epsilon
+        self.momentum, self.nesterov = float(momentum), bool(nesterov)
+        self.clipvalue = float(clipvalue) if clipvalue else 0.0
+        self.global_clipnorm = float(global_clipnorm) if global_clipnorm else 0.0
         self.iterations = 0
         self._tensors = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
         if not self._tensors:
             raise ValueError("optimizer got no trainable parameters")
-        if len(self.param_groups) != 1:
-            raise ValueError("one parameter group (the reference sets a single learning rate)")
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError(f"{len(self.param_groups)} parameter groups: the update kernel takes at most {MAX_GROUPS}")
+        for g in self.param_groups:
+            if g["weight_decay"] < 0:
+                raise ValueError("weight_decay must not be negative")
         self._ptrs, self._table, self._chunks, self._host, self._copied = None, None, None, None, None
         self._l2 = {}                # parameter -> lambda of its kernel_regularizer (set_l2): 2*lambda*w joins the gradient in the kernel
         self.coef_dev = None         # device float[6] the kernel reads its scalars from (set by a graph-capturing trainer)
+        self.group_coef_dev = None   # device float[groups][4] beside it (group_scalars): read only while coef_dev is set
+        self._norm = None            # device f64 [4]: N2, norm, the clip scale (a float in the third word's first half), unused
+
+    @property
+    def grouped(self):
+        """Whether step() needs embnet_optimizer_step_groups: any group, decay, multiplier, momentum or clip beyond the reference's."""
+        gs = self.param_groups
+        return (len(gs) != 1 or gs[0].get("weight_decay", 0.0) != 0 or gs[0].get("lr_mult", 1.0) != 1 or self.momentum != 0
+                or self.clipvalue != 0 or self.global_clipnorm != 0)
+
+    @property
+    def grad_norm(self):
+        """Device float64 scalar at a static address: the global gradient norm of the last step before clipping (0 before the
+        first one).  Only written with `global_clipnorm`; valid under graph replay."""
+        return self._norm_buffers()[0][1]
+
+    def _norm_buffers(self):
+        if self._norm is None:
+            dev = self._tensors[0].device
+            ce = _lib.lib().embnet_optimizer_chunk_elems()
+            n_chunks = sum(-(-p.numel() // ce) for p in self._tensors)
+            nbytes = _lib.lib().embnet_optimizer_grad_norm_workspace_bytes(n_chunks)
+            # the workspace's first 16 bytes are the arrival ticket: zero once, the kernel re-arms it
+            self._norm = (torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(-(-nbytes // 8), dtype=torch.float64, device=dev))
+        return self._norm
 
     # -- state ----------------------------------------------------------------------------
     def _slots(self, p):
         st = self.state[p]
-        n = {"sgd": 0, "rms_prop": 1, "adam": 2, "radam": 2}[self.rule]
+        n = {"sgd": 1 if self.momentum else 0, "rms_prop": 1, "adam": 2, "radam": 2}[self.rule]     # sgd's slot1: the velocity
         for i in range(n):
             if f"slot{i + 1}" not in st:
                 st[f"slot{i + 1}"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -87,6 +147,7 @@ class KerasOptimizer(torch.optim.Optimizer):
         lib = _lib.lib()
         dev = self._tensors[0].device
         rows, ptrs = [], []
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
         for p in self._tensors:
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                 raise _lib.EmbnetError("KerasOptimizer: parameters must be contiguous fp32 GPU tensors")
@@ -95,9 +156,9 @@ class KerasOptimizer(torch.optim.Optimizer):
                 raise _lib.EmbnetError("KerasOptimizer: gradients must be dense contiguous fp32")
             s1, s2 = self._slots(p)
             gp = g.data_ptr() if g is not None else 0
-            l2x2 = int(np.float32(2.0 * self._l2.get(id(p), 0.0)).view(np.uint32))      # {float l2x2; int32 pad} as one int64
+            l2x2 = int(np.float32(2.0 * self._l2.get(id(p), 0.0)).view(np.uint32))      # {float l2x2; int32 group} as one int64
             rows.append((p.data_ptr(), gp, s1.data_ptr() if s1 is not None else 0,
-                         s2.data_ptr() if s2 is not None else 0, p.numel(), l2x2))
+                         s2.data_ptr() if s2 is not None else 0, p.numel(), l2x2 | (group_of[id(p)] << 32)))
             ptrs.append(gp)
         if self._chunks is None:
             ce = lib.embnet_optimizer_chunk_elems()
@@ -143,19 +204,55 @@ class KerasOptimizer(torch.optim.Optimizer):
             self._build_table()
         self.iterations += 1
         L.WEIGHT_EPOCH[0] += 1                             # cached bf16 planes of conv kernels are stale from here on
-        lr = float(self.param_groups[0]["lr"])
-        rule, b1, b2, c1, c2 = self._coefficients(lr, self.iterations)
-        check(_lib.lib().embnet_optimizer_step(rule, self._table.data_ptr(), len(self._tensors), self._chunks.data_ptr(),
-                                               self._chunks.shape[0], lr, b1, b2, self.eps, c1, c2,
-                                               self.coef_dev.data_ptr() if self.coef_dev is not None else None,
-                                               _lib.stream()))
+        if self.grouped:
+            self._step_groups()
+        else:
+            lr = float(self.param_groups[0]["lr"])
+            rule, b1, b2, c1, c2 = self._coefficients(lr, self.iterations)
+            check(_lib.lib().embnet_optimizer_step(rule, self._table.data_ptr(), len(self._tensors), self._chunks.data_ptr(),
+                                                   self._chunks.shape[0], lr, b1, b2, self.eps, c1, c2,
+                                                   self.coef_dev.data_ptr() if self.coef_dev is not None else None,
+                                                   _lib.stream()))
         # planes and ranges of the conv kernels among the parameters, current again in one launch each (layers.refresh_tensors)
         L.refresh_tensors(self._tensors, self)
         return loss
 
+    def _group_rows(self, t):
+        """-> (kernel rule, b1, b2, c2, [[lr_g, c1_g, d_g, 0]] per group) of step t: lr_g = lr * lr_mult, c1_g the rule's c1 at
+        lr_g, d_g = (float)(lr_g * weight_decay) — all in double until the kernel's fp32."""
+        rows = []
+        for g in self.param_groups:
+            lr = float(g["lr"]) * float(g.get("lr_mult", 1.0))
+            rule, b1, b2, c1, c2 = self._coefficients(lr, t)
+            rows.append([lr, c1, lr * float(g.get("weight_decay", 0.0)), 0.0])
+        if self.momentum:
+            rule, b1 = MOMENTUM_RULE, 0.0
+        return rule, b1, b2, c2, rows
+
+    def _step_groups(self):
+        lib, stream = _lib.lib(), _lib.stream()
+        table, n, chunks, n_chunks = self._table.data_ptr(), len(self._tensors), self._chunks.data_ptr(), self._chunks.shape[0]
+        scale = None
+        if self.global_clipnorm:
+            norm, ws = self._norm_buffers()
+            scale = norm.data_ptr() + 16
+            check(lib.embnet_optimizer_grad_norm(table, n, chunks, n_chunks, self.global_clipnorm, ws.data_ptr(),
+                                                 ws.numel() * 8, norm.data_ptr(), scale, stream))
+        rule, b1, b2, c2, rows = self._group_rows(self.iterations)
+        rows = np.asarray(rows, dtype=np.float32)
+        on_dev = self.coef_dev is not None
+        if on_dev and self.group_coef_dev is None:
+            raise _lib.EmbnetError("KerasOptimizer: coef_dev without group_coef_dev (the groups' rows of group_scalars)")
+        check(lib.embnet_optimizer_step_groups(rule, table, n, chunks, n_chunks, rows.ctypes.data, rows.shape[0], b1, b2, self.eps,
+                                               c2, self.momentum, int(self.nesterov), self.clipvalue, scale,
+                                               self.coef_dev.data_ptr() if on_dev else None,
+                                               self.group_coef_dev.data_ptr() if on_dev else None, stream))
+
     def prepare_capture(self):
         """Allocate what a captured step() needs that cannot be allocated during stream capture."""
         self._graph_host = torch.empty((len(self._tensors), 6), dtype=torch.int64).pin_memory()
+        if self.global_clipnorm:
+            self._norm_buffers()                           # grad_norm keeps its address outside the graph's pool
         self._ptrs = None                                  # the captured step builds (and keeps) its own table
 
     def scalars(self, t):
@@ -164,6 +261,13 @@ class KerasOptimizer(torch.optim.Optimizer):
         lr = float(self.param_groups[0]["lr"])
         rule, b1, b2, c1, c2 = self._coefficients(lr, t)
         return rule, [lr, b1, b2, self.eps, c1, c2]
+
+    def group_scalars(self, t):
+        """-> the flat [lr_g, c1_g, d_g, 0] rows of step t, four floats per group: what a grouped step() passes, for
+        `group_coef_dev` (beside `coef_dev`, whose b1, b2, eps and c2 a grouped step reads); [] when step() is not grouped."""
+        if not self.grouped:
+            return []
+        return [v for row in self._group_rows(t)[4] for v in row]
 
 
 def save_optimizer_state(path, opt, named_params, extra=None):

@@ -159,6 +159,8 @@ class TripletTrainer:
                 ev.synchronize()
         _, coef = self.opt.scalars(self.opt.iterations + 1)
         self._ring_np[slot, :6] = coef
+        if self._state.numel() > 12:                        # a grouped optimizer: four floats per group behind the fixed row
+            self._ring_np[slot, 12:] = self.opt.group_scalars(self.opt.iterations + 1)
         self._ring_np[slot, 6:8].view("uint64")[0] = ((self.seed << 20) + self.step_no) & (2 ** 64 - 1)
         self._ring_np[slot, 8:10].view("uint64")[0] = self._since_capture
         row = self._ring[slot]
@@ -170,14 +172,17 @@ class TripletTrainer:
 
     def _capture(self, images):
         dev = self._tuple(images)[0].device
-        self._state = torch.zeros(12, dtype=torch.float32, device=dev)           # lr, b1, b2, eps, c1, c2 | seed (uint64) | steps since capture (uint64) | pad
-        self._ring = torch.zeros((256, 12), dtype=torch.float32).pin_memory()
+        # lr, b1, b2, eps, c1, c2 | seed (uint64) | steps since capture (uint64) | pad | lr_g, c1_g, d_g, 0 per group (KerasOptimizer.group_scalars)
+        width = 12 + len(self.opt.group_scalars(self.opt.iterations + 1))
+        self._state = torch.zeros(width, dtype=torch.float32, device=dev)
+        self._ring = torch.zeros((256, width), dtype=torch.float32).pin_memory()
         self._since_capture = 0
         self._drops = [m for m in self.model.modules() if isinstance(m, (L.Dropout, L.DropConnect))]
         self._ring_np = self._ring.numpy()                                        # same memory
         self._ring_pos, self._ring_events = 0, [None, None]
         self._gx = self._inputs_like(images)
         self.opt.coef_dev = self._state
+        self.opt.group_coef_dev = self._state[12:] if width > 12 else None
         self.opt.prepare_capture()
         it0, st0 = self.opt.iterations, self.step_no
         drop_steps = [m._step for m in self._drops]
@@ -426,7 +431,7 @@ class SiameseTrainer(TripletTrainer):
 class ProxyTrainer(TripletTrainer):
     """The training step of the proxy / classification losses with TripletTrainer's machinery: its own step context, the
     weight-gradient slab sums deferred to one launch per flush, the KerasOptimizer's one-launch update — the proxies are one more
-    tensor of its single group — and, graph=True / 'auto', the whole step captured once into a HIP graph and replayed, the labels
+    tensor of its single group, or a group of their own with a rate multiplier and a decay (optimizers.KerasOptimizer) — and, graph=True / 'auto', the whole step captured once into a HIP graph and replayed, the labels
     copied into a static buffer beside the images.
 
     base_model: images -> embeddings [N, E];  head: a proxies.ProxyHead whose parameter the optimizer (and the reducer) must hold;

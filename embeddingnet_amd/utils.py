@@ -25,29 +25,63 @@ OPTIONAL_SECTION = ("SOFTMAX_PRETRAINING", "softmax")
 class OptimizerSpec:
     """What `get_optimizer(name, lr)` returns: the optimizer's rule and learning rate, bound to parameters later."""
 
-    def __init__(self, name, learning_rate):
+    def __init__(self, name, learning_rate, params=None):
         self.name, self.learning_rate = name, float(learning_rate)
+        self.params = check_optimizer_params(params)
 
     @property
     def rule(self):
         """reference utils.py:144-152: 'adam', 'rms_prop', 'radam', anything else is plain SGD."""
         return self.name if self.name in ("adam", "rms_prop", "radam") else "sgd"
 
-    def build(self, parameters):
+    def build(self, parameters, proxies=None):
+        """parameters: the model's.  Without `optimizer_params` the reference's optimizer over one group (`proxies`, when a
+        proxy mode has them, are one more tensor of it).  With them up to three groups: 'kernels' — parameters with two or more
+        dimensions, which get `weight_decay` — 'other' — BatchNorm parameters and biases, never decayed — and 'proxies' with
+        `proxy_lr_mult` and `proxy_weight_decay`; `group_names` on the optimizer lists the groups built."""
         from .optimizers import KerasOptimizer
-        return KerasOptimizer(parameters, self.rule, self.learning_rate)
+        parameters = list(parameters)
+        proxies = list(proxies or [])
+        if not self.params:
+            return KerasOptimizer(parameters + proxies, self.rule, self.learning_rate)
+        o = self.params
+        if not proxies and ("proxy_lr_mult" in o or "proxy_weight_decay" in o):
+            raise ValueError("optimizer_params: proxy_lr_mult / proxy_weight_decay belong to the proxy modes")
+        groups = [("kernels", dict(params=[p for p in parameters if p.dim() >= 2], weight_decay=float(o.get("weight_decay", 0.0)))),
+                  ("other", dict(params=[p for p in parameters if p.dim() < 2])),
+                  ("proxies", dict(params=proxies, lr_mult=float(o.get("proxy_lr_mult", 1.0)),
+                                   weight_decay=float(o.get("proxy_weight_decay", 0.0))))]
+        groups = [(n, g) for n, g in groups if g["params"]]
+        kwargs = {k: o[k] for k in ("momentum", "nesterov", "epsilon", "beta_1", "beta_2", "clipvalue", "global_clipnorm") if k in o}
+        opt = KerasOptimizer([g for _, g in groups], self.rule, self.learning_rate, **kwargs)
+        opt.group_names = [n for n, _ in groups]
+        return opt
 
     def __repr__(self):
-        return f"OptimizerSpec({self.name!r}, lr={self.learning_rate})"
+        extra = f", params={self.params}" if self.params else ""
+        return f"OptimizerSpec({self.name!r}, lr={self.learning_rate}{extra})"
 
 
-def get_optimizer(name, learning_rate):
-    return OptimizerSpec(name, learning_rate)
+OPTIMIZER_PARAMS = ("weight_decay", "momentum", "nesterov", "epsilon", "beta_1", "beta_2", "clipvalue", "global_clipnorm",
+                    "proxy_lr_mult", "proxy_weight_decay")
+
+
+def check_optimizer_params(params):
+    """TRAIN.optimizer_params -> a dict with known keys only (unknown ones are refused)."""
+    params = dict(params or {})
+    unknown = set(params) - set(OPTIMIZER_PARAMS)
+    if unknown:
+        raise ValueError(f"optimizer_params: unknown keys {sorted(unknown)} ({', '.join(OPTIMIZER_PARAMS)})")
+    return params
+
+
+def get_optimizer(name, learning_rate, params=None):
+    return OptimizerSpec(name, learning_rate, params)
 
 
 def _finish_section(section, input_shape):
     """A section that drives training (TRAIN-like or SOFTMAX_PRETRAINING): optimizer name -> object."""
-    section['optimizer'] = get_optimizer(section['optimizer'], section['learning_rate'])
+    section['optimizer'] = get_optimizer(section['optimizer'], section['learning_rate'], section.get('optimizer_params'))
     if input_shape is not None:
         section['input_shape'] = input_shape
         # The reference builds albumentations pipelines only under the misspelt key 'augmentations_type'

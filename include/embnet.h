@@ -1485,6 +1485,56 @@ int embnet_optimizer_chunk_elems(void);
 int embnet_optimizer_step(int rule, const void* table, int n_tensors, const int32_t* chunks, int n_chunks,
                           float lr, float b1, float b2, float eps, float c1, float c2, const float* coef_dev, void* stream);
 
+/* ------------------------------------------------------------------ optimizer update with parameter groups
+ * The same launch over the same table and chunk list, with a learning rate and a decoupled weight decay per parameter group,
+ * gradient clipping, and Keras' SGD momentum — what the published recipes of the proxy losses need (Proxy-Anchor: AdamW, the
+ * proxies at 100 x the backbone's rate, gradients clipped; SoftTriple: centres at 1e-2 against 1e-4; ArcFace / CosFace: SGD with
+ * momentum 0.9 and weight decay 5e-4).  The descriptor keeps its 48 bytes; its trailing int32 is the tensor's group here:
+ *             { float* w; const float* g; float* slot1; float* slot2; int64 n; float l2x2; int32 group; }
+ * (embnet_optimizer_step goes on ignoring that word.)  A group index outside [0, n_groups) is read as the nearest valid one.
+ *   group_coef      HOST float [n_groups][4] = { lr_g, c1_g, d_g, 0 }, 1 <= n_groups <= EMBNET_OPT_MAX_GROUPS, copied into the
+ *                   launch arguments: the group's rate, its c1 (the c1 of the rule above at lr_g), and d_g = (float)(lr_g * wd_g);
+ *   group_coef_dev  NULL, or the same rows in DEVICE memory, read instead (a captured step replays with current rates);
+ *   coef_dev        NULL, or device float[6] as above: b1, b2, eps and c2 are read from it (its lr and c1 are not used);
+ *   momentum, nesterov   only with rule EMBNET_OPT_MOMENTUM;
+ *   clipvalue       0: off;  > 0: every gradient element is clamped to [-clipvalue, clipvalue];
+ *   clip_scale_dev  NULL: off;  else a device float s that every gradient element is multiplied with — the `scale` that
+ *                   embnet_optimizer_grad_norm left (global_clipnorm).  The two clips are exclusive.
+ * Per element, in this order (fp32):
+ *     g' = fma(l2x2, w, g)
+ *     clipvalue c > 0:      g' = min(max(g', -c), c)
+ *     clip_scale_dev:       g' = g' * s
+ *     d_g != 0:             w  = fma(-d_g, w, w)             [Keras AdamW: variable -= variable * wd * lr, before the rule]
+ *     the rule with lr_g / c1_g — the five rules above, arithmetic unchanged — or
+ *     EMBNET_OPT_MOMENTUM   v = momentum*v - lr_g*g';  w += nesterov ? momentum*v - lr_g*g' : v        (slot1 = v; Keras' SGD)
+ * A tensor with g == NULL is skipped entirely: no decay, slots untouched.  Aligned whole chunks go through float4, tails and
+ * unaligned tensors element by element.  Bits: a tensor that no option touches (no clip, d_g = 0, one of the five old rules) goes
+ * through embnet_optimizer_step's own per-element code at its group's rate, so with one group and no option the result is that
+ * entry point's, bit for bit, and several groups without options are as many one-group steps.  Where an option acts (and for the
+ * momentum rule) every rounding is pinned — slot updates as one fma each, rms = fma(b1, rms, ((1-b1) g') g'),
+ * m = fma(1-b1, g', b1 m), v = fma((1-b2) g', g', b2 v), w = fma(-lr, g', w) for SGD, the velocity as written above with
+ * fma(momentum, v, -(lr g')) — and is the same on both paths: a tail or an unaligned tensor gets the bits of a whole aligned chunk.
+ * HBM-bound at the same 12 .. 28 bytes per element (the momentum rule: 20).
+ *
+ * embnet_optimizer_grad_norm: one launch in front of the update when global_clipnorm is set.  A workgroup adds (double)g'^2
+ * (g' = fma(l2x2, w, g) in fp32, as the update forms it; w is only read where l2x2 != 0) over one chunk at a time and writes that
+ * chunk's partial (0 for a tensor without a gradient); the last workgroup to arrive adds the partials — thread j the partials j, j + 256, ... in ascending
+ * order, then the 256 sums in a fixed tree — and writes
+ *     norm_out[0] = N2 = sum g'^2,   norm_out[1] = sqrt(N2),   *scale_out = (float)(clipnorm / max(sqrt(N2), clipnorm))
+ * (TensorFlow's clip_by_global_norm).  No floating-point atomics, a fixed order: the same inputs give the same bits.  Non-finite
+ * gradients follow IEEE arithmetic.  workspace: embnet_optimizer_grad_norm_workspace_bytes(n_chunks) bytes, 16-byte aligned, its
+ * first 16 bytes ZERO before the first launch (the arrival ticket, which re-arms itself); the partials behind it are fully
+ * overwritten by every launch.  clipnorm > 0.  Reads 4 B per element (8 where a tensor has l2). */
+#define EMBNET_OPT_MAX_GROUPS 8
+enum { EMBNET_OPT_MOMENTUM = 5 };
+int embnet_optimizer_step_groups(int rule, const void* table, int n_tensors, const int32_t* chunks, int n_chunks,
+                                 const float* group_coef, int n_groups, float b1, float b2, float eps, float c2,
+                                 float momentum, int nesterov, float clipvalue, const float* clip_scale_dev,
+                                 const float* coef_dev, const float* group_coef_dev, void* stream);
+size_t embnet_optimizer_grad_norm_workspace_bytes(int n_chunks);
+int embnet_optimizer_grad_norm(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, float clipnorm,
+                               void* workspace, size_t workspace_bytes, double* norm_out, float* scale_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -567,7 +567,10 @@ def main():
             named['proxy_head/proxies'] = head.proxies
         return named
 
-    opt = p_train['optimizer'].build(params)
+    # TRAIN.optimizer_params (utils.OptimizerSpec.build): groups 'kernels' / 'other' / 'proxies' with their decay and rate multiplier;
+    # without the key this is the reference's optimizer over `params`, the proxies one more tensor of its single group
+    opt = p_train['optimizer'].build(params[:len(params) - (head is not None)], proxies=[head.proxies] if head is not None else None)
+    clipnorm = bool(getattr(opt, 'global_clipnorm', 0))
     lr0 = p_train['learning_rate']
     if args.resume_from is not None:                  # optimizer slots and step count, when the checkpoint has them (Keras'
         # load_model restores the optimizer with the weights; the epoch count and LR schedule restart, as in the reference)
@@ -630,7 +633,10 @@ def main():
                 g['lr'] = lr
             trainable.train()
             losses, xbm_counts, violating, active_pairs = [], [], [], []
+            norm_sum = torch.zeros((), dtype=torch.float64, device=dev) if clipnorm else None     # summed on the device, read once per epoch
             for _ in range(len(train_gen)):
+                if norm_sum is not None and losses:
+                    norm_sum += opt.grad_norm             # the step before's norm before clipping (the last one joins behind the loop)
                 if siamese:
                     (x1, x2), y = train_gen[0]
                     losses.append(trainer.step(torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev),
@@ -664,6 +670,9 @@ def main():
                     msg += f' - reg {trainer.last_reg.item():.4f}'
             if active_pairs:                              # this rank's: hinges above zero per step, positives' and drawn negatives'
                 msg += f' - active_pairs {torch.stack(active_pairs).float().mean().item():.1f}'
+            if norm_sum is not None and losses:           # this rank's: the mean global gradient norm before clipping
+                norm_sum += opt.grad_norm
+                msg += f' - grad_norm {norm_sum.item() / len(losses):.4g}'
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
