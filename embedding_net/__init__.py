@@ -8,7 +8,7 @@ import importlib.util
 import sys
 
 _MODULES = ("backbones", "clustering", "datagenerators", "kmeans", "losses_and_accuracies", "models", "parallel", "proxies", "retrieval",
-            "train_step", "utils", "verification", "xbm")
+            "train_step", "utils", "verification", "weight_average", "xbm")
 
 
 class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):

@@ -50,13 +50,15 @@ class TripletTrainer:
     dict(beta, alpha, cutoff, nonzero_loss_cutoff), defaults 1.2, 0.2, 0.5, 1.4; `margin` is not used; the draws are keyed by the
     step's seed, from device memory in a replayed step, as the fused path's; last_triplets = (the N (K-1) drawn triplets, active
     hinges A [1]) and last_pair_counts = int32 [3]: active positive hinges, active negative hinges, A).  Under data
-    parallelism every mode mines and normalises per rank."""
+    parallelism every mode mines and normalises per rank.
+    averager: a weight_average.WeightAverager (every trainer takes one): its one update launch follows the optimizer's in every
+    step, eager, captured or replayed; without one no branch of a step changes."""
     GRAPH_WARMUP = 8          # graph='auto' decides here: see _probe
     LOSS_PARAMS = {mode: keys for mode, (_, keys, _) in ops.PAIR_LOSS_MODES.items() if keys is not None}
     # (last_triplets / last_total are the replayed step's own buffers in graph mode: read them before the next step)
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5,
-                 negatives_selection_mode="semihard", seed=0, reducer=None, graph=None, loss_params=None):
+                 negatives_selection_mode="semihard", seed=0, reducer=None, graph=None, loss_params=None, averager=None):
         self.p, self.k, self.margin, self.mode = int(k_classes), int(k_samples), float(margin), negatives_selection_mode
         if self.mode not in tuple(ops.MINING_MODES) + ("batch_hard",) + tuple(ops.PAIR_LOSS_MODES):
             raise KeyError(self.mode)
@@ -65,13 +67,15 @@ class TripletTrainer:
                              f"not {self.mode!r}")
         self.loss_params = self._checked_loss_params(self.mode, loss_params)
         # one gradient per parameter and step: kernels write the reducer's flat buffer in place
-        self._setup(base_model, optimizer, seed, reducer, graph, direct=True)
+        self._setup(base_model, optimizer, seed, reducer, graph, direct=True, averager=averager)
         # one launch for distance matrix + mining + hinge + mean when the batch fits the fused kernel (N <= 512)
         self.fused_loss = os.environ.get("EMBNET_FUSED_LOSS", "1") == "1"
 
-    def _setup(self, model, optimizer, seed, reducer, graph, direct):
+    def _setup(self, model, optimizer, seed, reducer, graph, direct, averager=None):
         """What every trainer's constructor does behind its own argument checks.  direct: whether each parameter gets ONE
-        gradient contribution per step, so that the kernels may write the reducer's flat buffer in place."""
+        gradient contribution per step, so that the kernels may write the reducer's flat buffer in place.
+        averager: a weight_average.WeightAverager (or None): its one update launch follows the optimizer's in every step."""
+        self.averager = averager
         env = os.environ.get("EMBNET_GRAPH", "0")
         self.graph_mode = ({"1": True, "auto": "auto"}.get(env, False)) if graph is None else (graph if graph == "auto" else bool(graph))
         self._graph, self._graph_failed = None, False
@@ -163,6 +167,8 @@ class TripletTrainer:
             self._ring_np[slot, 12:] = self.opt.group_scalars(self.opt.iterations + 1)
         self._ring_np[slot, 6:8].view("uint64")[0] = ((self.seed << 20) + self.step_no) & (2 ** 64 - 1)
         self._ring_np[slot, 8:10].view("uint64")[0] = self._since_capture
+        if self.averager is not None:                       # float 10: the averager's coefficient of this step
+            self._ring_np[slot, 10] = self.averager.coefficient(self.opt.iterations + 1)
         row = self._ring[slot]
         self._state.copy_(row, non_blocking=True)
         if slot % 128 == 127:                               # last copy out of this half: its event guards the half's next lap
@@ -172,7 +178,7 @@ class TripletTrainer:
 
     def _capture(self, images):
         dev = self._tuple(images)[0].device
-        # lr, b1, b2, eps, c1, c2 | seed (uint64) | steps since capture (uint64) | pad | lr_g, c1_g, d_g, 0 per group (KerasOptimizer.group_scalars)
+        # lr, b1, b2, eps, c1, c2 | seed (uint64) | steps since capture (uint64) | averager's c, pad | lr_g, c1_g, d_g, 0 per group (KerasOptimizer.group_scalars)
         width = 12 + len(self.opt.group_scalars(self.opt.iterations + 1))
         self._state = torch.zeros(width, dtype=torch.float32, device=dev)
         self._ring = torch.zeros((256, width), dtype=torch.float32).pin_memory()
@@ -185,6 +191,7 @@ class TripletTrainer:
         self.opt.group_coef_dev = self._state[12:] if width > 12 else None
         self.opt.prepare_capture()
         it0, st0 = self.opt.iterations, self.step_no
+        avg0 = self.averager.counters() if self.averager is not None else None
         drop_steps = [m._step for m in self._drops]
         try:
             self._inputs_copy(images)
@@ -205,8 +212,7 @@ class TripletTrainer:
                         self._gout = self._eager_step(self._gx, with_update=False)
                     g2 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g2, pool=g.pool()):
-                        self.opt.step()
-                        L.refresh_weight_planes(self.model)
+                        self._update()
                     self._graph_opt = g2
             finally:
                 L.GRAPH_TICK = None
@@ -226,6 +232,8 @@ class TripletTrainer:
             # capturing ran the Python side once without executing anything: the counters advanced, the weights did not —
             # whether or not the capture succeeded
             self.opt.iterations, self.step_no = it0, st0
+            if self.averager is not None:
+                self.averager.set_counters(avg0)
             for m, st in zip(self._drops, drop_steps):
                 m._step = st
 
@@ -251,6 +259,8 @@ class TripletTrainer:
         self.step_no += 1
         self._push_state()
         self.opt.iterations += 1
+        if self.averager is not None:                       # the launch is in the graph and reads the row _push_state wrote
+            self.averager.advance(self.opt.iterations)
         for m in self._drops:                               # what the layers' forward() does in an eager step
             if m.training and m.enabled and m.rate > 0:
                 m._step += 1
@@ -391,9 +401,16 @@ class TripletTrainer:
         if self.reducer is not None:
             self.reducer.finish()
         if with_update:
-            self.opt.step()
-            L.refresh_weight_planes(self.model)     # bf16 planes of the patch convs' kernels, one launch (layers.py)
+            self._update()
         return mean.detach()
+
+    def _update(self):
+        self.opt.step()
+        L.refresh_weight_planes(self.model)     # bf16 planes of the patch convs' kernels, one launch (layers.py)
+        if self.averager is not None:
+            # one more launch: eager steps pass the coefficient by value, a captured step reads it from the state row
+            t = self.opt.iterations if self._keras_opt else self.step_no
+            self.averager.update(t, self._state[10:11] if self._graph_state_live() else None)
 
 
 class SiameseTrainer(TripletTrainer):
@@ -410,9 +427,9 @@ class SiameseTrainer(TripletTrainer):
 
     ANY_LOSS_CAPTURES = True
 
-    def __init__(self, siamese_model, optimizer, loss_fn=None, seed=0, reducer=None, graph=None):
+    def __init__(self, siamese_model, optimizer, loss_fn=None, seed=0, reducer=None, graph=None, averager=None):
         # two gradient contributions per shared parameter: autograd accumulates, no in-place sinks
-        self._setup(siamese_model, optimizer, seed, reducer, graph, direct=False)
+        self._setup(siamese_model, optimizer, seed, reducer, graph, direct=False, averager=averager)
         self.last_triplets = None
         if loss_fn is None:
             from .losses_and_accuracies import contrastive_loss as loss_fn
@@ -457,7 +474,8 @@ class ProxyTrainer(TripletTrainer):
     LOSS_PARAMS = {mode: keys for mode, (_, keys) in LOSS_MODES.items()}
     ANY_LOSS_CAPTURES = True
 
-    def __init__(self, base_model, head, optimizer, loss="proxy_anchor", loss_params=None, seed=0, reducer=None, graph=None):
+    def __init__(self, base_model, head, optimizer, loss="proxy_anchor", loss_params=None, seed=0, reducer=None, graph=None,
+                 averager=None):
         if loss not in self.LOSS_MODES:
             raise KeyError(loss)
         self.loss_params = self._checked_loss_params(loss, loss_params)
@@ -471,7 +489,7 @@ class ProxyTrainer(TripletTrainer):
                              "and the head's)")
         self.head, self.mode = head, loss
         # one gradient per parameter and step, the proxies' included
-        self._setup(base_model, optimizer, seed, reducer, graph, direct=True)
+        self._setup(base_model, optimizer, seed, reducer, graph, direct=True, averager=averager)
         self.last_triplets = self.last_reg = None
 
     def loss(self, inputs):
@@ -516,9 +534,9 @@ class XbmTrainer(TripletTrainer):
 
     def __init__(self, base_model, optimizer, k_classes, k_samples, margin=0.5, negatives_selection_mode="semihard", seed=0,
                  reducer=None, graph=None, loss_params=None, memory=None, xbm_loss="contrastive", xbm_params=None, weight=1.0,
-                 start_iteration=0):
+                 start_iteration=0, averager=None):
         super().__init__(base_model, optimizer, k_classes, k_samples, margin, negatives_selection_mode, seed, reducer, graph,
-                         loss_params)
+                         loss_params, averager=averager)
         if xbm_loss not in ops.XBM_LOSS_MODES:
             raise KeyError(xbm_loss)
         keys = ops.XBM_LOSS_MODES[xbm_loss][1]

@@ -79,9 +79,55 @@ def get_optimizer(name, learning_rate, params=None):
     return OptimizerSpec(name, learning_rate, params)
 
 
+WEIGHT_AVERAGING_KEYS = ("mode", "decay", "warmup", "start_epoch", "update_every", "evaluate")
+
+
+def check_weight_averaging(section):
+    """TRAIN.weight_averaging -> a dict with every key filled in (weight_average.WeightAverager's arguments, in epochs where the
+    trainer counts steps); unknown keys, wrong types and values outside their range are refused.
+      mode          'ema' | 'swa'
+      decay         ema only, inside (0, 1), default 0.999;   warmup: ema only, a boolean, default true
+      start_epoch   default 0: the averaging starts after that many epochs
+      update_every  a step count >= 1, or 'epoch' (one update per epoch); default 1 for ema, 'epoch' for swa
+      evaluate      'averaged' (default): validation, monitor and the final encodings use the averages;  'model': the live weights"""
+    if not isinstance(section, dict):
+        raise ValueError("weight_averaging: a mapping of " + ", ".join(WEIGHT_AVERAGING_KEYS))
+    unknown = set(section) - set(WEIGHT_AVERAGING_KEYS)
+    if unknown:
+        raise ValueError(f"weight_averaging: unknown keys {sorted(unknown)} ({', '.join(WEIGHT_AVERAGING_KEYS)})")
+    mode = section.get("mode")
+    if mode not in ("ema", "swa"):
+        raise ValueError(f"weight_averaging: mode must be 'ema' or 'swa' (got {mode!r})")
+    out = dict(mode=mode)
+    if mode == "swa":
+        for key in ("decay", "warmup"):
+            if key in section:
+                raise ValueError(f"weight_averaging: {key} belongs to mode 'ema', not 'swa'")
+    else:
+        decay, warmup = section.get("decay", 0.999), section.get("warmup", True)
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < decay < 1.0:
+            raise ValueError(f"weight_averaging: decay must be a number inside (0, 1) (got {decay!r})")
+        if not isinstance(warmup, bool):
+            raise ValueError(f"weight_averaging: warmup must be true or false (got {warmup!r})")
+        out.update(decay=float(decay), warmup=warmup)
+    start = section.get("start_epoch", 0)
+    if isinstance(start, bool) or not isinstance(start, int) or start < 0:
+        raise ValueError(f"weight_averaging: start_epoch must be a whole number >= 0 (got {start!r})")
+    every = section.get("update_every", 1 if mode == "ema" else "epoch")
+    if every != "epoch" and (isinstance(every, bool) or not isinstance(every, int) or every < 1):
+        raise ValueError(f"weight_averaging: update_every must be a step count >= 1 or 'epoch' (got {every!r})")
+    evaluate = section.get("evaluate", "averaged")
+    if evaluate not in ("averaged", "model"):
+        raise ValueError(f"weight_averaging: evaluate must be 'averaged' or 'model' (got {evaluate!r})")
+    out.update(start_epoch=start, update_every=every, evaluate=evaluate)
+    return out
+
+
 def _finish_section(section, input_shape):
     """A section that drives training (TRAIN-like or SOFTMAX_PRETRAINING): optimizer name -> object."""
     section['optimizer'] = get_optimizer(section['optimizer'], section['learning_rate'], section.get('optimizer_params'))
+    if 'weight_averaging' in section:
+        section['weight_averaging'] = check_weight_averaging(section['weight_averaging'])
     if input_shape is not None:
         section['input_shape'] = input_shape
         # The reference builds albumentations pipelines only under the misspelt key 'augmentations_type'

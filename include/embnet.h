@@ -1535,6 +1535,29 @@ size_t embnet_optimizer_grad_norm_workspace_bytes(int n_chunks);
 int embnet_optimizer_grad_norm(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, float clipnorm,
                                void* workspace, size_t workspace_bytes, double* norm_out, float* scale_out, void* stream);
 
+/* ------------------------------------------------------------------ averaged weights (EMA / SWA)
+ * An averaged copy of every tensor of a model, kept by one launch per step beside the one-launch optimizer update, and a second
+ * kernel that exchanges the model's tensors with their averages so that the averaged model is evaluated in place
+ * (embeddingnet_amd/weight_average.py).  The exponential moving average and the stochastic weight average (the equal mean of
+ * snapshots; Izmailov et al.) are the same per-element step with a host-computed coefficient c: EMA c = 1 - decay, SWA
+ * c = 1 / (snapshots so far + 1).
+ *   table   device array of n_tensors descriptors, 32 bytes each: { float* w; float* avg; int64 n; int64 reserved; } (reserved 0)
+ *   chunks  device int32 [n_chunks][2] = (tensor index, chunk index within it), chunk = embnet_optimizer_chunk_elems()
+ *           consecutive elements — the optimizer's list format; every element of every tensor covered exactly once.  A workgroup
+ *           whose pair points outside the table or past the tensor's end does nothing.
+ * embnet_weight_average_update: c is the argument, or *c_dev when c_dev is not NULL (device float: a captured HIP graph of the
+ * training step replays with the step's current coefficient).  Per element, in fp32:
+ *     !(c > 0)   nothing is read or written — the whole launch exits at once; a NaN read from c_dev counts as this case
+ *     c >= 1     avg = w, a copy of the bits (a + 1 (w - a) is not w in fp32)
+ *     otherwise  d = w - avg;  p = c * d;  avg = avg + p         — three roundings, never an fma
+ * Aligned whole chunks go through float4, tails and tensors that are not 16-byte aligned element by element; both paths give the
+ * same bits.  Moves 12 bytes per element.  With c_dev == NULL, c must lie in [0, 1].
+ * embnet_weight_average_swap: w[i] <-> avg[i] as 32-bit words (NaN payloads survive), the same two paths, 16 bytes per element.
+ * Two swaps are the identity.  Neither kernel uses atomics or a workspace. */
+int embnet_weight_average_update(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, float c,
+                                 const float* c_dev, void* stream);
+int embnet_weight_average_swap(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,12 @@ floats, the kernels with their l2 regulariser) plus a [1000, 256] proxy tensor, 
   opt_clipvalue   the same with clipvalue
   opt_clipnorm    embnet_optimizer_grad_norm + the same with the norm's scale        (two launches)
 
+and three for the averaged weights (csrc/weight_average.hip) over the same tensors and the same chunk list:
+
+  opt_sgd         embnet_optimizer_step, rule 'sgd'           (12 B per element: the yardstick of the next leg)
+  average_update  embnet_weight_average_update, c = 1e-3      (12 B per element)
+  average_swap    embnet_weight_average_swap                  (16 B per element)
+
   python tools/optimizer_bench.py [--rounds 15] [--reps 20] [--json out.json]          (GPU box)
 
 All legs run in one process on the same table, in alternating rounds of `reps` back-to-back steps timed with events (a step is
@@ -72,6 +78,14 @@ def main():
             "opt_groups": groups, "opt_clipvalue": lambda: groups(clipvalue=10.0), "opt_clipnorm": clipnorm}
     nbytes = {k: 28.0 * n_elem for k in legs}
     nbytes["opt_clipnorm"] += 4.0 * n_elem + 4.0 * n_l2
+    # the averaged copies of the same tensors: { w, avg, n, 0 } rows over the optimizer's chunk list
+    averages = [p.detach().clone() for p in opt._tensors]
+    avg_rows = [(p.data_ptr(), v.data_ptr(), p.numel(), 0) for p, v in zip(opt._tensors, averages)]
+    avg_table = torch.from_numpy(np.asarray(avg_rows, dtype=np.uint64).view(np.int64)).to(dev)
+    legs["opt_sgd"] = lambda: check(lib.embnet_optimizer_step(0, table, n, chunks, n_chunks, lr, 0.0, 0.0, eps, 0.0, 0.0, None, stream))
+    legs["average_update"] = lambda: check(lib.embnet_weight_average_update(avg_table.data_ptr(), n, chunks, n_chunks, 1e-3, None, stream))
+    legs["average_swap"] = lambda: check(lib.embnet_weight_average_swap(avg_table.data_ptr(), n, chunks, n_chunks, stream))
+    nbytes.update(opt_sgd=12.0 * n_elem, average_update=12.0 * n_elem, average_swap=16.0 * n_elem)
     times = {k: [] for k in legs}
     for fn in legs.values():
         for _ in range(3):

@@ -20,6 +20,13 @@ GENERATOR.circle_loss: {m, gamma} sets Circle loss's parameters for negatives_se
 same two keys under GENERATOR.xbm scores the memory with it); the violating anchors are logged per epoch.
 GENERATOR.margin_loss: {beta, alpha, cutoff, nonzero_loss_cutoff} sets the margin loss's boundary and margin and the sampler's two
 cutoffs for negatives_selection_mode 'distance_weighted' (Wu et al., ICCV 2017); the active pairs per step are logged per epoch.
+TRAIN.weight_averaging: {mode, decay, warmup, start_epoch, update_every, evaluate} keeps an exponential moving average ('ema') or a
+stochastic weight average ('swa') of the model — and of the proxies in the proxy modes — by one more launch per step
+(embeddingnet_amd/weight_average.py; the keys: utils.check_weight_averaging).  With evaluate 'averaged' (the default) everything
+computed for validation — val_loss, the retrieval, MAP, NMI and verification values, and with them monitor, plateau, early stop and
+best checkpoint — is computed with the averages in the model, from the first update on; the epoch line adds `averaged <updates>`.
+weights/epoch_XXX.npz stays the live model; the averages go to averaged/epoch_XXX.npz beside it, in the same format (load_model
+serves it for inference), and the update count into the optimizer state; --resume_from restores both.
 `--synthetic` swaps the file loader for an in-memory synthetic dataset (no dataset ships with the repo).
 """
 import argparse
@@ -320,6 +327,21 @@ def _proxies_path(weights_path):
     return os.path.join(os.path.dirname(d), 'proxies', f)
 
 
+def _averaged_path(weights_path):
+    """<project>/weights/epoch_007.npz -> <project>/averaged/epoch_007.npz (the averaged weights of TRAIN.weight_averaging)."""
+    d, f = os.path.split(os.path.abspath(weights_path))
+    return os.path.join(os.path.dirname(d), 'averaged', f)
+
+
+def build_averager(section, modules, steps_per_epoch):
+    """TRAIN.weight_averaging (utils.check_weight_averaging's result) -> the WeightAverager over `modules`: epochs become steps."""
+    from embeddingnet_amd.weight_average import WeightAverager
+    every = steps_per_epoch if section['update_every'] == 'epoch' else section['update_every']
+    kw = dict(decay=section['decay'], warmup=section['warmup']) if section['mode'] == 'ema' else {}
+    return WeightAverager(modules, mode=section['mode'], start_iteration=section['start_epoch'] * steps_per_epoch,
+                          update_every=every, **kw)
+
+
 def save_proxies(path, head, class_names):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez(path, proxies=head.proxies.detach().cpu().numpy(), class_names=np.asarray(list(class_names), dtype=str),
@@ -572,6 +594,7 @@ def main():
     opt = p_train['optimizer'].build(params[:len(params) - (head is not None)], proxies=[head.proxies] if head is not None else None)
     clipnorm = bool(getattr(opt, 'global_clipnorm', 0))
     lr0 = p_train['learning_rate']
+    resumed_updates = 0
     if args.resume_from is not None:                  # optimizer slots and step count, when the checkpoint has them (Keras'
         # load_model restores the optimizer with the weights; the epoch count and LR schedule restart, as in the reference)
         from embeddingnet_amd.optimizers import load_optimizer_state
@@ -579,21 +602,45 @@ def main():
         if os.path.exists(opt_path):
             extra = load_optimizer_state(opt_path, opt, named_slots())
             print(f'resumed optimizer state from {opt_path} (iterations {opt.iterations}, saved after epoch {int(extra.get("epoch", 0))})')
+            resumed_updates = int(extra.get('n_averaged', 0))
+    averager, averaging = None, p_train.get('weight_averaging')
+    if averaging is not None:
+        # the averages start as copies of the model as it is now (initial, or resumed): the base model's tensors, BatchNorm moving
+        # statistics included, and the proxies.  Parameters' averages stay bitwise equal across data-parallel ranks (the same
+        # coefficient, the same weights); buffers' are rank-local and are averaged over the ranks when a checkpoint is written
+        averager = build_averager(averaging, [trainable] + ([head] if head is not None else []), len(train_gen))
+        if args.resume_from is not None:
+            avg_path = _averaged_path(args.resume_from)
+            if os.path.exists(avg_path):
+                with np.load(avg_path, allow_pickle=False) as d:
+                    averager.load_averaged({k: d[k] for k in d.files})          # other names or shapes are refused
+                averager.set_counters((opt.iterations, resumed_updates))
+                print(f'resumed averaged weights from {avg_path} (averaged {averager.n_averaged})')
+            else:
+                averager.set_counters((opt.iterations, 0))
+                print(f'no averaged weights at {avg_path}: the averages start from the resumed model')
+
+    def evaluation():
+        """What validation runs inside: the averages in the model once there are any (evaluate 'averaged'), else nothing."""
+        import contextlib
+        if averager is not None and averaging['evaluate'] == 'averaged' and averager.n_averaged > 0:
+            return averager.applied()
+        return contextlib.nullcontext()
     reducer = GradReducer(params) if world > 1 else None
     if siamese:
         # the Siamese step (reference train.py:108-119: fit of SiameseNet.model with contrastive_loss) as a trainer: its own step
         # context, one-launch optimizer, and a captured step where the host cannot keep up (EMBNET_GRAPH=auto)
         from embeddingnet_amd.train_step import SiameseTrainer
-        trainer = SiameseTrainer(model.model, opt, contrastive_loss, seed=rank, reducer=reducer)
+        trainer = SiameseTrainer(model.model, opt, contrastive_loss, seed=rank, reducer=reducer, averager=averager)
     elif proxy_mode:
         # each rank's loss covers its own batch against ALL proxies; the reducer's mean over the ranks' gradients is the gradient
         # of the mean of the ranks' losses, for the (replicated) proxies as for the backbone (train_step.ProxyTrainer)
         from embeddingnet_amd.train_step import ProxyTrainer
         trainer = ProxyTrainer(model.base_model, head, opt, loss=p_gen['negatives_selection_mode'], loss_params=loss_params,
-                               seed=rank, reducer=reducer)
+                               seed=rank, reducer=reducer, averager=averager)
     else:
         kw = dict(margin=p_gen['margin'], negatives_selection_mode=p_gen['negatives_selection_mode'], seed=rank, reducer=reducer,
-                  loss_params=loss_params)
+                  loss_params=loss_params, averager=averager)
         if xbm is not None:
             # each rank keeps a memory of its own batches (nothing is gathered); it starts empty, after a resume too
             from embeddingnet_amd.train_step import XbmTrainer
@@ -676,49 +723,52 @@ def main():
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
+            if averager is not None:
+                msg += f' - averaged {averager.n_averaged}'
             value = epoch_loss
             if val_gen is not None:
-                trainable.eval()
-                vals = []
-                with torch.no_grad():
-                    for _ in range(len(val_gen)):
-                        xs, y = val_gen[0]
-                        xs = [torch.from_numpy(a).to(dev) for a in xs]
-                        if siamese:
-                            out = model.model(xs)[0]
-                            vals.append(contrastive_loss(torch.from_numpy(y).to(dev), out))
-                        else:
-                            vals.append(triplet_loss(p_gen['margin'])(None, model.model(xs)).mean())
-                value = all_reduce_mean(float(torch.stack(vals).mean().item()))
-                history['val_loss'].append(value)
-                msg += f' - val_loss {value:.4f}'
-                if retrieval_ks:
-                    # every rank evaluates the whole validation set (BN buffers are rank-local, decisions must agree): the
-                    # values pass through all_reduce_mean like val_loss
+                with evaluation():                    # (TRAIN.weight_averaging: the averaged weights, planes and ranges)
+                    trainable.eval()
+                    vals = []
                     with torch.no_grad():
-                        found = model.calculate_retrieval_metrics(data_loader, ks=retrieval_ks)
-                    for name in [f'recall@{k}' for k in retrieval_ks] + ['mrr']:
-                        history['val_' + name].append(all_reduce_mean(float(found[name])))
-                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
-                if retrieval_map:
-                    with torch.no_grad():
-                        found = model.calculate_map_at_r(data_loader)
-                    for name in ('map@r', 'r_precision'):
-                        history['val_' + name].append(all_reduce_mean(float(found[name])))
-                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
-                if clustering_nmi:
-                    with torch.no_grad():
-                        found = model.calculate_clustering_metrics(data_loader)
-                    history['val_nmi'].append(all_reduce_mean(float(found['nmi'])))
-                    msg += f" - val_nmi {history['val_nmi'][-1]:.4f}"
-                if verification:
-                    with torch.no_grad():
-                        found = model.calculate_verification_metrics(data_loader, fars=verification['fars'],
-                                                                     bins=verification['bins'])
-                    for name in verification_names(verification):
-                        history['val_' + name].append(all_reduce_mean(float(found[name])))
-                        msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
-                value = monitored_value(monitor, history, epoch_loss)    # lower is better for plateau, early stop, best checkpoint
+                        for _ in range(len(val_gen)):
+                            xs, y = val_gen[0]
+                            xs = [torch.from_numpy(a).to(dev) for a in xs]
+                            if siamese:
+                                out = model.model(xs)[0]
+                                vals.append(contrastive_loss(torch.from_numpy(y).to(dev), out))
+                            else:
+                                vals.append(triplet_loss(p_gen['margin'])(None, model.model(xs)).mean())
+                    value = all_reduce_mean(float(torch.stack(vals).mean().item()))
+                    history['val_loss'].append(value)
+                    msg += f' - val_loss {value:.4f}'
+                    if retrieval_ks:
+                        # every rank evaluates the whole validation set (BN buffers are rank-local, decisions must agree): the
+                        # values pass through all_reduce_mean like val_loss
+                        with torch.no_grad():
+                            found = model.calculate_retrieval_metrics(data_loader, ks=retrieval_ks)
+                        for name in [f'recall@{k}' for k in retrieval_ks] + ['mrr']:
+                            history['val_' + name].append(all_reduce_mean(float(found[name])))
+                            msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                    if retrieval_map:
+                        with torch.no_grad():
+                            found = model.calculate_map_at_r(data_loader)
+                        for name in ('map@r', 'r_precision'):
+                            history['val_' + name].append(all_reduce_mean(float(found[name])))
+                            msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                    if clustering_nmi:
+                        with torch.no_grad():
+                            found = model.calculate_clustering_metrics(data_loader)
+                        history['val_nmi'].append(all_reduce_mean(float(found['nmi'])))
+                        msg += f" - val_nmi {history['val_nmi'][-1]:.4f}"
+                    if verification:
+                        with torch.no_grad():
+                            found = model.calculate_verification_metrics(data_loader, fars=verification['fars'],
+                                                                         bins=verification['bins'])
+                        for name in verification_names(verification):
+                            history['val_' + name].append(all_reduce_mean(float(found[name])))
+                            msg += f" - val_{name} {history['val_' + name][-1]:.4f}"
+                    value = monitored_value(monitor, history, epoch_loss)    # lower is better for plateau, early stop, best checkpoint
             if rank == 0:
                 print(msg, flush=True)
             improved, stop, lr_end = plateau.update(value, lr)   # `value` is the all-reduced mean: same decisions on every rank
@@ -726,12 +776,19 @@ def main():
                 g['lr'] = lr_end
             if improved:
                 average_buffers(trainable)                # BN moving statistics: mean over the ranks' local batches
+                if averager is not None:
+                    averager.average_buffers()            # ... and their averages, which are rank-local too
             if improved and rank == 0:
                 path = os.path.join(paths['weights'], f'epoch_{epoch + 1:03d}.npz')
                 model.save_weights(path)
                 from embeddingnet_amd.optimizers import save_optimizer_state
                 os.makedirs(os.path.dirname(_optimizer_state_path(path)), exist_ok=True)
-                save_optimizer_state(_optimizer_state_path(path), opt, named_slots(), extra={'epoch': epoch + 1})
+                extra = {'epoch': epoch + 1}
+                if averager is not None:
+                    extra['n_averaged'] = averager.n_averaged
+                    os.makedirs(os.path.dirname(_averaged_path(path)), exist_ok=True)
+                    np.savez(_averaged_path(path), **{k: v.detach().cpu().numpy() for k, v in averager.averaged.items()})
+                save_optimizer_state(_optimizer_state_path(path), opt, named_slots(), extra=extra)
                 if head is not None:
                     save_proxies(_proxies_path(path), head, data_loader.class_names)
                 print(f'{monitor} improved to {history[monitor][-1]:.5f}, saving model to {path}')
