@@ -19,12 +19,16 @@
 //    conv.hip's fixed-order slab sum).  A STAGE is 32 positions: the dy rows of a stage go to one of NS slots, the x rows to
 //    a ring of 256 positions that slides with the stages (a stage needs x rows q .. q + 31 + 2 (OW+1) + 2);  unit u of the
 //    load stream = (x block u, dy stage u - HB) is requested D stages before the stage that needs it;
-//  * 8 waves = 4 (32-channel, 32-filter) blocks x 2 halves of the stage (16 positions = one K step of
-//    v_mfma_f32_32x32x16_bf16 each); a wave holds its block's NINE tap accumulators (144 registers) and per stage reads one
-//    dy fragment and nine shifted x fragments, both with ds_read_b64_tr_b16 (positions are the reduction index: the
-//    hardware transpose delivers 8 consecutive positions of one channel) — 60 reads for 54 MFMAs;  the two halves' sums meet
-//    in LDS after the loop;
-//  * waves 0-3 issue the x DMAs, waves 4-7 the dy DMAs (3 per wave and stage, counted s_waitcnt vmcnt); one s_barrier per stage.
+//  * 8 waves = 2 tap groups (taps 0-4, taps 5-8) x 2 32-channel blocks x 2 halves of the stage (16 positions = one K step of
+//    v_mfma_f32_32x32x16_bf16 / _f16 each); a wave holds the accumulators of its taps for BOTH 32-filter blocks (32 x 64 per
+//    tap: 160 or 128 registers) and per stage reads the two dy fragments and its five or four shifted x fragments, both with
+//    ds_read_b64_tr_b16 (positions are the reduction index: the hardware transpose delivers 8 consecutive positions of one
+//    channel) — an x fragment serves both filter blocks: 28 reads for 30 MFMAs and 24 for 24 in the two-piece fp16 form (the
+//    nine-tap, one-filter-block wave this replaces: 40 for 27), 42 for 60 and 36 for 48 in the three-piece bf16 form.  The two
+//    waves of a SIMD (w, w + 4) are the two tap groups of one (channel block, half);  the two halves' sums meet in LDS after
+//    the loop.  Every accumulator sees the matrix instructions of the nine-tap form in their order: the same bits;
+//  * waves 0-3 issue the x DMAs, waves 4-7 the dy DMAs (3 or 2 per wave and stage, behind the stage's first tap; counted
+//    s_waitcnt vmcnt); one s_barrier per stage.
 // LDS: (plane, chunk) images are 32-byte position rows; the two chunks of a 32-channel block lie 128 (mod 256) bytes apart,
 // so the two 16-lane groups of a transposed read's 32-lane pass cover all 64 banks at any tap shift.
 // Same pieces and six-term products as gemm_mainloop3 (fp32-exact split, include/embnet.h); the summation order over the
@@ -52,7 +56,9 @@ constexpr int NS = 4, D = 3;                 // dy slots, prefetch distance in s
 constexpr int DCH = 32 * 32 + 128;           // bytes of one (plane, chunk) image of a dy slot
 constexpr int X_BYTES = 12 * XCH, DY_SLOT = 12 * DCH;
 constexpr int LDS_BYTES = X_BYTES + NS * DY_SLOT;        // 155 136
-static_assert(4 * 144 * 64 * 4 <= LDS_BYTES, "the half sums of four waves fit the operand buffers");
+constexpr int NINE = 9, TG0 = 5;             // taps; taps of tap group 0 (group 1 holds the other NINE - TG0)
+static_assert(TG0 >= NINE - TG0, "a wave's accumulator array is sized for group 0");
+static_assert(2 * NINE * 32 * 64 * 4 <= LDS_BYTES, "the half sums of four waves (two of each tap group) fit the operand buffers");
 
 struct Params {
   const unsigned short* xp;    // [3][C/16][N*H*W][16]
@@ -68,7 +74,7 @@ struct Params {
 // F16: the planes hold two fp16 pieces + a scale (gemm_engine.h, EMBNET_PLANES_F16): a loader wave places two (plane, chunk) images
 // per unit instead of three (the LDS layout keeps its twelve-image pitch), three matrix products per tap instead of six, the sums
 // x 1 / (s_x s_dy) on the way out
-template <bool STAG, bool F16 = false>
+template <bool F16>
 __global__ __launch_bounds__(512) void conv_wgrad_planes_kernel(const Params p) {
   constexpr int NP = F16 ? 2 : 3;                           // planes = (plane, chunk) images per loader wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -121,108 +127,117 @@ __global__ __launch_bounds__(512) void conv_wgrad_planes_kernel(const Params p) 
     for (int i = 0; i < NP; ++i) dma16(rs, loff[i] + slot, vo, soff[i]);
   };
 
-  // ---- this wave's block and fragment addresses -------------------------------------------------------------------------
-  const int cb = (wave & 3) >> 1, kb = wave & 1, par = wave >> 2;
+  // ---- this wave's block, tap group and fragment addresses --------------------------------------------------------------
+  // waves w and w + 4 share a SIMD: the same (channel block, half), taps 0-4 on one and 5-8 on the other — 30 + 24 MFMAs per
+  // SIMD and stage in the fp16 form, as before; a wave's x fragment of a tap feeds BOTH filter blocks
+  const int tg = wave >> 2, cb = (wave & 3) >> 1, par = wave & 1;
   const int g = lane >> 4, p4 = lane & 3, q4 = (lane & 15) >> 2, hh = g >> 1;
   const int PWs = p.PWs;
   typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
   const unsigned char* const xa = smem + (2 * cb + (g & 1)) * XCH + p4 * 8;
-  const unsigned char* const ba = smem + X_BYTES + (2 * kb + (g & 1)) * DCH + (16 * par + 8 * hh + q4) * 32 + p4 * 8;
+  const unsigned char* const ba = smem + X_BYTES + (g & 1) * DCH + (16 * par + 8 * hh + q4) * 32 + p4 * 8;   // filter block kb: + 2 kb DCH
   const int row_in_stage = 16 * par + 8 * hh + q4;
 
-  f32x16 acc[9];
+  f32x16 acc[TG0][2];                                        // [tap of the group][filter block]; group 1 uses the first NINE - TG0
 #pragma unroll
-  for (int t = 0; t < 9; ++t)
+  for (int t = 0; t < TG0; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][kb][r] = 0.f;
 
-  // STAG: waves 4-7 run HALF A STAGE behind waves 0-3 (the partner waves of a SIMD then alternate between the barrier / DMA-issue
-  // / fragment-read phase and the MFMA phase instead of meeting in both: microarchitecture guide, 'Two waves per SIMD', item 9).
-  // A stage becomes two ticks with a barrier each; the early waves' stage start is the late waves' stage middle.  The x loaders
-  // (early) issue at their stage MIDDLE (the block they overwrite is read by the late waves until then), the dy loaders (late) at
-  // their stage START; each group waits for its own requests in front of the barrier that starts the OTHER group's stage.
-  // (Measured slower, DESIGN 3.13: only STAG = false is instantiated.)
-  const bool late = STAG && wave >= 4;
+  // the stages of one tap group (T0 .. T0 + NT - 1); both groups execute the same barriers and the same DMA issues
+  auto run = [&](auto T0c, auto NTc) {
+    constexpr int T0 = decltype(T0c)::value, NT = decltype(NTc)::value;
+    for (int j = 0; j < nst; ++j) {
+      asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (D - 1)) : "memory");   // unit j + HB has landed (this wave's part)
+      __builtin_amdgcn_s_barrier();                                            // ... everybody's; stage j - 1 is done everywhere
+      const unsigned char* bs = ba + (j & (NS - 1)) * DY_SLOT;
+      bf16x8 b[2][NP];
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(bs + (2 * kb + q * 4) * DCH));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(bs + (2 * kb + q * 4) * DCH + 4 * 32));
+          const s16x8 w = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+          b[kb][q] = __builtin_bit_cast(bf16x8, w);
+        }
+      const int base_row = 32 * j + row_in_stage;
+      auto load_a = [&](int tap, bf16x8 (&a)[NP]) {
+        const int sh = (tap / 3) * PWs + tap % 3;
+        const unsigned char* lo_p = xa + ((base_row + sh) & (XR - 1)) * 32;
+        const unsigned char* hi_p = xa + ((base_row + sh + 4) & (XR - 1)) * 32;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(lo_p + q * 4 * XCH));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(hi_p + q * 4 * XCH));
+          const s16x8 w = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+          a[q] = __builtin_bit_cast(bf16x8, w);
+        }
+      };
+      bf16x8 a[2][NP];
+      load_a(T0, a[0]);
+      constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        if (t + 1 < NT) load_a(T0 + t + 1, a[(t + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);          // the next tap's reads go out BEFORE this tap's MFMAs (six of them; twelve on six products)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          if constexpr (F16) {
+            constexpr int FA[3] = {0, 1, 0}, FB[3] = {1, 0, 0};      // smallest first
+#pragma unroll
+            for (int e = 0; e < 3; ++e)
+              acc[t][kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[t & 1][FA[e]]), __builtin_bit_cast(f16x8, b[kb][FB[e]]), acc[t][kb], 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 6; ++e)
+              acc[t][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[t & 1][PA[e]], b[kb][PB[e]], acc[t][kb], 0, 0, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);          // one tap's fragments ahead, not the whole group's (registers)
+        // the stage's DMA request behind the first tap's MFMAs: its address arithmetic runs beside them instead of in front of
+        // the stage's first fragment reads (it overwrites a ring block and the slot last read in stage j - 1 or earlier)
+        if (t == 0) { issue(j + HB + D); __builtin_amdgcn_sched_barrier(0); }
+      }
+    }
+  };
   for (int u = 0; u < HB + D; ++u) issue(u);
-  if (late) {                                                    // tick 0 belongs to the early waves' first half stage
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (D - 1)) : "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-  for (int j = 0; j < nst; ++j) {
-    if (!late) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (D - 1)) : "memory");   // unit j + HB has landed (this wave's part)
-    __builtin_amdgcn_s_barrier();                                            // ... everybody's; stage j - 1 is done everywhere
-    if (!STAG || late) issue(j + HB + D);
-    const unsigned char* bs = ba + (j & (NS - 1)) * DY_SLOT;
-    bf16x8 b[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(bs + q * 4 * DCH));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(bs + q * 4 * DCH + 4 * 32));
-      const s16x8 w = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-      b[q] = __builtin_bit_cast(bf16x8, w);
-    }
-    const int base_row = 32 * j + row_in_stage;
-    auto load_a = [&](int tap, bf16x8 (&a)[NP]) {
-      const int sh = (tap / 3) * PWs + tap % 3;
-      const unsigned char* lo_p = xa + ((base_row + sh) & (XR - 1)) * 32;
-      const unsigned char* hi_p = xa + ((base_row + sh + 4) & (XR - 1)) * 32;
-#pragma unroll
-      for (int q = 0; q < NP; ++q) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(lo_p + q * 4 * XCH));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(hi_p + q * 4 * XCH));
-        const s16x8 w = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        a[q] = __builtin_bit_cast(bf16x8, w);
-      }
-    };
-    bf16x8 a[2][NP];
-    load_a(0, a[0]);
-    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      if (STAG && t == 5) {                                      // the stage's middle = the other group's stage start
-        if (late) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (D - 1)) : "memory");
-        __builtin_amdgcn_s_barrier();
-        if (!late) issue(j + HB + D);
-      }
-      if (t + 1 < 9) load_a(t + 1, a[(t + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);          // the next tap's reads go out BEFORE this tap's MFMAs
-      if constexpr (F16) {
-        constexpr int FA[3] = {0, 1, 0}, FB[3] = {1, 0, 0};      // smallest first
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[t & 1][FA[e]]), __builtin_bit_cast(f16x8, b[FB[e]]), acc[t], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 6; ++e)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[t & 1][PA[e]], b[PB[e]], acc[t], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one tap's fragments ahead, not all nine (registers)
-    }
-  }
-  if (STAG && !late) __builtin_amdgcn_s_barrier();               // the late waves' last half stage
+  if (tg == 0) run(std::integral_constant<int, 0>{}, std::integral_constant<int, TG0>{});
+  else run(std::integral_constant<int, TG0>{}, std::integral_constant<int, NINE - TG0>{});
 
   // ---- the two halves meet in LDS; half 0 stores --------------------------------------------------------------------------
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // no DMA (the run-ahead requests past the end) lands after this
   __syncthreads();
-  float* red = reinterpret_cast<float*>(smem) + (wave & 3) * (144 * 64) + lane;
+  const int nt = tg ? NINE - TG0 : TG0, t0 = tg ? TG0 : 0;
+  float* red = reinterpret_cast<float*>(smem) + (tg ? 2 * TG0 + cb * (NINE - TG0) : cb * TG0) * (32 * 64) + lane;
   if (par == 1) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < TG0; ++t)
+      if (t < nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) red[(t * 16 + r) * 64] = acc[t][r];
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) red[((t * 2 + kb) * 16 + r) * 64] = acc[t][kb][r];
   }
   __syncthreads();
   if (par == 0) {
     const int h = lane >> 5;
     // (the two factors one after the other: each is a normal number, their product need not be — gemm_engine.h scale_exponent_of)
     const float osx = F16 ? planes_scale_slot(p.xp, (long)(p.x_plane_bytes >> 1))[1] : 1.f, osd = F16 ? planes_scale_slot(p.dyp, (long)(p.dy_plane_bytes >> 1))[1] : 1.f;
-    float* o = p.out + (long)split * p.slab_elems + (long)(c0 + 32 * cb + 4 * h) * p.K + k0 + 32 * kb + (lane & 31);
     const long tap_stride = (long)p.C * p.K;
+    float* o = p.out + (long)split * p.slab_elems + t0 * tap_stride + (long)(c0 + 32 * cb + 4 * h) * p.K + k0 + (lane & 31);
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < TG0; ++t)
+      if (t < nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        o[t * tap_stride + (long)((r & 3) + 8 * (r >> 2)) * p.K] = F16 ? ((acc[t][r] + red[(t * 16 + r) * 64]) * osx) * osd : acc[t][r] + red[(t * 16 + r) * 64];
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float s = acc[t][kb][r] + red[((t * 2 + kb) * 16 + r) * 64];
+            o[t * tap_stride + (long)((r & 3) + 8 * (r >> 2)) * p.K + 32 * kb] = F16 ? (s * osx) * osd : s;
+          }
   }
 }
 
@@ -289,14 +304,14 @@ extern "C" int embnet_conv2d_wgrad_planes_f32(const void* x_planes, const void* 
   p.stages_per_split = pl.stages_per_split; p.HB = pl.HB; p.slab_elems = 9l * c * k;
   hipStream_t st = (hipStream_t)stream;
   allow_big_lds<conv_wgrad_planes_kernel<false>>();
-  allow_big_lds<conv_wgrad_planes_kernel<false, true>>();
+  allow_big_lds<conv_wgrad_planes_kernel<true>>();
   const int grid = (pl.tiles * pl.splits + 7) / 8 * 8;
   {
     const double m = (double)n * h * wd;
-    EMBNET_TRACE_FLOP(planes_f16() ? "void embnet::wgp::conv_wgrad_planes_kernel<false, true>(embnet::wgp::Params)"
+    EMBNET_TRACE_FLOP(planes_f16() ? "void embnet::wgp::conv_wgrad_planes_kernel<true>(embnet::wgp::Params)"
                                    : "void embnet::wgp::conv_wgrad_planes_kernel<false>(embnet::wgp::Params)", 2.0 * m * k * 9.0 * c,
                       (planes_f16() ? 4.0 : 6.0) * m * (c + k) + 4.0 * 9.0 * c * k * pl.splits, st);
-    if (planes_f16()) conv_wgrad_planes_kernel<false, true><<<grid, 512, LDS_BYTES, st>>>(p);
+    if (planes_f16()) conv_wgrad_planes_kernel<true><<<grid, 512, LDS_BYTES, st>>>(p);
     else conv_wgrad_planes_kernel<false><<<grid, 512, LDS_BYTES, st>>>(p);
   }
   if (pl.splits > 1 && reduce) launch_slab_reduce((const float*)workspace, pl.splits, 9l * c * k, dw, st);
