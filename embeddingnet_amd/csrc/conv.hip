@@ -15,6 +15,7 @@
 // Roofline: MFMA f32 (157.3 TFLOP/s); algorithmic FLOP = 2 * N*OH*OW * K * R*S*C per pass.
 #include "gemm_engine.h"
 #include "conv_geom.h"
+#include "multi_tensor.h"
 #include "../../include/embnet.h"
 #include <stdlib.h>
 
@@ -1026,7 +1027,7 @@ static bool ranges_ok(const Ranges& r) {
 }
 
 // Ranges of many tensors in two launches (the kernels of a model's gather convs, once per optimizer step): table rows
-// (tensor, elements, slot), chunks = (row, chunk of 4096 elements) pairs — the layout of embnet_conv_weight_planes' lists.
+// (tensor, elements, slot), chunks = (row, chunk) pairs — the multi-tensor form of multi_tensor.h.
 struct RangeTensor { const float* x; long n; uint32_t* slot; };
 static_assert(sizeof(RangeTensor) == 24, "descriptor layout is part of the ABI (include/embnet.h)");
 __global__ __launch_bounds__(256) void range_zero_kernel(const RangeTensor* __restrict__ table, int n) {
@@ -1034,21 +1035,22 @@ __global__ __launch_bounds__(256) void range_zero_kernel(const RangeTensor* __re
   if (i < n) *table[i].slot = 0u;
 }
 __global__ __launch_bounds__(256) void range_multi_kernel(const RangeTensor* __restrict__ table, const int* __restrict__ chunks) {
-  const RangeTensor t = table[chunks[2 * blockIdx.x]];
-  const long e0 = (long)chunks[2 * blockIdx.x + 1] * 4096;
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const RangeTensor t = table[c.tensor];
+  const long e0 = c.first;
   float m = 0.f;
 #pragma unroll 4
-  for (int u = 0; u < 16; ++u) {
+  for (int u = 0; u < MT_CHUNK / 256; ++u) {
     const long e = e0 + u * 256 + threadIdx.x;
     m = fmaxf(m, e < t.n ? fabsf(t.x[e]) : 0.f);
   }
   range_emit_block(t.slot, m);                           // (a kernel has a few hundred chunks at most: one word takes them)
 }
-extern "C" int embnet_range_chunk_elems(void) { return 4096; }
+extern "C" int embnet_range_chunk_elems(void) { return MT_CHUNK; }
 extern "C" int embnet_range_multi(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, void* stream) {
   EMBNET_CHECK_ARG(table && chunks && n_tensors > 0 && n_chunks > 0, "range_multi: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  EMBNET_TRACE("embnet::range_multi_kernel", TRACE_BYTES, 4.0 * 4096 * n_chunks, stream);
+  EMBNET_TRACE("embnet::range_multi_kernel", TRACE_BYTES, 4.0 * MT_CHUNK * n_chunks, stream);
   range_zero_kernel<<<cdiv(n_tensors, 256), 256, 0, st>>>((const RangeTensor*)table, n_tensors);
   range_multi_kernel<<<n_chunks, 256, 0, st>>>((const RangeTensor*)table, chunks);
   return check_launch("range_multi");

@@ -27,6 +27,7 @@
 // 14x14x256 ResNet18 layers where conv.hip's forward kernel reaches 155 / 156 / 183.
 #include "gemm_engine.h"
 #include "conv_geom.h"
+#include "multi_tensor.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
@@ -786,10 +787,11 @@ struct WPlanesTensor { const float* w; unsigned short* out; int R, S, C, K, flip
 static_assert(sizeof(WPlanesTensor) == 40, "descriptor layout is part of the ABI (include/embnet.h)");
 // f16 = 1: two fp16 pieces of w s, s from the slot (gemm_engine.h) — weight_absmax_kernel / weight_scale_kernel below put it there
 __global__ __launch_bounds__(256) void weight_planes_kernel(const WPlanesTensor* __restrict__ table, const int* __restrict__ chunks, int f16) {
-  const WPlanesTensor t = table[chunks[2 * blockIdx.x]];
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const WPlanesTensor t = table[c.tensor];
   const int rows = t.flip ? t.C : t.K, red = t.flip ? t.K : t.C, ncc = red / 16;
   const long plane = (long)t.R * t.S * t.C * t.K, total4 = plane / 4;
-  const long i = (long)chunks[2 * blockIdx.x + 1] * 1024 + threadIdx.x;
+  const long i = c.first / 4 + threadIdx.x;             // in float4s: MT_CHUNK / 4 of them per chunk
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const long i4 = i + u * 256;
@@ -818,12 +820,13 @@ __global__ __launch_bounds__(256) void weight_planes_kernel(const WPlanesTensor*
   }
 }
 
-// the largest |w| of each kernel: a workgroup per chunk of 4096 elements (the chunk list of the planes pass), one atomic per workgroup
+// the largest |w| of each kernel: a workgroup per chunk (the chunk list of the planes pass, multi_tensor.h), one atomic per workgroup
 // — an unsigned maximum of bit patterns: independent of the order, so reproducible
 __global__ __launch_bounds__(256) void weight_absmax_kernel(const WPlanesTensor* __restrict__ table, const int* __restrict__ chunks) {
-  const WPlanesTensor t = table[chunks[2 * blockIdx.x]];
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const WPlanesTensor t = table[c.tensor];
   const long plane = (long)t.R * t.S * t.C * t.K, total4 = plane / 4;
-  const long i = (long)chunks[2 * blockIdx.x + 1] * 1024 + threadIdx.x;
+  const long i = c.first / 4 + threadIdx.x;
   float m = 0.f;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -1020,10 +1023,10 @@ extern "C" int embnet_planes_from_f32(const float* x, long pixels, int c, void* 
   return check_launch("planes_from_f32");
 }
 
-extern "C" int embnet_conv_weight_planes_chunk_elems(void) { return 4096; }
+extern "C" int embnet_conv_weight_planes_chunk_elems(void) { return MT_CHUNK; }
 extern "C" int embnet_conv_weight_planes(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, void* stream) {
   EMBNET_CHECK_ARG(table && chunks && n_tensors > 0 && n_chunks > 0, "conv_weight_planes: bad argument");
-  EMBNET_TRACE("embnet::patch::weight_planes_kernel", TRACE_BYTES, 10.0 * 4096 * n_chunks, stream);
+  EMBNET_TRACE("embnet::patch::weight_planes_kernel", TRACE_BYTES, 10.0 * MT_CHUNK * n_chunks, stream);
   if (planes_f16()) {                                       // each kernel's own range first (both layouts of a kernel find the same)
     hipStream_t st = (hipStream_t)stream;
     weight_scale_kernel<<<cdiv(n_tensors, 256), 256, 0, st>>>((const WPlanesTensor*)table, n_tensors, 0);

@@ -5,7 +5,8 @@
 // :44-75 (BatchNormalization, Dropout), :110-116 (GlobalAveragePooling2D) and the zoo ResNet blocks.
 // Roofline: HBM.  Algorithmic bytes per element are noted at each kernel.
 #include "common.h"
-#include "gemm_engine.h"        // split4: the three bf16 pieces of an fp32 value (planes for conv_patch.hip)
+#include "multi_tensor.h"
+#include "gemm_engine.h"       // split4: the three bf16 pieces of an fp32 value (planes for conv_patch.hip)
 #include <stdlib.h>
 #include "../../include/embnet.h"
 
@@ -1240,14 +1241,15 @@ __global__ __launch_bounds__(256) void relu_bwd_colsum_kernel(const float* __res
 }
 
 // Sum over several tensors of alpha_t * sum(x_t^2) — all the kernel_regularizer=l2(lambda) terms of a model
-// (backbones.py:22-36) in one launch pair: chunk c = (tensor, 4096-element block) -> partial[c]; one workgroup adds the
+// (backbones.py:22-36) in one launch pair (multi_tensor.h): chunk c = (tensor, chunk) -> partial[c]; one workgroup adds the
 // partials in double, in chunk order (reproducible).
 struct SumsqTensor { const float* x; long n; float alpha; int pad; };
 static_assert(sizeof(SumsqTensor) == 24, "descriptor layout is part of the ABI (include/embnet.h)");
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const SumsqTensor* __restrict__ table, const int* __restrict__ chunks,
                                                           float* __restrict__ partial) {
-  const SumsqTensor t = table[chunks[2 * blockIdx.x]];
-  const long first = (long)chunks[2 * blockIdx.x + 1] * 4096, end = min(first + 4096, t.n);
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const SumsqTensor t = table[c.tensor];
+  const long first = c.first, end = min(first + MT_CHUNK, t.n);
   float s = 0.f;
   for (long i = first + threadIdx.x; i < end; i += 256) s = fmaf(t.x[i], t.x[i], s);
   s = block_sum256(s);
@@ -2336,12 +2338,12 @@ extern "C" int embnet_pad_channels(const float* x, long pixels, int cin, int cou
   return embnet_pad_channels_ex(x, pixels, cin, cout, y, nullptr, stream);
 }
 
-extern "C" int embnet_sumsq_chunk_elems(void) { return 4096; }
+extern "C" int embnet_sumsq_chunk_elems(void) { return MT_CHUNK; }
 extern "C" int embnet_sumsq_multi(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, float* out, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   EMBNET_CHECK_ARG(table && chunks && out && workspace && n_tensors > 0 && n_chunks > 0, "sumsq_multi: bad argument");
   if (workspace_bytes < (size_t)n_chunks * sizeof(float)) return fail(EMBNET_EWORKSPACE, "sumsq_multi: workspace too small");
-  { EMBNET_TRACE("embnet::sumsq_multi_kernel", TRACE_BYTES, 4.0 * 4096 * n_chunks, stream);
+  { EMBNET_TRACE("embnet::sumsq_multi_kernel", TRACE_BYTES, 4.0 * MT_CHUNK * n_chunks, stream);
     sumsq_multi_kernel<<<n_chunks, 256, 0, S(stream)>>>((const SumsqTensor*)table, chunks, (float*)workspace); }
   sum_partials_kernel<<<1, 256, 0, S(stream)>>>((const float*)workspace, n_chunks, out);
   return check_launch("sumsq_multi");

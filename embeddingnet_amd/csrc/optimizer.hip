@@ -1,22 +1,21 @@
 // One launch updates every trainable tensor of a model with the update rule of the Keras optimizer the
 // reference builds in /root/reference/embedding_net/utils.py:143-153 (SGD / Adam / RMSprop / keras_radam RAdam,
-// library defaults, only `lr` passed).  Multi-tensor: a device table of {w, g, slot1, slot2, n} descriptors and a
-// device list of (tensor, first element) chunks, so the step is one kernel instead of ~10 framework launches per
-// rule (ResNet18: 62 tensors, 11.3 M floats).  HBM-bound: 4 B/element x (w r+w, g r, slots r+w) = 12..28 B/element.
+// library defaults, only `lr` passed).  Multi-tensor (multi_tensor.h) over a table of {w, g, slot1, slot2, n}
+// descriptors, so the step is one kernel instead of ~10 framework launches per rule (ResNet18: 62 tensors,
+// 11.3 M floats).  HBM-bound: 4 B/element x (w r+w, g r, slots r+w) = 12..28 B/element.
 // The scalar coefficients (bias corrections, RAdam's rectifier) are computed on the host in double and passed in;
 // the arithmetic per element is the rule's own order in fp32.
 // l2x2 = 2*lambda of the tensor's kernel_regularizer=l2(lambda) (backbones.py:22-36; 0 for none): the regulariser's
 // gradient 2*lambda*w is added to g here, which is what Keras' loss + regulariser differentiates to, so no separate
 // 2*lambda*w tensors or accumulation launches exist.
 #include "common.h"
+#include "multi_tensor.h"
 #include "../../include/embnet.h"
 
 namespace embnet {
 
 struct OptTensor { float* w; const float* g; float* s1; float* s2; long n; float l2x2; int group; };   // group: embnet_optimizer_step_groups only
 static_assert(sizeof(OptTensor) == 48, "descriptor layout is part of the ABI (include/embnet.h)");
-
-constexpr int OPT_CHUNK = 4096;          // elements per workgroup: 256 threads x 4 float4
 
 struct OptCoef { float lr, b1, b2, eps, c1, c2; };
 
@@ -36,44 +35,45 @@ __device__ __forceinline__ void opt_update(float& w, float g, float& s1, float& 
   }
 }
 
+// One workgroup's chunk of one tensor under an update rule: mt_walk's float4 path where the chunk is whole and every pointer
+// 16-byte aligned, element by element on tails and unaligned tensors.  update(w, g', slot1, slot2), g' = fma(l2x2, w, g).
+template <int RULE, class Update>
+__device__ __forceinline__ void opt_walk(const OptTensor& t, long first, Update update) {
+  constexpr bool S1 = RULE != EMBNET_OPT_SGD, S2 = RULE >= EMBNET_OPT_ADAM && RULE <= EMBNET_OPT_RADAM_WARM;
+  const bool vec = (((uintptr_t)t.w | (uintptr_t)t.g | (uintptr_t)t.s1 | (uintptr_t)t.s2) & 15) == 0;
+  mt_walk(first, t.n, vec,
+          [&](long i) {
+            float4 w = *reinterpret_cast<const float4*>(t.w + i);
+            float4 g = *reinterpret_cast<const float4*>(t.g + i);
+            g.x = fmaf(t.l2x2, w.x, g.x); g.y = fmaf(t.l2x2, w.y, g.y); g.z = fmaf(t.l2x2, w.z, g.z); g.w = fmaf(t.l2x2, w.w, g.w);
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (S1) a = *reinterpret_cast<const float4*>(t.s1 + i);
+            if (S2) b = *reinterpret_cast<const float4*>(t.s2 + i);
+            update(w.x, g.x, a.x, b.x); update(w.y, g.y, a.y, b.y);
+            update(w.z, g.z, a.z, b.z); update(w.w, g.w, a.w, b.w);
+            *reinterpret_cast<float4*>(t.w + i) = w;
+            if (S1) *reinterpret_cast<float4*>(t.s1 + i) = a;
+            if (S2) *reinterpret_cast<float4*>(t.s2 + i) = b;
+          },
+          [&](long i) {
+            float w = t.w[i], a = S1 ? t.s1[i] : 0.f, b = S2 ? t.s2[i] : 0.f;
+            update(w, fmaf(t.l2x2, w, t.g[i]), a, b);
+            t.w[i] = w;
+            if (S1) t.s1[i] = a;
+            if (S2) t.s2[i] = b;
+          });
+}
+
 template <int RULE>
 __global__ __launch_bounds__(256) void opt_step_kernel(const OptTensor* __restrict__ table, const int* __restrict__ chunks,
                                                        OptCoef k, const float* __restrict__ coef_dev) {
   if (coef_dev) {                                          // step-dependent scalars from device memory: a captured graph replays
     k.lr = coef_dev[0]; k.b1 = coef_dev[1]; k.b2 = coef_dev[2]; k.eps = coef_dev[3]; k.c1 = coef_dev[4]; k.c2 = coef_dev[5];
   }
-  const int ti = chunks[2 * blockIdx.x];
-  const long first = (long)chunks[2 * blockIdx.x + 1] * OPT_CHUNK;
-  const OptTensor t = table[ti];
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const OptTensor t = table[c.tensor];
   if (!t.g) return;                                        // no gradient this step: Keras skips the variable
-  constexpr bool S1 = RULE != EMBNET_OPT_SGD, S2 = RULE >= EMBNET_OPT_ADAM;
-  const long end = min(first + OPT_CHUNK, t.n);
-  const bool vec = (((uintptr_t)t.w | (uintptr_t)t.g | (uintptr_t)t.s1 | (uintptr_t)t.s2) & 15) == 0;
-  if (vec && end - first == OPT_CHUNK) {
-#pragma unroll
-    for (int it = 0; it < OPT_CHUNK / 1024; ++it) {
-      const long i = first + it * 1024 + threadIdx.x * 4;
-      float4 w = *reinterpret_cast<const float4*>(t.w + i);
-      float4 g = *reinterpret_cast<const float4*>(t.g + i);
-      g.x = fmaf(t.l2x2, w.x, g.x); g.y = fmaf(t.l2x2, w.y, g.y); g.z = fmaf(t.l2x2, w.z, g.z); g.w = fmaf(t.l2x2, w.w, g.w);
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-      if (S1) a = *reinterpret_cast<const float4*>(t.s1 + i);
-      if (S2) b = *reinterpret_cast<const float4*>(t.s2 + i);
-      opt_update<RULE>(w.x, g.x, a.x, b.x, k); opt_update<RULE>(w.y, g.y, a.y, b.y, k);
-      opt_update<RULE>(w.z, g.z, a.z, b.z, k); opt_update<RULE>(w.w, g.w, a.w, b.w, k);
-      *reinterpret_cast<float4*>(t.w + i) = w;
-      if (S1) *reinterpret_cast<float4*>(t.s1 + i) = a;
-      if (S2) *reinterpret_cast<float4*>(t.s2 + i) = b;
-    }
-    return;
-  }
-  for (long i = first + threadIdx.x; i < end; i += 256) {
-    float w = t.w[i], a = S1 ? t.s1[i] : 0.f, b = S2 ? t.s2[i] : 0.f;
-    opt_update<RULE>(w, fmaf(t.l2x2, w, t.g[i]), a, b, k);
-    t.w[i] = w;
-    if (S1) t.s1[i] = a;
-    if (S2) t.s2[i] = b;
-  }
+  opt_walk<RULE>(t, c.first, [&](float& w, float g, float& s1, float& s2) { opt_update<RULE>(w, g, s1, s2, k); });
 }
 
 // ---- parameter groups, decoupled decay, clipping, momentum (embnet_optimizer_step_groups) ---------------------------------------
@@ -85,41 +85,6 @@ __global__ __launch_bounds__(256) void opt_step_kernel(const OptTensor* __restri
 // same walk over the very same opt_update here: with one group and no option the result is opt_step_kernel's, bit for bit, and a
 // group's rate is all that tells two groups without options apart.  Where an option acts, every rounding is written out (contraction
 // off, explicit fmaf), the same on both paths: there a tail or an unaligned tensor gets the bits of a whole aligned chunk.
-
-// opt_step_kernel's walk over one workgroup's chunk with the rule as a parameter: float4 where the chunk is whole and every pointer
-// 16-byte aligned, element by element on tails and unaligned tensors.  update(w, g', slot1, slot2), g' = fma(l2x2, w, g).
-// (opt_step_kernel keeps its own copy of the loops, so that its machine code stays what it was.)
-template <int RULE, class Update>
-__device__ __forceinline__ void opt_walk(const OptTensor& t, long first, Update update) {
-  constexpr bool S1 = RULE != EMBNET_OPT_SGD, S2 = RULE >= EMBNET_OPT_ADAM && RULE <= EMBNET_OPT_RADAM_WARM;
-  const long end = min(first + OPT_CHUNK, t.n);
-  const bool vec = (((uintptr_t)t.w | (uintptr_t)t.g | (uintptr_t)t.s1 | (uintptr_t)t.s2) & 15) == 0;
-  if (vec && end - first == OPT_CHUNK) {
-#pragma unroll
-    for (int it = 0; it < OPT_CHUNK / 1024; ++it) {
-      const long i = first + it * 1024 + threadIdx.x * 4;
-      float4 w = *reinterpret_cast<const float4*>(t.w + i);
-      float4 g = *reinterpret_cast<const float4*>(t.g + i);
-      g.x = fmaf(t.l2x2, w.x, g.x); g.y = fmaf(t.l2x2, w.y, g.y); g.z = fmaf(t.l2x2, w.z, g.z); g.w = fmaf(t.l2x2, w.w, g.w);
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-      if (S1) a = *reinterpret_cast<const float4*>(t.s1 + i);
-      if (S2) b = *reinterpret_cast<const float4*>(t.s2 + i);
-      update(w.x, g.x, a.x, b.x); update(w.y, g.y, a.y, b.y);
-      update(w.z, g.z, a.z, b.z); update(w.w, g.w, a.w, b.w);
-      *reinterpret_cast<float4*>(t.w + i) = w;
-      if (S1) *reinterpret_cast<float4*>(t.s1 + i) = a;
-      if (S2) *reinterpret_cast<float4*>(t.s2 + i) = b;
-    }
-    return;
-  }
-  for (long i = first + threadIdx.x; i < end; i += 256) {
-    float w = t.w[i], a = S1 ? t.s1[i] : 0.f, b = S2 ? t.s2[i] : 0.f;
-    update(w, fmaf(t.l2x2, w, t.g[i]), a, b);
-    t.w[i] = w;
-    if (S1) t.s1[i] = a;
-    if (S2) t.s2[i] = b;
-  }
-}
 
 constexpr int OPT_MOMENTUM_NESTEROV = EMBNET_OPT_MOMENTUM + 1;        // kernel-side rule code: the ABI passes `nesterov` beside the rule
 
@@ -156,9 +121,8 @@ __global__ __launch_bounds__(256) void opt_step_groups_kernel(const OptTensor* _
                                                               OptGroups G, OptShared h, const float* __restrict__ coef_dev,
                                                               const float* __restrict__ group_dev,
                                                               const float* __restrict__ clip_scale_dev) {
-  const int ti = chunks[2 * blockIdx.x];
-  const long first = (long)chunks[2 * blockIdx.x + 1] * OPT_CHUNK;
-  const OptTensor t = table[ti];
+  const MtChunk c = mt_chunk(chunks, blockIdx.x);
+  const OptTensor t = table[c.tensor];
   if (!t.g) return;                                        // no gradient this step: no decay either, slots untouched
   const int gi = min(max(t.group, 0), h.n_groups - 1);     // whatever the word holds, the row is inside the arrays
   OptCoef k{0.f, h.b1, h.b2, h.eps, 0.f, h.c2};
@@ -171,11 +135,11 @@ __global__ __launch_bounds__(256) void opt_step_groups_kernel(const OptTensor* _
   const float cv = h.clipvalue;
   const bool scaled = clip_scale_dev != nullptr;
   if (OLD_RULE && !(cv > 0.f) && !scaled && decay == 0.f) {  // no option touches this tensor: opt_step_kernel's walk (see above)
-    opt_walk<OLD_RULE ? RULE : 0>(t, first, [&](float& w, float g, float& s1, float& s2) { opt_update<OLD_RULE ? RULE : 0>(w, g, s1, s2, k); });
+    opt_walk<OLD_RULE ? RULE : 0>(t, c.first, [&](float& w, float g, float& s1, float& s2) { opt_update<OLD_RULE ? RULE : 0>(w, g, s1, s2, k); });
     return;
   }
   const float cs = scaled ? *clip_scale_dev : 1.f;
-  opt_walk<RULE>(t, first, [&](float& w, float g, float& s1, float& s2) { opt_update_options<RULE>(w, g, s1, s2, k, cv, scaled, cs, decay); });
+  opt_walk<RULE>(t, c.first, [&](float& w, float g, float& s1, float& s2) { opt_update_options<RULE>(w, g, s1, s2, k, cv, scaled, cs, decay); });
 }
 
 // ---- the global gradient norm (embnet_optimizer_grad_norm) -------------------------------------------------------------------------
@@ -190,17 +154,17 @@ __global__ __launch_bounds__(256) void opt_grad_norm_kernel(const OptTensor* __r
                                                             int n_chunks, float clipnorm, int* ticket, double* part,
                                                             double* norm_out, float* scale_out) {
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const int ti = chunks[2 * c];
-    const long first = (long)chunks[2 * c + 1] * OPT_CHUNK;
-    const OptTensor t = table[ti];
+    const MtChunk ch = mt_chunk(chunks, c);
+    const long first = ch.first;
+    const OptTensor t = table[ch.tensor];
     double acc = 0.0;
     if (t.g) {                                             // workgroup-uniform; a tensor without a gradient is not in the norm
-      const long end = min(first + OPT_CHUNK, t.n);
+      const long end = min(first + MT_CHUNK, t.n);
       const bool l2 = t.l2x2 != 0.f;                       // the weight is only read where it joins the gradient
       const bool vec = (((uintptr_t)t.w | (uintptr_t)t.g) & 15) == 0;
-      if (vec && end - first == OPT_CHUNK) {
+      if (vec && end - first == MT_CHUNK) {
 #pragma unroll
-        for (int it = 0; it < OPT_CHUNK / 1024; ++it) {
+        for (int it = 0; it < MT_CHUNK / 1024; ++it) {
           const long i = first + it * 1024 + threadIdx.x * 4;
           float4 g = *reinterpret_cast<const float4*>(t.g + i);
           if (l2) {
@@ -211,7 +175,7 @@ __global__ __launch_bounds__(256) void opt_grad_norm_kernel(const OptTensor* __r
           acc += (double)g.z * (double)g.z; acc += (double)g.w * (double)g.w;
         }
       } else {                                             // the same elements per thread in the same order: the same bits
-        for (int it = 0; it < OPT_CHUNK / 1024; ++it) {
+        for (int it = 0; it < MT_CHUNK / 1024; ++it) {
           for (int j = 0; j < 4; ++j) {
             const long i = first + it * 1024 + threadIdx.x * 4 + j;
             if (i >= end) break;
@@ -242,7 +206,7 @@ __global__ __launch_bounds__(256) void opt_grad_norm_kernel(const OptTensor* __r
 
 using namespace embnet;
 
-extern "C" int embnet_optimizer_chunk_elems(void) { return OPT_CHUNK; }
+extern "C" int embnet_optimizer_chunk_elems(void) { return MT_CHUNK; }
 
 extern "C" int embnet_optimizer_step(int rule, const void* table, int n_tensors, const int32_t* chunks, int n_chunks,
                                      float lr, float b1, float b2, float eps, float c1, float c2, const float* coef_dev,
@@ -255,7 +219,7 @@ extern "C" int embnet_optimizer_step(int rule, const void* table, int n_tensors,
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: chunk count x chunk size x 4 B x (w read+write, g read, each slot read+write)
   EMBNET_TRACE("embnet::opt_step_kernel", TRACE_BYTES,
-               4.0 * n_chunks * OPT_CHUNK * (rule == EMBNET_OPT_SGD ? 3 : (rule == EMBNET_OPT_RMSPROP ? 5 : 7)), s);
+               4.0 * n_chunks * MT_CHUNK * (rule == EMBNET_OPT_SGD ? 3 : (rule == EMBNET_OPT_RMSPROP ? 5 : 7)), s);
   switch (rule) {
     case EMBNET_OPT_SGD: opt_step_kernel<EMBNET_OPT_SGD><<<n_chunks, 256, 0, s>>>(t, chunks, k, coef_dev); break;
     case EMBNET_OPT_RMSPROP: opt_step_kernel<EMBNET_OPT_RMSPROP><<<n_chunks, 256, 0, s>>>(t, chunks, k, coef_dev); break;
@@ -287,7 +251,7 @@ extern "C" int embnet_optimizer_step_groups(int rule, const void* table, int n_t
   const OptTensor* t = (const OptTensor*)table;
   hipStream_t s = (hipStream_t)stream;
   const int slots = rule == EMBNET_OPT_SGD ? 0 : (rule == EMBNET_OPT_RMSPROP || rule == EMBNET_OPT_MOMENTUM ? 1 : 2);
-  EMBNET_TRACE("embnet::opt_step_groups_kernel", TRACE_BYTES, 4.0 * n_chunks * OPT_CHUNK * (3 + 2 * slots), s);
+  EMBNET_TRACE("embnet::opt_step_groups_kernel", TRACE_BYTES, 4.0 * n_chunks * MT_CHUNK * (3 + 2 * slots), s);
 #define EMBNET_OPT_GROUPS_LAUNCH(R) \
   opt_step_groups_kernel<R><<<n_chunks, 256, 0, s>>>(t, chunks, G, h, coef_dev, group_coef_dev, clip_scale_dev)
   switch (rule) {
@@ -320,7 +284,7 @@ extern "C" int embnet_optimizer_grad_norm(const void* table, int n_tensors, cons
   hipStream_t s = (hipStream_t)stream;
   OptNormWorkspace* ws = (OptNormWorkspace*)workspace;
   // algorithmic bytes: one read of g (w besides where a tensor has l2: not counted, the table is on the device)
-  EMBNET_TRACE("embnet::opt_grad_norm_kernel", TRACE_BYTES, 4.0 * n_chunks * OPT_CHUNK, s);
+  EMBNET_TRACE("embnet::opt_grad_norm_kernel", TRACE_BYTES, 4.0 * n_chunks * MT_CHUNK, s);
   opt_grad_norm_kernel<<<n_chunks < OPT_NORM_GRID ? n_chunks : OPT_NORM_GRID, 256, 0, s>>>(
       (const OptTensor*)table, chunks, n_chunks, clipnorm, &ws->ticket, (double*)(ws + 1), norm_out, scale_out);
   return check_launch("optimizer_grad_norm");

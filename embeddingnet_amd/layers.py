@@ -21,6 +21,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import check, ptr, stream
+from .multi_tensor import Plan, f32_i32_word
 
 
 def env_switch(var, default):
@@ -411,6 +412,17 @@ DY_PLANES = _CtxDict("dy_planes")
 _ACT_PLANES = _CtxDict("act_planes")
 _ACT_RANGE = _CtxDict("act_range")
 WEIGHT_EPOCH = [0]
+# what a kernel tensor may carry beside itself (entry attribute -> the multi-tensor call that makes it, its chunk size)
+_SIDE_CALLS = {"_embnet_wplanes": ("embnet_conv_weight_planes", "embnet_conv_weight_planes_chunk_elems"),
+               "_embnet_wrange": ("embnet_range_multi", "embnet_range_chunk_elems")}
+
+
+def _entry_plan(attr, rows, sizes, dev):
+    return Plan(rows, sizes, getattr(_lib.lib(), _SIDE_CALLS[attr][1])(), dev)
+
+
+def _entry_launch(attr, plan):
+    check(getattr(_lib.lib(), _SIDE_CALLS[attr][0])(*plan.args, stream()))
 
 
 def _wplanes_entry(w):
@@ -418,7 +430,6 @@ def _wplanes_entry(w):
     hand a new model the planes of a freed one whose storage it inherited."""
     e = getattr(w, "_embnet_wplanes", None)
     if e is None or e["ptr"] != w.data_ptr() or e["shape"] != tuple(w.shape):
-        import numpy as np
         r, s, c, k = w.shape
         dev = w.device
         e = dict(ptr=w.data_ptr(), shape=tuple(w.shape), epoch=-1, version=-1,
@@ -427,10 +438,8 @@ def _wplanes_entry(w):
         rows = [(w.data_ptr(), e["fwd"].data_ptr(), r | (s << 32), c | (k << 32), 0)]
         if e["bwd"] is not None:
             rows.append((w.data_ptr(), e["bwd"].data_ptr(), r | (s << 32), c | (k << 32), 1))
-        ce = _lib.lib().embnet_conv_weight_planes_chunk_elems()
         e["rows"] = rows
-        e["table"] = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
-        e["chunks"] = torch.tensor([(i, j) for i in range(len(rows)) for j in range(-(-w.numel() // ce))], dtype=torch.int32, device=dev)
+        e["plan"] = _entry_plan("_embnet_wplanes", rows, [w.numel()] * len(rows), dev)
         w._embnet_wplanes = e
         _SIDE_GEN[0] += 1
     return e
@@ -441,7 +450,7 @@ def weight_planes(w, flip):
     (one launch for both) when the kernel changed since they were made."""
     e = _wplanes_entry(w)
     if e["epoch"] != WEIGHT_EPOCH[0] or e["version"] != w._version:
-        check(_lib.lib().embnet_conv_weight_planes(e["table"].data_ptr(), len(e["rows"]), e["chunks"].data_ptr(), e["chunks"].shape[0], stream()))
+        _entry_launch("_embnet_wplanes", e["plan"])
         e["epoch"], e["version"] = WEIGHT_EPOCH[0], w._version
     return e["bwd"] if flip else e["fwd"]
 
@@ -450,25 +459,22 @@ def _current(e, w):
     return e["epoch"] == WEIGHT_EPOCH[0] and e["version"] == w._version
 
 
-def _refresh_planes_of(ws, holder):
-    """ONE launch for the planes of the kernels `ws` (all of them have planes); the launch plan is cached on `holder`.  Nothing is
-    launched when every entry is current (a trainer and its optimizer may both ask after the same update)."""
-    import numpy as np
-    if not ws or all(_current(w._embnet_wplanes, w) for w in ws):
+def _refresh_of(ws, holder, attr):
+    """ONE call (planes: one launch, ranges: two) for the `attr` entries of the kernels `ws` (all of them have one); the launch plan
+    is cached on `holder`.  Nothing is launched when every entry is current (a trainer and its optimizer may both ask after the same
+    update)."""
+    entries = [getattr(w, attr) for w in ws]
+    if not ws or all(_current(e, w) for e, w in zip(entries, ws)):
         return
-    key = tuple(id(w._embnet_wplanes) for w in ws)
-    plan = getattr(holder, "_wplanes_plan", None)
-    if plan is None or plan["key"] != key:
-        rows = [r for w in ws for r in w._embnet_wplanes["rows"]]
-        ce = _lib.lib().embnet_conv_weight_planes_chunk_elems()
-        sizes = [w.numel() for w in ws for _ in w._embnet_wplanes["rows"]]
-        dev = ws[0].device
-        plan = dict(key=key, n=len(rows), table=torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev),
-                    chunks=torch.tensor([(i, j) for i, n in enumerate(sizes) for j in range(-(-n // ce))], dtype=torch.int32, device=dev))
-        holder._wplanes_plan = plan
-    check(_lib.lib().embnet_conv_weight_planes(plan["table"].data_ptr(), plan["n"], plan["chunks"].data_ptr(), plan["chunks"].shape[0], stream()))
-    for w in ws:
-        e = w._embnet_wplanes
+    key = tuple(id(e) for e in entries)
+    slot = attr.replace("_embnet", "") + "_plan"              # _wplanes_plan, _wrange_plan
+    cached = getattr(holder, slot, None)
+    if cached is None or cached[0] != key:
+        cached = (key, _entry_plan(attr, [r for e in entries for r in e["rows"]],
+                                   [w.numel() for w, e in zip(ws, entries) for _ in e["rows"]], ws[0].device))
+        setattr(holder, slot, cached)
+    _entry_launch(attr, cached[1])
+    for e, w in zip(entries, ws):
         e["epoch"], e["version"] = WEIGHT_EPOCH[0], w._version
 
 
@@ -485,8 +491,8 @@ def refresh_weight_planes(module):
     """Rebuild the planes of every kernel that has them, in ONE launch (called by the trainer right after the optimizer
     step, so that the next forward finds them current; inside a captured step this launch is part of the graph)."""
     kernels = [m.kernel for m in module.modules() if isinstance(m, Conv2D)]
-    _refresh_ranges_of(_with_entry(kernels, "_embnet_wrange"), module)        # (the gather convs' kernel ranges ride along)
-    _refresh_planes_of(_with_entry(kernels, "_embnet_wplanes"), module)
+    _refresh_of(_with_entry(kernels, "_embnet_wrange"), module, "_embnet_wrange")        # (the gather convs' kernel ranges ride along)
+    _refresh_of(_with_entry(kernels, "_embnet_wplanes"), module, "_embnet_wplanes")
 
 
 _SIDE_GEN = [0]             # bumped whenever a kernel tensor gains a planes / range entry
@@ -499,8 +505,8 @@ def refresh_tensors(tensors, holder):
     plan = getattr(holder, "_side_plan", None)
     if plan is None or plan[0] != _SIDE_GEN[0]:
         plan = holder._side_plan = (_SIDE_GEN[0], _with_entry(tensors, "_embnet_wrange"), _with_entry(tensors, "_embnet_wplanes"))
-    _refresh_ranges_of(plan[1], holder)
-    _refresh_planes_of(plan[2], holder)
+    _refresh_of(plan[1], holder, "_embnet_wrange")
+    _refresh_of(plan[2], holder, "_embnet_wplanes")
 
 
 # ---- three products per fp32 product on the gather convs (csrc/conv.hip "Ranges"; include/embnet.h ABI 21) --------------------------
@@ -525,14 +531,10 @@ DY_RANGE = _CtxDict("dy_range")
 def _range_entry(w):
     e = getattr(w, "_embnet_wrange", None)
     if e is None or e["ptr"] != w.data_ptr() or e["n"] != w.numel():
-        import numpy as np
-        dev = w.device
-        slot = torch.zeros(1, dtype=torch.int32, device=dev)
-        ce = _lib.lib().embnet_range_chunk_elems()
+        slot = torch.zeros(1, dtype=torch.int32, device=w.device)
         rows = [(w.data_ptr(), w.numel(), slot.data_ptr())]
         e = dict(ptr=w.data_ptr(), n=w.numel(), epoch=-1, version=-1, slot=slot, rows=rows,
-                 table=torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev),
-                 chunks=torch.tensor([(0, j) for j in range(-(-w.numel() // ce))], dtype=torch.int32, device=dev))
+                 plan=_entry_plan("_embnet_wrange", rows, [w.numel()], w.device))
         w._embnet_wrange = e
         _SIDE_GEN[0] += 1
     return e
@@ -542,35 +544,14 @@ def weight_range(w):
     """The range slot of kernel tensor `w` (uint32 bit pattern of max |w|, on the device), refreshed when the kernel changed."""
     e = _range_entry(w)
     if e["epoch"] != WEIGHT_EPOCH[0] or e["version"] != w._version:
-        check(_lib.lib().embnet_range_multi(e["table"].data_ptr(), 1, e["chunks"].data_ptr(), e["chunks"].shape[0], stream()))
+        _entry_launch("_embnet_wrange", e["plan"])
         e["epoch"], e["version"] = WEIGHT_EPOCH[0], w._version
     return e["slot"]
 
 
-def _refresh_ranges_of(ws, holder):
-    """Every kernel range of `ws` in one call (two launches); nothing when all are current."""
-    import numpy as np
-    if not ws or all(_current(w._embnet_wrange, w) for w in ws):
-        return
-    key = tuple(id(w._embnet_wrange) for w in ws)
-    plan = getattr(holder, "_wrange_plan", None)
-    if plan is None or plan["key"] != key:
-        rows = [w._embnet_wrange["rows"][0] for w in ws]
-        ce = _lib.lib().embnet_range_chunk_elems()
-        dev = ws[0].device
-        plan = dict(key=key, n=len(rows), table=torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev),
-                    chunks=torch.tensor([(i, j) for i, w in enumerate(ws) for j in range(-(-w.numel() // ce))],
-                                        dtype=torch.int32, device=dev))
-        holder._wrange_plan = plan
-    check(_lib.lib().embnet_range_multi(plan["table"].data_ptr(), plan["n"], plan["chunks"].data_ptr(), plan["chunks"].shape[0], stream()))
-    for w in ws:
-        e = w._embnet_wrange
-        e["epoch"], e["version"] = WEIGHT_EPOCH[0], w._version
-
-
 def refresh_weight_ranges(module):
     """Every kernel range of `module` that exists, in one call (two launches)."""
-    _refresh_ranges_of(_with_entry([m.kernel for m in module.modules() if isinstance(m, Conv2D)], "_embnet_wrange"), module)
+    _refresh_of(_with_entry([m.kernel for m in module.modules() if isinstance(m, Conv2D)], "_embnet_wrange"), module, "_embnet_wrange")
 
 
 def _rptr(r):
@@ -2534,9 +2515,8 @@ class _L2MultiFn(torch.autograd.Function):
     def forward(ctx, with_grad, plan, *kernels):
         lib = _lib.lib()
         out = torch.empty((), device=kernels[0].device, dtype=torch.float32)
-        ws = workspace(4 * plan["chunks"].shape[0], out.device)
-        check(lib.embnet_sumsq_multi(plan["table"].data_ptr(), len(kernels), plan["chunks"].data_ptr(), plan["chunks"].shape[0],
-                                     ptr(out), ptr(ws), ws.numel() * 4, stream()))
+        ws = workspace(4 * plan["launch"].chunks.shape[0], out.device)
+        check(lib.embnet_sumsq_multi(*plan["launch"].args, ptr(out), ptr(ws), ws.numel() * 4, stream()))
         ctx.with_grad, ctx.lams = with_grad, plan["lams"]
         if with_grad:
             ctx.save_for_backward(*kernels)
@@ -2559,21 +2539,14 @@ class _L2MultiFn(torch.autograd.Function):
 def regularization_loss(module, with_grad=True):
     """Sum of the l2 kernel regularisers declared on Conv2D/Dense layers (Keras adds it to the loss).
     with_grad=False: value only (see _L2MultiFn)."""
-    import numpy as np
     ks = regularized_kernels(module)
     if not ks:
         return None
     key = tuple((k.data_ptr(), k.numel(), lam) for k, lam in ks)
     plan = getattr(module, "_l2_plan", None)
     if plan is None or plan["key"] != key:               # descriptor table + chunk list, rebuilt only if storage moved
-        dev = ks[0][0].device
-        ce = _lib.lib().embnet_sumsq_chunk_elems()
-        rows = np.zeros((len(ks), 3), dtype=np.int64)
-        for i, (k, lam) in enumerate(ks):
-            rows[i, 0], rows[i, 1] = k.data_ptr(), k.numel()
-            rows[i, 2] = int(np.float32(lam).view(np.uint32))               # {float alpha; int32 pad} in one int64
-        chunks = [(i, c) for i, (k, _) in enumerate(ks) for c in range(-(-k.numel() // ce))]
-        plan = dict(key=key, table=torch.from_numpy(rows).to(dev), lams=[lam for _, lam in ks],
-                    chunks=torch.tensor(chunks, dtype=torch.int32, device=dev))
+        plan = dict(key=key, lams=[lam for _, lam in ks],
+                    launch=Plan([(k.data_ptr(), k.numel(), f32_i32_word(lam)) for k, lam in ks], [k.numel() for k, _ in ks],
+                                _lib.lib().embnet_sumsq_chunk_elems(), ks[0][0].device))
         module._l2_plan = plan
     return _L2MultiFn.apply(bool(with_grad), plan, *[k for k, _ in ks])

@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from ._lib import check
 from . import layers as L
+from .multi_tensor import chunk_list, f32_i32_word, pack_rows
 
 RULE = {"sgd": 0, "rms_prop": 1, "adam": 2, "radam": 3}
 MAX_GROUPS = 8               # EMBNET_OPT_MAX_GROUPS
@@ -93,9 +94,7 @@ class KerasOptimizer(torch.optim.Optimizer):
     def _norm_buffers(self):
         if self._norm is None:
             dev = self._tensors[0].device
-            ce = _lib.lib().embnet_optimizer_chunk_elems()
-            n_chunks = sum(-(-p.numel() // ce) for p in self._tensors)
-            nbytes = _lib.lib().embnet_optimizer_grad_norm_workspace_bytes(n_chunks)
+            nbytes = _lib.lib().embnet_optimizer_grad_norm_workspace_bytes(self._chunk_list().shape[0])
             # the workspace's first 16 bytes are the arrival ticket: zero once, the kernel re-arms it
             self._norm = (torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(-(-nbytes // 8), dtype=torch.float64, device=dev))
         return self._norm
@@ -143,8 +142,14 @@ class KerasOptimizer(torch.optim.Optimizer):
             return 3, b1, b2, lr * r_t / (1.0 - b1 ** t), 1.0 / (1.0 - b2 ** t)
         return 4, b1, b2, lr / (1.0 - b1 ** t), 0.0
 
+    def _chunk_list(self):
+        """The static half of the launch (multi_tensor.py): parameters keep their sizes."""
+        if self._chunks is None:
+            sizes = [p.numel() for p in self._tensors]
+            self._chunks = torch.from_numpy(chunk_list(sizes, _lib.lib().embnet_optimizer_chunk_elems())).to(self._tensors[0].device)
+        return self._chunks
+
     def _build_table(self):
-        lib = _lib.lib()
         dev = self._tensors[0].device
         rows, ptrs = [], []
         group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
@@ -156,22 +161,19 @@ class KerasOptimizer(torch.optim.Optimizer):
                 raise _lib.EmbnetError("KerasOptimizer: gradients must be dense contiguous fp32")
             s1, s2 = self._slots(p)
             gp = g.data_ptr() if g is not None else 0
-            l2x2 = int(np.float32(2.0 * self._l2.get(id(p), 0.0)).view(np.uint32))      # {float l2x2; int32 group} as one int64
-            rows.append((p.data_ptr(), gp, s1.data_ptr() if s1 is not None else 0,
-                         s2.data_ptr() if s2 is not None else 0, p.numel(), l2x2 | (group_of[id(p)] << 32)))
+            rows.append((p.data_ptr(), gp, s1.data_ptr() if s1 is not None else 0, s2.data_ptr() if s2 is not None else 0,
+                         p.numel(), f32_i32_word(2.0 * self._l2.get(id(p), 0.0), group_of[id(p)])))     # {float l2x2; int32 group}
             ptrs.append(gp)
-        if self._chunks is None:
-            ce = lib.embnet_optimizer_chunk_elems()
-            ck = [(i, c) for i, p in enumerate(self._tensors) for c in range(-(-p.numel() // ce))]
-            self._chunks = torch.tensor(ck, dtype=torch.int32, device=dev)
+        self._chunk_list()
+        rows = torch.from_numpy(pack_rows(rows))
         if torch.cuda.is_current_stream_capturing():
             # a captured step keeps a table (and its pinned source) of its own: replays re-run the upload node, and eager
             # steps in between must not rewrite what it copies from; no host wait is legal inside a capture either
             host = getattr(self, "_graph_host", None)     # pinned memory cannot be allocated while capturing: prepare_capture()
-            if host is None or host.shape[0] != len(rows):
+            if host is None or host.shape[0] != rows.shape[0]:
                 raise _lib.EmbnetError("KerasOptimizer: call prepare_capture() before capturing a step")
-            host.copy_(torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)))
-            self._table = torch.empty((len(rows), 6), dtype=torch.int64, device=dev)
+            host.copy_(rows)
+            self._table = torch.empty_like(rows, device=dev)
             self._table.copy_(host, non_blocking=True)
             self._ptrs = ptrs
             return
@@ -179,14 +181,13 @@ class KerasOptimizer(torch.optim.Optimizer):
         # tables, so that the host never waits for the upload of the step before (one table + an event wait kept the host
         # at most one step ahead of the GPU: 5 ms of host time per ResNet18 step went into that wait)
         if not hasattr(self, "_ring"):
-            self._ring = [[torch.empty((len(rows), 6), dtype=torch.int64).pin_memory(),
-                           torch.empty((len(rows), 6), dtype=torch.int64, device=dev), None] for _ in range(4)]
+            self._ring = [[torch.empty_like(rows).pin_memory(), torch.empty_like(rows, device=dev), None] for _ in range(4)]
             self._ring_i = 0
         self._ring_i = (self._ring_i + 1) % len(self._ring)
         slot = self._ring[self._ring_i]
         if slot[2] is not None:
             slot[2].synchronize()                         # the upload issued four rebuilds ago
-        slot[0].copy_(torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)))
+        slot[0].copy_(rows)
         slot[1].copy_(slot[0], non_blocking=True)
         slot[2] = torch.cuda.Event()
         slot[2].record()

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from ._lib import check
 from . import layers as L
+from .multi_tensor import Plan
 
 MODES = ("ema", "swa")
 
@@ -77,20 +78,14 @@ class WeightAverager:
                 raise _lib.EmbnetError(f"WeightAverager: {name} is not a contiguous fp32 GPU tensor ({t.dtype}, {t.device})")
         with torch.no_grad():
             self.averaged = {name: t.detach().clone(memory_format=torch.contiguous_format) for name, t in self._named.items()}
-        lib = _lib.lib()
-        dev = next(iter(self._named.values())).device
         live, avgs = list(self._named.values()), list(self.averaged.values())
-        ce = lib.embnet_optimizer_chunk_elems()
-        self._n = len(live)
-        self._table = self._rows(live, avgs, dev)             # { w, avg, n, 0 }
-        self._table_back = self._rows(avgs, live, dev)        # the roles exchanged: copy_to() is an update with c = 1
-        self._chunks = torch.tensor([(i, c) for i, t in enumerate(live) for c in range(-(-t.numel() // ce))],
-                                    dtype=torch.int32, device=dev)
+        self._plan = self._rows(live, avgs)                   # { w, avg, n, 0 }
+        self._plan_back = self._rows(avgs, live)              # the roles exchanged: copy_to() is an update with c = 1
 
     @staticmethod
-    def _rows(ws, avgs, dev):
-        rows = [(w.data_ptr(), a.data_ptr(), w.numel(), 0) for w, a in zip(ws, avgs)]
-        return torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)).to(dev)
+    def _rows(ws, avgs):
+        return Plan([(w.data_ptr(), a.data_ptr(), w.numel(), 0) for w, a in zip(ws, avgs)], [w.numel() for w in ws],
+                    _lib.lib().embnet_optimizer_chunk_elems(), ws[0].device)
 
     @staticmethod
     def _collect(modules):
@@ -140,8 +135,7 @@ class WeightAverager:
             return                                            # nothing to do, and nobody replays this call
         if torch.is_tensor(c_dev):
             c_dev = c_dev.data_ptr()
-        check(_lib.lib().embnet_weight_average_update(self._table.data_ptr(), self._n, self._chunks.data_ptr(),
-                                                      self._chunks.shape[0], c, c_dev, _lib.stream()))
+        check(_lib.lib().embnet_weight_average_update(*self._plan.args, c, c_dev, _lib.stream()))
 
     def _refresh(self):
         L.WEIGHT_EPOCH[0] += 1                                # every cached plane and range is stale from here on ...
@@ -149,8 +143,7 @@ class WeightAverager:
             L.refresh_weight_planes(m)                        # ... and current again, eagerly: a replayed graph never asks
 
     def _swap(self):
-        check(_lib.lib().embnet_weight_average_swap(self._table.data_ptr(), self._n, self._chunks.data_ptr(),
-                                                    self._chunks.shape[0], _lib.stream()))
+        check(_lib.lib().embnet_weight_average_swap(*self._plan.args, _lib.stream()))
         self._refresh()
 
     @contextlib.contextmanager
@@ -174,8 +167,7 @@ class WeightAverager:
         """One-way: the model's tensors become the averages (for export); the live weights are lost."""
         if self._applied:
             raise _lib.EmbnetError("WeightAverager.copy_to inside applied()")
-        check(_lib.lib().embnet_weight_average_update(self._table_back.data_ptr(), self._n, self._chunks.data_ptr(),
-                                                      self._chunks.shape[0], 1.0, None, _lib.stream()))
+        check(_lib.lib().embnet_weight_average_update(*self._plan_back.args, 1.0, None, _lib.stream()))
         self._refresh()
 
     def average_buffers(self, process_group=None):

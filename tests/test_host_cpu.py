@@ -34,7 +34,8 @@ def test_library_exports_every_declared_symbol():
     # simple2's Flatten -> Dense(512) at batch 32: 8 output tiles, 400 K tiles -> split; ResNet heads: not
     assert bound.embnet_dense_fwd_workspace_bytes(32, 12800, 512) == 58 * 32 * 512 * 4
     assert bound.embnet_dense_fwd_workspace_bytes(128, 512, 128) == 0
-    assert bound.embnet_sumsq_chunk_elems() == 4096 and bound.embnet_optimizer_chunk_elems() == 4096
+    assert (bound.embnet_sumsq_chunk_elems() == 4096 and bound.embnet_optimizer_chunk_elems() == 4096
+            and bound.embnet_range_chunk_elems() == 4096 and bound.embnet_conv_weight_planes_chunk_elems() == 4096)
 
 
 def test_invalid_arguments_are_rejected_without_a_gpu():

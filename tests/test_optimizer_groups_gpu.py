@@ -393,6 +393,66 @@ def test_captured_step_replays_with_every_groups_coefficients(dev):
             assert torch.equal(u, v), (i, ["loss", "grad_norm", "proxies", "weights", "slots"][j])
 
 
+# ------------------------------------------------------------------------------------------------ 6b. the launches beside the update
+def test_step_leaves_planes_and_ranges_current_through_cached_plans(dev, monkeypatch):
+    """After KerasOptimizer.step() on BatchNorm -> 3x3 conv 16 -> 32 (patch kernel: kernel planes) -> BatchNorm -> 1x1 conv 32 -> 16
+    (gather kernel on three products: a kernel range), 8x8 images: the optimizer's chunk list is the hand-written one, both side
+    entries are current, asking again launches nothing, the next step makes one call per kind from the plans cached on the
+    optimizer, and the regularisers' value is their float64 sum (2e-6 relative, test_round3_gpu.py's tolerance)."""
+    from embeddingnet_amd import _lib
+    from embeddingnet_amd import layers as L
+    from embeddingnet_amd.optimizers import KerasOptimizer
+    lib = _lib.lib()
+    torch.manual_seed(3)
+    net = torch.nn.Sequential()
+    net.bn0, net.c3 = L.BatchNormalization(16), L.Conv2D(16, 32, 3, padding="same", use_bias=False, l2=2e-4)
+    net.bn1, net.c1 = L.BatchNormalization(32), L.Conv2D(32, 16, 1, l2=1e-3)
+    net.c1.f16 = True
+    net.to(dev).train()
+    opt = KerasOptimizer(net.parameters(), "sgd", 0.05)
+    x = torch.randn(4, 8, 8, 16, device=dev)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        net.c1(net.bn1(net.c3(net.bn0(x, planes_for=net.c3)))).square().sum().backward()
+        opt.step()
+
+    step()
+    ce = lib.embnet_optimizer_chunk_elems()
+    assert net.c3.kernel.numel() > ce                                            # more than one chunk
+    assert opt._chunks.dtype == torch.int32 and opt._chunks.device == x.device
+    assert opt._chunks.cpu().tolist() == [[i, c] for i, p in enumerate(opt._tensors) for c in range(-(-p.numel() // ce))]
+    planes, rng = net.c3.kernel._embnet_wplanes, net.c1.kernel._embnet_wrange
+
+    def current():
+        return all(e["epoch"] == L.WEIGHT_EPOCH[0] and e["version"] == w._version
+                   for e, w in ((planes, net.c3.kernel), (rng, net.c1.kernel)))
+
+    assert current()
+    assert rng["slot"].cpu().view(torch.int32).item() == net.c1.kernel.detach().abs().max().cpu().view(torch.int32).item()
+    calls = {"embnet_conv_weight_planes": 0, "embnet_range_multi": 0}
+
+    def counted(name, fn):
+        def call(*args):
+            calls[name] += 1
+            return fn(*args)
+        return call
+
+    for name in calls:
+        monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    L.refresh_tensors(opt._tensors, opt)
+    L.refresh_weight_planes(net)
+    assert calls == {"embnet_conv_weight_planes": 0, "embnet_range_multi": 0}
+    cached = opt._wplanes_plan, opt._wrange_plan
+    step()
+    assert calls == {"embnet_conv_weight_planes": 1, "embnet_range_multi": 1} and current()
+    assert opt._wplanes_plan is cached[0] and opt._wrange_plan is cached[1]
+    assert rng["slot"].cpu().view(torch.int32).item() == net.c1.kernel.detach().abs().max().cpu().view(torch.int32).item()
+    want = sum(lam * float((w.detach().double() ** 2).sum()) for w, lam in ((net.c3.kernel, 2e-4), (net.c1.kernel, 1e-3)))
+    val = L.regularization_loss(net, with_grad=False)
+    assert abs(val.item() - want) <= 2e-6 * want
+
+
 # ------------------------------------------------------------------------------------------------ 7. CLI
 def _cli(tmp_path, name, extra=()):
     cfg = open(os.path.join(ROOT, "configs", f"{name}.yml")).read().replace("work_dirs/", str(tmp_path) + "/")
