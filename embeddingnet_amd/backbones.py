@@ -17,6 +17,7 @@ from torch import nn
 
 from . import layers as L
 from . import ops
+from .utils import check_pooling
 
 
 def default_device():
@@ -263,9 +264,17 @@ def get_backbone(input_shape,
                  embeddings_normalization=True,
                  backbone_weights='imagenet',
                  freeze_backbone=False,
+                 pooling=None,
                  **kwargs):
     """Same contract as the reference: returns (base_model, backbone_model); extra MODEL keys
-    (mode, distance_type, ...) are swallowed.  Build-side extras: seed=<int>, device=<torch.device>."""
+    (mode, distance_type, ...) are swallowed.  Build-side extras: seed=<int>, device=<torch.device>.
+    pooling (MODEL key `pooling`; not in the reference): how the ResNet / EfficientNet head turns the feature map into a
+    vector.  None or 'avg': GlobalAveragePooling2D, the reference's head (layer name `gap`).  'gem', or a mapping
+    {'type': 'gem', 'p': 3.0, 'eps': 1e-6, 'learnable': True, 'per_channel': False}: generalised-mean pooling (layers.GeM,
+    layer name `gem`, weight `gem/p`) in its place.  'simple' and 'simple2' do not pool: anything but 'avg' is refused.
+    A ResNet ends in a ReLU, so GeM's clamp only lifts exact zeros to eps.  EfficientNet's last activation is swish, whose
+    negative values (down to -0.28) meet the clamp: they pool as eps and receive no gradient."""
+    pooling = check_pooling(pooling, backbone_name)
     seed = int(kwargs.get("seed", 0))
     device = kwargs.get("device") or default_device()
     gen = torch.Generator().manual_seed(seed)
@@ -306,7 +315,12 @@ def get_backbone(input_shape,
             for p in backbone.parameters():
                 if id(p) not in tail:
                     p.requires_grad_(False)
-        head = Seq(gap=L.GlobalAveragePooling2D(),
+        if pooling is None:
+            pool = dict(gap=L.GlobalAveragePooling2D())
+        else:
+            pool = dict(gem=L.GeM(p=pooling["p"], eps=pooling["eps"], learnable=pooling["learnable"],
+                                  per_channel=pooling["per_channel"], channels=backbone.out_channels))
+        head = Seq(**pool,
                    dense1=L.Dense(backbone.out_channels, encodings_len // 2, activation="relu", gen=gen),
                    dense2=L.Dense(encodings_len // 2, encodings_len, activation="relu", gen=gen))
     if embeddings_normalization:

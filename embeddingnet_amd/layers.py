@@ -2165,6 +2165,76 @@ class GlobalAveragePooling2D(nn.Module):
         return _GapFn.apply(x, with_skip)
 
 
+_GEM_WS = {}
+
+
+class _GemFn(torch.autograd.Function):
+    """embnet_gem_fwd / embnet_gem_bwd.  p stays on the device: neither pass reads it on the host.  When p wants a gradient the
+    forward also writes dy/dp [n,c], and the backward's float64 reduction turns it into dp; otherwise neither is launched."""
+
+    @staticmethod
+    def forward(ctx, x, p, eps):
+        x = _c(x)
+        n, h, w, c = x.shape
+        y = torch.empty((n, c), device=x.device, dtype=torch.float32)
+        learn = ctx.needs_input_grad[1]
+        dydp = torch.empty_like(y) if learn else None
+        stride = int(p.numel() > 1)
+        check(_lib.lib().embnet_gem_fwd(ptr(x), n, h * w, c, ptr(p), stride, eps, ptr(y), ptr(dydp), stream()))
+        ctx.cfg = (n, h, w, c, stride, eps)
+        ctx.save_for_backward(*((x, y, p) + ((dydp,) if learn else ())))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        n, h, w, c, stride, eps = ctx.cfg
+        x, y, p = ctx.saved_tensors[:3]
+        learn = len(ctx.saved_tensors) == 4 and ctx.needs_input_grad[1]
+        dy = _c(dy)
+        lib = _lib.lib()
+        dx = torch.empty_like(x)
+        dydp = dp = ws = None
+        if learn:
+            dydp, dp = ctx.saved_tensors[3], torch.empty_like(p)
+            key = (x.device.index, stream(), c)            # zeroed once: the kernel re-arms the arrival ticket in it
+            if key not in _GEM_WS:
+                _GEM_WS[key] = torch.zeros(lib.embnet_gem_bwd_workspace_bytes(c) // 8 + 1, dtype=torch.float64, device=x.device)
+            ws = _GEM_WS[key]
+        check(lib.embnet_gem_bwd(ptr(dy), ptr(x), ptr(y), ptr(p), stride, eps, n, h * w, c, ptr(dx), ptr(dydp), ptr(dp), ptr(ws),
+                                 ws.numel() * 8 if learn else 0, stream()))
+        return dx, dp, None
+
+
+class GeM(nn.Module):
+    """Generalised-mean pooling (Radenovic et al., TPAMI 2019): x[n,h,w,c] -> y[n,c] = (mean_hw max(x, eps)^p)^(1/p).  p = 1 is the
+    mean of the clamped map, p -> inf its maximum.  `p` has shape [1], or [channels] with per_channel=True; learnable=True makes
+    it a parameter (one-dimensional: the optimizer groups never decay it), otherwise it is a buffer, saved and loaded with the
+    weights but not trained, and no gradient work for it is launched.
+    p <= 0 is refused here.  Nothing constrains p while it is trained: should training drive it to 0 or below, the results are
+    undefined (NaN or inf, no out-of-bounds access).  Values below eps, negative ones included, are clamped to eps and get no
+    gradient."""
+
+    def __init__(self, p=3.0, eps=1e-6, learnable=True, per_channel=False, channels=None):
+        super().__init__()
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0:
+            raise ValueError(f"GeM: p must be a number > 0 (got {p!r})")
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps > 0:
+            raise ValueError(f"GeM: eps must be a number > 0 (got {eps!r})")
+        if per_channel and (isinstance(channels, bool) or not isinstance(channels, int) or channels < 1):
+            raise ValueError(f"GeM: per_channel=True needs channels, a whole number >= 1 (got {channels!r})")
+        self.eps, self.learnable, self.per_channel = float(eps), bool(learnable), bool(per_channel)
+        value = torch.full((channels if per_channel else 1,), float(p), dtype=torch.float32)
+        if self.learnable:
+            self.p = nn.Parameter(value)
+        else:
+            self.register_buffer("p", value)
+
+    def forward(self, x):
+        if self.per_channel and x.shape[-1] != self.p.numel():
+            raise _lib.EmbnetError(f"GeM: {self.p.numel()} exponents for {x.shape[-1]} channels")
+        return _GemFn.apply(x, self.p, self.eps)
+
+
 class Flatten(nn.Module):
     """(h, w, c) order — a view on NHWC, no kernel."""
 

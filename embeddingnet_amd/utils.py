@@ -123,6 +123,46 @@ def check_weight_averaging(section):
     return out
 
 
+POOLING_TYPES = ("avg", "gem")
+POOLING_KEYS = ("type", "p", "eps", "learnable", "per_channel")
+
+
+def check_pooling(pooling, backbone_name=None):
+    """MODEL.pooling -> None for the average-pooling head (None, 'avg', {'type': 'avg'}), or for GeM ('gem' or a mapping with
+    type 'gem') a dict with every key of layers.GeM filled in: p (3.0), eps (1e-6), learnable (true), per_channel (false).
+    Unknown types, unknown keys and wrong value types are refused by key; so is anything but 'avg' for the backbones whose
+    heads do not pool ('simple', 'simple2')."""
+    if pooling is None or isinstance(pooling, str):
+        pooling = {"type": pooling or "avg"}
+    if not isinstance(pooling, dict):
+        raise ValueError(f"pooling: a type name ({', '.join(POOLING_TYPES)}) or a mapping of {', '.join(POOLING_KEYS)} "
+                         f"(got {pooling!r})")
+    unknown = set(pooling) - set(POOLING_KEYS)
+    if unknown:
+        raise ValueError(f"pooling: unknown keys {sorted(unknown, key=str)} ({', '.join(POOLING_KEYS)})")
+    kind = pooling.get("type")
+    if kind not in POOLING_TYPES:
+        raise ValueError(f"pooling: type must be one of {', '.join(POOLING_TYPES)} (got {kind!r})")
+    if kind == "avg":
+        if len(pooling) > 1:
+            raise ValueError(f"pooling: {sorted(set(pooling) - {'type'})} belong to type 'gem', not 'avg'")
+        return None
+    if backbone_name in ("simple", "simple2"):
+        raise ValueError(f"pooling: type 'gem' needs a pooling head; the head of backbone '{backbone_name}' does not pool")
+    out = dict(type="gem")
+    for key, default in (("p", 3.0), ("eps", 1e-6)):
+        v = pooling.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+            raise ValueError(f"pooling: {key} must be a number > 0 (got {v!r})")
+        out[key] = float(v)
+    for key, default in (("learnable", True), ("per_channel", False)):
+        v = pooling.get(key, default)
+        if not isinstance(v, bool):
+            raise ValueError(f"pooling: {key} must be true or false (got {v!r})")
+        out[key] = v
+    return out
+
+
 def _finish_section(section, input_shape):
     """A section that drives training (TRAIN-like or SOFTMAX_PRETRAINING): optimizer name -> object."""
     section['optimizer'] = get_optimizer(section['optimizer'], section['learning_rate'], section.get('optimizer_params'))
@@ -141,6 +181,8 @@ def parse_params(filename='configs/road_signs.yml'):
         cfg = yaml.safe_load(ymlfile)
     params = {key: (cfg[section] if section != "ENCODINGS" else cfg.get(section, {})) for section, key in SECTIONS}
     shape = params['model']['input_shape']
+    if 'pooling' in params['model']:                       # refused here, before anything is loaded or built
+        check_pooling(params['model']['pooling'], params['model'].get('backbone_name', 'simple'))
     params['generator']['input_shape'] = shape
     params['generator']['augmentations'] = None
     _finish_section(params['train'], None)

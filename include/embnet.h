@@ -869,6 +869,37 @@ int embnet_gap_fwd(const float* x, int n, int hw, int c, float* y, void* stream)
 int embnet_gap_bwd(const float* dy, int n, int hw, int c, const float* dx_add, float* dx, void* stream);   /* dx_add (NULL or
     [n,hw,c], c % 4 == 0): gradient of x's other consumer, summed in the same pass */
 
+/* Generalised-mean pooling (GeM, Radenovic et al., TPAMI 2019; no reference code: the reference pools with the mean only):
+ * y[n,c] = (mean_hw max(x, eps)^p)^(1/p) on x[n,hw,c].  The exponent is read from DEVICE memory, p[0] when p_stride == 0 and
+ * p[ch * p_stride] (p_stride == 1: one exponent per channel) otherwise; the host never reads it, so a captured launch replays
+ * with whatever the exponent holds then.  p > 0 and eps > 0 (eps is checked, p cannot be: with p <= 0 or NaN the results are
+ * undefined, though nothing is written out of bounds).
+ * The arithmetic, per (sample, channel), all fp32 (library log2f / exp2f, IEEE division, no fast-math forms):
+ *   z_i = fmaxf(x_i, eps);  M = max_i z_i;  r_i = z_i / M  in (0, 1];  l_i = log2f(r_i);  e_i = exp2f(p * l_i);
+ *   s = (sum_i e_i) / hw;   y = M * exp2f(log2f(s) / p).
+ * The sum is normalised by the maximum, so no power overflows or flushes at any amplitude with eps / M >= 2^-126: every e_i is
+ * in (0, 1] and the largest is exactly 1.  With `dydp` ([n,c], NULL: not formed) the same pass gives
+ *   t = (sum_i e_i * (l_i * ln2)) / hw;   dydp = y * (t / (p * s) - (log2f(s) * ln2) / (p * p)) = dy/dp   (M cancels).
+ * Summation order over hw (fixed by the shape alone, never by the scheduling):  c % 4 == 0 (gem_fwd4_kernel: one workgroup per
+ * sample and 64 channels, 16 channel quads x 16 pixel lanes): lane j adds its pixels j, j + 16, ... in ascending order from 0,
+ * then the 16 lane sums are added in ascending lane order from lane 0's.  c % 4 != 0 (gem_fwd_kernel, one thread per (sample,
+ * channel)): pixels in ascending order.  x is read from memory once while hw <= 144 (nine pixels per lane stay in registers);
+ * beyond that the second sweep reads it again.
+ * bwd:  dx_i = (dy / hw) * exp2f((p - 1) * log2f(z_i / y)) where x_i >= eps, exactly 0 where x_i < eps (torch.clamp's gradient);
+ * z_i / y <= hw^(1/p), so nothing overflows.  x, dy, y and dx may not alias.  With `dp` (then dydp is required; NULL: no
+ * reduction is launched) the exponent's gradient, summed in float64 in a fixed order and rounded once:
+ *   p_stride == 0: dp[0] = sum_{n,c} dy * dydp;   p_stride == 1: dp[ch] = sum_n dy * dydp.
+ * Order: per channel the samples j, j + 16, ... ascending in 16 lanes, the lanes ascending; p_stride == 0: then the 16 channels of
+ * a workgroup ascending, the workgroups' partials in 256 strided chains and block_sum256's tree.  No floating-point atomics.
+ * workspace >= embnet_gem_bwd_workspace_bytes(c) when dp is given (else it may be NULL), 16-byte aligned, its first 16 bytes
+ * ZERO before the first launch (the arrival ticket, which re-arms itself); one workspace serves one stream at a time.
+ * n <= 65535. */
+int embnet_gem_fwd(const float* x, int n, int hw, int c, const float* p, int p_stride, float eps, float* y, float* dydp,
+                   void* stream);
+size_t embnet_gem_bwd_workspace_bytes(int c);
+int embnet_gem_bwd(const float* dy, const float* x, const float* y, const float* p, int p_stride, float eps, int n, int hw, int c,
+                   float* dx, const float* dydp, float* dp, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Elementwise helpers of the backward pass and the residual blocks. */
 int embnet_relu_bwd(const float* dy, const float* y, long total, float* dz, void* stream);   /* dz = dy*[y>0] */
 /* the same on dy/y[m,c] plus dbias[c] = column sums of dz, one pass (Conv2D / Dense with bias and a fused ReLU);

@@ -663,6 +663,8 @@ def main():
     for name in verification_names(verification):
         history['val_' + name] = []
     n_epochs = min(p_train['n_epochs'], args.max_epochs or p_train['n_epochs'])
+    from embeddingnet_amd.layers import GeM
+    gem_layers = [m for m in trainable.modules() if isinstance(m, GeM)]     # MODEL.pooling 'gem': the exponent is logged per epoch
 
     # triplet mode: batches are planned on this thread and decoded / uploaded ahead of the step (input_pipeline.Feeder: the
     # role of Keras' fit_generator enqueuer, reference train.py:172-177)
@@ -725,6 +727,8 @@ def main():
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
             if averager is not None:
                 msg += f' - averaged {averager.n_averaged}'
+            if gem_layers:                                # the live exponent (the mean of a per-channel one), read once per epoch
+                msg += f' - gem_p {torch.cat([m.p.detach().reshape(-1) for m in gem_layers]).mean().item():.4f}'
             value = epoch_loss
             if val_gen is not None:
                 with evaluation():                    # (TRAIN.weight_averaging: the averaged weights, planes and ranges)
