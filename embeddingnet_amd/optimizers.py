@@ -15,6 +15,10 @@ clipping by value or by global norm — what the proxy losses' papers train with
 backbone's rate, clipped gradients; SoftTriple: centres at 1e-2 against 1e-4; ArcFace / CosFace: SGD, momentum 0.9, decay 5e-4).
 An optimizer that uses any of them steps through `embnet_optimizer_step_groups` (still one launch; `global_clipnorm` puts
 `embnet_optimizer_grad_norm` in front of it); one group with none of them issues the call it always issued.
+
+The layer-wise adaptive rules 'lars' and 'lamb' (large-batch training; SupCon and SimCLR are LARS recipes) scale every tensor's
+step by a trust ratio eta |w| / |u|: two launches per step, `embnet_optimizer_layerwise_norms` and
+`embnet_optimizer_layerwise_step` (csrc/layerwise.hip), the norms in f64 on the device and bitwise reproducible.
 """
 import math
 
@@ -29,10 +33,11 @@ from .multi_tensor import chunk_list, f32_i32_word, pack_rows
 RULE = {"sgd": 0, "rms_prop": 1, "adam": 2, "radam": 3}
 MAX_GROUPS = 8               # EMBNET_OPT_MAX_GROUPS
 MOMENTUM_RULE = 5            # EMBNET_OPT_MOMENTUM: 'sgd' with a momentum
+LAYERWISE = {"lars": 0, "lamb": 1}       # EMBNET_LAYERWISE_*: entry points and codes of their own
 
 
 class KerasOptimizer(torch.optim.Optimizer):
-    """rule: 'sgd' | 'rms_prop' | 'adam' | 'radam' (the names utils.get_optimizer dispatches on).
+    """rule: 'sgd' | 'rms_prop' | 'adam' | 'radam' (the names utils.get_optimizer dispatches on) | 'lars' | 'lamb'.
 
     params: a parameter list, or torch-style groups (at most 8) with the keys
       lr            the group's base rate (default: `lr`); a schedule may overwrite it at any time
@@ -44,21 +49,38 @@ class KerasOptimizer(torch.optim.Optimizer):
     c / max(norm, c), norm the 2-norm over every gradient of the step (TensorFlow's clip_by_global_norm); `grad_norm` then holds
     the norm before clipping.  The two are exclusive.  Both act on the gradient after the l2 regularisers' part joined it.
     Under data parallelism step() runs after the gradient all-reduce, so every rank holds the same gradients and computes the
-    same norm in the same order: no extra collective, and the ranks' weights stay bitwise equal."""
+    same norm in the same order: no extra collective, and the ranks' weights stay bitwise equal.
 
-    def __init__(self, params, rule, lr, beta_1=0.9, beta_2=0.999, rho=0.9, epsilon=1e-7, momentum=0.0, nesterov=False,
-                 clipvalue=None, global_clipnorm=None):
-        if rule not in RULE:
+    'lars' (SimCLR's LARSOptimizer form; momentum 0.9 unless given, nesterov allowed) and 'lamb' (beta_1, beta_2, epsilon as
+    'adam'; no momentum) take one more group key:
+      trust_coefficient  eta (default: the constructor's `trust_coefficient`, which is 1e-3 for 'lars' and 1 for 'lamb'); the
+                    group's tensors step at lr * lr_mult * r, r = eta |w| / |u| per tensor (1 where a norm is zero); 0 exempts the
+                    group from adaptation (r = 1), as the papers exempt BatchNorm parameters and biases
+    and under these two rules `weight_decay` is COUPLED: it joins the direction whose norm is taken, u = g' + weight_decay * w
+    for 'lars' and u = m_hat / (sqrt(v_hat) + epsilon) + weight_decay * w for 'lamb' (with eta = 0: SGD with L2 decay, and AdamW).
+    The clips act on the gradient in front, as above.  `trust_ratios` holds every tensor's r of the last step."""
+
+    def __init__(self, params, rule, lr, beta_1=0.9, beta_2=0.999, rho=0.9, epsilon=1e-7, momentum=None, nesterov=False,
+                 clipvalue=None, global_clipnorm=None, trust_coefficient=None):
+        if rule not in RULE and rule not in LAYERWISE:
             raise KeyError(rule)
+        self.layerwise = rule in LAYERWISE
+        if momentum is None:
+            momentum = 0.9 if rule == "lars" else 0.0
         if momentum < 0 or (clipvalue is not None and clipvalue < 0) or (global_clipnorm is not None and global_clipnorm < 0):
             raise ValueError("momentum, clipvalue and global_clipnorm must not be negative")
         if clipvalue and global_clipnorm:
             raise ValueError("clipvalue and global_clipnorm are exclusive")
         if nesterov and not momentum:
             raise ValueError("nesterov needs a momentum")
-        if momentum and rule != "sgd":
-            raise ValueError(f"momentum belongs to rule 'sgd', not {rule!r}")
-        super().__init__(params, dict(lr=float(lr), lr_mult=1.0, weight_decay=0.0))
+        if (momentum or nesterov) and rule not in ("sgd", "lars"):
+            raise ValueError(f"momentum and nesterov belong to the rules 'sgd' and 'lars', not {rule!r}")
+        if trust_coefficient is not None and not self.layerwise:
+            raise ValueError(f"trust_coefficient belongs to the rules 'lars' and 'lamb', not {rule!r}")
+        defaults = dict(lr=float(lr), lr_mult=1.0, weight_decay=0.0)
+        if self.layerwise:
+            defaults["trust_coefficient"] = float({"lars": 1e-3, "lamb": 1.0}[rule] if trust_coefficient is None else trust_coefficient)
+        super().__init__(params, defaults)
         self.rule, self.b1, self.b2, self.rho, self.eps = rule, beta_1, beta_2, rho, epsilon
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
         self.clipvalue = float(clipvalue) if clipvalue else 0.0
@@ -72,17 +94,20 @@ class KerasOptimizer(torch.optim.Optimizer):
         for g in self.param_groups:
             if g["weight_decay"] < 0:
                 raise ValueError("weight_decay must not be negative")
+            if self.layerwise and not g["trust_coefficient"] >= 0:
+                raise ValueError("trust_coefficient must not be negative")
         self._ptrs, self._table, self._chunks, self._host, self._copied = None, None, None, None, None
         self._l2 = {}                # parameter -> lambda of its kernel_regularizer (set_l2): 2*lambda*w joins the gradient in the kernel
         self.coef_dev = None         # device float[6] the kernel reads its scalars from (set by a graph-capturing trainer)
         self.group_coef_dev = None   # device float[groups][4] beside it (group_scalars): read only while coef_dev is set
         self._norm = None            # device f64 [4]: N2, norm, the clip scale (a float in the third word's first half), unused
+        self._stats = None           # 'lars' / 'lamb': (device f64 [tensors][3] = W2, U2, {float r, 0}; the norms' workspace)
 
     @property
     def grouped(self):
         """Whether step() needs embnet_optimizer_step_groups: any group, decay, multiplier, momentum or clip beyond the reference's."""
         gs = self.param_groups
-        return (len(gs) != 1 or gs[0].get("weight_decay", 0.0) != 0 or gs[0].get("lr_mult", 1.0) != 1 or self.momentum != 0
+        return (self.layerwise or len(gs) != 1 or gs[0].get("weight_decay", 0.0) != 0 or gs[0].get("lr_mult", 1.0) != 1 or self.momentum != 0
                 or self.clipvalue != 0 or self.global_clipnorm != 0)
 
     @property
@@ -99,10 +124,35 @@ class KerasOptimizer(torch.optim.Optimizer):
             self._norm = (torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(-(-nbytes // 8), dtype=torch.float64, device=dev))
         return self._norm
 
+    def _layerwise_buffers(self):
+        if self._stats is None:
+            dev = self._tensors[0].device
+            nbytes = _lib.lib().embnet_optimizer_layerwise_workspace_bytes(self._chunk_list().shape[0])
+            # the workspace's first 16 bytes are the arrival ticket: zero once, the kernel re-arms it
+            self._stats = (torch.zeros((len(self._tensors), 3), dtype=torch.float64, device=dev),
+                           torch.zeros(-(-nbytes // 8), dtype=torch.float64, device=dev))
+        return self._stats
+
+    @property
+    def trust_ratios(self):
+        """Device float32 [tensors] at a static address (a view of the norms kernel's stats, in the order of the optimizer's
+        trainable parameters): every tensor's trust ratio r of the last step — 1 for an exempt group, a tensor without a
+        gradient or a zero norm; 0 before the first step.  Rules 'lars' and 'lamb' only; valid under graph replay."""
+        if not self.layerwise:
+            raise AttributeError(f"trust_ratios belong to the rules 'lars' and 'lamb', not {self.rule!r}")
+        return self._layerwise_buffers()[0].view(torch.float32)[:, 4]
+
+    @property
+    def adapted(self):
+        """Indices (into `trust_ratios`) of the tensors whose group has a trust coefficient above zero."""
+        eta = {id(p): g["trust_coefficient"] for g in self.param_groups for p in g["params"]}
+        return [i for i, p in enumerate(self._tensors) if eta[id(p)] > 0]
+
     # -- state ----------------------------------------------------------------------------
     def _slots(self, p):
         st = self.state[p]
-        n = {"sgd": 1 if self.momentum else 0, "rms_prop": 1, "adam": 2, "radam": 2}[self.rule]     # sgd's slot1: the velocity
+        # sgd's and lars' slot1: the velocity (lars keeps it at momentum 0 too)
+        n = {"sgd": 1 if self.momentum else 0, "rms_prop": 1, "adam": 2, "radam": 2, "lars": 1, "lamb": 2}[self.rule]
         for i in range(n):
             if f"slot{i + 1}" not in st:
                 st[f"slot{i + 1}"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -205,7 +255,9 @@ class KerasOptimizer(torch.optim.Optimizer):
             self._build_table()
         self.iterations += 1
         L.WEIGHT_EPOCH[0] += 1                             # cached bf16 planes of conv kernels are stale from here on
-        if self.grouped:
+        if self.layerwise:
+            self._step_layerwise()
+        elif self.grouped:
             self._step_groups()
         else:
             lr = float(self.param_groups[0]["lr"])
@@ -249,17 +301,55 @@ class KerasOptimizer(torch.optim.Optimizer):
                                                self.coef_dev.data_ptr() if on_dev else None,
                                                self.group_coef_dev.data_ptr() if on_dev else None, stream))
 
+    def _layerwise_rows(self):
+        """-> [[lr_g, 0, wd_g, eta_g]] per group: the rate, the decay ITSELF (it joins the direction) and the trust coefficient."""
+        return [[float(g["lr"]) * float(g.get("lr_mult", 1.0)), 0.0, float(g.get("weight_decay", 0.0)), float(g["trust_coefficient"])]
+                for g in self.param_groups]
+
+    def _step_layerwise(self):
+        lib, stream = _lib.lib(), _lib.stream()
+        table, n, chunks, n_chunks = self._table.data_ptr(), len(self._tensors), self._chunks.data_ptr(), self._chunks.shape[0]
+        scale = None
+        if self.global_clipnorm:
+            norm, ws = self._norm_buffers()
+            scale = norm.data_ptr() + 16
+            check(lib.embnet_optimizer_grad_norm(table, n, chunks, n_chunks, self.global_clipnorm, ws.data_ptr(),
+                                                 ws.numel() * 8, norm.data_ptr(), scale, stream))
+        stats, ws = self._layerwise_buffers()
+        code, (_, b1, b2, eps, c1, c2) = self.scalars(self.iterations)
+        rows = np.asarray(self._layerwise_rows(), dtype=np.float32)
+        on_dev = self.coef_dev is not None
+        if on_dev and self.group_coef_dev is None:
+            raise _lib.EmbnetError("KerasOptimizer: coef_dev without group_coef_dev (the groups' rows of group_scalars)")
+        coef_dev = self.coef_dev.data_ptr() if on_dev else None
+        group_dev = self.group_coef_dev.data_ptr() if on_dev else None
+        check(lib.embnet_optimizer_layerwise_norms(code, table, n, chunks, n_chunks, rows.ctypes.data, rows.shape[0], b1, b2, eps, c1, c2,
+                                                   self.clipvalue, scale, coef_dev, group_dev, ws.data_ptr(), ws.numel() * 8,
+                                                   stats.data_ptr(), stream))
+        check(lib.embnet_optimizer_layerwise_step(code, table, n, chunks, n_chunks, rows.ctypes.data, rows.shape[0], b1, b2, eps, c1, c2,
+                                                  self.momentum, int(self.nesterov), self.clipvalue, scale, coef_dev, group_dev,
+                                                  stats.data_ptr(), stream))
+
     def prepare_capture(self):
         """Allocate what a captured step() needs that cannot be allocated during stream capture."""
         self._graph_host = torch.empty((len(self._tensors), 6), dtype=torch.int64).pin_memory()
         if self.global_clipnorm:
             self._norm_buffers()                           # grad_norm keeps its address outside the graph's pool
+        if self.layerwise:
+            self._layerwise_buffers()                      # so do trust_ratios
         self._ptrs = None                                  # the captured step builds (and keeps) its own table
 
     def scalars(self, t):
         """-> (kernel rule, [lr, b1, b2, eps, c1, c2]) of step t (1-based): what step() passes, for a caller that keeps
         them in device memory (`coef_dev`) across graph replays."""
         lr = float(self.param_groups[0]["lr"])
+        if self.layerwise:                                 # LAMB's bias corrections; LARS has none
+            if self.rule == "lars":
+                return LAYERWISE["lars"], [lr, self.b1, self.b2, self.eps, 0.0, 0.0]
+            # from the betas as the kernel holds them: its 1 - b2 is 1 - 0.999f, 1.3e-5 off 1e-3 in relative terms, and only
+            # 1 / (1 - 0.999f^t) makes v c2 the weighted mean it stands for (likewise m c1)
+            b1, b2 = float(np.float32(self.b1)), float(np.float32(self.b2))
+            return LAYERWISE["lamb"], [lr, self.b1, self.b2, self.eps, 1.0 / (1.0 - b1 ** t), 1.0 / (1.0 - b2 ** t)]
         rule, b1, b2, c1, c2 = self._coefficients(lr, t)
         return rule, [lr, b1, b2, self.eps, c1, c2]
 
@@ -268,6 +358,8 @@ class KerasOptimizer(torch.optim.Optimizer):
         `group_coef_dev` (beside `coef_dev`, whose b1, b2, eps and c2 a grouped step reads); [] when step() is not grouped."""
         if not self.grouped:
             return []
+        if self.layerwise:                                 # [lr_g, 0, wd_g, eta_g]
+            return [v for row in self._layerwise_rows() for v in row]
         return [v for row in self._group_rows(t)[4] for v in row]
 
 

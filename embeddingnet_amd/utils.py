@@ -31,28 +31,36 @@ class OptimizerSpec:
 
     @property
     def rule(self):
-        """reference utils.py:144-152: 'adam', 'rms_prop', 'radam', anything else is plain SGD."""
-        return self.name if self.name in ("adam", "rms_prop", "radam") else "sgd"
+        """reference utils.py:144-152: 'adam', 'rms_prop', 'radam', anything else is plain SGD — and, beyond the reference, the
+        layer-wise adaptive 'lars' and 'lamb'."""
+        return self.name if self.name in ("adam", "rms_prop", "radam") + LAYERWISE_RULES else "sgd"
 
     def build(self, parameters, proxies=None):
         """parameters: the model's.  Without `optimizer_params` the reference's optimizer over one group (`proxies`, when a
         proxy mode has them, are one more tensor of it).  With them up to three groups: 'kernels' — parameters with two or more
         dimensions, which get `weight_decay` — 'other' — BatchNorm parameters and biases, never decayed — and 'proxies' with
-        `proxy_lr_mult` and `proxy_weight_decay`; `group_names` on the optimizer lists the groups built."""
+        `proxy_lr_mult` and `proxy_weight_decay`; `group_names` on the optimizer lists the groups built.
+        'lars' and 'lamb' always get these groups, with or without `optimizer_params`: 'other' is neither decayed nor adapted
+        (trust coefficient 0: the exclusion of BatchNorm parameters and biases in SimCLR's and LAMB's recipes, which also covers a
+        GeM exponent), 'kernels' and 'proxies' are adapted with `trust_coefficient` (default: the rule's)."""
         from .optimizers import KerasOptimizer
         parameters = list(parameters)
         proxies = list(proxies or [])
-        if not self.params:
-            return KerasOptimizer(parameters + proxies, self.rule, self.learning_rate)
+        layerwise = self.rule in LAYERWISE_RULES
         o = self.params
+        if "trust_coefficient" in o and not layerwise:
+            raise ValueError(f"optimizer_params: trust_coefficient belongs to the optimizers 'lars' and 'lamb', not {self.name!r}")
+        if not o and not layerwise:
+            return KerasOptimizer(parameters + proxies, self.rule, self.learning_rate)
         if not proxies and ("proxy_lr_mult" in o or "proxy_weight_decay" in o):
             raise ValueError("optimizer_params: proxy_lr_mult / proxy_weight_decay belong to the proxy modes")
         groups = [("kernels", dict(params=[p for p in parameters if p.dim() >= 2], weight_decay=float(o.get("weight_decay", 0.0)))),
-                  ("other", dict(params=[p for p in parameters if p.dim() < 2])),
+                  ("other", dict(params=[p for p in parameters if p.dim() < 2], **(dict(trust_coefficient=0.0) if layerwise else {}))),
                   ("proxies", dict(params=proxies, lr_mult=float(o.get("proxy_lr_mult", 1.0)),
                                    weight_decay=float(o.get("proxy_weight_decay", 0.0))))]
         groups = [(n, g) for n, g in groups if g["params"]]
-        kwargs = {k: o[k] for k in ("momentum", "nesterov", "epsilon", "beta_1", "beta_2", "clipvalue", "global_clipnorm") if k in o}
+        kwargs = {k: o[k] for k in ("momentum", "nesterov", "epsilon", "beta_1", "beta_2", "clipvalue", "global_clipnorm",
+                                    "trust_coefficient") if k in o}
         opt = KerasOptimizer([g for _, g in groups], self.rule, self.learning_rate, **kwargs)
         opt.group_names = [n for n, _ in groups]
         return opt
@@ -63,15 +71,20 @@ class OptimizerSpec:
 
 
 OPTIMIZER_PARAMS = ("weight_decay", "momentum", "nesterov", "epsilon", "beta_1", "beta_2", "clipvalue", "global_clipnorm",
-                    "proxy_lr_mult", "proxy_weight_decay")
+                    "proxy_lr_mult", "proxy_weight_decay", "trust_coefficient")
+LAYERWISE_RULES = ("lars", "lamb")
 
 
 def check_optimizer_params(params):
-    """TRAIN.optimizer_params -> a dict with known keys only (unknown ones are refused)."""
+    """TRAIN.optimizer_params -> a dict with known keys only (unknown ones are refused; so is a `trust_coefficient` that is not a
+    number >= 0)."""
     params = dict(params or {})
     unknown = set(params) - set(OPTIMIZER_PARAMS)
     if unknown:
         raise ValueError(f"optimizer_params: unknown keys {sorted(unknown)} ({', '.join(OPTIMIZER_PARAMS)})")
+    eta = params.get("trust_coefficient", 0.0)
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0:
+        raise ValueError(f"optimizer_params: trust_coefficient must be a number >= 0 (got {eta!r})")
     return params
 
 

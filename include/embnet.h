@@ -1566,6 +1566,60 @@ size_t embnet_optimizer_grad_norm_workspace_bytes(int n_chunks);
 int embnet_optimizer_grad_norm(const void* table, int n_tensors, const int32_t* chunks, int n_chunks, float clipnorm,
                                void* workspace, size_t workspace_bytes, double* norm_out, float* scale_out, void* stream);
 
+/* ------------------------------------------------------------------ layer-wise adaptive updates (LARS / LAMB)
+ * LARS (You et al. 2017, in the form of SimCLR's LARSOptimizer) and LAMB (You et al. 2020): every tensor's step is scaled by a
+ * trust ratio r = eta |w| / |u|, u the tensor's update direction, so that a large batch's large rate moves every layer by the
+ * same fraction of its own norm.  Two launches over the optimizer's table and chunk list above — the 48-byte descriptors
+ * { w, g, slot1, slot2, n, l2x2, group } and the (tensor, chunk) pairs — with ONE more precondition: the chunks of a tensor are
+ * consecutive and ascending in the list (as embeddingnet_amd/multi_tensor.py's chunk_list builds them: tensor by tensor).
+ * The rules have codes of their own (embnet_optimizer_step_groups goes on refusing everything past EMBNET_OPT_MOMENTUM).
+ *   group_coef      HOST float [n_groups][4] = { lr_g, 0, wd_g, eta_g }, 1 <= n_groups <= EMBNET_OPT_MAX_GROUPS: the group's rate,
+ *                   its weight decay ITSELF (not lr * wd: the decay joins the direction, below) and its trust coefficient;
+ *                   eta_g == 0 exempts the group from adaptation (r = 1: BatchNorm parameters and biases in the papers);
+ *   group_coef_dev  NULL, or the same rows in DEVICE memory, read instead (a captured step replays with current rates);
+ *   coef_dev        NULL, or device float[6] = lr, b1, b2, eps, c1, c2: b1, b2, eps, c1 and c2 are read from it (its lr is not);
+ *   c1, c2          LAMB's bias corrections 1/(1-b1^t) and 1/(1-b2^t), computed by the host in double, passed in fp32 — best
+ *                   from b1 and b2 as fp32 holds them, so that m*c1 and v*c2 are weighted means (1 - 0.999f is 1.3e-5 off 1e-3);
+ *   clipvalue, clip_scale_dev   as embnet_optimizer_step_groups: exclusive; the scale is what embnet_optimizer_grad_norm left.
+ * Both entry points launch one kernel, allocate nothing and never wait for the device: a stream capture records them.
+ * Per element, fp32, contraction off, every rounding as written (fma = one rounding):
+ *     g' = fma(l2x2, w, g);   clipvalue c > 0: g' = min(max(g', -c), c);   clip_scale_dev: g' = g' * s
+ *     LARS   u = fma(wd_g, w, g')
+ *     LAMB   m = fma(1-b1, g', b1*m);  v = fma((1-b2)*g', g', b2*v);  u = fma(wd_g, w, (m*c1) / (sqrtf(v*c2) + eps))
+ * per tensor, in f64:  W2 = sum (double)w^2,  U2 = sum (double)u^2
+ *     r = (eta_g > 0 && W2 > 0 && U2 > 0) ? (float)(eta_g * sqrt(W2) / sqrt(U2)) : 1        (f64 until the one conversion)
+ *     LARS   s = lr_g * r;  su = s * u;  v = fma(momentum, v, su);  w = w - (nesterov ? fma(momentum, v, su) : v)     (slot1 = v)
+ *     LAMB   s = lr_g * r;  w = fma(-s, u, w)                                                         (slot1 = m, slot2 = v)
+ * A tensor with g == NULL (or without a slot its rule keeps) is skipped entirely: weight and slots untouched.
+ *
+ * embnet_optimizer_layerwise_norms: at most 512 workgroups walk the chunks; each chunk's W2 and U2 partial is the sum over its
+ * elements — thread j of 256 adds elements 1024 i + 4 j .. 4 j + 3 (i = 0..3) of the chunk in ascending order, the 64 lanes of a
+ * wave meet in a butterfly (offsets 32 .. 1), the four waves are added left to right — on the float4 path and element by element
+ * alike.  For LAMB this pass writes m and v back.  The last workgroup to arrive then adds each tensor's partials p_0 .. p_{k-1}
+ * (chunk order): lane j of one wave adds p_j, p_{j+64}, ... in ascending order onto 0, and the 64 sums meet in the same
+ * butterfly.  That order depends on nothing but the tensor's size: not on the grid, not on the order of arrival.  No
+ * floating-point atomics; the same inputs give the same bits.  It writes, with vector stores,
+ *     stats_out[tensor] = { double W2; double U2; float r; float pad (0); }        24 bytes per tensor, 8-byte aligned
+ * and { 0, 0, 1 } for a tensor that was skipped.  A tensor without elements has no chunk and gets no row.
+ * workspace: embnet_optimizer_layerwise_workspace_bytes(n_chunks) bytes, 16-byte aligned, its first 16 bytes ZERO before the
+ * first launch (the arrival ticket, which re-arms itself: no memset per step); the partials behind it are overwritten by every
+ * launch.  Moves 8 bytes per element for LARS, 24 for LAMB.
+ * embnet_optimizer_layerwise_step: one workgroup per chunk; reads r from `stats`.  LAMB recomputes u from the stored m, v and the
+ * weight by the expression above — the norm is of the vector that is applied — and does not read the gradient.  Aligned whole
+ * chunks go through float4, tails and unaligned tensors element by element, to the same bits.  momentum, nesterov: LARS only.
+ * Moves 20 bytes per element for LARS, 16 for LAMB. */
+enum { EMBNET_LAYERWISE_LARS = 0, EMBNET_LAYERWISE_LAMB = 1 };
+size_t embnet_optimizer_layerwise_workspace_bytes(int n_chunks);
+int embnet_optimizer_layerwise_norms(int rule, const void* table, int n_tensors, const int32_t* chunks, int n_chunks,
+                                     const float* group_coef, int n_groups, float b1, float b2, float eps, float c1, float c2,
+                                     float clipvalue, const float* clip_scale_dev, const float* coef_dev,
+                                     const float* group_coef_dev, void* workspace, size_t workspace_bytes, void* stats_out,
+                                     void* stream);
+int embnet_optimizer_layerwise_step(int rule, const void* table, int n_tensors, const int32_t* chunks, int n_chunks,
+                                    const float* group_coef, int n_groups, float b1, float b2, float eps, float c1, float c2,
+                                    float momentum, int nesterov, float clipvalue, const float* clip_scale_dev,
+                                    const float* coef_dev, const float* group_coef_dev, const void* stats, void* stream);
+
 /* ------------------------------------------------------------------ averaged weights (EMA / SWA)
  * An averaged copy of every tensor of a model, kept by one launch per step beside the one-launch optimizer update, and a second
  * kernel that exchanges the model's tensors with their averages so that the averaged model is evaluated in place

@@ -13,6 +13,12 @@ and three for the averaged weights (csrc/weight_average.hip) over the same tenso
   average_update  embnet_weight_average_update, c = 1e-3      (12 B per element)
   average_swap    embnet_weight_average_swap                  (16 B per element)
 
+and the layer-wise adaptive rules (csrc/layerwise.hip), three groups, 'other' exempt, two launches per step, each also alone:
+
+  lars, lamb                embnet_optimizer_layerwise_norms + embnet_optimizer_layerwise_step   (8 + 20 and 24 + 16 B per element)
+  lars_norms, lamb_norms    the norms launch alone (its last workgroup adds every tensor's partials)
+  lars_step, lamb_step      the update alone, at the trust ratios the last norms launch left
+
   python tools/optimizer_bench.py [--rounds 15] [--reps 20] [--json out.json]          (GPU box)
 
 All legs run in one process on the same table, in alternating rounds of `reps` back-to-back steps timed with events (a step is
@@ -86,6 +92,25 @@ def main():
     legs["average_update"] = lambda: check(lib.embnet_weight_average_update(avg_table.data_ptr(), n, chunks, n_chunks, 1e-3, None, stream))
     legs["average_swap"] = lambda: check(lib.embnet_weight_average_swap(avg_table.data_ptr(), n, chunks, n_chunks, stream))
     nbytes.update(opt_sgd=12.0 * n_elem, average_update=12.0 * n_elem, average_swap=16.0 * n_elem)
+    # the layer-wise rules over the same table and groups ('other' exempt): the norms launch, then the update
+    lw_rows = np.asarray([[lr, 0, 1e-4, 1e-3], [lr, 0, 0, 0], [100 * lr, 0, 0, 1e-3]], dtype=np.float32)
+    stats = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    lw_bytes = lib.embnet_optimizer_layerwise_workspace_bytes(n_chunks)
+    lw_ws = torch.zeros(-(-lw_bytes // 8), dtype=torch.float64, device=dev)          # (the ticket in front: zero once)
+
+    def layerwise(code, momentum, norms=True, step=True):
+        if norms:
+            check(lib.embnet_optimizer_layerwise_norms(code, table, n, chunks, n_chunks, lw_rows.ctypes.data, 3, b1, b2, eps, 1.5, 1.01,
+                                                       0.0, None, None, None, lw_ws.data_ptr(), lw_ws.numel() * 8, stats.data_ptr(), stream))
+        if step:
+            check(lib.embnet_optimizer_layerwise_step(code, table, n, chunks, n_chunks, lw_rows.ctypes.data, 3, b1, b2, eps, 1.5, 1.01,
+                                                      momentum, 0, 0.0, None, None, None, stats.data_ptr(), stream))
+
+    legs.update(lars=lambda: layerwise(0, 0.9), lars_norms=lambda: layerwise(0, 0.9, step=False),
+                lars_step=lambda: layerwise(0, 0.9, norms=False), lamb=lambda: layerwise(1, 0.0),
+                lamb_norms=lambda: layerwise(1, 0.0, step=False), lamb_step=lambda: layerwise(1, 0.0, norms=False))
+    nbytes.update(lars=28.0 * n_elem, lars_norms=8.0 * n_elem, lars_step=20.0 * n_elem, lamb=40.0 * n_elem, lamb_norms=24.0 * n_elem,
+                  lamb_step=16.0 * n_elem)
     times = {k: [] for k in legs}
     for fn in legs.values():
         for _ in range(3):

@@ -593,7 +593,9 @@ def main():
     # without the key this is the reference's optimizer over `params`, the proxies one more tensor of its single group
     opt = p_train['optimizer'].build(params[:len(params) - (head is not None)], proxies=[head.proxies] if head is not None else None)
     clipnorm = bool(getattr(opt, 'global_clipnorm', 0))
-    lr0 = p_train['learning_rate']
+    # optimizers 'lars' / 'lamb': the tensors whose steps are adapted (every group but 'other'), for the epoch line's trust ratios
+    adapted = torch.tensor(opt.adapted, dtype=torch.long, device=dev) if getattr(opt, 'layerwise', False) else None
+    lr0 =p_train['learning_rate']
     resumed_updates = 0
     if args.resume_from is not None:                  # optimizer slots and step count, when the checkpoint has them (Keras'
         # load_model restores the optimizer with the weights; the epoch count and LR schedule restart, as in the reference)
@@ -722,6 +724,9 @@ def main():
             if norm_sum is not None and losses:           # this rank's: the mean global gradient norm before clipping
                 norm_sum += opt.grad_norm
                 msg += f' - grad_norm {norm_sum.item() / len(losses):.4g}'
+            if adapted is not None and adapted.numel() and losses:      # this rank's: the last step's trust ratios, smallest..largest
+                ratios = opt.trust_ratios[adapted]
+                msg += f' - trust {ratios.min().item():.3g}..{ratios.max().item():.3g}'
             if xbm is not None:                           # this rank's memory: labelled slots now, pairs kept over the epoch
                 kept = torch.stack(xbm_counts).sum(0).tolist() if xbm_counts else [0, 0]
                 msg += f' - xbm_filled {memory.filled()} - xbm_kept {kept[0]}+{kept[1]}'
